@@ -2,6 +2,7 @@
 """Benchmark of the DrawingSpinUp hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config drawing|unet|nsr50k|frames]
+                    [--full] [--dump-outputs DIR]
 
 `--config drawing` (default; BASELINE.json's metric, configs[4] per GPU): one "step" = ONE drawing
 through the hot path on each rank (weak scaling, one drawing per GPU per step):
@@ -25,6 +26,13 @@ frames sharded over the ranks (strong scaling).
 `--gpus N` with N > 1 launched WITHOUT torch.distributed.run spawns the N ranks itself (one
 process per GPU, RCCL), so `python bench.py --gpus 8` and the torchrun form measure the same job.
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+the per-stage seconds measured inside the clock).  `--full` adds what costs time or runs of its own:
+the sampled HIP-event kernel timing inside the timed region and the `roofline` object built from it
+(with `--config drawing` and drawings in flight: one more drawing alone after the clock), the
+stylisation stage re-run with the other arithmetic switches, and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned (see `_dump_outputs`) as .npy files.
 """
 import argparse
 import json
@@ -53,7 +61,13 @@ def parse(argv=None):
     ap.add_argument("--mv-steps", type=int, default=75)
     ap.add_argument("--nsr-steps", type=int, default=3000)
     ap.add_argument("--frames", type=int, default=24)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel timing / roofline, the stylisation switches beside the clock, one drawing "
+                         "alone after the clock (drawings in flight) and the CPU baseline; off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: fixed seeded samples of the large ones)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--inflight", type=int, default=3,
                     help="--config drawing: drawings in flight per GPU (one Python thread + one stream + "
                          "one DrawingPipeline each); 1 = one drawing at a time, as in rounds 1-5")
@@ -205,6 +219,84 @@ class KernelTimer:
         return rows
 
 
+class _NoTimer:
+    """A plain run (no --full): the timed loops switch it on and off, nothing is recorded."""
+    enabled = False
+
+    def summary(self):
+        return []
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: the arrays the last timed step handed to its caller, for output-for-output
+# comparisons of two builds.  uint8 / float16 / float32 arrays are written as float32, float64 and
+# integer arrays as float64 (exact).  An array of more than `cap` elements is written as
+# <name>_sample.npy: its flattened elements at np.unique(default_rng(0).integers(0, size, cap)),
+# the same indices in every run with the same arguments.
+# ------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def _to_numpy(t):
+    import numpy as np
+    if isinstance(t, torch.Tensor):
+        t = t.detach()
+        t = (t.to(torch.float64) if t.dtype in (torch.float64, torch.int32, torch.int64)
+             else t.to(torch.float32)).cpu().numpy()
+    a = np.asarray(t)
+    return a.astype(np.float64 if a.dtype in (np.float64, np.int32, np.int64) else np.float32, copy=False)
+
+
+def _dump_outputs(dirname, arrays):
+    """arrays: {name: (tensor or array, cap in elements or None)}; returns {file: shape}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out, total = {}, 0
+    for name, (t, cap) in arrays.items():
+        a = _to_numpy(t)
+        if cap is not None and a.size > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, cap))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise ValueError(f"--dump-outputs: more than {DUMP_LIMIT_BYTES} bytes at {name}")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        out[name + ".npy"] = list(a.shape)
+    return out
+
+
+MESH_SUMMARY_FIELDS = ("n_verts", "n_faces", "p05_x", "p05_y", "p05_z", "median_x", "median_y", "median_z",
+                       "p95_x", "p95_y", "p95_z", "mean_color_r", "mean_color_g", "mean_color_b")
+
+
+def _mesh_summary(pipe):
+    """The mesh a pipeline's last drawing left on its rank (after save_mesh's post-processing when
+    it ran) as MESH_SUMMARY_FIELDS (float64; zeros for a missing / empty mesh).  Its vertex and
+    face counts vary from run to run (the optimisation's float atomics are not bitwise
+    reproducible), so the arrays themselves have no fixed shape to compare; the summary has.
+    Percentiles rather than extremes: a few stray faces far from the surface move min / max."""
+    import numpy as np
+    mesh = getattr(pipe, "last_mesh_post", None) or getattr(pipe, "last_mesh", None) or {}
+    get = lambda k: (None if mesh.get(k) is None else
+                     np.asarray(mesh[k].detach().cpu() if isinstance(mesh[k], torch.Tensor) else mesh[k],
+                                np.float64))
+    v, f, c = get("verts"), get("faces"), get("colors")
+    out = np.zeros(len(MESH_SUMMARY_FIELDS), np.float64)
+    if v is None or f is None or v.size == 0 or f.size == 0:
+        return out
+    v = v.reshape(-1, 3)
+    col = c.reshape(-1, c.shape[-1])[:, :3].mean(0) if c is not None and c.size else np.zeros(3)
+    out[:] = [v.shape[0], f.size // 3, *np.percentile(v, [5, 50, 95], axis=0).reshape(-1), *col]
+    return out
+
+
+def _frames_arrays(frames, prefix="frames"):
+    """Stylised frames (..., 4, H, W) uint8: a fixed sample of 2^22 values and every frame's
+    per-channel sums (float64, all pixels)."""
+    return {prefix: (frames, 1 << 22),
+            prefix + "_channel_sums": (frames.to(torch.float64).sum(dim=(-1, -2)), None)}
+
+
 # ------------------------------------------------------------------------------------------------
 # CPU baseline: the same operators on the GPU box's host cores, bounded samples.
 # ------------------------------------------------------------------------------------------------
@@ -290,8 +382,11 @@ def run(args):
     assert torch.cuda.is_available(), "bench.py needs a GPU"
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    timer = KernelTimer()
-    timer.install()
+    if args.full:
+        timer = KernelTimer()
+        timer.install()
+    else:
+        timer = _NoTimer()
     if args.config == "unet":
         out = bench_unet(args, ddist, rank, world, dev, timer)
     elif args.config == "nsr50k":
@@ -421,6 +516,8 @@ def _inflight_loop(args, ddist, rank, dev, timer, pipes, inputs, stage_t, sub_t,
                 lat.append(t4 - t0)
                 if gv is not None:
                     gathered["views"], gathered["frames"] = gv, gf
+                    if "last" in gathered and j >= n_drawings - K:        # --dump-outputs: the last step's drawings
+                        gathered["last"][j] = (gv, gf)
         for t in th:
             t.join()
 
@@ -432,11 +529,13 @@ def _inflight_loop(args, ddist, rank, dev, timer, pipes, inputs, stage_t, sub_t,
     _sync(dev); ddist.barrier()
     elapsed = ddist.max_over_ranks(time.time() - t0, dev)
     timer.enabled = False
+    if "last" in gathered:                  # before the drawing alone below replaces pipes[0]'s mesh
+        gathered["meshes"] = {(args.steps - 1) * K + k: _mesh_summary(p_) for k, p_ in enumerate(pipes)}
     info = {"latency": {"mean": sum(lat) / max(len(lat), 1), "max": max(lat) if lat else None,
                         "drawings": len(lat)},
             "schedule": {"start_skew_s": skew, "nsr_slots": slots, "onewave_grid": grid_cap}}
-    # one drawing alone, beside the clock: the kernel families without co-running drawings
-    if rank == 0 and hasattr(timer, "fam"):
+    # one drawing alone, beside the clock (--full): the kernel families without co-running drawings
+    if rank == 0 and hasattr(timer, "fam") and getattr(args, "full", False):
         concurrent = timer.summary()
         saved = (timer.fam, dict(timer._calls))
         from drawingspinup_amd.nsr import system as nsr_system
@@ -651,13 +750,31 @@ def bench_drawing(args, ddist, rank, world, dev, timer, pipe=None):
         dsu_lib_.check(dsu_lib_.lib().dsu_set_nsr_side_stream_priority(side_prio), "dsu_set_nsr_side_stream_priority")
         dsu_lib_.check(dsu_lib_.lib().dsu_set_nsr_side_stream_pooling(int(getattr(args, "side_pool", 0) or 0)),
                        "dsu_set_nsr_side_stream_pooling")
+    dump = getattr(args, "dump_outputs", None)
+    if dump:
+        gathered["last"] = {}
     if inflight == 1:
         elapsed, last = _timed_loop(args, ddist, dev, timer, one_drawing)
+        if dump and "views" in gathered:                  # rank 0
+            gathered["last"][args.steps - 1] = (gathered["views"], gathered["frames"])
+            gathered["meshes"] = {args.steps - 1: _mesh_summary(pipe)}
     else:
         elapsed, flight = _inflight_loop(args, ddist, rank, dev, timer, pipes, inputs, stage_t, sub_t, gathered)
     if rank != 0:
         return None
     assert len(gathered["views"]) == world and len(gathered["frames"]) == world
+    dumped = None
+    if dump:
+        # the last timed step's drawings (index j of the timed region; with drawings in flight the
+        # last K): the views and frames gathered from every rank, a summary of each mesh rank 0 kept
+        js = sorted(gathered["last"])
+        views = torch.stack([torch.stack(list(gathered["last"][j][0])) for j in js])      # (K, world, 12, 3, 256, 256)
+        frames = torch.stack([torch.stack(list(gathered["last"][j][1])) for j in js])     # (K, world, n, 4, 512, 512)
+        arrays = {"views": (views, 1 << 23), **_frames_arrays(frames)}
+        import numpy as np
+        meshes = gathered.get("meshes", {})
+        arrays["mesh_summary"] = (np.stack([meshes[j] for j in sorted(meshes)]), None)   # (K, MESH_SUMMARY_FIELDS)
+        dumped = _dump_outputs(dump, arrays)
     # seconds per DRAWING and stage (with drawings in flight: wall time of the stage on its stream,
     # beside the other drawings' kernels — the stages of one drawing then add up to its latency)
     per = {k: v / (args.steps * inflight) for k, v in stage_t.items()}
@@ -667,53 +784,55 @@ def bench_drawing(args, ddist, rank, world, dev, timer, pipe=None):
     # products (finer than the cuDNN TF32 the reference gets by default), IS-Net in exact f32 (f32
     # ONNX session).  Beside the clock, for comparison with earlier rounds' lines: the stage with
     # every layer on bf16 x 3, and with every layer in exact f32.
-    per["style_all_bf16x3"] = _style_seconds_with(pipe, inputs[(True, args.steps - 1)], dev,
-                                                  EVAL_X3=True, EVAL_DEFORM_X3=True)
-    per["style_all_exact_f32"] = _style_seconds_with(pipe, inputs[(True, args.steps - 1)], dev,
-                                                     EVAL_X3=False, EVAL_DEFORM_X3=False)
-    stages = {
-        "mv": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
-               "achieved": 2.913 * args.mv_steps / max(per["mv"], 1e-9)},
-        # achieved = ALGORITHMIC flops (0.84 TFLOP per frame for the two generators:
-        # 0.298 stage 1 + 0.544 stage 2) / stage time, against the bf16 MFMA peak the contract names.
-        # Stage 1 runs exact f32 products (f32 MFMA peak 157.3 TFLOP/s), stage 2 three bf16 MFMA
-        # products per f32 product: the stage is a mix of the two pipes, so the fraction against
-        # either single peak understates it; the per-pipe peaks are listed beside it.
-        "style": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
-                  "achieved": 0.84 * args.frames / max(per["style"], 1e-9),
-                  "stage1_tflop_exact_f32": 0.298 * args.frames,
-                  "stage2_tflop_bf16x3_issued": 3 * 0.544 * args.frames,
-                  "f32_mfma_peak": F32_MFMA_PEAK_TF},
-    }
-    for st in stages.values():
-        st["frac"] = st["achieved"] / st["peak"]
-    # matrix-pipe busy share of the wave cycles and the parked / issue-stalled shares of the stage's
-    # MFMA kernels, from the SQ pass (profiles/round{5,4}_pmc.json; one UNet forward / one frame)
-    for name, pre in (("mv", ("conv_f16_kernel", "mv_attention_kernel")), ("style", ("conv_x3_kernel",))):
-        for field in ("mfma_busy_of_wave_cycles", "parked_frac", "issue_stall_frac"):
-            v = _sq_share(pre, field)
-            if v is not None:
-                stages[name][field] = v
-    roof = _roofline(timer, {"stages": stages,
-                             "traffic_note": "HBM-side bytes per launch of the dominant family "
-                                             "(MLP part + scatter): (2 x FETCH_SIZE + "
-                                             "WRITE_SIZE) of separate rocprofv3 --pmc passes "
-                                             "(roofline.traffic_source, tools/pmc_round6.sh) relative to "
-                                             "that workload's algorithmic bytes, applied to this run's "
-                                             "mean algorithmic bytes per launch"})
-    if flight and roof is not None:
-        # kernel timing of ONE drawing alone beside the clock (the timed region's event pairs see the
-        # kernels of the other drawings in flight inside their intervals)
-        roof["in_flight"] = inflight
-        roof["note_in_flight"] = ("avg_launch_ms / achieved / frac are HIP-event intervals inside the timed region, "
-                                  "where %d drawings share the GPU: an interval contains the co-running kernels' "
-                                  "share of the machine; roofline.alone = the same families with one drawing alone "
-                                  "on the GPU (one more drawing after the clock, one workgroup per CU for the one-wave kernels, "
-                                  "side stream at normal priority as for one drawing at a time)" % inflight)
-        roof["alone"] = flight.get("alone")
-        lead = next((r for r in (roof["alone"] or []) if r.get("kernel") == roof.get("kernel")), None)
-        if lead:                                  # the leading family alone, next to the shared-machine figures
-            roof["frac_alone"], roof["avg_launch_ms_alone"] = lead["frac"], lead["avg_launch_ms"]
+    roof = None
+    if args.full:
+        per["style_all_bf16x3"] = _style_seconds_with(pipe, inputs[(True, args.steps - 1)], dev,
+                                                      EVAL_X3=True, EVAL_DEFORM_X3=True)
+        per["style_all_exact_f32"] = _style_seconds_with(pipe, inputs[(True, args.steps - 1)], dev,
+                                                         EVAL_X3=False, EVAL_DEFORM_X3=False)
+        stages = {
+            "mv": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
+                   "achieved": 2.913 * args.mv_steps / max(per["mv"], 1e-9)},
+            # achieved = ALGORITHMIC flops (0.84 TFLOP per frame for the two generators:
+            # 0.298 stage 1 + 0.544 stage 2) / stage time, against the bf16 MFMA peak the contract names.
+            # Stage 1 runs exact f32 products (f32 MFMA peak 157.3 TFLOP/s), stage 2 three bf16 MFMA
+            # products per f32 product: the stage is a mix of the two pipes, so the fraction against
+            # either single peak understates it; the per-pipe peaks are listed beside it.
+            "style": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
+                      "achieved": 0.84 * args.frames / max(per["style"], 1e-9),
+                      "stage1_tflop_exact_f32": 0.298 * args.frames,
+                      "stage2_tflop_bf16x3_issued": 3 * 0.544 * args.frames,
+                      "f32_mfma_peak": F32_MFMA_PEAK_TF},
+        }
+        for st in stages.values():
+            st["frac"] = st["achieved"] / st["peak"]
+        # matrix-pipe busy share of the wave cycles and the parked / issue-stalled shares of the stage's
+        # MFMA kernels, from the SQ pass (profiles/round{5,4}_pmc.json; one UNet forward / one frame)
+        for name, pre in (("mv", ("conv_f16_kernel", "mv_attention_kernel")), ("style", ("conv_x3_kernel",))):
+            for field in ("mfma_busy_of_wave_cycles", "parked_frac", "issue_stall_frac"):
+                v = _sq_share(pre, field)
+                if v is not None:
+                    stages[name][field] = v
+        roof = _roofline(timer, {"stages": stages,
+                                 "traffic_note": "HBM-side bytes per launch of the dominant family "
+                                                 "(MLP part + scatter): (2 x FETCH_SIZE + "
+                                                 "WRITE_SIZE) of separate rocprofv3 --pmc passes "
+                                                 "(roofline.traffic_source, tools/pmc_round6.sh) relative to "
+                                                 "that workload's algorithmic bytes, applied to this run's "
+                                                 "mean algorithmic bytes per launch"})
+        if flight and roof is not None:
+            # kernel timing of ONE drawing alone beside the clock (the timed region's event pairs see the
+            # kernels of the other drawings in flight inside their intervals)
+            roof["in_flight"] = inflight
+            roof["note_in_flight"] = ("avg_launch_ms / achieved / frac are HIP-event intervals inside the timed region, "
+                                      "where %d drawings share the GPU: an interval contains the co-running kernels' "
+                                      "share of the machine; roofline.alone = the same families with one drawing alone "
+                                      "on the GPU (one more drawing after the clock, one workgroup per CU for the one-wave kernels, "
+                                      "side stream at normal priority as for one drawing at a time)" % inflight)
+            roof["alone"] = flight.get("alone")
+            lead = next((r for r in (roof["alone"] or []) if r.get("kernel") == roof.get("kernel")), None)
+            if lead:                                  # the leading family alone, next to the shared-machine figures
+                roof["frac_alone"], roof["avg_launch_ms_alone"] = lead["frac"], lead["avg_launch_ms"]
     out = {
         "metric": "drawings/sec end-to-end (512x512, 6 views, 24 frames)",
         "value": world * inflight * args.steps / elapsed, "unit": "drawings/s", "n_gpus": world,
@@ -755,11 +874,13 @@ def bench_drawing(args, ddist, rank, world, dev, timer, pipe=None):
                        "style_stage2": "f32 activations, bf16 x 3 products, f32 accumulation (2^-15 "
                                        "per product; reference: cuDNN with TF32 allowed by default, 2^-11)"},
                    "stage_seconds_rank0": per, "weights_broadcast_bytes": bcast_bytes,
-                   "gathered_bytes_per_step": sum(t.numel() * t.element_size() for k in gathered
+                   "gathered_bytes_per_step": sum(t.numel() * t.element_size() for k in ("views", "frames")
                                                   for t in gathered[k])},
         "roofline": roof,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.nsr_steps, args.frames, args.mv_steps)
     return out
 
@@ -789,7 +910,7 @@ def bench_unet(args, ddist, rank, world, dev, timer):
     assert out.shape == (12, 4, 32, 32) and bool(torch.isfinite(out).all())
     fps = world * args.steps / elapsed
     tflop = 2.913                                  # algorithmic flops of one forward
-    return {"metric": "multi-view UNet forwards/sec (6 views x 2 domains, 256x256, B=12)",
+    res = {"metric": "multi-view UNet forwards/sec (6 views x 2 domains, 256x256, B=12)",
             "value": fps, "unit": "forwards/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
@@ -798,9 +919,14 @@ def bench_unet(args, ddist, rank, world, dev, timer):
                                    "latents, one CLIP token, 10 class-label values; random-init weights "
                                    "of the shipped architecture (320/640/1280/1280, 2 layers per block)",
                        "parallelism": f"replica x{world}"},
-            "roofline": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
-                         "achieved": tflop * fps / world, "frac": tflop * fps / world / F16_MFMA_PEAK_TF,
-                         "traffic": None, "kernels": timer.summary()[:3]}}
+            "roofline": None}
+    if args.full:
+        res["roofline"] = {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
+                           "achieved": tflop * fps / world, "frac": tflop * fps / world / F16_MFMA_PEAK_TF,
+                           "traffic": None, "kernels": timer.summary()[:3]}
+    if args.dump_outputs:                          # rank 0's noise prediction of the last step
+        res["dumped_outputs"] = _dump_outputs(args.dump_outputs, {"unet_out": (out, None)})
+    return res
 
 
 def bench_nsr50k(args, ddist, rank, world, dev, timer):
@@ -826,11 +952,11 @@ def bench_nsr50k(args, ddist, rank, world, dev, timer):
             samples[0] += int(r["n_samples"])
         return r
 
-    elapsed, _ = _timed_loop(args, ddist, dev, timer, step)
+    elapsed, last = _timed_loop(args, ddist, dev, timer, step)
     if rank != 0:
         return None
     n = samples[0] / max(args.steps, 1)
-    return {"metric": "NSR optimisation iterations/sec (128^3 occupancy grid, 50k rays/iter)",
+    res = {"metric": "NSR optimisation iterations/sec (128^3 occupancy grid, 50k rays/iter)",
             "value": world * args.steps / elapsed, "unit": "iterations/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -843,7 +969,14 @@ def bench_nsr50k(args, ddist, rank, world, dev, timer):
                        "samples_per_iteration": n, "samples_per_s": world * n * args.steps / elapsed,
                        "point_evaluations_per_s": world * 7 * (n + 4096) * args.steps / elapsed,
                        "parallelism": f"replica x{world}"},
-            "roofline": _roofline(timer)}
+            "roofline": _roofline(timer) if args.full else None}
+    if args.dump_outputs:
+        # rank 0's last step: its loss terms and ray / sample counts, and the parameters it updated
+        arrays = {"loss_" + k: (v, None) for k, v in last.items() if isinstance(v, torch.Tensor)}
+        arrays["counts"] = (torch.tensor([last["n_samples"], last["n_rays"]], dtype=torch.int64), None)
+        arrays.update({"param_" + k.replace(".", "_"): (v, 1 << 20) for k, v in sysm.model.named_parameters()})
+        res["dumped_outputs"] = _dump_outputs(args.dump_outputs, arrays)
+    return res
 
 
 def bench_frames(args, ddist, rank, world, dev, timer, pipe=None, size=512):
@@ -872,7 +1005,7 @@ def bench_frames(args, ddist, rank, world, dev, timer, pipe=None, size=512):
     # rank 0 puts the shards back in frame order (frame f = row f // N of rank f % N's part)
     ordered = torch.stack([parts[f % world][f // world] for f in range(args.frames)])
     fps = args.frames * args.steps / elapsed
-    return {"metric": "stylised frames/sec (512x512, stage 1 + stage 2)", "value": fps,
+    res = {"metric": "stylised frames/sec (512x512, stage 1 + stage 2)", "value": fps,
             "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None,
@@ -882,12 +1015,17 @@ def bench_frames(args, ddist, rank, world, dev, timer, pipe=None, size=512):
                                    "rank 0" % args.frames,
                        "frames_per_rank": len(mine), "parallelism": f"frame-shard x{world}",
                        "gathered_frames_checksum": int(ordered.to(torch.int64).sum())},
-            # algorithmic flops (0.84 TFLOP per frame) / time; the bf16 x 3 kernels
-            # issue three MFMA products per f32 product, reported beside it
-            "roofline": {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
-                         "achieved": 0.84 * fps, "frac": 0.84 * fps / F16_MFMA_PEAK_TF,
-                         "issued_mfma_tflops": 3 * 0.84 * fps, "f32_mfma_peak": F32_MFMA_PEAK_TF,
-                         "traffic": None, "kernels": timer.summary()[:3]}}
+            "roofline": None}
+    if args.full:
+        # algorithmic flops (0.84 TFLOP per frame) / time; the bf16 x 3 kernels
+        # issue three MFMA products per f32 product, reported beside it
+        res["roofline"] = {"bound": "mfma", "unit": "TFLOP/s", "peak": F16_MFMA_PEAK_TF,
+                           "achieved": 0.84 * fps, "frac": 0.84 * fps / F16_MFMA_PEAK_TF,
+                           "issued_mfma_tflops": 3 * 0.84 * fps, "f32_mfma_peak": F32_MFMA_PEAK_TF,
+                           "traffic": None, "kernels": timer.summary()[:3]}
+    if getattr(args, "dump_outputs", None):        # the last step's frames, gathered in frame order
+        res["dumped_outputs"] = _dump_outputs(args.dump_outputs, _frames_arrays(ordered))
+    return res
 
 
 def _spawn_worker(local_rank, args, port):

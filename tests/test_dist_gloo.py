@@ -4,6 +4,7 @@ import os
 import socket
 import sys
 
+import numpy as np
 import torch
 import torch.multiprocessing as mp
 
@@ -104,7 +105,7 @@ class _StubPipe:
         return torch.cat([rgb, (frames[:, 3:4] * 255).to(torch.uint8)], 1)
 
 
-def _bench_worker(rank, world, port, q):
+def _bench_worker(rank, world, port, q, dump_dir=None):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -128,18 +129,18 @@ def _bench_worker(rank, world, port, q):
     # the same with two drawings in flight per rank (bench._inflight_loop: worker threads, the
     # collectives kept in one order by the main thread)
     args = bench.parse(["--gpus", str(world), "--config", "drawing", "--frames", "3", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--inflight", "2"])
+                        "--warmup", "1", "--no-cpu-baseline", "--inflight", "2", "--dump-outputs", dump_dir])
     out_i = bench.bench_drawing(args, ddist, r, w, dev, _StubTimer(), pipe=[pipe, _StubPipe(rank + 7)])
     ddist.barrier()
     q.put((rank, threads, out_f, want, out_d, out_i))
     torch.distributed.destroy_process_group()
 
 
-def test_bench_frames_and_drawing_paths_world2():
+def test_bench_frames_and_drawing_paths_world2(tmp_path):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_bench_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, 2, port, q, str(tmp_path / "dump"))) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=300) for _ in procs)
@@ -153,6 +154,14 @@ def test_bench_frames_and_drawing_paths_world2():
     assert abs(i0["value"] - 2 * 2 * 2 / (i0["ms_per_step"] * 2e-3)) < 1e-6 * i0["value"]
     assert i0["config"]["latency_s"]["drawings"] == 4 and "2 drawings in flight" in i0["config"]["workload"]
     assert i0["config"]["gathered_bytes_per_step"] == 2 * (12 * 3 * 16 * 16 * 2 + 3 * 4 * 512 * 512)
+    # --dump-outputs: the last step's two drawings, both ranks' views in full, the frames sampled
+    assert i0["dumped_outputs"]["views.npy"] == [2, 2, 12, 3, 16, 16]
+    assert i0["dumped_outputs"]["frames_channel_sums.npy"] == [2, 2, 3, 4]
+    from bench import MESH_SUMMARY_FIELDS
+    assert i0["dumped_outputs"]["mesh_summary.npy"] == [2, len(MESH_SUMMARY_FIELDS)]          # stubs: no mesh
+    assert not np.load(tmp_path / "dump" / "mesh_summary.npy").any()
+    v = np.load(tmp_path / "dump" / "views.npy")
+    assert v.dtype == np.float32 and float(np.abs(v[:, 0] - v[:, 1]).max()) > 0    # the ranks' own drawings
     cores = len(os.sched_getaffinity(0))
     assert th0 == th1 == max(1, cores // 2)                # the ranks split the host cores
     assert f1 is None and d1 is None                       # only rank 0 reports

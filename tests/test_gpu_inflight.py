@@ -51,7 +51,7 @@ def test_bench_drawing_with_two_drawings_in_flight(dev):
     import bench
     from drawingspinup_amd import dist as ddist
     args = bench.parse(["--config", "drawing", "--steps", "1", "--warmup", "1", "--mv-steps", "2", "--nsr-steps", "48",
-                        "--frames", "4", "--no-cpu-baseline", "--inflight", "2", "--inflight-skew", "0.2"])
+                        "--frames", "4", "--full", "--no-cpu-baseline", "--inflight", "2", "--inflight-skew", "0.2"])
     timer = bench.KernelTimer()
     timer.install()
     out = bench.bench_drawing(args, ddist, 0, 1, dev, timer)

@@ -5,7 +5,7 @@ export PYTHONPATH=$(pwd) TMPDIR=/tmp
 O=gpurun_out/${1:-r6_inflight}; mkdir -p $O
 run() {
   tag=$1; shift
-  timeout 900 python bench.py --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline "$@" 2>$O/bench_$tag.err | tail -1 > $O/bench_$tag.json
+  timeout 900 python bench.py --full --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline "$@" 2>$O/bench_$tag.err | tail -1 > $O/bench_$tag.json
   python - $O/bench_$tag.json "$tag $*" <<'P'
 import json, sys
 j = json.loads(open(sys.argv[1]).read())

@@ -10,7 +10,7 @@ timeout 200 python tools/nsr_modes_probe.py 6 3000 1 1 2>/dev/null | grep '^{' |
 echo "# high, one stream per driver" | tee -a $O/summary.txt
 timeout 200 python tools/nsr_modes_probe.py 6 3000 1 0 2>/dev/null | grep '^{' | tee -a $O/summary.txt
 run() { echo -n "$*: " | tee -a $O/summary.txt
-  timeout 900 python bench.py --steps 4 --warmup 1 --no-cpu-baseline "$@" 2>/dev/null | tail -1 > $O/last.json
+  timeout 900 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline "$@" 2>/dev/null | tail -1 > $O/last.json
   python -c "import json,sys; j=json.loads(open(sys.argv[1]).read()); c=j['config']; print('value %.4f' % j['value'], {k: round(v,2) for k,v in c['stage_seconds_rank0'].items() if k in ('mv','nsr_fit','nsr_export','style')}, [(r['kernel'], round(r['avg_launch_ms'],4)) for r in j['roofline']['alone'][:2]])" $O/last.json | tee -a $O/summary.txt; }
 for rep in 1 2; do
   run --side-priority 1 --side-pool 0
