@@ -1125,52 +1125,48 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
     part[v] = (red[v] + red[PART_STRIDE + v]) + (red[2 * PART_STRIDE + v] + red[3 * PART_STRIDE + v]);
 }
 
-// ------------------------------------------------------------ K1, lean / software-pipelined form
+// ------------------------------------------------------------ K1, lean form at two waves per SIMD
 // The MLP part of the split backward again, for the case the optimisation runs (NL = 10 levels,
-// features from the forward's cache, ACT active levels known at compile time), restructured around
-// what the counters of the general kernel above say (profiles/round5_pmc.json): ONE wave per SIMD
-// whose instruction stream alternates VALU phases (48 % of the wave cycles: Softplus, sigmoid, bf16
-// splits, register shuffles — 22 % of the VALU instructions were v_accvgpr moves of values parked
-// in AGPRs) and MFMA phases during which the wave only waits to issue the next MFMA (27 %).
+// features from the forward's cache, ACT active levels known at compile time).
 //   * The six OFFSET evaluations (e = 1..6) carry one upstream gradient (on the SDF output) instead
-//     of the centre's 13: their own straight-line body without the 13-wide output arrays, the
-//     feature-gradient rows, the dOut staging and the gW1 GEMM; the centre evaluation keeps a body
-//     of its own.  The live state of the loop that does 6/7 of the work shrinks by ~50 registers.
-//   * ACT is a template parameter: layer 0 walks ACT + 2 k-pairs without a branch per level (every
-//     MFMA sat in its own basic block), the cache rows are ACT wide.
-//   * Inside an offset evaluation the two point halves are software-pipelined: the matrix pipe's
-//     long phases run beside the OTHER half's VALU work —
-//         L0(half 1) MFMAs            ||  Softplus(half 0)
-//         gW0(half 0) MFMAs (32 x 64) ||  Softplus, dPre, sigmoid, bf16 split of half 1
-//         gW0(half 1) MFMAs           ||  dIn stores, column-0 sums of gW1
-//     The interleave is written out in the source — a piece of VALU work behind every MFMA (pair),
-//     fenced with __builtin_amdgcn_sched_barrier(0): left to itself the scheduler issues a phase's
-//     MFMAs back to back and the VALU work after them (sched_group_barrier patterns did not change
-//     that here), which at one wave per SIMD is the serial form again.  The next evaluation's
-//     inputs (cache row hand-over, positions, upstream gradient) are prepared beside the last phase.
-// Every value is produced by the same operations in the same order as in sdf_fd_bwd_mfma_kernel
-// <NL, true, true>, the tail sharing included.  tests/test_gpu_hashgrid.py compares it with the general
-// kernel's cache-less form (no tail sharing there): MLP gradients bit-identical where the ranges are
-// whole iterations, equal to float summation order elsewhere.
-// gW0 of the OFFSET evaluations as bf16 x 3 on v_mfma_f32_32x32x16_bf16 (K = 16 points per MFMA): ablating
-// its 64 f32 MFMAs per evaluation took 46 us off the kernel although they run beside the other half's
-// VALU work (profiles/round6_pipe_ablation.txt).  Operands staged TRANSPOSED per wave:
-//   dPre^T [hi|mid][64 units][PT_ROW] bf16 — the hi / mid fragments the dIn product splits anyway —,
-//   In'^T  [hi|mid][32 input columns][PT_ROW] (rows nobody writes stay zero for the launch),
+//     of the centre's 13: their own body without the 13-wide output arrays, the feature-gradient
+//     rows and the gW1 GEMM; the centre evaluation keeps a body of its own.
+//   * ACT is a template parameter: layer 0 walks ACT + 2 k-pairs without a branch per level.
+//   * Two waves per SIMD (at most 256 registers per lane, 77 KB of LDS per workgroup: two workgroups
+//     per CU, or one beside another kernel's).  The weight fragments every wave reads are staged once
+//     per workgroup in LDS in the layout the MFMAs read (one 16-byte fragment per lane) and loaded per
+//     use; only the parameter-gradient accumulators live in registers for the whole launch.  The two
+//     point halves of a wave run one after the other: the matrix pipe's phases of one wave run beside
+//     the VALU work of the other wave of the SIMD.  (Round 6 interleaved the halves by hand inside one
+//     458-register wave: one wave per SIMD and one workgroup per CU, nothing of another kernel beside
+//     it.)
+// Every value is produced by the same operations in the same order as before (g_b1 bit-identical to
+// sdf_fd_bwd_mfma_kernel<NL, true, true>, tests/test_gpu_hashgrid.py).
+// The contractions over the points (gW0, and gW1 of the centre) and dIn, dPre of the centre and layer 0
+// of the recompute (ACT <= 6: its 2 KPA inputs fit one 16-deep MFMA) run as bf16 x 3 on
+// v_mfma_f32_32x32x16_bf16.  Operands of the contractions staged TRANSPOSED per wave:
+//   dPre^T (or H^T) [hi|mid][64 units][PT_ROW] bf16 — the hi / mid fragments the dIn product splits anyway —,
+//   In'^T [hi|mid][32 input columns][PT_ROW] (rows nobody writes stay zero for the launch); the centre's
+//   dOut^T borrows rows 0..12 of the In' image for its gW1 contraction and puts the zero rows back,
 // PT_ROW = 40 (80-byte rows: the 16-byte fragments of 16 lanes fall on 16 different bank quads).
-// 12 MFMAs of 32 clocks per point half instead of 32 of 64.  (-DDSU_PIPE_GW0_F32: the f32 form, A/B.)
 constexpr int PT_ROW = 40;
 constexpr int PT_IMGD = 2 * 64 * PT_ROW, PT_IMGI = 2 * 32 * PT_ROW;      // bf16 elements
-constexpr int PT_IMGO = 2 * 32 * PT_ROW;                                  // dOut^T of the centre evaluation (gW1)
-#ifdef DSU_PIPE_GW0_F32
-constexpr int PIPE_IMG_F = 0;
-#else
-constexpr int PIPE_IMG_F = (PT_IMGD + PT_IMGI + PT_IMGO) / 2;             // floats per wave (5120)
-#endif
-constexpr int PIPE_LDS_F = W1P_F + 4 * STAGE_F + 4 * PIPE_IMG_F;
+constexpr int PIPE_IMG_F = (PT_IMGD + PT_IMGI) / 2;                      // floats per wave (3840)
+// shared weights (floats): layer 0 [T][hi|mid][lane] bf16x8 (<= 6 levels) or [T][k-pair][lane] f32 (7)
+// | W1^T [T][hi|mid][lane] bf16x8 | W0'^T [T][g][hi|mid][lane] bf16x8 | W1 row 0 [64]
+constexpr int PW_W0 = 0;
+constexpr int PW_W1T = PW_W0 + 2 * 9 * 64;
+constexpr int PW_W0T = PW_W1T + 2 * 2 * 64 * 4;
+constexpr int PW_W1O0 = PW_W0T + 2 * 2 * 2 * 64 * 4;
+constexpr int PW_F = PW_W1O0 + 64;
+constexpr int PIPE_LDS_F = PW_F + 4 * PIPE_IMG_F;
+static_assert(PIPE_LDS_F * sizeof(float) <= 80 * 1024, "two workgroups per CU");
+static_assert(4 * PART_STRIDE <= PIPE_LDS_F, "the workgroup reduction reuses the LDS");
+static_assert(PW_W1T % 4 == 0 && PW_W0T % 4 == 0 && PW_F % 4 == 0, "16-byte fragments");
 
+// (7 levels, f32 layer 0: two waves per SIMD would spill ~28 registers; that instantiation stays at one)
 template <int NL, int ACT>
-__global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 2 : 1))) void sdf_fd_bwd_pipe_kernel(
     dsu_sdf_mlp mlp, const float* __restrict__ pts, int64_t n, float radius, float eps, float eps2,
     const float* __restrict__ d_sdf, const float* __restrict__ d_grad,
     const float* __restrict__ d_feature, const float* __restrict__ d_laplace,
@@ -1178,131 +1174,130 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
     const int32_t* __restrict__ perm) {
   static_assert(ACT >= 1 && ACT <= NL && 2 * NL + 4 <= 32, "layout");
   constexpr int KPA = ACT + 2;             // k-pairs walked by layer 0: ACT levels, xyz, (z, 1)
-  constexpr int FG = (2 * ACT + 3) / 4;    // float4 groups of feature columns staged per point
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* w1perm = lds;
-  float* b1s = lds + 2 * NOUT * 32;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, h = lane >> 5;
-  float* sd = lds + W1P_F + wave * STAGE_F;
-  float* sin_ = sd + 32 * SD_ROW;
-  float* sdo = sin_ + 32 * SIN_ROW;
-
-  // the scatter kernel's work counter (behind the dIn buffer) starts every launch at zero
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    *reinterpret_cast<int*>(dinbuf + (size_t)7 * (size_t)n * NL) = 0;
-
-  // ---- weights.  k-pair tt of layer 0 is the permuted input pair t = tt (level tt) or NL + tt - ACT
-  float w0a[2][KPA];
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int tt = 0; tt < KPA; ++tt) {
-      const int t = tt < ACT ? tt : NL + (tt - ACT);
-      w0a[T][tt] = w0p<NL>(mlp, 32 * T + l31, 2 * t + h);
-    }
-  // Layer 0 of the recompute as bf16 x 3 when its 2 KPA inputs fit one 16-deep MFMA (ACT <= 6, the
-  // optimisation's schedule): an ablation priced the 2 x KPA f32 MFMAs per point half at 51 us of the kernel.
-  // A fragments: W0'[unit 32 T + l31][input 8 h + t] hi / mid (inputs in the order of `in`).
+  static_assert(KPA <= 9, "layer-0 weights fit their LDS slot");
+  // column of the accumulator tile that holds gW1[unit][o]: 24..31, then the masked levels' 2 ACT ..
+  auto gw1_col = [](int o) { return o < 8 ? 2 * NL + 4 + o : 2 * ACT + (o - 8); };
+  static_assert(2 * NL + 4 + 8 == 32 && 2 * ACT + NOUT - 8 <= 2 * NL, "gW1 columns free of inputs");
 #ifdef DSU_PIPE_L0_F32
   constexpr bool L0BF = false;
 #else
   constexpr bool L0BF = 2 * KPA <= 16;
 #endif
-  bf16x8 w0b_hi[2], w0b_mid[2];
-  if constexpr (L0BF) {
-#pragma unroll
-    for (int T = 0; T < 2; ++T) {
-      float w[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int j = 8 * h + t, tt = j >> 1;
-        const bool real = j < 2 * KPA;
-        const int t_ = tt < ACT ? tt : NL + (tt - ACT);
-        const float v = w0p<NL>(mlp, 32 * T + l31, real ? 2 * t_ + (j & 1) : 0);
-        w[t] = real ? v : 0.0f;
-      }
-      bf16_split8(w, w0b_hi[T], w0b_mid[T]);
-    }
-  }
-  // the centre evaluation's dPre = W1^T . dOut (13 upstream gradients per point) as bf16 x 3 as well:
-  // A fragments W1[o = 8 h + t][unit 32 T + l31] hi / mid (outputs 13..15: zero)
-#ifdef DSU_PIPE_DPRE_VALU
-  constexpr bool DPBF = false;
-#else
-  constexpr bool DPBF = true;
-#endif
-  bf16x8 w1t_hi[2], w1t_mid[2];
-  if constexpr (DPBF) {
-#pragma unroll
-    for (int T = 0; T < 2; ++T) {
-      float w[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int o = 8 * h + t;
-        const float v = mlp.w1[(o < NOUT ? o : 0) * 64 + 32 * T + l31];
-        w[t] = o < NOUT ? v : 0.0f;
-      }
-      bf16_split8(w, w1t_hi[T], w1t_mid[T]);
-    }
-  }
-  float w1o0[2][16];
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) w1o0[T][r] = mlp.w1[feat_of(T, r, h)];
-  bf16x8 w0t_hi[2][2], w0t_mid[2][2];
+  __shared__ __attribute__((aligned(16))) float lds[PIPE_LDS_F];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  // weight reads go through `wo` (always 0), made opaque to the compiler at every point half: it would
+  // otherwise hoist them out of the loops as invariants and keep them in registers (spilled at 256)
+  int wo = 0;
+  auto weights_per_use = [&]() {};
+  const bf16x8* wfrag = reinterpret_cast<const bf16x8*>(lds);
+  auto frag_of = [&](int float_off, int idx) { return wfrag[wo + float_off / 4 + idx * 64 + lane]; };
+
+  // the scatter kernel's work counter (behind the dIn buffer) starts every launch at zero
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    *reinterpret_cast<int*>(dinbuf + (size_t)7 * (size_t)n * NL) = 0;
+
+  // ---- weights -> LDS, one group per wave.  k-pair tt of layer 0 is the permuted input pair t = tt
+  // (level tt) or NL + tt - ACT
   {
-    float w0t[2][16];
+    bf16x8* wst = reinterpret_cast<bf16x8*>(lds);
+    if (wave == 0) {
+      if constexpr (L0BF) {
+        // A fragments: W0'[unit 32 T + l31][input 8 h + t] hi / mid (inputs in the order of `in`)
 #pragma unroll
-    for (int T = 0; T < 2; ++T)
+        for (int T = 0; T < 2; ++T) {
+          float w[8];
+#pragma unroll
+          for (int t = 0; t < 8; ++t) {
+            const int j = 8 * h + t, tt = j >> 1;
+            const bool real = j < 2 * KPA;
+            const int t_ = tt < ACT ? tt : NL + (tt - ACT);
+            const float v = w0p<NL>(mlp, 32 * T + l31, real ? 2 * t_ + (j & 1) : 0);
+            w[t] = real ? v : 0.0f;
+          }
+          bf16x8 hi, mid;
+          bf16_split8(w, hi, mid);
+          wst[PW_W0 / 4 + (2 * T + 0) * 64 + lane] = hi;
+          wst[PW_W0 / 4 + (2 * T + 1) * 64 + lane] = mid;
+        }
+      } else {
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+          for (int tt = 0; tt < KPA; ++tt) {
+            const int t = tt < ACT ? tt : NL + (tt - ACT);
+            lds[PW_W0 + (T * KPA + tt) * 64 + lane] = w0p<NL>(mlp, 32 * T + l31, 2 * t + h);
+          }
+      }
+    } else if (wave == 1) {
+      // the centre evaluation's dPre = W1^T . dOut: A fragments W1[o = 8 h + t][unit 32 T + l31] hi / mid
+      // (outputs 13..15: zero)
+#pragma unroll
+      for (int T = 0; T < 2; ++T) {
+        float w[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const int o = 8 * h + t;
+          const float v = mlp.w1[(o < NOUT ? o : 0) * 64 + 32 * T + l31];
+          w[t] = o < NOUT ? v : 0.0f;
+        }
+        bf16x8 hi, mid;
+        bf16_split8(w, hi, mid);
+        wst[PW_W1T / 4 + (2 * T + 0) * 64 + lane] = hi;
+        wst[PW_W1T / 4 + (2 * T + 1) * 64 + lane] = mid;
+      }
+      lds[PW_W1O0 + lane] = mlp.w1[lane];
+    } else {
+      // dIn = W0'^T . dPre: A fragments W0'[unit feat_of(T, 8 g + t, h)][input l31] hi / mid
+      const int T = wave - 2;
+      float w0t[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w0t[T][r] = l31 < MC<NL>::KIN ? w0p<NL>(mlp, feat_of(T, r, h), l31) : 0.0f;
+        w0t[r] = l31 < MC<NL>::KIN ? w0p<NL>(mlp, feat_of(T, r, h), l31) : 0.0f;
 #pragma unroll
-    for (int T = 0; T < 2; ++T)
-#pragma unroll
-      for (int g = 0; g < 2; ++g) bf16_split8(&w0t[T][8 * g], w0t_hi[T][g], w0t_mid[T][g]);
+      for (int g = 0; g < 2; ++g) {
+        bf16x8 hi, mid;
+        bf16_split8(&w0t[8 * g], hi, mid);
+        wst[PW_W0T / 4 + ((2 * T + g) * 2 + 0) * 64 + lane] = hi;
+        wst[PW_W0T / 4 + ((2 * T + g) * 2 + 1) * 64 + lane] = mid;
+      }
+    }
   }
-  load_w1perm(w1perm, b1s, mlp);
-  // In' and dOut rows: the columns nobody writes (masked levels, padding) stay zero for the launch
-  for (int t = lane; t < 2 * 32 * SIN_ROW; t += 64) sin_[t] = 0.0f;
-#ifndef DSU_PIPE_GW0_F32
-  __bf16* imgD = reinterpret_cast<__bf16*>(lds + W1P_F + 4 * STAGE_F + wave * PIPE_IMG_F);
+  __bf16* imgD = reinterpret_cast<__bf16*>(lds + PW_F + wave * PIPE_IMG_F);
   __bf16* imgI = imgD + PT_IMGD;
-  __bf16* imgO = imgI + PT_IMGI;
-  for (int t = lane; t < (PT_IMGI + PT_IMGO) / 2; t += 64) reinterpret_cast<uint32_t*>(imgI)[t] = 0u;
-#endif
+  for (int t = lane; t < PT_IMGI / 2; t += 64) reinterpret_cast<uint32_t*>(imgI)[t] = 0u;
   __syncthreads();
 
-  f32x16 gw0[2], gw1[2];
+  // ONE accumulator tile pair for both contractions over the points: gw0[Ti][unit][column] holds gW0 in
+  // the input columns of In' (features 0 .. 2 ACT - 1, (x, y, z, 1) at 2 NL ..) and gW1 of the centre in
+  // columns no input uses (gw1_col): each contraction's B image is zero in the other's columns
+  f32x16 gw0[2];
 #pragma unroll
   for (int T = 0; T < 2; ++T)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) gw0[T][r] = gw1[T][r] = 0.0f;
+    for (int r = 0; r < 16; ++r) gw0[T][r] = 0.0f;
   float gb1[NOUT];
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) gb1[o] = 0.0f;
-  float gw1c0[2][16];
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) gw1c0[T][r] = 0.0f;
 
   // ---- pieces shared by the two evaluation bodies
-  // B operands of layer 0 for both point halves from the lane's own inputs
-  auto l0_half = [&](const float (&b)[KPA], f32x16 (&acc)[2]) {
+  // layer 0 of one point half in f32 (7 levels): B operands from the lane's own inputs
+  auto l0_half = [&](const float (&in)[2 * KPA], int half, f32x16 (&acc)[2]) {
+    float b[KPA];                              // this half's B operands only (both: 18 more registers)
+#pragma unroll
+    for (int tt = 0; tt < KPA; ++tt) {
+      float b0, b1;
+      swap_halves(in[2 * tt], in[2 * tt + 1], b0, b1);
+      b[tt] = half ? b1 : b0;
+    }
 #pragma unroll
     for (int T = 0; T < 2; ++T) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[T][r] = 0.0f;
 #pragma unroll
       for (int tt = 0; tt < KPA; ++tt)
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 16)
-        acc[T][tt & 15] += w0a[T][tt] * b[tt];        // (timing ablation: no layer-0 MFMAs)
-#else
-        acc[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0a[T][tt], b[tt], acc[T], 0, 0, 0);
-#endif
+        acc[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[wo + PW_W0 + (T * KPA + tt) * 64 + lane], b[tt],
+                                                      acc[T], 0, 0, 0);
     }
   };
   // B fragments of layer 0 for both point halves from the lane's own inputs: packed bf16 hi / mid pairs,
@@ -1336,9 +1331,10 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
     for (int T = 0; T < 2; ++T) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[T][r] = 0.0f;
-      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0b_hi[T], bh, acc[T], 0, 0, 0);
-      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0b_hi[T], bm, acc[T], 0, 0, 0);
-      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0b_mid[T], bh, acc[T], 0, 0, 0);
+      const bf16x8 ah = frag_of(PW_W0, 2 * T), am = frag_of(PW_W0, 2 * T + 1);
+      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[T], 0, 0, 0);
+      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[T], 0, 0, 0);
+      acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[T], 0, 0, 0);
     }
   };
   auto softplus2 = [&](f32x16 (&acc)[2]) {
@@ -1347,108 +1343,8 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
 #pragma unroll
       for (int r = 0; r < 16; r += 2) softplus_inplace2(acc[T], r);
   };
-  // dPre -> sigmoid factor -> dIn MFMAs of one hidden tile (bf16 x 3, as in the general kernel)
-  auto din_tile = [&](int T, float (&dpre)[16], const f32x16& H, f32x16& din) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(H[r] * -144.26950408889634f);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      bf16x8 bh, bm;
-      bf16_split8(&dpre[8 * g], bh, bm);
-      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din, 0, 0, 0);
-      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din, 0, 0, 0);
-      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din, 0, 0, 0);
-    }
-  };
-  auto stage_rows = [&](float* dst, int T, const float* v /*16*/) {   // [point][hidden] rows
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd)
-      *reinterpret_cast<float4*>(&dst[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
-          make_float4(v[4 * qd], v[4 * qd + 1], v[4 * qd + 2], v[4 * qd + 3]);
-  };
-  auto stage_in = [&](const float (&in)[2 * KPA]) {                   // own-half lanes: In' row
-#pragma unroll
-    for (int g = 0; g < FG; ++g) {
-      float4 v;
-      v.x = in[4 * g];
-      v.y = in[4 * g + 1];
-      v.z = 4 * g + 2 < 2 * ACT ? in[(4 * g + 2) < 2 * ACT ? 4 * g + 2 : 0] : 0.0f;
-      v.w = 4 * g + 3 < 2 * ACT ? in[(4 * g + 3) < 2 * ACT ? 4 * g + 3 : 0] : 0.0f;
-      *reinterpret_cast<float4*>(&sin_[l31 * SIN_ROW + 4 * g]) = v;
-    }
-    *reinterpret_cast<float4*>(&sin_[l31 * SIN_ROW + 2 * NL]) =
-        make_float4(in[2 * ACT], in[2 * ACT + 1], in[2 * ACT + 2], in[2 * ACT + 3]);
-  };
-  // contraction over the 32 staged points: acc[T][feat][col] += rowsA[point][feat] * rowsB[point][col]
-  auto gemm_points = [&](f32x16 (&acc)[2], const float* rowsB) {
-    float q[2][12];
-    auto ld = [&](int tb, float* d) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pr = 2 * (4 * tb + u) + h;
-        d[3 * u + 0] = sd[pr * SD_ROW + l31];
-        d[3 * u + 1] = sd[pr * SD_ROW + 32 + l31];
-        d[3 * u + 2] = rowsB[pr * SIN_ROW + l31];
-      }
-    };
-    ld(0, q[0]);
-#pragma unroll
-    for (int tb = 0; tb < 4; ++tb) {
-      if (tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float* d = q[tb & 1] + 3 * u;
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], acc[1], 0, 0, 0);
-      }
-    }
-  };
-  // the same contraction with a piece of other work behind the two MFMAs of every point pair
-  // (filler(integral_constant<k>), k = 0..15), fenced so that the interleave stays as written: at
-  // one wave per SIMD an MFMA phase issued back to back is time the wave only waits for the pipe
-  auto gemm_points_with = [&](f32x16 (&acc)[2], const float* rowsB, auto&& filler) {
-    float q[2][12];
-    auto ld = [&](int tb, float* d) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pr = 2 * (4 * tb + u) + h;
-        d[3 * u + 0] = sd[pr * SD_ROW + l31];
-        d[3 * u + 1] = sd[pr * SD_ROW + 32 + l31];
-        d[3 * u + 2] = rowsB[pr * SIN_ROW + l31];
-      }
-    };
-    ld(0, q[0]);
-    auto step = [&](auto kc) {
-      constexpr int K = decltype(kc)::value;
-      constexpr int tb = K / 4, u = K % 4;
-      if (u == 0 && tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
-      const float* d = q[tb & 1] + 3 * u;
-#if !(defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 8))
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], acc[1], 0, 0, 0);
-#else
-      acc[0][K & 15] += d[0] * d[2];                 // (timing ablation: the staged operands stay live)
-      acc[1][K & 15] += d[1] * d[2];
-#endif
-      filler(kc);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    step(std::integral_constant<int, 0>{});  step(std::integral_constant<int, 1>{});
-    step(std::integral_constant<int, 2>{});  step(std::integral_constant<int, 3>{});
-    step(std::integral_constant<int, 4>{});  step(std::integral_constant<int, 5>{});
-    step(std::integral_constant<int, 6>{});  step(std::integral_constant<int, 7>{});
-    step(std::integral_constant<int, 8>{});  step(std::integral_constant<int, 9>{});
-    step(std::integral_constant<int, 10>{}); step(std::integral_constant<int, 11>{});
-    step(std::integral_constant<int, 12>{}); step(std::integral_constant<int, 13>{});
-    step(std::integral_constant<int, 14>{}); step(std::integral_constant<int, 15>{});
-  };
   auto store_din = [&](int e, const f32x16& din, int64_t pi, int64_t r1) {
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 2)
-    if (pi < r1 && din[0] == 12345.678f) {        // (timing ablation: no dIn stores)
-#else
     if (pi < r1) {
-#endif
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
         const int la = ((r & 3) + 8 * (r >> 2)) / 2;      // this register pair's level for h = 0
@@ -1459,10 +1355,9 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
       }
     }
   };
-
-#ifndef DSU_PIPE_GW0_F32
-  // hi / mid fragments of dPre (registers 8 g + t of tile T = units 32 T + (t & 3) + 8 (2 g + (t >> 2)) + 4 h
-  // of the point in column l31) -> the transposed image, two-byte stores at compile-time offsets
+  // dPre x sigmoid of hidden tile T -> dIn MFMAs (bf16 x 3) and the hi / mid fragments -> dPre^T image
+  // (registers 8 g + t of tile T = units 32 T + (t & 3) + 8 (2 g + (t >> 2)) + 4 h of the point in
+  // column l31; two-byte stores at compile-time offsets)
   auto stage_dpre_T = [&](int T, int g, const bf16x8& bh, const bf16x8& bm) {
     __bf16* base = imgD + 4 * h * PT_ROW + l31;
 #pragma unroll
@@ -1470,6 +1365,21 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
       const int u = 32 * T + (t & 3) + 8 * (2 * g + (t >> 2));
       base[u * PT_ROW] = bh[t];
       base[(64 + u) * PT_ROW] = bm[t];
+    }
+  };
+  auto din_tile = [&](int T, float (&dpre)[16], const f32x16& H, f32x16& din) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(H[r] * -144.26950408889634f);
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      bf16x8 bh, bm;
+      bf16_split8(&dpre[8 * g], bh, bm);
+      const bf16x8 ah = frag_of(PW_W0T, (2 * T + g) * 2), am = frag_of(PW_W0T, (2 * T + g) * 2 + 1);
+      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, din, 0, 0, 0);
+      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, din, 0, 0, 0);
+      din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, din, 0, 0, 0);
+      stage_dpre_T(T, g, bh, bm);
     }
   };
   // the lane's own inputs -> rows (input columns) of In'^T: features at their column, (x, y, z, 1) at 2 NL ..
@@ -1483,38 +1393,26 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
       base[(32 + row) * PT_ROW] = (__bf16)(in[j] - (float)hi);
     }
   };
-  // acc[Ti][unit][column] += dPre^T . In' over the 32 staged points; a quarter of the filler's 16 pieces
-  // behind each group of three MFMAs, fenced as in gemm_points_with
-  auto gemm_T_with = [&](f32x16 (&acc)[2], const __bf16* imgB, auto&& filler) {
+  // acc[Ti][unit][column] += imgD^T . imgB over the 32 staged points (bf16 x 3)
+  auto gemm_T = [&](f32x16 (&acc)[2], const __bf16* imgB) {
     auto frag = [&](const __bf16* img, int row, int ks) {
       return *reinterpret_cast<const bf16x8*>(img + row * PT_ROW + 16 * ks + 8 * h);
     };
-    auto step = [&](auto sc) {
-      constexpr int S = decltype(sc)::value;
-      constexpr int ks = S >> 1, Ti = S & 1;
+#pragma unroll
+    for (int S = 0; S < 4; ++S) {
+      const int ks = S >> 1, Ti = S & 1;
       const bf16x8 bh = frag(imgB, l31, ks), bm = frag(imgB + 32 * PT_ROW, l31, ks);
       const bf16x8 ah = frag(imgD, 32 * Ti + l31, ks), am = frag(imgD + 64 * PT_ROW, 32 * Ti + l31, ks);
       acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[Ti], 0, 0, 0);
       acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[Ti], 0, 0, 0);
       acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[Ti], 0, 0, 0);
-      filler(std::integral_constant<int, 4 * S + 0>{});
-      filler(std::integral_constant<int, 4 * S + 1>{});
-      filler(std::integral_constant<int, 4 * S + 2>{});
-      filler(std::integral_constant<int, 4 * S + 3>{});
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{});
-    step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 3>{});
+    }
   };
-#endif
+
   const int64_t per = ((n + gridDim.x - 1) / gridDim.x + 31) / 32 * 32;
   const int64_t r0 = blockIdx.x * per;
   const int64_t r1 = r0 + per < n ? r0 + per : n;
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 1)   // (timing ablation, variant build: prologue + epilogue only)
-  for (int64_t bbase = r1; bbase < r1; bbase += blockDim.x) {
-#else
   for (int64_t bbase = r0; bbase < r1; bbase += blockDim.x) {
-#endif
     // (the last, partial iteration of a range is shared by the waves as in the general kernel)
     int blk = wave, e_start = 0, e_step = 1;
     {
@@ -1575,9 +1473,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
     };
 
     int e = e_start;
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 32)
-    if (e == 0) { if (e + e_step < 7) handover(); e += e_step; }   // (timing ablation: no centre evaluation)
-#endif
     if (e == 0) {
       // ------------------------------------------------ centre evaluation: 13 upstream gradients
       float in[2 * KPA];
@@ -1594,101 +1489,42 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
       }
 #pragma unroll
       for (int o = 0; o < NOUT; ++o) gb1[o] += dout[o];
-      float b0[KPA], b1[KPA];
       bf16x8 cbh0, cbm0, cbh1, cbm1;
-      if constexpr (L0BF) {
+      if constexpr (L0BF)
         pack_operands(in, std::integral_constant<int, (2 * KPA <= 16 ? 2 * KPA : 16)>{}, cbh0, cbm0, cbh1, cbm1);
-      } else {
-#pragma unroll
-        for (int tt = 0; tt < KPA; ++tt) swap_halves(in[2 * tt], in[2 * tt + 1], b0[tt], b1[tt]);
-      }
       bf16x8 dbh0, dbm0, dbh1, dbm1;           // dOut of the column's point, both halves (B fragments)
-      if constexpr (DPBF) pack_operands(dout, std::integral_constant<int, NOUT>{}, dbh0, dbm0, dbh1, dbm1);
+      pack_operands(dout, std::integral_constant<int, NOUT>{}, dbh0, dbm0, dbh1, dbm1);
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         if (half == 1 && !live1) break;
-        float d[NOUT];
-        if constexpr (!DPBF) {
-#pragma unroll
-          for (int o = 0; o < NOUT; ++o) {
-            const float other = partner32(dout[o], h);
-            d[o] = (h == half) ? dout[o] : other;
-          }
-        }
+        weights_per_use();
         f32x16 Hh[2];
         if constexpr (L0BF) l0_bf(half ? cbh1 : cbh0, half ? cbm1 : cbm0, Hh);
-        else l0_half(half ? b1 : b0, Hh);
+        else l0_half(in, half, Hh);
         softplus2(Hh);
         f32x16 din;
 #pragma unroll
         for (int r = 0; r < 16; ++r) din[r] = 0.0f;
 #pragma unroll
         for (int T = 0; T < 2; ++T) {
+          f32x16 dacc;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dacc[r] = 0.0f;
+          const bf16x8 bh = half ? dbh1 : dbh0, bm = half ? dbm1 : dbm0;
+          const bf16x8 ah = frag_of(PW_W1T, 2 * T), am = frag_of(PW_W1T, 2 * T + 1);
+          dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, dacc, 0, 0, 0);
+          dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, dacc, 0, 0, 0);
+          dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, dacc, 0, 0, 0);
           float dpre[16];
-          if constexpr (DPBF) {
-            f32x16 dacc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dacc[r] = 0.0f;
-            const bf16x8 bh = half ? dbh1 : dbh0, bm = half ? dbm1 : dbm0;
-            dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1t_hi[T], bh, dacc, 0, 0, 0);
-            dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1t_hi[T], bm, dacc, 0, 0, 0);
-            dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1t_mid[T], bh, dacc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dpre[r] = dacc[r];
-          } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dpre[r] = w1o0[T][r] * d[0];
-          const float* wp = w1perm + h * NOUT * 32 + T * 16;
-#ifdef DSU_PIPE_CENTRE_UNROLL
-#pragma unroll DSU_PIPE_CENTRE_UNROLL
-#else
-#pragma unroll       // (fully unrolled: the 48 weight reads of a tile are in flight together: -2.4 us; by 3: +7 us)
-#endif
-          for (int o = 1; o < NOUT; ++o) {
-            const float4* w4 = reinterpret_cast<const float4*>(wp + o * 32);
-            const float dv = d[o];
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-              const float4 w = w4[qd];
-              dpre[4 * qd + 0] = fmaf(w.x, dv, dpre[4 * qd + 0]);
-              dpre[4 * qd + 1] = fmaf(w.y, dv, dpre[4 * qd + 1]);
-              dpre[4 * qd + 2] = fmaf(w.z, dv, dpre[4 * qd + 2]);
-              dpre[4 * qd + 3] = fmaf(w.w, dv, dpre[4 * qd + 3]);
-            }
-          }
-          }
-#ifdef DSU_PIPE_GW0_F32
+          for (int r = 0; r < 16; ++r) dpre[r] = dacc[r];
           din_tile(T, dpre, Hh[T], din);
-          stage_rows(sd, T, dpre);
-#else
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(Hh[T][r] * -144.26950408889634f);
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            bf16x8 bh, bm;
-            bf16_split8(&dpre[8 * g], bh, bm);
-            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din, 0, 0, 0);
-            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din, 0, 0, 0);
-            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din, 0, 0, 0);
-            stage_dpre_T(T, g, bh, bm);
-          }
-#endif
         }
-#ifndef DSU_PIPE_GW0_F32
-        // the centre's two contractions over the points as bf16 x 3 as well: gW0 from dPre^T / In'^T, then
-        // gW1[unit][o'] from the hidden activations (split here) and dOut^T (13 rows of a 32-row image)
-        if (h == half) {
-          stage_in_T(in);
-#pragma unroll
-          for (int o = 0; o < NOUT; ++o) {
-            const __bf16 hi = (__bf16)dout[o];
-            imgO[o * PT_ROW + l31] = hi;
-            imgO[(32 + o) * PT_ROW + l31] = (__bf16)(dout[o] - (float)hi);
-          }
-        }
+        // the centre's two contractions over the points: gW0 from dPre^T / In'^T, then gW1[unit][o']
+        // from the hidden activations (split here) and dOut^T (rows 0..12 of the In' image meanwhile)
+        if (h == half) stage_in_T(in);
         __builtin_amdgcn_wave_barrier();
-        gemm_T_with(gw0, imgI, [](auto) {});
+        gemm_T(gw0, imgI);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int T = 0; T < 2; ++T)
@@ -1701,47 +1537,50 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
             bf16_split8(hv, bh, bm);
             stage_dpre_T(T, g, bh, bm);
           }
-        __builtin_amdgcn_wave_barrier();
-        gemm_T_with(gw1, imgO, [](auto) {});
-        __builtin_amdgcn_wave_barrier();
-        store_din(0, din, wave_first + half * 32 + l31, r1);
-      }
-#else
-        if (h == half) {
-          stage_in(in);
+        if (h == half) {                       // In' rows -> 0, dOut^T into the gW1 rows
+          __bf16* base = imgI + l31;
 #pragma unroll
-          for (int o4 = 0; o4 < 4; ++o4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (4 * o4 + 0 < NOUT) v.x = dout[(4 * o4 + 0) < NOUT ? 4 * o4 + 0 : 0];
-            if (4 * o4 + 1 < NOUT) v.y = dout[(4 * o4 + 1) < NOUT ? 4 * o4 + 1 : 0];
-            if (4 * o4 + 2 < NOUT) v.z = dout[(4 * o4 + 2) < NOUT ? 4 * o4 + 2 : 0];
-            if (4 * o4 + 3 < NOUT) v.w = dout[(4 * o4 + 3) < NOUT ? 4 * o4 + 3 : 0];
-            *reinterpret_cast<float4*>(&sdo[l31 * SIN_ROW + 4 * o4]) = v;
+          for (int j = 0; j < 2 * KPA; ++j) {
+            const int row = j < 2 * ACT ? j : 2 * NL + (j - 2 * ACT);
+            base[row * PT_ROW] = (__bf16)0.0f;
+            base[(32 + row) * PT_ROW] = (__bf16)0.0f;
+          }
+          const float dl_ = valid ? dl : 0.0f;
+#pragma unroll
+          for (int o = 0; o < NOUT; ++o) {
+            // dOut again from the upstream gradients (the same operations: not kept live through the GEMMs)
+            float v = valid && d_feature ? d_feature[gi * NOUT + o] : 0.0f;
+            if (o == 0 && valid) v += ds - 6.0f * dl_ / eps2;
+            const __bf16 hi = (__bf16)v;
+            base[gw1_col(o) * PT_ROW] = hi;
+            base[(32 + gw1_col(o)) * PT_ROW] = (__bf16)(v - (float)hi);
           }
         }
         __builtin_amdgcn_wave_barrier();
-        gemm_points(gw0, sin_);
+        gemm_T(gw0, imgI);
         __builtin_amdgcn_wave_barrier();
-        // hidden activations of this half's points -> LDS, then gW1[feat][o'] += H^T . dOut
+        if (h == half) {                       // the gW1 rows back to zero
+          __bf16* base = imgI + l31;
 #pragma unroll
-        for (int T = 0; T < 2; ++T) {
-          float hv[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) hv[r] = Hh[T][r];
-          stage_rows(sd, T, hv);
+          for (int o = 0; o < NOUT; ++o) {
+            base[gw1_col(o) * PT_ROW] = (__bf16)0.0f;
+            base[(32 + gw1_col(o)) * PT_ROW] = (__bf16)0.0f;
+          }
         }
-        __builtin_amdgcn_wave_barrier();
-        gemm_points(gw1, sdo);
-        __builtin_amdgcn_wave_barrier();
         store_din(0, din, wave_first + half * 32 + l31, r1);
       }
-#endif
       if (e + e_step < 7) handover();
       e += e_step;
     }
     // ------------------------------------------------ offset evaluations: one upstream gradient
-    // loop-carried: the inputs and the upstream gradient of the evaluation about to run, prepared
-    // beside the previous evaluation's last MFMA phase
+    // gW1[unit][0] of the offsets per point column of the lane (summed into the tile behind the loop:
+    // not live through the centre evaluation)
+    float gw1c0[2][16];
+#pragma unroll
+    for (int T = 0; T < 2; ++T)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gw1c0[T][r] = 0.0f;
+    // loop-carried: the inputs and the upstream gradient of the evaluation about to run
     float in[2 * KPA];
     float dout0 = 0.0f;
     float q3[3] = {0.f, 0.f, 0.f};
@@ -1786,179 +1625,66 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
       const float other0 = partner32(dout0, h);
       const float d0h0 = h == 0 ? dout0 : other0;       // gradient of the point this lane column holds
       const float d0h1 = h == 1 ? dout0 : other0;       //   in half 0 / half 1
-      float b0[KPA], b1[KPA];
       bf16x8 obh0, obm0, obh1, obm1;
-      if constexpr (L0BF) {
+      if constexpr (L0BF)
         pack_operands(in, std::integral_constant<int, (2 * KPA <= 16 ? 2 * KPA : 16)>{}, obh0, obm0, obh1, obm1);
-      } else {
 #pragma unroll
-        for (int tt = 0; tt < KPA; ++tt) swap_halves(in[2 * tt], in[2 * tt + 1], b0[tt], b1[tt]);
-      }
-      f32x16 H0[2], H1[2], din0, din1;
-      float dp0[2][16], dp1[2][16];
-      // P1: layer 0 of half 0
-      if constexpr (L0BF) l0_bf(obh0, obm0, H0);
-      else l0_half(b0, H0);
-      __builtin_amdgcn_sched_barrier(0);
-      // P2: layer 0 of half 1  ||  Softplus of half 0 (+ its column-0 sums of gW1), a few hidden units
-      // behind every MFMA; the fences keep the interleave the source spells out
+      for (int half = 0; half < 2; ++half) {
+        if (half == 1 && !live1) break;
+        weights_per_use();
+        const float d0 = half ? d0h1 : d0h0;
+        f32x16 Hh[2];
+        if constexpr (L0BF) l0_bf(half ? obh1 : obh0, half ? obm1 : obm0, Hh);
+        else l0_half(in, half, Hh);
+        softplus2(Hh);
 #pragma unroll
-      for (int T = 0; T < 2; ++T)
+        for (int T = 0; T < 2; ++T)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) H1[T][r] = 0.0f;
-      if constexpr (L0BF) {
+          for (int r = 0; r < 16; ++r) gw1c0[T][r] = fmaf(Hh[T][r], d0, gw1c0[T][r]);
+        f32x16 din;
 #pragma unroll
-        for (int mi = 0; mi < 6; ++mi) {
-          constexpr int NM = 6;
-          const int T = mi / 3, term = mi % 3;
-          H1[T] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(term == 2 ? w0b_mid[T] : w0b_hi[T],
-                                                         term == 1 ? obm1 : obh1, H1[T], 0, 0, 0);
+        for (int r = 0; r < 16; ++r) din[r] = 0.0f;
 #pragma unroll
-          for (int v = 0; v < 32; v += 2)
-            if (v * NM / 32 == mi) {
-              softplus_inplace2(H0[v >> 4], v & 15);
-              gw1c0[v >> 4][v & 15] = fmaf(H0[v >> 4][v & 15], d0h0, gw1c0[v >> 4][v & 15]);
-              gw1c0[v >> 4][(v & 15) + 1] = fmaf(H0[v >> 4][(v & 15) + 1], d0h0, gw1c0[v >> 4][(v & 15) + 1]);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
+        for (int T = 0; T < 2; ++T) {
+          float dpre[16];
 #pragma unroll
-      for (int mi = 0; mi < 2 * KPA; ++mi) {
-        constexpr int NM = 2 * KPA;
-        const int T = mi / KPA, tt = mi % KPA;
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 16)
-        H1[T][tt & 15] += w0a[T][tt] * b1[tt];
-#else
-        H1[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0a[T][tt], b1[tt], H1[T], 0, 0, 0);
-#endif
-#pragma unroll
-        for (int v = 0; v < 32; v += 2)
-          if (v * NM / 32 == mi) {
-            softplus_inplace2(H0[v >> 4], v & 15);
-            gw1c0[v >> 4][v & 15] = fmaf(H0[v >> 4][v & 15], d0h0, gw1c0[v >> 4][v & 15]);
-            gw1c0[v >> 4][(v & 15) + 1] = fmaf(H0[v >> 4][(v & 15) + 1], d0h0, gw1c0[v >> 4][(v & 15) + 1]);
+          for (int q = 0; q < 4; ++q) {                 // W1[0][feat_of(T, 4 q + j, h)], j = 0..3
+            const float4 w = *reinterpret_cast<const float4*>(&lds[wo + PW_W1O0 + 32 * T + 8 * q + 4 * h]);
+            dpre[4 * q + 0] = w.x * d0;
+            dpre[4 * q + 1] = w.y * d0;
+            dpre[4 * q + 2] = w.z * d0;
+            dpre[4 * q + 3] = w.w * d0;
           }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      }
-      // P3: dPre / sigmoid / dIn of half 0, rows to LDS
-#pragma unroll
-      for (int r = 0; r < 16; ++r) din0[r] = 0.0f;
-#pragma unroll
-      for (int T = 0; T < 2; ++T) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dp0[T][r] = w1o0[T][r] * d0h0;
-#ifdef DSU_PIPE_GW0_F32
-        din_tile(T, dp0[T], H0[T], din0);
-        stage_rows(sd, T, dp0[T]);
-#else
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          dp0[T][r] *= 1.0f - __builtin_amdgcn_exp2f(H0[T][r] * -144.26950408889634f);
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          bf16x8 bh, bm;
-          bf16_split8(&dp0[T][8 * g], bh, bm);
-          din0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din0, 0, 0, 0);
-          din0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din0, 0, 0, 0);
-          din0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din0, 0, 0, 0);
-          stage_dpre_T(T, g, bh, bm);
+          din_tile(T, dpre, Hh[T], din);
         }
-#endif
+        if (h == half) stage_in_T(in);
+        __builtin_amdgcn_wave_barrier();
+        gemm_T(gw0, imgI);
+        __builtin_amdgcn_wave_barrier();
+        store_din(e, din, wave_first + half * 32 + l31, r1);
       }
-#ifdef DSU_PIPE_GW0_F32
-      if (h == 0) stage_in(in);
-#else
-      if (h == 0) stage_in_T(in);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      // P4: gW0 over half 0's points  ||  Softplus, column-0 sums, dPre x sigmoid of half 1: two
-      // hidden units behind the two MFMAs of every point pair
-#ifdef DSU_PIPE_GW0_F32
-      gemm_points_with(gw0, sin_, [&](auto kc) {
-#else
-      gemm_T_with(gw0, imgI, [&](auto kc) {
-#endif
-        constexpr int K = decltype(kc)::value;
-        softplus_inplace2(H1[(2 * K) >> 4], (2 * K) & 15);
-#pragma unroll
-        for (int v = 2 * K; v < 2 * K + 2; ++v) {
-          const int T = v >> 4, r = v & 15;
-          gw1c0[T][r] = fmaf(H1[T][r], d0h1, gw1c0[T][r]);
-          dp1[T][r] = (w1o0[T][r] * d0h1) *
-                      (1.0f - __builtin_amdgcn_exp2f(H1[T][r] * -144.26950408889634f));
-        }
-      });
-      // P5: dIn of half 1; half 0's dIn out; half 1's rows to LDS (behind the reads of P4)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) din1[r] = 0.0f;
-#pragma unroll
-      for (int T = 0; T < 2; ++T)
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          bf16x8 bh, bm;
-          bf16_split8(&dp1[T][8 * g], bh, bm);
-          din1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din1, 0, 0, 0);
-          din1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din1, 0, 0, 0);
-          din1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din1, 0, 0, 0);
-#ifndef DSU_PIPE_GW0_F32
-          if (live1) stage_dpre_T(T, g, bh, bm);          // (behind P4's reads of the image: in-order LDS queue)
-#endif
-        }
-      store_din(e, din0, wave_first + l31, r1);
-      const int en = e + e_step < 7 ? e + e_step : 6;    // next evaluation (clamped: unused at the end)
-      if (live1) {
-#ifdef DSU_PIPE_GW0_F32
-#pragma unroll
-        for (int T = 0; T < 2; ++T) stage_rows(sd, T, dp1[T]);
-        if (h == 1) stage_in(in);
-#else
-        if (h == 1) stage_in_T(in);
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-        // P6: gW0 over half 1's points  ||  half 1's dIn out, the next evaluation's inputs
-#ifdef DSU_PIPE_GW0_F32
-        gemm_points_with(gw0, sin_, [&](auto kc) {
-#else
-        gemm_T_with(gw0, imgI, [&](auto kc) {
-#endif
-          constexpr int K = decltype(kc)::value;
-          if (K == 1) store_din(e, din1, wave_first + 32 + l31, r1);
-          if (K == 3) {
-#pragma unroll
-            for (int l = 0; l < ACT; ++l) {
-              vm_take(rwn[l]);
-              rw[l] = rwn[l];
-            }
-          }
-          if (K == 5) prep_unpack();
-          if (K == 7) prep_point(en);
-          if (K == 9) prep_request(en);
-          if (K == 11) prep_dout(en);
-        });
-      } else {
-#pragma unroll
-        for (int l = 0; l < ACT; ++l) {
-          vm_take(rwn[l]);
-          rw[l] = rwn[l];
-        }
-        prep_unpack();
-        prep_point(en);
-        prep_request(en);
-        prep_dout(en);
-      }
+      // the next evaluation's inputs (clamped: unused at the end)
+      const int en = e + e_step < 7 ? e + e_step : 6;
+      handover();
+      prep_unpack();
+      prep_point(en);
+      prep_request(en);
+      prep_dout(en);
     }
+#pragma unroll
+    for (int T = 0; T < 2; ++T)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float c0 = gw1c0[T][r];                      // sum over the 32 point columns of this half
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) c0 += __shfl_xor(c0, off);
+        if (l31 == gw1_col(0)) gw0[T][r] += c0;
+      }
   }
 
-#if defined(DSU_PIPE_ABL) && (DSU_PIPE_ABL & 4)
-  partials[(size_t)blockIdx.x * PART_STRIDE + threadIdx.x] =      // (timing ablation: no reduction)
-      gw0[0][0] + gw0[1][1] + gw1[0][2] + gw1[1][3] + gw1c0[0][4] + gw1c0[1][5] + gb1[0];
-  return;
-#endif
   // ---- workgroup reduction of the parameter-gradient tiles -> one partial vector per workgroup
   __syncthreads();
-  float* red = lds + W1P_F;                     // [4 waves][PART_STRIDE] (fits: 4*4160 floats)
+  float* red = lds;                             // [4 waves][PART_STRIDE] over the weights and images
   {
     float* rr = red + wave * PART_STRIDE;
 #pragma unroll
@@ -1966,11 +1692,11 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int feat = feat_of(T, r, h);
-        float c0 = gw1c0[T][r];                      // sum over the 32 point columns of this half
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) c0 += __shfl_xor(c0, off);
-        rr[PART_GW0 + feat * 32 + l31] = gw0[T][r];
-        rr[PART_GW1 + feat * 32 + l31] = gw1[T][r] + (l31 == 0 ? c0 : 0.0f);
+        const bool input = l31 < 2 * ACT || (l31 >= 2 * NL && l31 < 2 * NL + 4);
+        rr[PART_GW0 + feat * 32 + l31] = input ? gw0[T][r] : 0.0f;
+        const int o = l31 >= 2 * NL + 4 ? l31 - (2 * NL + 4) : (l31 >= 2 * ACT && l31 < 2 * ACT + NOUT - 8 ? l31 - 2 * ACT + 8 : -1);
+        if (o >= 0) rr[PART_GW1 + feat * 32 + o] = gw0[T][r];
+        if (l31 >= NOUT) rr[PART_GW1 + feat * 32 + l31] = 0.0f;
       }
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) gb1[o] += __shfl_xor(gb1[o], 32);
@@ -1990,34 +1716,25 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_pipe_kernel(
 }
 
 template <int NL, int ACT>
-bool launch_bwd_pipe_one(uint32_t active, int blocks, size_t shm, hipStream_t s, const dsu_sdf_mlp& mlp,
+bool launch_bwd_pipe_one(uint32_t active, int blocks, hipStream_t s, const dsu_sdf_mlp& mlp,
                          const float* pts, int64_t n, float radius, float eps, float eps2,
                          const float* d_sdf, const float* d_grad, const float* d_feature,
                          const float* d_laplace, float* partials, const __half2* enc, float2* dinbuf,
                          const int32_t* perm) {
   if ((int)active != ACT) return false;
-  static bool lds_ok = false;
-  if (!lds_ok) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sdf_fd_bwd_pipe_kernel<NL, ACT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(PIPE_LDS_F * sizeof(float))) != hipSuccess)
-      return false;
-    lds_ok = true;
-  }
-  (void)shm;
-  sdf_fd_bwd_pipe_kernel<NL, ACT><<<dim3(blocks), dim3(256), PIPE_LDS_F * sizeof(float), s>>>(
+  sdf_fd_bwd_pipe_kernel<NL, ACT><<<dim3(blocks), dim3(256), 0, s>>>(
       mlp, pts, n, radius, eps, eps2, d_sdf, d_grad, d_feature, d_laplace, partials, enc, dinbuf, perm);
   return true;
 }
 
 template <int NL>
-bool launch_bwd_pipe(uint32_t active, int blocks, size_t shm, hipStream_t s, const dsu_sdf_mlp& mlp,
+bool launch_bwd_pipe(uint32_t active, int blocks, hipStream_t s, const dsu_sdf_mlp& mlp,
                      const float* pts, int64_t n, float radius, float eps, float eps2,
                      const float* d_sdf, const float* d_grad, const float* d_feature,
                      const float* d_laplace, float* partials, const __half2* enc, float2* dinbuf,
                      const int32_t* perm) {
 #define DSU_PIPE_TRY(A)                                                                          \
-  if (launch_bwd_pipe_one<NL, A>(active, blocks, shm, s, mlp, pts, n, radius, eps, eps2, d_sdf,   \
+  if (launch_bwd_pipe_one<NL, A>(active, blocks, s, mlp, pts, n, radius, eps, eps2, d_sdf,       \
                                  d_grad, d_feature, d_laplace, partials, enc, dinbuf, perm))      \
     return true;
   DSU_PIPE_TRY(4) DSU_PIPE_TRY(5) DSU_PIPE_TRY(6) DSU_PIPE_TRY(7)
@@ -2540,9 +2257,9 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
 }
 
 #ifndef DSU_BWD_MFMA_MAX_BLOCKS
-#define DSU_BWD_MFMA_MAX_BLOCKS 256
+#define DSU_BWD_MFMA_MAX_BLOCKS 512
 #endif
-constexpr int BWD_MFMA_MAX_BLOCKS = DSU_BWD_MFMA_MAX_BLOCKS;   // one workgroup per CU (458 registers: one wave per SIMD)
+constexpr int BWD_MFMA_MAX_BLOCKS = DSU_BWD_MFMA_MAX_BLOCKS;   // two workgroups per CU (the pipelined form: <= 256 registers, 77 KB)
 
 }  // namespace
 
@@ -2744,7 +2461,7 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
   if (!workspace || workspace_bytes < need) return DSU_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const float eps2 = (float)((double)eps * (double)eps);
-  // (the workspace is sized for one workgroup per CU; dsu_set_onewave_grid_cap may launch fewer)
+  // (the workspace is sized for two workgroups per CU; dsu_set_onewave_grid_cap may launch fewer)
   const int blocks = dsu_onewave_blocks(n, 256, BWD_MFMA_MAX_BLOCKS);
   const int ablate = dsu_ab_int("DSU_BWD_ABLATE", 0);
   if (bwd_split()) {
@@ -2771,7 +2488,7 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
         static int use_pipe = -1;
         if (use_pipe < 0) use_pipe = dsu_ab_int("DSU_BWD_PIPE", 1) != 0;
         if (use_pipe && enc_cache && ablate == 0)
-          piped = launch_bwd_pipe<NL>(active_levels, blocks, shm1, s, *mlp, pts, n, radius, eps, eps2,
+          piped = launch_bwd_pipe<NL>(active_levels, blocks, s, *mlp, pts, n, radius, eps, eps2,
                                       d_sdf, d_grad, d_feature, d_laplace, (float*)workspace,
                                       (const __half2*)enc_cache, dinbuf, perm);
       }
@@ -2780,7 +2497,7 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
             (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, d_sdf,
             d_grad, d_feature, d_laplace, grad_table, (float*)workspace, (const __half2*)enc_cache,
             dinbuf, perm, ablate);
-      // the MLP part holds every SIMD with one 458-register wave; what a caller wants to run
+      // the MLP part fills every SIMD with two 256-register waves; what a caller wants to run
       // beside the rest of the backward (two 96-register waves per SIMD) waits for this event
       if (mid_event && hipEventRecord((hipEvent_t)mid_event, s) != hipSuccess) return DSU_ELAUNCH;
       // same-cell run merge (DPP segmented sums over 16 lanes) only where neighbouring lanes of the
