@@ -70,37 +70,6 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(GridMeta m, int nl,
 }
 
 // ---------------------------------------------------------------- fused SDF network
-// LDS image of the MLP parameters (all f32):
-//   w0t [DIN][64]  (transposed so the 64 hidden units of one input are contiguous)
-//   b0  [64]
-//   w1  [13][64]
-//   b1  [16]
-template <int NL>
-struct MlpLds {
-  static constexpr int DIN = 3 + 2 * NL;
-  static constexpr int W0T = 0;
-  static constexpr int B0 = DIN * HID;
-  static constexpr int W1 = B0 + HID;
-  static constexpr int B1 = W1 + NOUT * HID;
-  static constexpr int TOTAL = B1 + 16;
-};
-
-template <int NL>
-__device__ __forceinline__ void load_mlp_to_lds(float* lds, const float* __restrict__ w0,
-                                                const float* __restrict__ b0,
-                                                const float* __restrict__ w1,
-                                                const float* __restrict__ b1) {
-  using L = MlpLds<NL>;
-  for (int t = threadIdx.x; t < L::DIN * HID; t += blockDim.x) {
-    int k = t / HID, j = t % HID;
-    lds[L::W0T + t] = w0[j * L::DIN + k];
-  }
-  for (int t = threadIdx.x; t < HID; t += blockDim.x) lds[L::B0 + t] = b0[t];
-  for (int t = threadIdx.x; t < NOUT * HID; t += blockDim.x) lds[L::W1 + t] = w1[t];
-  for (int t = threadIdx.x; t < 16; t += blockDim.x) lds[L::B1 + t] = t < NOUT ? b1[t] : 0.0f;
-  __syncthreads();
-}
-
 // Encode one contracted point into the MLP input vector (xyz*2-1, masked features).
 template <int NL, int LMAX = NL>
 __device__ __forceinline__ void encode_input(const __half2* __restrict__ table,
@@ -118,97 +87,16 @@ __device__ __forceinline__ void encode_input(const __half2* __restrict__ table,
   }
 }
 
-// hidden pre-activations: pre[j] = b0[j] + sum_k w0[j][k]*in[k], k < kmax
-template <int NL>
-__device__ __forceinline__ void layer0(const float* lds, const float* in, int kmax, float* pre) {
-  using L = MlpLds<NL>;
-  const float4* b4 = reinterpret_cast<const float4*>(lds + L::B0);
-#pragma unroll
-  for (int j4 = 0; j4 < HID / 4; ++j4) {
-    float4 b = b4[j4];
-    pre[4 * j4 + 0] = b.x;
-    pre[4 * j4 + 1] = b.y;
-    pre[4 * j4 + 2] = b.z;
-    pre[4 * j4 + 3] = b.w;
-  }
-#pragma unroll
-  for (int k = 0; k < L::DIN; ++k) {
-    if (k < kmax) {
-      const float4* w4 = reinterpret_cast<const float4*>(lds + L::W0T + k * HID);
-      const float v = in[k];
-#pragma unroll
-      for (int j4 = 0; j4 < HID / 4; ++j4) {
-        float4 w = w4[j4];  // wave-uniform address: LDS broadcast read
-        pre[4 * j4 + 0] = fmaf(w.x, v, pre[4 * j4 + 0]);
-        pre[4 * j4 + 1] = fmaf(w.y, v, pre[4 * j4 + 1]);
-        pre[4 * j4 + 2] = fmaf(w.z, v, pre[4 * j4 + 2]);
-        pre[4 * j4 + 3] = fmaf(w.w, v, pre[4 * j4 + 3]);
-      }
-    }
-  }
-}
-
-template <int NL>
-__device__ __forceinline__ float layer1_row(const float* lds, const float* h, int o) {
-  using L = MlpLds<NL>;
-  const float4* w4 = reinterpret_cast<const float4*>(lds + L::W1 + o * HID);
-  float acc = lds[L::B1 + o];
-#pragma unroll
-  for (int j4 = 0; j4 < HID / 4; ++j4) {
-    float4 w = w4[j4];
-    acc = fmaf(w.x, h[4 * j4 + 0], acc);
-    acc = fmaf(w.y, h[4 * j4 + 1], acc);
-    acc = fmaf(w.z, h[4 * j4 + 2], acc);
-    acc = fmaf(w.w, h[4 * j4 + 3], acc);
-  }
-  return acc;
-}
-
-// Both layers streamed over groups of four hidden units: pre-activation (same k-ascending fma
-// chain as layer0), Softplus, then the group's contribution to each of the NO outputs (same
-// j-ascending fma chain as layer1_row) — bit-identical results, but the 64 hidden activations
-// never exist at once (199 -> ~90 VGPRs: twice the resident waves to hide the table gathers).
-template <int NL, int NO, int LMAX = NL>
-__device__ __forceinline__ void mlp_stream(const float* lds, const float* in, int kmax,
-                                           float* out /*NO*/) {
-  using L = MlpLds<NL>;
-#pragma unroll
-  for (int o = 0; o < NO; ++o) out[o] = lds[L::B1 + o];
-  const float4* b4 = reinterpret_cast<const float4*>(lds + L::B0);
-#pragma unroll 2
-  for (int j4 = 0; j4 < HID / 4; ++j4) {
-    const float4 b = b4[j4];
-    float p0 = b.x, p1 = b.y, p2 = b.z, p3 = b.w;
-#pragma unroll
-    for (int k = 0; k < 3 + 2 * LMAX; ++k) {
-      if (k < kmax) {
-        const float4 w = reinterpret_cast<const float4*>(lds + L::W0T + k * HID)[j4];
-        const float v = in[k];
-        p0 = fmaf(w.x, v, p0);
-        p1 = fmaf(w.y, v, p1);
-        p2 = fmaf(w.z, v, p2);
-        p3 = fmaf(w.w, v, p3);
-      }
-    }
-    p0 = softplus100(p0); p1 = softplus100(p1); p2 = softplus100(p2); p3 = softplus100(p3);
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-      const float4 w = reinterpret_cast<const float4*>(lds + L::W1 + o * HID)[j4];
-      float acc = out[o];
-      acc = fmaf(w.x, p0, acc);
-      acc = fmaf(w.y, p1, acc);
-      acc = fmaf(w.z, p2, acc);
-      acc = fmaf(w.w, p3, acc);
-      out[o] = acc;
-    }
-  }
-}
-
-// Same chains with the weights read through the SCALAR cache (constant address space, uniform
+// Both layers streamed over groups of four hidden units: pre-activation (k-ascending fma chain),
+// Softplus, then the group's contribution to each of the NO outputs (j-ascending fma chain), so
+// that the 64 hidden activations never exist at once (199 -> ~90 VGPRs: twice the resident waves
+// to hide the table gathers).
+// The weights are read through the SCALAR cache (constant address space, uniform
 // addresses -> s_load into SGPR operands of the FMAs) instead of LDS broadcasts: a wave-wide
 // ds_read_b128 occupies the CU's one LDS port for 8 clocks whether or not the lanes share the
 // address, 368 of them per evaluation made the LDS port, shared by the four SIMDs, the kernel's
-// bottleneck (-DDSU_FWD_SGPR_W).
+// bottleneck (measured on MI355X, 262 144 ray-ordered samples: forward 0.225 -> 0.173 ms at 4
+// levels, 0.309 -> 0.236 ms at 7; 77 instead of 135-156 VGPRs, no LDS at all).
 typedef __attribute__((address_space(4))) const float cfloat_t;
 __device__ __forceinline__ const cfloat_t* as_const(const float* p) {
   return (const cfloat_t*)(uintptr_t)p;
@@ -250,35 +138,11 @@ __device__ __forceinline__ void mlp_stream_sgpr(const dsu_sdf_mlp& mlp, const fl
   }
 }
 
-// default: scalar-cache weights (measured on MI355X, 262 144 ray-ordered samples: forward 0.225 ->
-// 0.173 ms at 4 levels, 0.309 -> 0.236 ms at 7; 77 instead of 135-156 VGPRs, no LDS at all).
-// -DDSU_FWD_LDS_W keeps the LDS-broadcast form for A/B runs.
-#ifndef DSU_FWD_LDS_W
-#define DSU_MLP_STREAM(NLv, NOv, LMAXv, lds, mlp, in, kmax, out) \
-  mlp_stream_sgpr<NLv, NOv, LMAXv>(mlp, in, kmax, out)
-#define DSU_FWD_LOAD_MLP(NLv, lds, mlp)
-#define DSU_FWD_LDS_BYTES(NLv) ((size_t)0)
-// no LDS, no barrier: any workgroup size works; one-wave workgroups (-DDSU_FWD_THREADS=64, finer
-// balance of n / 64 waves over the SIMDs) measured no faster than 256 (0.1945 vs 0.187 ms)
-#ifndef DSU_FWD_THREADS
-#define DSU_FWD_THREADS 256
-#endif
-#else
-#define DSU_MLP_STREAM(NLv, NOv, LMAXv, lds, mlp, in, kmax, out) \
-  mlp_stream<NLv, NOv, LMAXv>(lds, in, kmax, out)
-#define DSU_FWD_LOAD_MLP(NLv, lds, mlp) load_mlp_to_lds<NLv>(lds, mlp.w0, mlp.b0, mlp.w1, mlp.b1)
-#define DSU_FWD_LDS_BYTES(NLv) (MlpLds<NLv>::TOTAL * sizeof(float))
-#define DSU_FWD_THREADS 256
-#endif
-
+// no LDS, no barrier: any workgroup size works; one-wave workgroups (64 threads, finer balance of
+// n / 64 waves over the SIMDs) measured no faster than 256 (0.1945 vs 0.187 ms)
+constexpr int FWD_THREADS = 256;
 // hidden units per group of the level-outer forward (scalar weight registers: JB x (DIN + 14))
-#ifndef DSU_FWD_JB
-#define DSU_FWD_JB 2
-#endif
-// 1: the forward's offset evaluations in packed-f32 pairs (0: one evaluation per instruction, rounds 5-6a)
-#ifndef DSU_FWD_PK
-#define DSU_FWD_PK 1
-#endif
+constexpr int FWD_JB = 2;
 
 // points of the export's lattice formed in the kernel (dsu_sdf_fwd_lattice): x-slabs from x0
 struct SdfLattice {
@@ -293,9 +157,6 @@ __global__ __launch_bounds__(256) void sdf_fwd_kernel(const __half2* __restrict_
                                                       const float* __restrict__ pts, int64_t n,
                                                       float radius, uint32_t active,
                                                       float* __restrict__ out, SdfLattice lat) {
-  using L = MlpLds<NL>;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  DSU_FWD_LOAD_MLP(NL, lds, mlp);
   const int kmax = 3 + 2 * (int)active;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -312,10 +173,10 @@ __global__ __launch_bounds__(256) void sdf_fwd_kernel(const __half2* __restrict_
     float x = contract(px, radius);
     float y = contract(py, radius);
     float z = contract(pz, radius);
-    float in[L::DIN];
+    float in[3 + 2 * NL];
     encode_input<NL>(table, m, active, x, y, z, in);
     float o_[NO];
-    DSU_MLP_STREAM(NL, NO, NL, lds, mlp, in, kmax, o_);
+    mlp_stream_sgpr<NL, NO, NL>(mlp, in, kmax, o_);
 #pragma unroll
     for (int o = 0; o < NO; ++o) out[i * NO + o] = o_[o];
   }
@@ -331,9 +192,6 @@ __global__ __launch_bounds__(256) void sdf_fd_fwd_kernel(
     uint32_t active, float* __restrict__ sdf, float* __restrict__ grad,
     float* __restrict__ feature, float* __restrict__ laplace, __half2* __restrict__ enc,
     const int32_t* __restrict__ perm) {
-  using L = MlpLds<NL>;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  DSU_FWD_LOAD_MLP(NL, lds, mlp);
   const int kmax = 3 + 2 * (int)active;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -356,7 +214,7 @@ __global__ __launch_bounds__(256) void sdf_fd_fwd_kernel(
           q[a] = fminf(fmaxf(v, -radius), radius);
         }
       }
-      float in[L::DIN];
+      float in[3 + 2 * NL];
       encode_input<NL, LMAX>(table, m, active, contract(q[0], radius), contract(q[1], radius),
                              contract(q[2], radius), in);
       if (enc != nullptr) {
@@ -367,27 +225,15 @@ __global__ __launch_bounds__(256) void sdf_fd_fwd_kernel(
         for (int l = 0; l < LMAX; ++l)
           if ((uint32_t)l < active) row[l] = __floats2half2_rn(in[3 + 2 * l], in[3 + 2 * l + 1]);
       }
-#if defined(DSU_FWD_ABLATE) && (DSU_FWD_ABLATE & 1)
-      if (true) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3 + 2 * LMAX; ++k) acc += k < kmax ? in[k] : 0.0f;
-        s[e] = acc;
-        if (e == 0 && feature != nullptr) {
-#pragma unroll
-          for (int o = 0; o < NOUT; ++o) feature[oi * NOUT + o] = acc;
-        }
-      } else
-#endif
       if (e == 0 && feature != nullptr) {
         float o_[NOUT];
-        DSU_MLP_STREAM(NL, NOUT, LMAX, lds, mlp, in, kmax, o_);
+        mlp_stream_sgpr<NL, NOUT, LMAX>(mlp, in, kmax, o_);
         s[0] = o_[0];
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) feature[oi * NOUT + o] = o_[o];
       } else {
         float o_[1];
-        DSU_MLP_STREAM(NL, 1, LMAX, lds, mlp, in, kmax, o_);
+        mlp_stream_sgpr<NL, 1, LMAX>(mlp, in, kmax, o_);
         s[e] = o_[0];
       }
     }
@@ -432,7 +278,7 @@ __global__ __launch_bounds__(256) void sdf_fd_fwd_kernel(
 // Then the MLP with the hidden units outer and the 7 evaluations inner: one set of scalar weight
 // loads serves 7 evaluations; the interpolated features stay packed f16 in registers and enter
 // the f32 FMAs through the mixed-precision form (widening is exact), the FMA chains (k ascending
-// for the pre-activations, j ascending for the outputs) are those of mlp_stream.
+// for the pre-activations, j ascending for the outputs) are those of mlp_stream_sgpr.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ __half2 interp8(const float (&fr)[3], const __half2* v) {
   __half2 acc = __float2half2_rn(0.0f);
@@ -449,24 +295,13 @@ __device__ __forceinline__ __half2 interp8(const float (&fr)[3], const __half2* 
   return acc;
 }
 
-// probe builds (tools/fwd_phase_probe.py): DSU_FWD_ABLATE bit 0 = no MLP, bit 1 = no table traffic
-#if defined(DSU_FWD_ABLATE) && (DSU_FWD_ABLATE & 2)
-__device__ __forceinline__ __half2 fwd_fake_load(uint32_t idx) {
-  uint32_t b = (idx & 0x03FF03FFu) | 0x20002000u;
-  return *reinterpret_cast<__half2*>(&b);
-}
-#define DSU_FWD_LOAD(lvl, idx) fwd_fake_load(idx)
-#else
-#define DSU_FWD_LOAD(lvl, idx) (lvl)[idx]
-#endif
-
 // One level of the 7 evaluations of a regular point, as function templates so that the level
 // index is a constant in every instance (a `#pragma unroll`ed loop over levels with this body is
 // refused by the optimizer beyond a size limit, and f[][l] then lives in scratch).
 // What one level keeps between issuing its requests and interpolating: the centre's fractions, the
 // six offsets' fraction / cell step along their axis, the centre's corners, the new faces.
-// (plain arrays with constant indices, two slots; a struct passed down by reference ended up in
-// scratch memory)
+// (plain arrays with constant indices; a struct passed down by reference ended up in scratch
+// memory)
 struct FdLevelState {
   float (&fc)[3];
   float (&fa)[6];
@@ -507,7 +342,7 @@ __device__ __forceinline__ void fd_level_issue(const __half2* __restrict__ table
   };
 #pragma unroll
   for (int c = 0; c < 8; ++c)
-    st.v[c] = DSU_FWD_LOAD(lvl, index(term[0][c & 1], term[1][(c >> 1) & 1], term[2][(c >> 2) & 1]));
+    st.v[c] = lvl[index(term[0][c & 1], term[1][(c >> 1) & 1], term[2][(c >> 2) & 1])];
 #pragma unroll
   for (int t = 0; t < 6; ++t) {
     const int ax = t >> 1, a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
@@ -525,7 +360,7 @@ __device__ __forceinline__ void fd_level_issue(const __half2* __restrict__ table
         tt[ax] = tn;
         tt[a1] = term[a1][k & 1];
         tt[a2] = term[a2][k >> 1];
-        st.g[t][k] = DSU_FWD_LOAD(lvl, index(tt[0], tt[1], tt[2]));
+        st.g[t][k] = lvl[index(tt[0], tt[1], tt[2])];
       }
     }
   }
@@ -561,39 +396,26 @@ __device__ __forceinline__ void fd_level_finish(const FdLevelState& st, __half2 
   }
 }
 
-// requests of level l + 1 go out before level l is interpolated (DSU_FWD_PIPE=1, two level states
-// alive) or after it (0)
-#ifndef DSU_FWD_PIPE
-#define DSU_FWD_PIPE 0
-#endif
-
+// Level by level: the requests of level l + 1 go out after level l is interpolated (issuing them
+// before, with two level states alive, lost its A/B).
 template <int ACT, int ND, int... Ls>
 __device__ __forceinline__ void fd_levels(const __half2* __restrict__ table, const GridMeta& m,
                                           const float (&q)[7][3], __half2 (&f)[7][ACT], bool& bad,
                                           std::integer_sequence<int, Ls...>) {
-  float fc[2][3], fa[2][6];
-  int rel[2][6];
-  __half2 v[2][8], g[2][6][4];
+  float fc[3], fa[6];
+  int rel[6];
+  __half2 v[8], g[6][4];
   auto issue = [&](auto lc) {
     constexpr int l = decltype(lc)::value;
-    if constexpr (l < ACT) {
-      constexpr int sl = DSU_FWD_PIPE ? (l & 1) : 0;
-      FdLevelState st{fc[sl], fa[sl], rel[sl], v[sl], g[sl]};
-      fd_level_issue<l, ND>(table, m, q, st, bad);
-    }
+    FdLevelState st{fc, fa, rel, v, g};
+    fd_level_issue<l, ND>(table, m, q, st, bad);
   };
   auto finish = [&](auto lc) {
     constexpr int l = decltype(lc)::value;
-    constexpr int sl = DSU_FWD_PIPE ? (l & 1) : 0;
-    const FdLevelState st{fc[sl], fa[sl], rel[sl], v[sl], g[sl]};
+    const FdLevelState st{fc, fa, rel, v, g};
     fd_level_finish<l, ACT>(st, f);
   };
-#if DSU_FWD_PIPE
-  issue(std::integral_constant<int, 0>{});
-  ((issue(std::integral_constant<int, Ls + 1>{}), finish(std::integral_constant<int, Ls>{})), ...);
-#else
   ((issue(std::integral_constant<int, Ls>{}), finish(std::integral_constant<int, Ls>{})), ...);
-#endif
 }
 
 // One irregular point evaluated by a whole wave: same lookups (lookup_level), same FMA chains (k
@@ -675,12 +497,10 @@ __device__ __forceinline__ void fd_point_by_wave(
 }
 
 // waves per SIMD the register allocation aims at: 4 (128 VGPRs) up to 4 active levels, 3 (168) beyond
-#ifndef DSU_FWD_WAVES
-#define DSU_FWD_WAVES (ACT <= 4 ? 4 : 3)
-#endif
+constexpr int fwd_waves(int act) { return act <= 4 ? 4 : 3; }
 
 template <int NL, int ACT, int ND, bool FEAT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSU_FWD_WAVES, DSU_FWD_WAVES)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fwd_waves(ACT), fwd_waves(ACT))))
 void sdf_fd_fwd_shared_kernel(
     const __half2* __restrict__ table, GridMeta m, dsu_sdf_mlp mlp,
     const float* __restrict__ pts, int64_t n, float radius, float eps, float eps2,
@@ -691,7 +511,7 @@ void sdf_fd_fwd_shared_kernel(
   const cfloat_t* b0 = as_const(mlp.b0);
   const cfloat_t* w1 = as_const(mlp.w1);
   const cfloat_t* b1 = as_const(mlp.b1);
-  __shared__ float fix_lds[DSU_FWD_THREADS / 64][7 * (3 + 2 * ACT) + 7 * HID];
+  __shared__ float fix_lds[FWD_THREADS / 64][7 * (3 + 2 * ACT) + 7 * HID];
   // the wave iterates together: an irregular point is redone by all its lanes (fd_point_by_wave)
   for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < n;
        base += (int64_t)gridDim.x * blockDim.x) {
@@ -737,7 +557,6 @@ void sdf_fd_fwd_shared_kernel(
       }
     }
     // ---- MLP: groups of hidden units outer, evaluations inner
-#if DSU_FWD_PK
     // The six offset evaluations as three (+eps, -eps) pairs in packed-f32 arithmetic (v_pk_fma_f32 /
     // v_pk_mul_f32 / v_pk_add_f32: two IEEE operations per lane and issue slot, the scalar weight
     // broadcast to both halves): the same operations in the same order per evaluation (k ascending
@@ -772,11 +591,11 @@ void sdf_fd_fwd_shared_kernel(
 #pragma unroll
     for (int t = 0; t < 3; ++t) sp[t] = splat2(b1[0]);
 #pragma unroll 1
-    for (int j = 0; j < HID; j += DSU_FWD_JB) {
+    for (int j = 0; j < HID; j += FWD_JB) {
       {
-        float h[DSU_FWD_JB];
+        float h[FWD_JB];
 #pragma unroll
-        for (int r = 0; r < DSU_FWD_JB; ++r) {
+        for (int r = 0; r < FWD_JB; ++r) {
           float acc = b0[j + r];
 #pragma unroll
           for (int k = 0; k < KIN; ++k) acc = fmaf(w0[(j + r) * DIN + k], in0[k], acc);
@@ -785,13 +604,13 @@ void sdf_fd_fwd_shared_kernel(
 #pragma unroll
         for (int o = 0; o < NO0; ++o)
 #pragma unroll
-          for (int r = 0; r < DSU_FWD_JB; ++r) o0[o] = fmaf(w1[o * HID + j + r], h[r], o0[o]);
+          for (int r = 0; r < FWD_JB; ++r) o0[o] = fmaf(w1[o * HID + j + r], h[r], o0[o]);
       }
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        f32x2 h[DSU_FWD_JB];
+        f32x2 h[FWD_JB];
 #pragma unroll
-        for (int r = 0; r < DSU_FWD_JB; ++r) {
+        for (int r = 0; r < FWD_JB; ++r) {
           f32x2 acc = splat2(b0[j + r]);
 #pragma unroll
           for (int k = 0; k < KIN; ++k)
@@ -799,7 +618,7 @@ void sdf_fd_fwd_shared_kernel(
           h[r] = softplus100_pair(acc);
         }
 #pragma unroll
-        for (int r = 0; r < DSU_FWD_JB; ++r)
+        for (int r = 0; r < FWD_JB; ++r)
           sp[t] = __builtin_elementwise_fma(splat2(w1[j + r]), h[r], sp[t]);
       }
     }
@@ -808,58 +627,6 @@ void sdf_fd_fwd_shared_kernel(
       s[2 * t + 1] = sp[t].x;
       s[2 * t + 2] = sp[t].y;
     }
-#else
-    float xin[7][3];
-#pragma unroll
-    for (int e = 0; e < 7; ++e)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) xin[e][a] = q[e][a] * 2.0f + -1.0f;
-    constexpr int NO0 = FEAT ? NOUT : 1;
-    float o0[NO0], s[7];
-#pragma unroll
-    for (int o = 0; o < NO0; ++o) o0[o] = b1[o];
-#pragma unroll
-    for (int e = 1; e < 7; ++e) s[e] = b1[0];
-#if defined(DSU_FWD_ABLATE) && (DSU_FWD_ABLATE & 1)
-#pragma unroll
-    for (int e = 1; e < 7; ++e)
-#pragma unroll
-      for (int l = 0; l < ACT; ++l) s[e] += __low2float(f[e][l]) + __high2float(f[e][l]) + xin[e][l % 3];
-#pragma unroll
-    for (int l = 0; l < ACT; ++l) o0[0] += __low2float(f[0][l]) + __high2float(f[0][l]) + xin[0][l % 3];
-#pragma unroll 1
-    for (int j = HID; j < HID; j += DSU_FWD_JB) {
-#else
-#pragma unroll 1
-    for (int j = 0; j < HID; j += DSU_FWD_JB) {
-#endif
-#pragma unroll
-      for (int e = 0; e < 7; ++e) {
-        float h[DSU_FWD_JB];
-#pragma unroll
-        for (int r = 0; r < DSU_FWD_JB; ++r) {
-          float acc = b0[j + r];
-#pragma unroll
-          for (int a = 0; a < 3; ++a) acc = fmaf(w0[(j + r) * DIN + a], xin[e][a], acc);
-#pragma unroll
-          for (int l = 0; l < ACT; ++l) {
-            acc = fmaf(w0[(j + r) * DIN + 3 + 2 * l], __low2float(f[e][l]), acc);
-            acc = fmaf(w0[(j + r) * DIN + 4 + 2 * l], __high2float(f[e][l]), acc);
-          }
-          h[r] = softplus100(acc);
-        }
-        if (e == 0) {
-#pragma unroll
-          for (int o = 0; o < NO0; ++o)
-#pragma unroll
-            for (int r = 0; r < DSU_FWD_JB; ++r) o0[o] = fmaf(w1[o * HID + j + r], h[r], o0[o]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < DSU_FWD_JB; ++r) s[e] = fmaf(w1[j + r], h[r], s[e]);
-        }
-      }
-    }
-#endif
     s[0] = o0[0];
     if (regular) {
       if (FEAT) {
@@ -893,12 +660,8 @@ void sdf_fd_fwd_shared_kernel(
   }
 }
 
-#ifndef DSU_FWD_SHARED_LO
-#define DSU_FWD_SHARED_LO 4
-#endif
-#ifndef DSU_FWD_SHARED_HI
-#define DSU_FWD_SHARED_HI 7
-#endif
+// active-level counts the level-outer kernel is instantiated for
+constexpr int FWD_SHARED_LO = 4, FWD_SHARED_HI = 7;
 
 template <int... Ks>
 void fd_shared_launch(uint32_t active, bool feat, int blocks, hipStream_t s, const __half2* table,
@@ -918,328 +681,17 @@ void fd_shared_launch(uint32_t active, bool feat, int blocks, hipStream_t s, con
     if (res + res * res + res * res * res >= 2 * hsize) return;
   }
   auto one = [&](auto act_c) {
-    constexpr int ACT = DSU_FWD_SHARED_LO + decltype(act_c)::value;
+    constexpr int ACT = FWD_SHARED_LO + decltype(act_c)::value;
     if ((int)active != ACT) return;
     if (feat)
-      sdf_fd_fwd_shared_kernel<10, ACT, ND, true><<<dim3(blocks), dim3(DSU_FWD_THREADS), 0, s>>>(
+      sdf_fd_fwd_shared_kernel<10, ACT, ND, true><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           table, m, mlp, pts, n, radius, eps, eps2, sdf, grad, feature, laplace, enc, perm);
     else
-      sdf_fd_fwd_shared_kernel<10, ACT, ND, false><<<dim3(blocks), dim3(DSU_FWD_THREADS), 0, s>>>(
+      sdf_fd_fwd_shared_kernel<10, ACT, ND, false><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           table, m, mlp, pts, n, radius, eps, eps2, sdf, grad, feature, laplace, enc, perm);
     launched = true;
   };
   (one(std::integral_constant<int, Ks>{}), ...);
-}
-
-// LDS carve-up of the backward kernel (floats): MLP image | 4 per-wave staging areas | cache
-template <int NL>
-struct BwdLds {
-  static constexpr int DIN = 3 + 2 * NL;
-  static constexpr int PB = 8;
-  static constexpr int DINP = (DIN + 3) & ~3;
-  static constexpr int DOP = 16;
-  static constexpr int STAGE = PB * 65 * 2 + PB * DINP + PB * DOP;
-  static constexpr int RED = 4 * (DIN + 1 + NOUT + 1) * 64;
-  static constexpr int CACHE_OFF = MlpLds<NL>::TOTAL + 4 * STAGE;
-  static constexpr int CACHE = 3 * GC_SLOTS;
-  // the final block reduction reuses staging + cache space
-  static constexpr int EXTRA = (4 * STAGE + CACHE) > RED ? (4 * STAGE + CACHE) : RED;
-  static constexpr int TOTAL = MlpLds<NL>::TOTAL + EXTRA;
-};
-
-template <int NL>
-struct PartialLayout {
-  static constexpr int DIN = 3 + 2 * NL;
-  static constexpr int W0 = 0;
-  static constexpr int B0 = HID * DIN;
-  static constexpr int W1 = B0 + HID;
-  static constexpr int B1 = W1 + NOUT * HID;
-  static constexpr int USED = B1 + NOUT;
-  static constexpr int STRIDE = (USED + 63) & ~63;
-};
-
-// Backward of the 7-evaluation forward.  One point per lane; the per-wave outer products
-// for the MLP parameter gradients go through LDS so that lane j owns row j of g_w0 / column
-// j of g_w1 in registers for the whole grid-stride loop (no per-point atomics on the MLP).
-template <int NL>
-__global__ __launch_bounds__(256) void sdf_fd_bwd_kernel(
-    const __half2* __restrict__ table, GridMeta m, dsu_sdf_mlp mlp,
-    const float* __restrict__ pts, int64_t n, float radius, float eps, float eps2,
-    uint32_t active, const float* __restrict__ d_sdf, const float* __restrict__ d_grad,
-    const float* __restrict__ d_feature, const float* __restrict__ d_laplace,
-    float* __restrict__ gtable, float* __restrict__ partials) {
-  using L = MlpLds<NL>;
-  constexpr int DIN = L::DIN;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  load_mlp_to_lds<NL>(lds, mlp.w0, mlp.b0, mlp.w1, mlp.b1);
-  // per-wave staging area behind the parameters, holding PB points at a time:
-  //   dpre[PB][65], h[PB][65], in[PB][DIN+1], dout[PB][NOUT+1]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  constexpr int PB = BwdLds<NL>::PB;
-  constexpr int DINP = BwdLds<NL>::DINP;   // rows padded so they can be read back as float4
-  constexpr int DOP = BwdLds<NL>::DOP;
-  constexpr int STAGE = BwdLds<NL>::STAGE;
-  float* stage = lds + L::TOTAL + wave * STAGE;
-  // workgroup-private gradient cache (open addressing, <=3 probes, overflow -> global atomic):
-  // the 7x8 corner contributions of neighbouring samples of a ray hit the same few hundred
-  // table entries, so they are summed with LDS atomics and each touched entry costs ONE
-  // global atomic pair per workgroup pass instead of one per contribution.
-  uint32_t* c_keys = reinterpret_cast<uint32_t*>(lds + BwdLds<NL>::CACHE_OFF);
-  float* c_vals = lds + BwdLds<NL>::CACHE_OFF + GC_SLOTS;
-  for (int t = threadIdx.x; t < GC_SLOTS; t += blockDim.x) {
-    c_keys[t] = GC_EMPTY;
-    c_vals[2 * t] = 0.0f;
-    c_vals[2 * t + 1] = 0.0f;
-  }
-  __syncthreads();
-  float* s_dpre = stage;
-  float* s_h = s_dpre + PB * 65;
-  float* s_in = s_h + PB * 65;
-  float* s_do = s_in + PB * DINP;
-
-  const int kmax = 3 + 2 * (int)active;
-  float acc_w0[DIN];  // lane j: g_w0[j][:]
-  float acc_w1[NOUT]; // lane j: g_w1[:][j]
-  float acc_b0 = 0.0f;
-  float acc_b1 = 0.0f;  // lane o < NOUT: g_b1[o]
-#pragma unroll
-  for (int k = 0; k < DIN; ++k) acc_w0[k] = 0.0f;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc_w1[o] = 0.0f;
-
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  // the whole workgroup iterates together (inactive lanes contribute zeros)
-  for (int64_t bbase = blockIdx.x * (int64_t)blockDim.x; bbase < n; bbase += stride) {
-    const int64_t i = bbase + threadIdx.x;
-    const bool valid = i < n;
-    float p[3] = {0.f, 0.f, 0.f};
-    float ds = 0.f, dl = 0.f, dg[3] = {0.f, 0.f, 0.f};
-    if (valid) {
-      p[0] = pts[i * 3 + 0];
-      p[1] = pts[i * 3 + 1];
-      p[2] = pts[i * 3 + 2];
-      if (d_sdf) ds = d_sdf[i];
-      if (d_laplace) dl = d_laplace[i];
-      if (d_grad) {
-        dg[0] = d_grad[i * 3 + 0];
-        dg[1] = d_grad[i * 3 + 1];
-        dg[2] = d_grad[i * 3 + 2];
-      }
-    }
-#pragma unroll 1
-    for (int e = 0; e < 7; ++e) {
-      float q[3] = {p[0], p[1], p[2]};
-      if (e > 0) {
-        const int ax = (e - 1) >> 1;
-        const float d = ((e - 1) & 1) ? -eps : eps;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          float v = q[a] + (a == ax ? d : 0.0f);
-          q[a] = fminf(fmaxf(v, -radius), radius);
-        }
-      }
-      const float cx = contract(q[0], radius), cy = contract(q[1], radius),
-                  cz = contract(q[2], radius);
-      float in[DIN];
-      encode_input<NL>(table, m, active, cx, cy, cz, in);
-      float pre[HID];
-      layer0<NL>(lds, in, kmax, pre);
-      // upstream gradient on the 13 outputs of this evaluation
-      float dout[NOUT];
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) dout[o] = 0.0f;
-      if (valid) {
-        if (e == 0) {
-          if (d_feature) {
-#pragma unroll
-            for (int o = 0; o < NOUT; ++o) dout[o] = d_feature[i * NOUT + o];
-          }
-          dout[0] += ds - 6.0f * dl / eps2;
-        } else {
-          const int ax = (e - 1) >> 1;
-          const float sgn = ((e - 1) & 1) ? -1.0f : 1.0f;
-          dout[0] = sgn * 0.5f * dg[ax] / eps + dl / eps2;
-        }
-      }
-      // d_h = W1^T dout ; d_pre = d_h * softplus'(pre) ; h = softplus(pre)
-      float dpre[HID];
-#pragma unroll
-      for (int j = 0; j < HID; ++j) dpre[j] = 0.0f;
-      const int no = (e == 0) ? NOUT : 1;
-      for (int o = 0; o < no; ++o) {
-        const float4* w4 = reinterpret_cast<const float4*>(lds + L::W1 + o * HID);
-        const float dv = dout[o];
-#pragma unroll
-        for (int j4 = 0; j4 < HID / 4; ++j4) {
-          float4 w = w4[j4];
-          dpre[4 * j4 + 0] = fmaf(w.x, dv, dpre[4 * j4 + 0]);
-          dpre[4 * j4 + 1] = fmaf(w.y, dv, dpre[4 * j4 + 1]);
-          dpre[4 * j4 + 2] = fmaf(w.z, dv, dpre[4 * j4 + 2]);
-          dpre[4 * j4 + 3] = fmaf(w.w, dv, dpre[4 * j4 + 3]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < HID; ++j) {
-        dpre[j] *= softplus100_grad(pre[j]);
-        pre[j] = softplus100(pre[j]);  // pre now holds h
-      }
-
-      // d_in[k] = sum_j w0[j][k] dpre[j]  for feature inputs only, then scatter to the table
-      {
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-          if ((uint32_t)l < active) {
-            float d0 = 0.f, d1 = 0.f;
-            const float4* wa = reinterpret_cast<const float4*>(lds + L::W0T + (3 + 2 * l) * HID);
-            const float4* wb = reinterpret_cast<const float4*>(lds + L::W0T + (4 + 2 * l) * HID);
-#pragma unroll
-            for (int j4 = 0; j4 < HID / 4; ++j4) {
-              float4 a = wa[j4], b = wb[j4];
-              d0 = fmaf(a.x, dpre[4 * j4 + 0], d0);
-              d0 = fmaf(a.y, dpre[4 * j4 + 1], d0);
-              d0 = fmaf(a.z, dpre[4 * j4 + 2], d0);
-              d0 = fmaf(a.w, dpre[4 * j4 + 3], d0);
-              d1 = fmaf(b.x, dpre[4 * j4 + 0], d1);
-              d1 = fmaf(b.y, dpre[4 * j4 + 1], d1);
-              d1 = fmaf(b.z, dpre[4 * j4 + 2], d1);
-              d1 = fmaf(b.w, dpre[4 * j4 + 3], d1);
-            }
-            if (valid && (d0 != 0.0f || d1 != 0.0f)) {
-              const uint32_t hsize = m.off[l + 1] - m.off[l];
-              CellPos cp = cell_of(m.scale[l], cx, cy, cz);
-#pragma unroll
-              for (int c = 0; c < 8; ++c) {
-                uint32_t idx = grid_index(m.hashed[l], hsize, m.res[l], cp.c[0] + (c & 1),
-                                          cp.c[1] + ((c >> 1) & 1), cp.c[2] + ((c >> 2) & 1));
-                float w = corner_weight(cp, c);
-                grad_cache_add(c_keys, c_vals, gtable, m.off[l] + idx, w * d0, w * d1);
-              }
-            }
-          }
-        }
-      }
-      // wave-local outer products, PB points at a time (wave-synchronous: the LDS ops of
-      // one wave execute in order, the barriers only pin the compiler's schedule)
-#pragma unroll 1
-      for (int q = 0; q < 64 / PB; ++q) {
-        __builtin_amdgcn_wave_barrier();
-        if ((lane / PB) == q) {
-          const int r = lane % PB;
-#pragma unroll
-          for (int j = 0; j < HID; ++j) {
-            s_dpre[r * 65 + j] = dpre[j];
-            s_h[r * 65 + j] = pre[j];
-          }
-#pragma unroll
-          for (int k = 0; k < DINP; ++k) s_in[r * DINP + k] = k < DIN ? in[k] : 0.0f;
-#pragma unroll
-          for (int o = 0; o < DOP; ++o) s_do[r * DOP + o] = o < NOUT ? dout[o] : 0.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int pnt = 0; pnt < PB; ++pnt) {
-          const float dp = s_dpre[pnt * 65 + lane];
-          acc_b0 += dp;
-          const float4* in4 = reinterpret_cast<const float4*>(s_in + pnt * DINP);
-#pragma unroll
-          for (int k4 = 0; k4 < DINP / 4; ++k4) {
-            if (4 * k4 < kmax) {
-              const float4 v = in4[k4];   // wave-uniform address: broadcast
-              acc_w0[4 * k4 + 0] = fmaf(dp, v.x, acc_w0[4 * k4 + 0]);
-              if (4 * k4 + 1 < DIN) acc_w0[4 * k4 + 1] = fmaf(dp, v.y, acc_w0[4 * k4 + 1]);
-              if (4 * k4 + 2 < DIN) acc_w0[4 * k4 + 2] = fmaf(dp, v.z, acc_w0[4 * k4 + 2]);
-              if (4 * k4 + 3 < DIN) acc_w0[4 * k4 + 3] = fmaf(dp, v.w, acc_w0[4 * k4 + 3]);
-            }
-          }
-          const float hh = s_h[pnt * 65 + lane];
-          const float4* do4 = reinterpret_cast<const float4*>(s_do + pnt * DOP);
-          if (e == 0) {
-#pragma unroll
-            for (int o4 = 0; o4 < 4; ++o4) {
-              const float4 v = do4[o4];
-              acc_w1[4 * o4 + 0] = fmaf(v.x, hh, acc_w1[4 * o4 + 0]);
-              if (4 * o4 + 1 < NOUT) acc_w1[4 * o4 + 1] = fmaf(v.y, hh, acc_w1[4 * o4 + 1]);
-              if (4 * o4 + 2 < NOUT) acc_w1[4 * o4 + 2] = fmaf(v.z, hh, acc_w1[4 * o4 + 2]);
-              if (4 * o4 + 3 < NOUT) acc_w1[4 * o4 + 3] = fmaf(v.w, hh, acc_w1[4 * o4 + 3]);
-            }
-            if (lane < NOUT) acc_b1 += s_do[pnt * DOP + lane];
-          } else {
-            const float d0v = s_do[pnt * DOP];
-            acc_w1[0] = fmaf(d0v, hh, acc_w1[0]);
-            if (lane == 0) acc_b1 += d0v;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    // flush the gradient cache: one global atomic pair per touched entry, then reset
-    __syncthreads();
-    for (int t = threadIdx.x; t < GC_SLOTS; t += blockDim.x) {
-      const uint32_t key = c_keys[t];
-      if (key != GC_EMPTY) {
-        unsafeAtomicAdd(gtable + (size_t)key * 2, c_vals[2 * t]);
-        unsafeAtomicAdd(gtable + (size_t)key * 2 + 1, c_vals[2 * t + 1]);
-        c_keys[t] = GC_EMPTY;
-        c_vals[2 * t] = 0.0f;
-        c_vals[2 * t + 1] = 0.0f;
-      }
-    }
-    __syncthreads();
-  }
-  // block-level reduction of the per-lane parameter-gradient accumulators through LDS, then
-  // ONE plain-store partial vector per workgroup (summed by reduce_partials_kernel): no
-  // same-address atomics on the 2.4k MLP gradient words.
-  constexpr int NQ = DIN + 1 + NOUT + 1;
-  __syncthreads();
-  float* red = lds + L::TOTAL;  // [4 waves][NQ][64], fits in the 4 staging areas
-  {
-    float* r = red + wave * NQ * 64;
-#pragma unroll
-    for (int k = 0; k < DIN; ++k) r[k * 64 + lane] = acc_w0[k];
-    r[DIN * 64 + lane] = acc_b0;
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) r[(DIN + 1 + o) * 64 + lane] = acc_w1[o];
-    r[(DIN + 1 + NOUT) * 64 + lane] = acc_b1;
-  }
-  __syncthreads();
-  float* part = partials + (size_t)blockIdx.x * PartialLayout<NL>::STRIDE;
-  for (int v = threadIdx.x; v < NQ * 64; v += blockDim.x) {
-    const float sum = (red[v] + red[NQ * 64 + v]) + (red[2 * NQ * 64 + v] + red[3 * NQ * 64 + v]);
-    const int q = v >> 6, ln = v & 63;
-    int dst;
-    if (q < DIN) dst = PartialLayout<NL>::W0 + ln * DIN + q;
-    else if (q == DIN) dst = PartialLayout<NL>::B0 + ln;
-    else if (q < DIN + 1 + NOUT) dst = PartialLayout<NL>::W1 + (q - DIN - 1) * HID + ln;
-    else dst = ln < NOUT ? PartialLayout<NL>::B1 + ln : -1;
-    if (dst >= 0) part[dst] = sum;
-  }
-}
-
-template <int NL>
-__global__ void reduce_partials_kernel(const float* __restrict__ partials, int nblocks,
-                                       float* __restrict__ g_w0, float* __restrict__ g_b0,
-                                       float* __restrict__ g_w1, float* __restrict__ g_b1) {
-  using P = PartialLayout<NL>;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P::USED) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int b = 0;
-  for (; b + 3 < nblocks; b += 4) {
-    s0 += partials[(size_t)b * P::STRIDE + i];
-    s1 += partials[(size_t)(b + 1) * P::STRIDE + i];
-    s2 += partials[(size_t)(b + 2) * P::STRIDE + i];
-    s3 += partials[(size_t)(b + 3) * P::STRIDE + i];
-  }
-  for (; b < nblocks; ++b) s0 += partials[(size_t)b * P::STRIDE + i];
-  const float s = (s0 + s1) + (s2 + s3);
-  if (i < P::B0) g_w0[i] += s;
-  else if (i < P::W1) g_b0[i - P::B0] += s;
-  else if (i < P::B1) g_w1[i - P::W1] += s;
-  else g_b1[i - P::B1] += s;
-}
-
-template <int NL>
-size_t bwd_lds_bytes() {
-  return (size_t)BwdLds<NL>::TOTAL * sizeof(float);
 }
 
 }  // namespace
@@ -1329,7 +781,7 @@ int dsu_hashgrid_encode_bwd(const dsu_hashgrid_cfg* cfg, const float* x, const f
   return DSU_OK;
 }
 
-int dsu_sdf_fwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
+int dsu_sdf_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
                 const float* pts, int64_t n, float radius, uint32_t active_levels,
                 uint32_t n_out, float* out, void* stream) {
   if (!cfg || !table_f16 || !mlp || (!pts && n) || (!out && n) || n < 0) return DSU_EINVAL;
@@ -1341,14 +793,13 @@ int dsu_sdf_fwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, const d
   if (rc) return rc;
   if (n == 0) return DSU_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_capped_blocks(n, DSU_FWD_THREADS, 8192 * (256 / DSU_FWD_THREADS));
+  const int blocks = dsu_capped_blocks(n, FWD_THREADS, 8192);
   DSU_DISPATCH_NL(cfg->n_levels, {
-    const size_t shm = DSU_FWD_LDS_BYTES(NL);
     if (n_out == 1)
-      sdf_fwd_kernel<NL, 1><<<dim3(blocks), dim3(DSU_FWD_THREADS), shm, s>>>(
+      sdf_fwd_kernel<NL, 1><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           (const __half2*)table_f16, m, *mlp, pts, n, radius, active_levels, out, SdfLattice{});
     else
-      sdf_fwd_kernel<NL, NOUT><<<dim3(blocks), dim3(DSU_FWD_THREADS), shm, s>>>(
+      sdf_fwd_kernel<NL, NOUT><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           (const __half2*)table_f16, m, *mlp, pts, n, radius, active_levels, out, SdfLattice{});
   });
   DSU_CHECK_LAUNCH();
@@ -1371,20 +822,19 @@ int dsu_sdf_fwd_lattice(const dsu_hashgrid_cfg* cfg, const void* table_f16, cons
   if (n == 0) return DSU_OK;
   SdfLattice lat{lin, res, x0, {lo3[0], lo3[1], lo3[2]}, {span3[0], span3[1], span3[2]}};
   hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_capped_blocks(n, DSU_FWD_THREADS, 8192 * (256 / DSU_FWD_THREADS));
+  const int blocks = dsu_capped_blocks(n, FWD_THREADS, 8192);
   DSU_DISPATCH_NL(cfg->n_levels, {
-    const size_t shm = DSU_FWD_LDS_BYTES(NL);
-    sdf_fwd_kernel<NL, 1, true><<<dim3(blocks), dim3(DSU_FWD_THREADS), shm, s>>>(
+    sdf_fwd_kernel<NL, 1, true><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
         (const __half2*)table_f16, m, *mlp, nullptr, n, radius, active_levels, out, lat);
   });
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
 
-int dsu_sdf_fd_fwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
+int dsu_sdf_fd_fwd_sorted(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
+                   const float* pts, const int32_t* perm, int64_t n, float radius, float eps,
                    uint32_t active_levels, float* sdf, float* grad, float* feature,
-                   float* laplace, void* enc_cache, const int32_t* perm, void* stream) {
+                   float* laplace, void* enc_cache, void* stream) {
   if (!cfg || !table_f16 || !mlp || (!pts && n) || (!sdf && n) || n < 0) return DSU_EINVAL;
   if (!mlp->w0 || !mlp->b0 || !mlp->w1 || !mlp->b1) return DSU_EINVAL;
   if (active_levels > cfg->n_levels || !(eps > 0.0f)) return DSU_EINVAL;
@@ -1394,31 +844,27 @@ int dsu_sdf_fd_fwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, cons
   if (n == 0) return DSU_OK;
   hipStream_t s = (hipStream_t)stream;
   const float eps2 = (float)((double)eps * (double)eps);
-  const int blocks = dsu_capped_blocks(n, DSU_FWD_THREADS, 8192 * (256 / DSU_FWD_THREADS));
-#if !defined(DSU_FWD_PER_EVAL) && !defined(DSU_FWD_LDS_W)
+  const int blocks = dsu_capped_blocks(n, FWD_THREADS, 8192);
   // level-outer kernel with shared corners: one instance per number of active levels of the
   // shipped grid (10 levels; the 3000-step schedule runs 4..6 of them, geometry.py:196-215);
   // anything else takes the evaluation-by-evaluation kernel below
-  if (cfg->n_levels == 10 && active_levels >= DSU_FWD_SHARED_LO && active_levels <= DSU_FWD_SHARED_HI &&
-      !dsu_ab_is("DSU_FWD_KERNEL", "per_eval")) {
+  if (cfg->n_levels == 10 && active_levels >= FWD_SHARED_LO && active_levels <= FWD_SHARED_HI) {
     bool launched = false;
     fd_shared_launch(active_levels, feature != nullptr, blocks, s, (const __half2*)table_f16, m, *mlp,
                      pts, n, radius, eps, eps2, sdf, grad, feature, laplace, (__half2*)enc_cache, perm,
-                     launched, std::make_integer_sequence<int, DSU_FWD_SHARED_HI - DSU_FWD_SHARED_LO + 1>{});
+                     launched, std::make_integer_sequence<int, FWD_SHARED_HI - FWD_SHARED_LO + 1>{});
     if (launched) {
       DSU_CHECK_LAUNCH();
       return DSU_OK;
     }
   }
-#endif
   DSU_DISPATCH_NL(cfg->n_levels, {
-    const size_t shm = DSU_FWD_LDS_BYTES(NL);
     if (active_levels <= 6)
-      sdf_fd_fwd_kernel<NL, 6><<<dim3(blocks), dim3(DSU_FWD_THREADS), shm, s>>>(
+      sdf_fd_fwd_kernel<NL, 6><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, sdf, grad,
           feature, laplace, (__half2*)enc_cache, perm);
     else
-      sdf_fd_fwd_kernel<NL, NL><<<dim3(blocks), dim3(DSU_FWD_THREADS), shm, s>>>(
+      sdf_fd_fwd_kernel<NL, NL><<<dim3(blocks), dim3(FWD_THREADS), 0, s>>>(
           (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, sdf, grad,
           feature, laplace, (__half2*)enc_cache, perm);
   });
@@ -1426,54 +872,20 @@ int dsu_sdf_fd_fwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, cons
   return DSU_OK;
 }
 
-constexpr int BWD_MAX_BLOCKS = 768;
-
-int64_t dsu_sdf_fd_bwd_workspace_bytes_valu(const dsu_hashgrid_cfg* cfg, int64_t n) {
-  if (!cfg || n < 0) return DSU_EINVAL;
-  const int blocks = dsu_capped_blocks(n, 256, BWD_MAX_BLOCKS);
-  switch (cfg->n_levels) {
-    case 10: return (int64_t)blocks * PartialLayout<10>::STRIDE * sizeof(float);
-    case 12: return (int64_t)blocks * PartialLayout<12>::STRIDE * sizeof(float);
-    default: return DSU_EUNSUP;
-  }
+int dsu_sdf_fd_fwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
+                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
+                          float eps, uint32_t active_levels, float* sdf, float* grad,
+                          float* feature, float* laplace, void* enc_cache, void* stream) {
+  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
+                               sdf, grad, feature, laplace, enc_cache, stream);
 }
 
-int dsu_sdf_fd_bwd_valu(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
+int dsu_sdf_fd_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
                    const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, const float* d_sdf, const float* d_grad,
-                   const float* d_feature, const float* d_laplace, float* grad_table,
-                   float* g_w0, float* g_b0, float* g_w1, float* g_b1, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
-  if (!cfg || !table_f16 || !mlp || (!pts && n) || n < 0) return DSU_EINVAL;
-  if (!mlp->w0 || !mlp->b0 || !mlp->w1 || !mlp->b1) return DSU_EINVAL;
-  if (!grad_table || !g_w0 || !g_b0 || !g_w1 || !g_b1) return DSU_EINVAL;
-  if (active_levels > cfg->n_levels || !(eps > 0.0f)) return DSU_EINVAL;
-  GridMeta m;
-  int rc = make_meta(cfg, &m);
-  if (rc) return rc;
-  if (n == 0) return DSU_OK;
-  const int64_t need = dsu_sdf_fd_bwd_workspace_bytes_valu(cfg, n);
-  if (need < 0) return (int)need;
-  if (!workspace || workspace_bytes < need) return DSU_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const float eps2 = (float)((double)eps * (double)eps);
-  const int blocks = dsu_capped_blocks(n, 256, BWD_MAX_BLOCKS);
-  DSU_DISPATCH_NL(cfg->n_levels, {
-    const size_t shm = bwd_lds_bytes<NL>();
-    if (shm > 64 * 1024) {
-      if (hipFuncSetAttribute((const void*)sdf_fd_bwd_kernel<NL>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shm) != hipSuccess)
-        return DSU_ELAUNCH;
-    }
-    sdf_fd_bwd_kernel<NL><<<dim3(blocks), dim3(256), shm, s>>>(
-        (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, d_sdf,
-        d_grad, d_feature, d_laplace, grad_table, (float*)workspace);
-    reduce_partials_kernel<NL><<<dim3((PartialLayout<NL>::USED + 255) / 256), dim3(256), 0, s>>>(
-        (const float*)workspace, blocks, g_w0, g_b0, g_w1, g_b1);
-  });
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
+                   uint32_t active_levels, float* sdf, float* grad, float* feature,
+                   float* laplace, void* stream) {
+  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
+                               sdf, grad, feature, laplace, nullptr, stream);
 }
 
 }  // extern "C"

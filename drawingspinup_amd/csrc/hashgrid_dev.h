@@ -68,11 +68,7 @@ __device__ __forceinline__ __half2 lookup_level(const __half2* __restrict__ tabl
                         p.c[2] + ((c >> 2) & 1));
   __half2 v[8];
 #pragma unroll
-#if defined(DSU_FWD_ABLATE) && (DSU_FWD_ABLATE & 2)      // probe builds: no table traffic
-  for (int c = 0; c < 8; ++c) { uint32_t b = (idx[c] & 0x03FF03FFu) | 0x20002000u; v[c] = *reinterpret_cast<__half2*>(&b); }
-#else
   for (int c = 0; c < 8; ++c) v[c] = lvl[idx[c]];  // 8 independent 4-byte gathers in flight
-#endif
   __half2 acc = __float2half2_rn(0.0f);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
@@ -111,10 +107,6 @@ __device__ __forceinline__ f32x2 softplus100_pair(f32x2 x) {
   const f32x2 mx = {dsu_relu(x.x), dsu_relu(x.y)};
   return mx + lg * splat2(0.0069314718055994531f);
 }
-__device__ __forceinline__ float softplus100_grad(float x) {
-  // sigmoid(100 x) = 1 / (1 + exp(-100 x)); exp2(+large) = inf -> rcp(inf) = 0
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -144.26950408889634f));
-}
 
 __device__ __forceinline__ float contract(float p, float radius) {
   // scale_anything(x, (-r, r), (0, 1))  (instant_nsr/models/utils.py:101-106)
@@ -122,31 +114,8 @@ __device__ __forceinline__ float contract(float p, float radius) {
   return d * (1.0f - 0.0f) + 0.0f;
 }
 
-constexpr int GC_LOG2 = 12;
-constexpr int GC_SLOTS = 1 << GC_LOG2;
+// key of an empty slot in the scatter kernel's LDS gradient cache
 constexpr uint32_t GC_EMPTY = 0xFFFFFFFFu;
-
-__device__ __forceinline__ void grad_cache_add(uint32_t* keys, float* vals,
-                                               float* __restrict__ gtable, uint32_t entry,
-                                               float v0, float v1) {
-  uint32_t slot = (entry * 2654435761u) >> (32 - GC_LOG2);
-#pragma unroll
-  for (int probe = 0; probe < 3; ++probe) {
-    const uint32_t old = atomicCAS(&keys[slot], GC_EMPTY, entry);
-    if (old == GC_EMPTY || old == entry) {
-      atomicAdd(&vals[2 * slot], v0);       // ds_add_f32
-      atomicAdd(&vals[2 * slot + 1], v1);
-      return;
-    }
-    slot = (slot + 1) & (GC_SLOTS - 1);
-  }
-  unsafeAtomicAdd(gtable + (size_t)entry * 2, v0);
-  unsafeAtomicAdd(gtable + (size_t)entry * 2 + 1, v1);
-}
-
-__device__ __forceinline__ uint32_t grad_cache_slot(uint32_t entry) {
-  return (entry * 2654435761u) >> (32 - GC_LOG2);
-}
 
 int make_meta(const dsu_hashgrid_cfg* cfg, GridMeta* m);
 

@@ -1,13 +1,20 @@
-// Fused hash-grid + SDF-MLP kernels, MFMA formulation (gfx950, v_mfma_f32_32x32x2_f32).
+// Geometry backward: gradients of the fused hash-grid + SDF-MLP (7-evaluation finite differences)
+// on the matrix pipe (gfx950).  Two kernels per call, on one stream:
+//   K1, the MLP part: recomputes the 23->64->13 MLP and runs its backward down to dIn, the gradient
+//       on the interpolated features of every (evaluation, point, level), and leaves one partial
+//       vector of parameter gradients per workgroup.
+//       * sdf_fd_bwd_mfma_kernel<NL, ENC>: the general kernel (any level count, with or without the
+//         forward's feature cache);
+//       * sdf_fd_bwd_pipe_kernel<10, ACT>: the lean, pipelined form of what the optimisation runs
+//         (NL = 10, features from the cache, ACT = 4..7 active levels).
+//   K2, sdf_fd_scatter_kernel<NL>: turns dIn into table gradients; its first workgroups sum K1's
+//       partial vectors.
+// The forward kernels (VALU) and the arithmetic contract are in hashgrid.hip.
 //
-// Same arithmetic contract and C entry points as the VALU kernels in hashgrid.hip (which stay
-// selectable with DSU_SDF_IMPL=valu for A/B runs); what changes is WHERE the 23->64->13 MLP
-// and its backward run: on the matrix pipe, in exact f32 (the f32 MFMA is bit-for-bit an fmaf
-// chain), with the activations never leaving registers between layers.
-//
-// One wave = 64 points, one point per lane for the hash-grid gathers.  Layer 0 is
+// General kernel: one wave = 64 points, one point per lane for the hash-grid gathers.  Layer 0 is
 //     Pre^T[64 hidden x 64 points] = W0'[64 x K] . In'^T[K x 64 points]
-// as 2 (hidden tiles) x 2 (point halves) 32x32 MFMA tiles; In' is the MLP input re-ordered
+// in exact f32 (v_mfma_f32_32x32x2_f32 is bit-for-bit an fmaf chain) as 2 (hidden tiles) x 2
+// (point halves) 32x32 MFMA tiles; In' is the MLP input re-ordered
 // {features | xyz | 1} so that the bias is a weight column and the two features of a level sit
 // in one accumulator quad.  The B operand of the 32x32x2 MFMA wants In'[point][2t] from lanes
 // 0-31 and In'[point][2t+1] from lanes 32-63: ONE v_permlane32_swap per k-pair turns the
@@ -19,33 +26,9 @@
 #include "hashgrid_dev.h"
 #include "partial_reduce.h"
 
-#include <stdlib.h>
-#include <string.h>
-
 #include <type_traits>
 
 using namespace dsu_hg;
-
-// Timing ablations (DSU_BWD_ABLATE=<bits>, tools/sdf_bwd_ablation.py) switch phases of the backward
-// off at run time.  -DDSU_NO_ABLATE (variant build) compiles the checks out.
-#ifdef DSU_NO_ABLATE
-#define DSU_ABL(bits) false
-#else
-#define DSU_ABL(bits) ((ablate & (bits)) != 0)
-#endif
-
-// -DDSU_BWD_PROF (variant build only): per-phase shader-clock totals of the backward kernel,
-// accumulated by every wave into dsu_bwd_prof[] and read back with dsu_debug_bwd_prof().
-#ifdef DSU_BWD_PROF
-__device__ unsigned long long dsu_bwd_prof[16];
-#define DSU_PROF_DECL unsigned long long pt__[16] = {0}; unsigned long long pc__ = __builtin_readcyclecounter();
-#define DSU_PROF(i) { const unsigned long long n__ = __builtin_readcyclecounter(); pt__[i] += n__ - pc__; pc__ = n__; }
-#define DSU_PROF_END if ((threadIdx.x & 63) == 0) { for (int i__ = 0; i__ < 16; ++i__) atomicAdd(&dsu_bwd_prof[i__], pt__[i__]); }
-#else
-#define DSU_PROF_DECL
-#define DSU_PROF(i)
-#define DSU_PROF_END
-#endif
 
 namespace {
 
@@ -53,16 +36,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // Softplus of two neighbouring accumulator values in packed-f32 instructions (softplus100_pair: same
-// bits as softplus100); DSU_PIPE_SP_SCALAR keeps the one-value form for A/B builds
+// bits as softplus100)
 __device__ __forceinline__ void softplus_inplace2(f32x16& acc, int r) {
-#ifdef DSU_PIPE_SP_SCALAR
-  acc[r] = softplus100(acc[r]);
-  acc[r + 1] = softplus100(acc[r + 1]);
-#else
   const f32x2 h = softplus100_pair(f32x2{acc[r], acc[r + 1]});
   acc[r] = h.x;
   acc[r + 1] = h.y;
-#endif
 }
 
 // x = hi + mid + O(2^-16 |x|) with hi, mid in bf16 (round to nearest even both times): the operands
@@ -123,14 +101,7 @@ __device__ __forceinline__ int dpp_i(int v) {
 
 // Takes a value over from the vector-memory pipeline: the compiler has to wait for the load that
 // produces it HERE, and every later use sees an ordinary register (no instruction is emitted).
-// (-DDSU_K1_ROLLED, variant build for A/B runs: no hand-overs and the point halves as a loop — the
-// waits then sit where the compiler puts them, as before round 3)
-#ifdef DSU_K1_ROLLED
-__device__ __forceinline__ void vm_take(float&) {}
-__device__ __forceinline__ void vm_take(__half2&) {}
-#define DSU_K1_HALF_UNROLL(c) 1
-#else
-#define DSU_K1_HALF_UNROLL(c) ((c) ? 2 : 1)
+// (Before round 3 the waits sat where the compiler put them.)
 __device__ __forceinline__ void vm_take(float& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void vm_take(__half2& x) {
   uint32_t u;
@@ -138,13 +109,11 @@ __device__ __forceinline__ void vm_take(__half2& x) {
   asm volatile("" : "+v"(u));
   __builtin_memcpy(&x, &u, 4);
 }
-#endif
 
 template <int NL>
 struct Frags {
   float w0[2][MC<NL>::KP];   // A operand of layer 0: W0'[32T + (lane&31)][2t + (lane>>5)]
   float w1o0[2][16];         // W1[0][feat_of(T, r, h)]
-  float b1o0;
 };
 
 template <int NL>
@@ -163,7 +132,6 @@ __device__ __forceinline__ void load_frags(const dsu_sdf_mlp& m, Frags<NL>& f, i
 #pragma unroll
     for (int r = 0; r < 16; ++r) f.w1o0[T][r] = m.w1[feat_of(T, r, h)];
   }
-  f.b1o0 = m.b1[0];
 }
 
 // MLP input of one contracted point in the permuted order
@@ -184,42 +152,11 @@ __device__ __forceinline__ void encode_input_p(const __half2* __restrict__ table
   in[2 * NL + 3] = 1.0f;
 }
 
-// acc[half][T]: hidden pre-activations; then softplus in place.
-template <int NL>
-__device__ __forceinline__ void layer0_mfma(const Frags<NL>& f, const float* in, uint32_t active,
-                                            f32x16 (&acc)[2][2], int ablate = 0) {
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int T = 0; T < 2; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][T][r] = 0.0f;
-#pragma unroll
-  for (int t = 0; t < MC<NL>::KP; ++t) {
-    if (t < NL && (uint32_t)t >= active) continue;   // masked level: both inputs are zero
-    float b0, b1;
-    swap_halves(in[2 * t], in[2 * t + 1], b0, b1);
-#pragma unroll
-    for (int T = 0; T < 2; ++T) {
-      acc[0][T] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w0[T][t], b0, acc[0][T], 0, 0, 0);
-      acc[1][T] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w0[T][t], b1, acc[1][T], 0, 0, 0);
-    }
-  }
-  if (DSU_ABL(32)) return;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int T = 0; T < 2; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][T][r] = softplus100(acc[a][T][r]);
-}
-
 // Hidden activations of ONE point half (the backward kernel walks the halves one at a time: a
 // `H[half]` array indexed by the run-time half lived in scratch memory, 320 B per lane).
 template <int NL>
 __device__ __forceinline__ void layer0_mfma_half(const Frags<NL>& f, const float* in,
-                                                 uint32_t active, int half, f32x16 (&acc)[2],
-                                                 int ablate = 0) {
+                                                 uint32_t active, int half, f32x16 (&acc)[2]) {
   // B operands of this half's points, one per k-pair
   float b[MC<NL>::KP];
 #pragma unroll
@@ -228,21 +165,6 @@ __device__ __forceinline__ void layer0_mfma_half(const Frags<NL>& f, const float
     swap_halves(in[2 * t], in[2 * t + 1], b0, b1);
     b[t] = half ? b1 : b0;
   }
-#ifdef DSU_L0_INTERLEAVED
-  // A/B variant: the two hidden tiles alternate per k-pair (the form before round 2's tile-major
-  // order; MFMAs on different accumulators back to back, all Softplus work afterwards)
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[T][r] = 0.0f;
-#pragma unroll
-  for (int t = 0; t < MC<NL>::KP; ++t) {
-    if (t < NL && (uint32_t)t >= active) continue;     // masked level: both inputs are zero
-#pragma unroll
-    for (int T = 0; T < 2; ++T)
-      acc[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w0[T][t], b[t], acc[T], 0, 0, 0);
-  }
-#else
   // tile by tile: the Softplus of tile 0 (VALU + transcendental unit) runs while the matrix pipe
   // works through the k-pairs of tile 1 (both tiles interleaved finished together and the 64
   // Softplus evaluations started only then: 1.5 k + 1.6 k clocks in sequence per half)
@@ -256,55 +178,13 @@ __device__ __forceinline__ void layer0_mfma_half(const Frags<NL>& f, const float
       acc[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w0[T][t], b[t], acc[T], 0, 0, 0);
     }
   }
-#endif
-  if (DSU_ABL(32)) return;
 #pragma unroll
   for (int T = 0; T < 2; ++T)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[T][r] = softplus100(acc[T][r]);
 }
 
-// out[0] of the lane's OWN point from the hidden activations spread over lane and lane^32
-template <int NL>
-__device__ __forceinline__ float layer1_o0(const Frags<NL>& f, const f32x16 (&H)[2][2], int h) {
-  float p0 = 0.0f, p1 = 0.0f;
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      p0 = fmaf(f.w1o0[T][r], H[0][T][r], p0);
-      p1 = fmaf(f.w1o0[T][r], H[1][T][r], p1);
-    }
-  const float send = h == 0 ? p1 : p0;
-  const float recv = __shfl_xor(send, 32);
-  return (h == 0 ? p0 : p1) + recv + f.b1o0;
-}
-
-// outputs 1..12 (the centre evaluation's feature vector); W1 rows permuted in LDS:
-// w1perm[h][o][T*16 + r] = W1[o][feat_of(T, r, h)]
-__device__ __forceinline__ void layer1_rest(const float* w1perm, const float* b1s,
-                                            const f32x16 (&H)[2][2], int h, float* out /*13*/) {
-  const float* wp = w1perm + h * NOUT * 32;
-#pragma unroll 1
-  for (int o = 1; o < NOUT; ++o) {
-    float p0 = 0.0f, p1 = 0.0f;
-    const float4* w4 = reinterpret_cast<const float4*>(wp + o * 32);
-#pragma unroll
-    for (int T = 0; T < 2; ++T)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 w = w4[T * 4 + q];
-        p0 = fmaf(w.x, H[0][T][4 * q + 0], p0); p1 = fmaf(w.x, H[1][T][4 * q + 0], p1);
-        p0 = fmaf(w.y, H[0][T][4 * q + 1], p0); p1 = fmaf(w.y, H[1][T][4 * q + 1], p1);
-        p0 = fmaf(w.z, H[0][T][4 * q + 2], p0); p1 = fmaf(w.z, H[1][T][4 * q + 2], p1);
-        p0 = fmaf(w.w, H[0][T][4 * q + 3], p0); p1 = fmaf(w.w, H[1][T][4 * q + 3], p1);
-      }
-    const float send = h == 0 ? p1 : p0;
-    const float recv = __shfl_xor(send, 32);
-    out[o] = (h == 0 ? p0 : p1) + recv + b1s[o];
-  }
-}
-
+// W1 rows permuted in LDS: w1perm[h][o][T*16 + r] = W1[o][feat_of(T, r, h)]
 __device__ __forceinline__ void load_w1perm(float* w1perm, float* b1s, const dsu_sdf_mlp& m) {
   for (int i = threadIdx.x; i < 2 * NOUT * 32; i += blockDim.x) {
     const int h = i / (NOUT * 32), o = (i / 32) % NOUT, tr = i % 32;
@@ -327,113 +207,14 @@ __device__ __forceinline__ void fd_point(const float p[3], int e, float eps, flo
   }
 }
 
-// ------------------------------------------------------------------------------- forward
-template <int NL, int NO>
-__global__ __launch_bounds__(256) void sdf_fwd_mfma_kernel(const __half2* __restrict__ table,
-                                                           GridMeta m, dsu_sdf_mlp mlp,
-                                                           const float* __restrict__ pts,
-                                                           int64_t n, float radius,
-                                                           uint32_t active,
-                                                           float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float w1perm[2 * NOUT * 32];
-  __shared__ float b1s[16];
-  const int lane = threadIdx.x & 63, h = lane >> 5;
-  Frags<NL> fr;
-  load_frags<NL>(mlp, fr, lane);
-  if (NO > 1) {
-    load_w1perm(w1perm, b1s, mlp);
-    __syncthreads();
-  }
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < n; base += stride) {
-    const int64_t i = base + threadIdx.x;
-    const bool valid = i < n;
-    const int64_t ii = valid ? i : n - 1;
-    float in[MC<NL>::KIN];
-    encode_input_p<NL>(table, m, active, contract(pts[ii * 3], radius),
-                       contract(pts[ii * 3 + 1], radius), contract(pts[ii * 3 + 2], radius), in);
-    f32x16 H[2][2];
-    layer0_mfma<NL>(fr, in, active, H);
-    float o[NOUT];
-    o[0] = layer1_o0<NL>(fr, H, h);
-    if (NO > 1) layer1_rest(w1perm, b1s, H, h, o);
-    if (valid) {
-#pragma unroll
-      for (int k = 0; k < NO; ++k) out[i * NO + k] = o[k];
-    }
-  }
-}
-
-template <int NL>
-__global__ __launch_bounds__(256) void sdf_fd_fwd_mfma_kernel(
-    const __half2* __restrict__ table, GridMeta m, dsu_sdf_mlp mlp,
-    const float* __restrict__ pts, int64_t n, float radius, float eps, float eps2,
-    uint32_t active, float* __restrict__ sdf, float* __restrict__ grad,
-    float* __restrict__ feature, float* __restrict__ laplace) {
-  __shared__ __attribute__((aligned(16))) float w1perm[2 * NOUT * 32];
-  __shared__ float b1s[16];
-  const int lane = threadIdx.x & 63, h = lane >> 5;
-  Frags<NL> fr;
-  load_frags<NL>(mlp, fr, lane);
-  load_w1perm(w1perm, b1s, mlp);
-  __syncthreads();
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < n; base += stride) {
-    const int64_t i = base + threadIdx.x;
-    const bool valid = i < n;
-    const int64_t ii = valid ? i : n - 1;
-    const float p[3] = {pts[ii * 3], pts[ii * 3 + 1], pts[ii * 3 + 2]};
-    float s[7];
-#pragma unroll 1
-    for (int e = 0; e < 7; ++e) {
-      float q[3];
-      fd_point(p, e, eps, radius, q);
-      float in[MC<NL>::KIN];
-      encode_input_p<NL>(table, m, active, contract(q[0], radius), contract(q[1], radius),
-                         contract(q[2], radius), in);
-      f32x16 H[2][2];
-      layer0_mfma<NL>(fr, in, active, H);
-      s[e] = layer1_o0<NL>(fr, H, h);
-      if (e == 0 && feature != nullptr) {
-        float o[NOUT];
-        o[0] = s[0];
-        layer1_rest(w1perm, b1s, H, h, o);
-        if (valid) {
-#pragma unroll
-          for (int k = 0; k < NOUT; ++k) feature[i * NOUT + k] = o[k];
-        }
-      }
-    }
-    if (valid) {
-      sdf[i] = s[0];
-      if (grad != nullptr) {
-        grad[i * 3 + 0] = 0.5f * (s[1] - s[2]) / eps;
-        grad[i * 3 + 1] = 0.5f * (s[3] - s[4]) / eps;
-        grad[i * 3 + 2] = 0.5f * (s[5] - s[6]) / eps;
-      }
-      if (laplace != nullptr) {
-        const float t0 = s[1] + s[2] - 2.0f * s[0];
-        const float t1 = s[3] + s[4] - 2.0f * s[0];
-        const float t2 = s[5] + s[6] - 2.0f * s[0];
-        laplace[i] = ((t0 + t1) + t2) / eps2;
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------- backward
-// LDS (floats): w1perm | b1s | 4 x per-wave staging {sd[32][68], sin[32][36], sdo[32][36]} | cache
+// LDS (floats): w1perm | b1s | 4 x per-wave staging {sd[32][68], sin[32][36], sdo[32][36]}
 constexpr int SD_ROW = 68, SIN_ROW = 36;
 constexpr int STAGE_F = 32 * SD_ROW + 2 * 32 * SIN_ROW;   // 4480 floats per wave
 constexpr int W1P_F = 2 * NOUT * 32 + 16;
-constexpr int BWD_CACHE_OFF = W1P_F + 4 * STAGE_F;
-// gradient cache: keys u32[GC_SLOTS] | accumulators i64[GC_SLOTS][2] in fixed point (see gc_fix)
-constexpr int BWD_LDS_F = BWD_CACHE_OFF + GC_SLOTS + 4 * GC_SLOTS;
-// per-wave contribution queue (aliases the staging area while the scatter of a half runs)
-constexpr int QCAP = 1408;                                 // (entry, d0, d1) triples
-static_assert(3 * QCAP <= STAGE_F, "queue must fit the staging area");
-static_assert((BWD_CACHE_OFF + GC_SLOTS) % 2 == 0, "i64 accumulators need 8-byte alignment");
+constexpr int K1_LDS_F = W1P_F + 4 * STAGE_F;
 
+// The scatter kernel accumulates table gradients in LDS before they go to the table.
 // LDS float atomics retire ~1 lane per 3 clocks per CU (measured, profiles/round1_lds_atomics.txt)
 // while integer atomics cost ~10 clocks per instruction whatever the lane count, so the cache
 // accumulates in 64-bit fixed point (2^-40 resolution, +-8.4e6 range): ~20x cheaper per
@@ -454,44 +235,24 @@ __device__ __forceinline__ float gc_unfix(unsigned long long a) {
   return (float)((double)(long long)a * (1.0 / (double)GC_FIX_SCALE));
 }
 
-// a queued contribution whose first cache slot is owned by another entry: two more probes, then
-// a global float atomic (the cache is full around that slot)
-__device__ __forceinline__ void gc_commit_from(uint32_t* keys, unsigned long long* acc,
-                                               float* __restrict__ gtable, uint32_t entry,
-                                               uint32_t slot, float v0, float v1) {
-#pragma unroll
-  for (int probe = 1; probe < 3; ++probe) {
-    slot = (slot + 1) & (GC_SLOTS - 1);
-    const uint32_t old = atomicCAS(&keys[slot], GC_EMPTY, entry);
-    if (old == GC_EMPTY || old == entry) {
-      atomicAdd(&acc[2 * slot], gc_fix(v0));
-      atomicAdd(&acc[2 * slot + 1], gc_fix(v1));
-      return;
-    }
-  }
-  unsafeAtomicAdd(gtable + (size_t)entry * 2, v0);
-  unsafeAtomicAdd(gtable + (size_t)entry * 2 + 1, v1);
-}
-
 // per-workgroup partial vector: gw0p[64 feat][32 k'] | gw1p[64 feat][32 o'] | gb1[16]
 constexpr int PART_GW0 = 0, PART_GW1 = 64 * 32, PART_GB1 = 2 * 64 * 32;
 constexpr int PART_STRIDE = 2 * 64 * 32 + 64;
 
-// SPLIT = false: one kernel does everything (table-gradient scatter included).
-// SPLIT = true : the kernel stops at dIn — the gradient on the interpolated features of every
-//   (evaluation, point, level) is written to `dinbuf` [eval][point][active level] float2 and
-//   sdf_fd_scatter_kernel turns it into table gradients.  Without the 80 KB gradient cache the
-//   MLP part fits two workgroups per CU (two waves per SIMD instead of one).
+// K1, general form.  The kernel stops at dIn — the gradient on the interpolated features of every
+// (evaluation, point, level) is written to `dinbuf` [evaluation][active level][point] float2 and
+// sdf_fd_scatter_kernel turns it into table gradients.  (One fused kernel with an 80 KB gradient
+// cache in LDS was slower: see dsu_sdf_fd_bwd_sorted_fold.)
 // ENC = true: the interpolated features come from the forward pass's cache (the table-gather path
 // and its 40+ scalar registers of level metadata are compiled out).
-template <int NL, bool SPLIT, bool ENC>
+template <int NL, bool ENC>
 __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
     const __half2* __restrict__ table, GridMeta m, dsu_sdf_mlp mlp,
     const float* __restrict__ pts, int64_t n, float radius, float eps, float eps2,
     uint32_t active, const float* __restrict__ d_sdf, const float* __restrict__ d_grad,
     const float* __restrict__ d_feature, const float* __restrict__ d_laplace,
-    float* __restrict__ gtable, float* __restrict__ partials, const __half2* __restrict__ enc,
-    float2* __restrict__ dinbuf, const int32_t* __restrict__ perm, int ablate) {
+    float* __restrict__ partials, const __half2* __restrict__ enc, float2* __restrict__ dinbuf,
+    const int32_t* __restrict__ perm) {
   constexpr int KIN = MC<NL>::KIN;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* w1perm = lds;
@@ -501,15 +262,9 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
   float* sd = lds + W1P_F + wave * STAGE_F;
   float* sin_ = sd + 32 * SD_ROW;
   float* sdo = sin_ + 32 * SIN_ROW;
-  uint32_t* c_keys = reinterpret_cast<uint32_t*>(lds + BWD_CACHE_OFF);
-  unsigned long long* c_acc =
-      reinterpret_cast<unsigned long long*>(lds + BWD_CACHE_OFF + GC_SLOTS);
-  uint32_t* q_ent = reinterpret_cast<uint32_t*>(sd);       // queue aliases sd/sin/sdo
-  float* q_v0 = sd + QCAP;
-  float* q_v1 = sd + 2 * QCAP;
 
   // the scatter kernel's work counter (behind the dIn buffer) starts every launch at zero
-  if (SPLIT && blockIdx.x == 0 && threadIdx.x == 0)
+  if (blockIdx.x == 0 && threadIdx.x == 0)
     *reinterpret_cast<int*>(dinbuf + (size_t)7 * (size_t)n * NL) = 0;
   Frags<NL> fr;
   load_frags<NL>(mlp, fr, lane);
@@ -520,7 +275,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       w0t[T][r] = l31 < KIN ? w0p<NL>(mlp, feat_of(T, r, h), l31) : 0.0f;
-#ifndef DSU_DIN_F32
   // dIn^T = W0'^T . dPre^T on the bf16 matrix pipe (bf16 x 3).  The contraction index of one
   // v_mfma_f32_32x32x16_bf16 is 8 values per lane half: lane (l31, h) supplies k = 8 h + t.  The
   // 32x32 accumulator layout of dPre already holds, in registers 8 g + t of a lane, hidden units
@@ -533,15 +287,7 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
   for (int T = 0; T < 2; ++T)
 #pragma unroll
     for (int g = 0; g < 2; ++g) bf16_split8(&w0t[T][8 * g], w0t_hi[T][g], w0t_mid[T][g]);
-#endif
   load_w1perm(w1perm, b1s, mlp);
-  if (!SPLIT) {
-    for (int t = threadIdx.x; t < GC_SLOTS; t += blockDim.x) {
-      c_keys[t] = GC_EMPTY;
-      c_acc[2 * t] = 0ull;
-      c_acc[2 * t + 1] = 0ull;
-    }
-  }
   __syncthreads();
 
   f32x16 gw0[2], gw1[2];   // [feat tile]: D[i = feat][j = k' or o']
@@ -558,7 +304,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) gw1c0[T][r] = 0.0f;
 
-  DSU_PROF_DECL
   // One contiguous range of points per workgroup (one workgroup per CU, one wave per SIMD): the
   // remainder of n over 256 CUs x 256 points is spread over ALL workgroups as a last partial
   // iteration of <= 32 points — one wave, one point half — instead of a full extra round on a
@@ -574,13 +319,11 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
     // per evaluation), so the waves share the blocks instead: all four take block 0 and every
     // fourth evaluation (two evaluations at most), or two waves per block and every second one.
     int blk = wave, e_start = 0, e_step = 1;
-#ifndef DSU_K1_PLAIN_TAIL
-    if (SPLIT && ENC) {
+    if (ENC) {
       const int64_t left = r1 - bbase;
       if (left <= 64) { blk = 0; e_start = wave; e_step = 4; }
       else if (left <= 128) { blk = wave & 1; e_start = wave >> 1; e_step = 2; }
     }
-#endif
     const int64_t i = bbase + blk * 64 + lane;
     const bool valid = i < r1;
     const int64_t ii = valid ? i : r1 - 1;
@@ -640,10 +383,7 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
       const float cx = contract(q[0], radius), cy = contract(q[1], radius),
                   cz = contract(q[2], radius);
       float in[KIN];
-      if (DSU_ABL(16)) {
-#pragma unroll
-        for (int k = 0; k < KIN; ++k) in[k] = cx * (float)k + cy;
-      } else if (ENC) {
+      if (ENC) {
         // features saved by the forward pass: no table gathers in the backward pass.  The row of
         // evaluation e was requested one evaluation earlier (at one wave per SIMD nothing else
         // hides the ~1.2 us of a dependent global load: 10 % of the kernel's clocks)
@@ -668,7 +408,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
       } else {
         encode_input_p<NL>(table, m, active, cx, cy, cz, in);
       }
-      DSU_PROF(0)   // positions + feature-cache row
       // upstream gradient on this evaluation's outputs (own point)
       float dout[NOUT];
 #pragma unroll
@@ -693,13 +432,11 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 #pragma unroll
       for (int o = 0; o < NOUT; ++o)
         if (o < no) gb1[o] += dout[o];
-      // partner's position (for the scatter of the other point half)
-      const float pcx = partner32(cx, h), pcy = partner32(cy, h), pcz = partner32(cz, h);
 
-      DSU_PROF(1)   // upstream gradient loads
-      // (SPLIT && ENC: both halves as straight-line code, so that the hand-over of the next row
+      // (ENC, NL <= 10: both halves as straight-line code, so that the hand-over of the next row
       // below is on every path and not inside a loop)
-#pragma unroll DSU_K1_HALF_UNROLL(SPLIT && ENC && NL <= 10)
+      constexpr int HALF_UNROLL = ENC && NL <= 10 ? 2 : 1;
+#pragma unroll HALF_UNROLL
       for (int half = 0; half < 2; ++half) {
         const bool live = wave_first + half * 32 < r1;       // a point in this half (wave-uniform)
         f32x16 din;
@@ -713,16 +450,9 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
           if (o < no) other = partner32(dout[o], h);
           d[o] = (h == half) ? dout[o] : other;
         }
-        DSU_PROF(2)   // partner shuffles
-        layer0_mfma_half<NL>(fr, in, active, half, Hh, ablate);
-        DSU_PROF(3)   // layer 0 + softplus
+        layer0_mfma_half<NL>(fr, in, active, half, Hh);
 #pragma unroll
         for (int r = 0; r < 16; ++r) din[r] = 0.0f;
-#ifdef DSU_DIN_2ACC
-        f32x16 din_b;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) din_b[r] = 0.0f;
-#endif
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int T = 0; T < 2; ++T) {
@@ -745,68 +475,24 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
               }
             }
           }
-#ifdef DSU_DIN_BATCH
-          // Staged variant (not measured yet): the 16 derivative factors first, then the 16 MFMAs of
-          // the tile back to back.  Interleaved as below, every MFMA on the ONE accumulator `din`
-          // has ~4 VALU issue slots in front of it, and MI355X_MICROARCH.md prices an extra issue
-          // slot between two MFMAs on the same accumulator at +43 cycles (+6 per further one): the
-          // phase runs at ~116 cycles per MFMA (profiles/round2_sdf_bwd_k1_phase_clocks.txt: 28 %
-          // of the kernel) instead of 64.  Same operations in the same order per value.
-          if (!DSU_ABL(64)) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-              dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(Hh[T][r] * -144.26950408889634f);
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              din = __builtin_amdgcn_mfma_f32_32x32x2f32(w0t[T][r], dpre[r], din, 0, 0, 0);
-          }
-#elif defined(DSU_DIN_2ACC)
-          // Staged variant (not measured yet): even / odd hidden units accumulate into two
-          // accumulators, so that the VALU work sits between MFMAs on DIFFERENT accumulators
-          // (~6 cycles per issue slot instead of the +43 cliff); the two partial sums are added
-          // after the second tile (summation order differs from the default: not bit-identical).
-          if (!DSU_ABL(64))
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(Hh[T][r] * -144.26950408889634f);
-            if (r & 1) din_b = __builtin_amdgcn_mfma_f32_32x32x2f32(w0t[T][r], dpre[r], din_b, 0, 0, 0);
-            else din = __builtin_amdgcn_mfma_f32_32x32x2f32(w0t[T][r], dpre[r], din, 0, 0, 0);
-          }
-#elif defined(DSU_DIN_F32)
-          if (!DSU_ABL(64))
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
+          for (int r = 0; r < 16; ++r)
             // softplus'(pre) = sigmoid(100 pre) = 1 - exp(-100 softplus(pre))
             dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(Hh[T][r] * -144.26950408889634f);
-            din = __builtin_amdgcn_mfma_f32_32x32x2f32(w0t[T][r], dpre[r], din, 0, 0, 0);
-          }
-#else
-          if (!DSU_ABL(64)) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-              // softplus'(pre) = sigmoid(100 pre) = 1 - exp(-100 softplus(pre))
-              dpre[r] *= 1.0f - __builtin_amdgcn_exp2f(Hh[T][r] * -144.26950408889634f);
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-              bf16x8 bh, bm;
-              bf16_split8(&dpre[8 * g], bh, bm);
-              din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din, 0, 0, 0);
-              din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din, 0, 0, 0);
-              din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din, 0, 0, 0);
-            }
+          for (int g = 0; g < 2; ++g) {
+            bf16x8 bh, bm;
+            bf16_split8(&dpre[8 * g], bh, bm);
+            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bh, din, 0, 0, 0);
+            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_hi[T][g], bm, din, 0, 0, 0);
+            din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0t_mid[T][g], bh, din, 0, 0, 0);
           }
-#endif
           // dPre of this half's points -> LDS rows [point][hidden] for the W0 gradient GEMM
 #pragma unroll
           for (int qd = 0; qd < 4; ++qd)
             *reinterpret_cast<float4*>(&sd[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
                 make_float4(dpre[4 * qd], dpre[4 * qd + 1], dpre[4 * qd + 2], dpre[4 * qd + 3]);
         }
-#ifdef DSU_DIN_2ACC
-#pragma unroll
-        for (int r = 0; r < 16; ++r) din[r] += din_b[r];
-#endif
-        DSU_PROF(4)   // dPre, sigmoid, dIn MFMAs, dPre staging
         if (h == half) {
 #pragma unroll
           for (int k4 = 0; k4 < 8; ++k4) {
@@ -829,20 +515,8 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
           }
         }
         __builtin_amdgcn_wave_barrier();
-        DSU_PROF(5)   // input / dOut staging
         // gW0[feat][k'] += sum_points dPre[point][feat] * In'[point][k']
-        if (!DSU_ABL(2) && !SPLIT) {
-          // the fused form (153 KB of LDS, scatter code resident) has no registers to spare for the
-          // read-ahead below (NL = 12 would spill)
-#pragma unroll 4
-          for (int t = 0; t < 16; ++t) {
-            const int pr = 2 * t + h;
-            const float b = sin_[pr * SIN_ROW + l31];
-            gw0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(sd[pr * SD_ROW + l31], b, gw0[0], 0, 0, 0);
-            gw0[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(sd[pr * SD_ROW + 32 + l31], b, gw0[1], 0, 0, 0);
-          }
-        }
-        if (!DSU_ABL(2) && SPLIT) {
+        {
           // operands of the next four k-pairs are requested from LDS before the eight MFMAs of the
           // current four are issued (with `#pragma unroll 4` the reads sat right in front of their
           // MFMAs behind `s_waitcnt lgkmcnt(0)`; the same change took texture_bwd from 231 to 169 us)
@@ -869,7 +543,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
           }
         }
         __builtin_amdgcn_wave_barrier();
-        DSU_PROF(6)   // gW0 GEMM
         if (e == 0) {
           // hidden activations of this half's points -> LDS, then gW1[feat][o'] += H^T . dOut
 #pragma unroll
@@ -879,36 +552,25 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
               *reinterpret_cast<float4*>(&sd[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
                   make_float4(Hh[T][4 * qd], Hh[T][4 * qd + 1], Hh[T][4 * qd + 2], Hh[T][4 * qd + 3]);
           __builtin_amdgcn_wave_barrier();
-          if (!DSU_ABL(2) && !SPLIT) {
-#pragma unroll 4
-            for (int t = 0; t < 16; ++t) {
-              const int pr = 2 * t + h;
-              const float b = sdo[pr * SIN_ROW + l31];
-              gw1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(sd[pr * SD_ROW + l31], b, gw1[0], 0, 0, 0);
-              gw1[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(sd[pr * SD_ROW + 32 + l31], b, gw1[1], 0, 0, 0);
+          float q[2][12];
+          auto ld = [&](int tb, float* d) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int pr = 2 * (4 * tb + u) + h;
+              d[3 * u + 0] = sd[pr * SD_ROW + l31];
+              d[3 * u + 1] = sd[pr * SD_ROW + 32 + l31];
+              d[3 * u + 2] = sdo[pr * SIN_ROW + l31];
             }
-          }
-          if (!DSU_ABL(2) && SPLIT) {
-            float q[2][12];
-            auto ld = [&](int tb, float* d) {
+          };
+          ld(0, q[0]);
 #pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                const int pr = 2 * (4 * tb + u) + h;
-                d[3 * u + 0] = sd[pr * SD_ROW + l31];
-                d[3 * u + 1] = sd[pr * SD_ROW + 32 + l31];
-                d[3 * u + 2] = sdo[pr * SIN_ROW + l31];
-              }
-            };
-            ld(0, q[0]);
+          for (int tb = 0; tb < 4; ++tb) {
+            if (tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
 #pragma unroll
-            for (int tb = 0; tb < 4; ++tb) {
-              if (tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                const float* d = q[tb & 1] + 3 * u;
-                gw1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], gw1[0], 0, 0, 0);
-                gw1[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], gw1[1], 0, 0, 0);
-              }
+            for (int u = 0; u < 4; ++u) {
+              const float* d = q[tb & 1] + 3 * u;
+              gw1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], gw1[0], 0, 0, 0);
+              gw1[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], gw1[1], 0, 0, 0);
             }
           }
         } else {
@@ -919,7 +581,6 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) gw1c0[T][r] = fmaf(Hh[T][r], d[0], gw1c0[T][r]);
         }
-        DSU_PROF(7)   // gW1 GEMM / column
         }  // live
         if (ENC && HANDOVER && half == 1 && e + e_step < 7) {
           // the next evaluation's row, requested ~30 k clocks ago; the stores in flight are the
@@ -931,166 +592,21 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
           }
         }
         if (!live) continue;
-        // scatter dIn rows held by this lane: input row i = (r&3) + 8(r>>2) + 4h, levels (i>>1)
-        if (SPLIT) {
-          // dIn of this half's points -> dinbuf: lane (l31, h) holds the feature pairs of levels
-          // {0,1,4,5,8,9} (h = 0) or {2,3,6,7} (h = 1) of point (half, l31)
-          // layout [evaluation][level][point]: the 32 lanes of a half write 256 contiguous bytes
-          const int64_t pi = wave_first + half * 32 + l31;
-          if (pi < r1) {
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              const int lev = ((r & 3) + 8 * (r >> 2)) / 2 + 2 * h;
-              if (lev < NL && (uint32_t)lev < active)
-                dinbuf[((size_t)e * active + lev) * n + pi] = make_float2(din[r], din[r + 1]);
-            }
-          }
-        } else if (!DSU_ABL(1)) {
-          const bool own = h == half;
-          const float sx = own ? cx : pcx, sy = own ? cy : pcy, sz = own ? cz : pcz;
-          const bool pv = __shfl(valid ? 1 : 0, half * 32 + l31) != 0;
-          // The staging area is free from here to the end of this half: it becomes the wave's
-          // queue of (table entry, d0, d1) contributions.  Producers are the few "leader" lanes
-          // of each level step; the queue is drained 64 contributions per instruction.
-          __builtin_amdgcn_wave_barrier();
-          int qn = 0;
-          auto drain = [&]() {
-            __builtin_amdgcn_wave_barrier();
-            // 4 queue items per lane per round: their slot claims (returning LDS atomics) are in
-            // flight together instead of one dependent claim -> add round trip per 64 items
-            for (int i0 = 0; i0 < qn; i0 += 256) {
-              uint32_t ent[4], slot[4], old[4];
-              float a0[4], a1[4];
-              bool on[4];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                const int i = i0 + 64 * u + lane;
-                on[u] = i < qn;
-                const int ii = on[u] ? i : 0;
-                ent[u] = q_ent[ii];
-                a0[u] = q_v0[ii];
-                a1[u] = q_v1[ii];
-                slot[u] = grad_cache_slot(ent[u]);
-              }
-#pragma unroll
-              for (int u = 0; u < 4; ++u)
-                old[u] = on[u] ? atomicCAS(&c_keys[slot[u]], GC_EMPTY, ent[u]) : ent[u];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                if (!on[u]) continue;
-                if (old[u] == GC_EMPTY || old[u] == ent[u]) {
-                  atomicAdd(&c_acc[2 * slot[u]], gc_fix(a0[u]));
-                  atomicAdd(&c_acc[2 * slot[u] + 1], gc_fix(a1[u]));
-                } else {
-                  gc_commit_from(c_keys, c_acc, gtable, ent[u], slot[u], a0[u], a1[u]);
-                }
-              }
-            }
-            __builtin_amdgcn_wave_barrier();
-            qn = 0;
-          };
+        // dIn of this half's points -> dinbuf: lane (l31, h) holds the feature pairs of levels
+        // {0,1,4,5,8,9} (h = 0) or {2,3,6,7} (h = 1) of point (half, l31)
+        // layout [evaluation][level][point]: the 32 lanes of a half write 256 contiguous bytes
+        const int64_t pi = wave_first + half * 32 + l31;
+        if (pi < r1) {
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
-            const int lev = ((r & 3) + 8 * (r >> 2)) / 2 + 2 * h;   // compile-time part + lane half
-            const bool lev_on = lev < NL && (uint32_t)lev < active;
-            if (((r & 3) + 8 * (r >> 2)) / 2 >= NL) continue;        // no lane has this level
-            // level metadata of BOTH lane halves with compile-time indices + a select: a
-            // lane-varying index into the kernel-argument struct would be served from scratch
-            // memory (a global-memory round trip per lookup at one wave per SIMD)
-            const int la = ((r & 3) + 8 * (r >> 2)) / 2;
-            const int lb = la + 2 < DSU_MAX_LEVELS ? la + 2 : la;
-            const float l_scale = h ? m.scale[lb] : m.scale[la];
-            const uint32_t l_off = h ? m.off[lb] : m.off[la];
-            const uint32_t l_end = h ? m.off[lb + 1] : m.off[la + 1];
-            const uint32_t l_res = h ? m.res[lb] : m.res[la];
-            const uint32_t l_hashed = h ? m.hashed[lb] : m.hashed[la];
-            bool lead = false;
-            float v[16];
-            CellPos cp;
-            if (lev_on) {
-              const bool on = pv;
-              const float d0 = on ? din[r] : 0.0f, d1 = on ? din[r + 1] : 0.0f;
-              cp = cell_of(l_scale, sx, sy, sz);
-              // Neighbouring lanes are neighbouring samples of a ray and mostly sit in the SAME
-              // cell: sum the 8x2 corner contributions over runs of equal cells inside each
-              // 16-lane row with DPP row shifts (segmented suffix scan); only the first lane of
-              // a run (the leader) emits the run's 8 corner contributions.
-#pragma unroll
-              for (int c = 0; c < 8; ++c) {
-                const float w = corner_weight(cp, c);
-                v[2 * c] = w * d0;
-                v[2 * c + 1] = w * d1;
-              }
-              const int key = (int)((cp.c[0] & 1023u) | ((cp.c[1] & 1023u) << 10) | ((cp.c[2] & 1023u) << 20));
-              const int l15 = lane & 15;
-              // The neighbour keys are fetched with ALL lanes active: written as
-              // `l15 == 15 || dpp(key) != key`, the short-circuit put the DPP move under a reduced
-              // EXEC mask, a disabled source lane reads as 0 (bound_ctrl), and lanes 14 / 1 of every
-              // row then always saw "different cell": lane 15's share of a run was dropped and
-              // lane 1's counted twice whenever they shared the cell of their neighbour.
-              const int key_next = dpp_i<0x101>(key), key_prev = dpp_i<0x111>(key);
-              int e = ((l15 == 15) | (key_next != key)) ? 1 : 0;   // run ends at this lane
-#define DSU_SEG_STEP(CTRL)                                              \
-              {                                                         \
-                const int eo = dpp_i<CTRL>(e);                          \
-                _Pragma("unroll") for (int k = 0; k < 16; ++k) {        \
-                  const float vo = dpp_f<CTRL>(v[k]);                   \
-                  v[k] += e ? 0.0f : vo;                                \
-                }                                                       \
-                e |= eo;                                                \
-              }
-              DSU_SEG_STEP(0x101) DSU_SEG_STEP(0x102) DSU_SEG_STEP(0x104) DSU_SEG_STEP(0x108)
-#undef DSU_SEG_STEP
-              lead = ((l15 == 0) | (key_prev != key)) && !DSU_ABL(4);  // first of its run
-            }
-            const unsigned long long bal = __ballot(lead);
-            if (lead) {
-              const int pos = qn + 8 * __popcll(bal & ((1ull << lane) - 1ull));
-              const uint32_t hsize = l_end - l_off;
-              uint32_t ent[8];
-#pragma unroll
-              for (int c = 0; c < 8; ++c)
-                ent[c] = l_off + grid_index(l_hashed, hsize, l_res,
-                                                 cp.c[0] + (c & 1), cp.c[1] + ((c >> 1) & 1),
-                                                 cp.c[2] + ((c >> 2) & 1));
-#pragma unroll
-              for (int q4 = 0; q4 < 2; ++q4) {
-                *reinterpret_cast<uint4*>(&q_ent[pos + 4 * q4]) =
-                    make_uint4(ent[4 * q4], ent[4 * q4 + 1], ent[4 * q4 + 2], ent[4 * q4 + 3]);
-                *reinterpret_cast<float4*>(&q_v0[pos + 4 * q4]) =
-                    make_float4(v[8 * q4], v[8 * q4 + 2], v[8 * q4 + 4], v[8 * q4 + 6]);
-                *reinterpret_cast<float4*>(&q_v1[pos + 4 * q4]) =
-                    make_float4(v[8 * q4 + 1], v[8 * q4 + 3], v[8 * q4 + 5], v[8 * q4 + 7]);
-              }
-            }
-            qn += 8 * __popcll(bal);
-            if (qn + 512 > QCAP) drain();
+            const int lev = ((r & 3) + 8 * (r >> 2)) / 2 + 2 * h;
+            if (lev < NL && (uint32_t)lev < active)
+              dinbuf[((size_t)e * active + lev) * n + pi] = make_float2(din[r], din[r + 1]);
           }
-          drain();
         }
-        DSU_PROF(8)   // dIn write-out or scatter
       }
     }
-    // flush the gradient cache: one global atomic pair per touched entry, then reset
-    if (SPLIT) continue;
-    __syncthreads();
-    for (int t = threadIdx.x; t < GC_SLOTS; t += blockDim.x) {
-      const uint32_t key = c_keys[t];
-      if (key != GC_EMPTY) {
-        if (!DSU_ABL(8)) {
-          unsafeAtomicAdd(gtable + (size_t)key * 2, gc_unfix(c_acc[2 * t]));
-          unsafeAtomicAdd(gtable + (size_t)key * 2 + 1, gc_unfix(c_acc[2 * t + 1]));
-        }
-        c_keys[t] = GC_EMPTY;
-        c_acc[2 * t] = 0ull;
-        c_acc[2 * t + 1] = 0ull;
-      }
-    }
-    __syncthreads();
-    DSU_PROF(9)     // cache flush
   }
-  DSU_PROF(10)
-  DSU_PROF_END
 
   // ---- workgroup reduction of the parameter-gradient tiles -> one partial vector per workgroup
   __syncthreads();
@@ -1141,7 +657,7 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 //     458-register wave: one wave per SIMD and one workgroup per CU, nothing of another kernel beside
 //     it.)
 // Every value is produced by the same operations in the same order as before (g_b1 bit-identical to
-// sdf_fd_bwd_mfma_kernel<NL, true, true>, tests/test_gpu_hashgrid.py).
+// sdf_fd_bwd_mfma_kernel<NL, true>, tests/test_gpu_hashgrid.py).
 // The contractions over the points (gW0, and gW1 of the centre) and dIn, dPre of the centre and layer 0
 // of the recompute (ACT <= 6: its 2 KPA inputs fit one 16-deep MFMA) run as bf16 x 3 on
 // v_mfma_f32_32x32x16_bf16.  Operands of the contractions staged TRANSPOSED per wave:
@@ -1178,11 +694,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
   // column of the accumulator tile that holds gW1[unit][o]: 24..31, then the masked levels' 2 ACT ..
   auto gw1_col = [](int o) { return o < 8 ? 2 * NL + 4 + o : 2 * ACT + (o - 8); };
   static_assert(2 * NL + 4 + 8 == 32 && 2 * ACT + NOUT - 8 <= 2 * NL, "gW1 columns free of inputs");
-#ifdef DSU_PIPE_L0_F32
-  constexpr bool L0BF = false;
-#else
   constexpr bool L0BF = 2 * KPA <= 16;
-#endif
   __shared__ __attribute__((aligned(16))) float lds[PIPE_LDS_F];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
@@ -1743,14 +1255,14 @@ bool launch_bwd_pipe(uint32_t active, int blocks, hipStream_t s, const dsu_sdf_m
 }
 
 // ---------------------------------------------------------------------------- K2: scatter
-// Table gradients from dinbuf (SPLIT path).  One point per thread, SC_THREADS threads per
+// Table gradients from dinbuf.  One point per thread, SC_THREADS threads per
 // workgroup, one LEVEL at a time for the workgroup's SC_THREADS points (so the 4096-slot cache only ever
 // holds one level's entries and is flushed per level), all 7 evaluations of that level back to
-// back.  Same segmented DPP merge, per-wave queue and fixed-point cache as the fused kernel.
-// Sizes (variant builds override them: -DDSU_SC_THREADS / -DDSU_SC_LOG2 / -DDSU_SC_QCAP).  With the
-// samples in Morton order a workgroup's points of one level touch a compact block of entries, so a
-// small cache is enough and what matters is how many waves a CU holds to hide the returning LDS
-// atomics: LDS bytes per workgroup = 20 * slots + 12 * QCAP * waves.
+// back: segmented DPP merge of same-cell runs, per-wave queue, fixed-point cache.
+// Sizes (threads / cache slots / queue triples / resident workgroups).  With the samples in Morton
+// order a workgroup's points of one level touch a compact block of entries, so a small cache is
+// enough and what matters is how many waves a CU holds to hide the returning LDS atomics: LDS bytes
+// per workgroup = 20 * slots + 12 * QCAP * waves.
 // Round 6: 256 threads, 1024 slots, 512-triple queues = 45 KB per workgroup, THREE workgroups per CU
 // (768 resident) instead of one 512-thread workgroup with 150 KB: pair 0.394 -> 0.362 ms in the
 // optimisation (same-box A/B of five shapes, profiles/round6_scatter_shapes_ab.txt: 512 / 2^12 / 704 /
@@ -1759,22 +1271,10 @@ bool launch_bwd_pipe(uint32_t active, int blocks, hipStream_t s, const dsu_sdf_m
 // about half as large, so the smaller dense tile still takes most items, and a CU's three workgroups
 // hide each other's barriers and returning atomics (and leave LDS to other kernels when several
 // drawings share the GPU).
-#ifndef DSU_SC_THREADS
-#define DSU_SC_THREADS 256
-#endif
-#ifndef DSU_SC_LOG2
-#define DSU_SC_LOG2 10
-#endif
-#ifndef DSU_SC_QCAP
-#define DSU_SC_QCAP 512
-#endif
-#ifndef DSU_SC_MAXBLOCKS
-#define DSU_SC_MAXBLOCKS 768
-#endif
-constexpr int SC_MAXBLOCKS = DSU_SC_MAXBLOCKS;                // resident workgroups (256 CUs x per-CU count)
-constexpr int SC_THREADS = DSU_SC_THREADS;
-constexpr int SC_QCAP = DSU_SC_QCAP;                          // triples per wave queue (>= 512 + 64)
-constexpr int SC_LOG2 = DSU_SC_LOG2;
+constexpr int SC_MAXBLOCKS = 768;                             // resident workgroups (256 CUs x per-CU count)
+constexpr int SC_THREADS = 256;
+constexpr int SC_QCAP = 512;                                  // triples per wave queue (>= 512 + 64)
+constexpr int SC_LOG2 = 10;
 constexpr int SC_SLOTS = 1 << SC_LOG2;
 constexpr int SC_LDS_F = SC_SLOTS + 4 * SC_SLOTS + (SC_THREADS / 64) * 3 * SC_QCAP;
 // Dense tile (see the kernel): the 512 Morton-ordered samples of one iteration touch a small box of
@@ -1804,13 +1304,6 @@ __device__ __forceinline__ void sc_commit_from(uint32_t* keys, unsigned long lon
   unsafeAtomicAdd(gtable + (size_t)entry * 2, v0);
   unsafeAtomicAdd(gtable + (size_t)entry * 2 + 1, v1);
 }
-
-#ifdef DSU_AB_SWITCHES
-// variant builds: per level, workgroups that took the dense tile / the cache, and the tile cells used
-__device__ unsigned long long dsu_sc_stat[3 * 16];
-// per workgroup: clocks of the last launch per level [block][16] (+ [15] = whole kernel)
-__device__ unsigned long long dsu_sc_clk[256 * 16];
-#endif
 
 // Sum of the MLP-part kernel's per-workgroup partial vectors into the reference-layout gradients:
 // 64 elements per workgroup, 16 interleaved slices of the workgroup range, then the slices in order
@@ -1854,12 +1347,6 @@ __device__ __forceinline__ void reduce_own_block(const OwnReduce& o, int blk, fl
 }
 
 template <int NL>
-__global__ void reduce_partials_mfma_kernel(OwnReduce o) {
-  __shared__ float red[16 * 64];
-  reduce_own_block<NL>(o, blockIdx.x, red);
-}
-
-template <int NL>
 __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
     GridMeta m, const float* __restrict__ pts, int64_t n, float radius, float eps, uint32_t active,
     const float2* __restrict__ dinbuf, float* __restrict__ gtable, int merge_levels,
@@ -1895,15 +1382,11 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
   if (threadIdx.x < 12) bbox[threadIdx.x] = (threadIdx.x % 6) < 3 ? 0x7fffffff : -0x7fffffff;
   int region = 0;                      // what the shared bytes are initialised for: 0 cache, 1 tile
   __syncthreads();
-#ifdef DSU_AB_SWITCHES
-  const unsigned long long clk_start = wall_clock64();
-  if (threadIdx.x < 15 && sc_block < 256) dsu_sc_clk[sc_block * 16 + threadIdx.x] = 0ull;   // per-level item time of this launch
-#endif
   // Work items = (512-point chunk of the Morton-ordered samples, level), handed out dynamically:
   // an item is self-contained (its tile is flushed at its end), items differ a lot in cost (how
   // many offsets leave their cell, tile or cache), and n / 512 chunks do not divide by the 256
   // resident workgroups — with one static range per workgroup the slowest ran 1.6x the mean
-  // (tools/scatter_stats.py) and a third, almost empty iteration cost every workgroup a full one.
+  // (per-workgroup clocks, round 5) and a third, almost empty iteration cost every workgroup a full one.
   // Item j = chunk j / active, level j % active.  Workgroup b starts with items b and b + G
   // (G = grid size); further ones come from `work_counter` (zeroed by the MLP-part kernel, which
   // precedes this one on the stream), fetched one item ahead so that the next item's loads can
@@ -1965,9 +1448,6 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
 #pragma unroll 1
   while (cur < n_items) {              // uniform over the workgroup
     {
-#ifdef DSU_AB_SWITCHES
-      const unsigned long long clk_item = wall_clock64();
-#endif
       const int64_t chunk = cur / (int64_t)active;
       const int lev = (int)(cur - chunk * (int64_t)active);
       const float l_scale = m.scale[lev];
@@ -2086,12 +1566,6 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
         if (threadIdx.x < 6) bbox[6 * (parity ^ 1) + threadIdx.x] = threadIdx.x < 3 ? 0x7fffffff : -0x7fffffff;
         parity ^= 1;
       }
-#ifdef DSU_AB_SWITCHES
-      if (threadIdx.x == 0) {
-        atomicAdd(&dsu_sc_stat[3 * lev + (dense ? 0 : 1)], 1ull);
-        atomicAdd(&dsu_sc_stat[3 * lev + 2], (unsigned long long)vol);
-      }
-#endif
       if ((int)dense != region) {        // uniform: the shared bytes change hands
         if (region == 0) {               // cache -> tile (the cache was flushed at the end of its item)
           for (int t = threadIdx.x; t < SC_TILE_CAP * 2; t += blockDim.x) tile[t] = 0ull;
@@ -2160,11 +1634,7 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
         const int l15 = lane & 15;
         const bool starts = ((l15 == 0) | (key_prev != key)) & flush;
         const int n_flush = __popcll(__ballot(flush)), n_start = __popcll(__ballot(starts));
-#if defined(DSU_SC_ABL) && (DSU_SC_ABL & 4)
-        if (false) {                                                   // (timing ablation: no run merge)
-#else
         if (lev < merge_levels && 4 * n_start <= 3 * n_flush) {      // uniform
-#endif
           // neighbour keys with all lanes active (a DPP move under the EXEC mask of a
           // short-circuit reads disabled source lanes as 0)
           int ee = ((l15 == 15) | (key_next != key)) ? 1 : 0;   // run ends at this lane
@@ -2188,12 +1658,8 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
               const int t = base + (c & 1) + ((c >> 1) & 1) * ddx + ((c >> 2) & 1) * ddxy;
-#if defined(DSU_SC_ABL) && (DSU_SC_ABL & 1)
-              if (v[2 * c] == 12345.678f) tile[2 * t] = gc_fix(v[2 * c + 1]) + (unsigned long long)t;   // (timing ablation: no LDS atomics)
-#else
               atomicAdd(&tile[2 * t], gc_fix(v[2 * c]));
               atomicAdd(&tile[2 * t + 1], gc_fix(v[2 * c + 1]));
-#endif
             }
           }
           continue;
@@ -2230,12 +1696,8 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
             const int y = rr / ddx, x = rr - y * ddx;
             const uint32_t g = l_off + grid_index(l_hashed, hsize, l_res, (uint32_t)(x0 + x),
                                                   (uint32_t)(y0 + y), (uint32_t)(z0 + z));
-#if !(defined(DSU_SC_ABL) && (DSU_SC_ABL & 2))
             unsafeAtomicAdd(gtable + (size_t)g * 2, gc_unfix(a0));
             unsafeAtomicAdd(gtable + (size_t)g * 2 + 1, gc_unfix(a1));
-#else
-            if (g == 0xffffffffu) gtable[0] = gc_unfix(a0) + gc_unfix(a1);      // (timing ablation: no global atomics)
-#endif
             tile[2 * t] = 0ull;
             tile[2 * t + 1] = 0ull;
           }
@@ -2244,22 +1706,13 @@ __global__ __launch_bounds__(SC_THREADS) void sdf_fd_scatter_kernel(
       } else {
         flush_cache();                   // cache mode: this item's entries (the next item may be a tile)
       }
-#ifdef DSU_AB_SWITCHES
-      if (threadIdx.x == 0 && sc_block < 256 && lev < 15) dsu_sc_clk[sc_block * 16 + lev] += wall_clock64() - clk_item;
-#endif
       cur = nxt;
       nxt = after_next;
     }
   }
-#ifdef DSU_AB_SWITCHES
-  if (threadIdx.x == 0 && sc_block < 256) dsu_sc_clk[sc_block * 16 + 15] = wall_clock64() - clk_start;
-#endif
 }
 
-#ifndef DSU_BWD_MFMA_MAX_BLOCKS
-#define DSU_BWD_MFMA_MAX_BLOCKS 512
-#endif
-constexpr int BWD_MFMA_MAX_BLOCKS = DSU_BWD_MFMA_MAX_BLOCKS;   // two workgroups per CU (the pipelined form: <= 256 registers, 77 KB)
+constexpr int BWD_MFMA_MAX_BLOCKS = 512;   // two workgroups per CU (the pipelined form: <= 256 registers, 77 KB)
 
 }  // namespace
 
@@ -2270,122 +1723,7 @@ constexpr int BWD_MFMA_MAX_BLOCKS = DSU_BWD_MFMA_MAX_BLOCKS;   // two workgroups
     default: return DSU_EUNSUP;                        \
   }
 
-// VALU implementations (hashgrid.hip), kept for A/B runs: DSU_SDF_IMPL=valu
-extern "C" int dsu_sdf_fwd_valu(const dsu_hashgrid_cfg*, const void*, const dsu_sdf_mlp*,
-                                const float*, int64_t, float, uint32_t, uint32_t, float*, void*);
-extern "C" int dsu_sdf_fd_fwd_valu(const dsu_hashgrid_cfg*, const void*, const dsu_sdf_mlp*,
-                                   const float*, int64_t, float, float, uint32_t, float*, float*,
-                                   float*, float*, void*, const int32_t*, void*);
-extern "C" int dsu_sdf_fd_bwd_valu(const dsu_hashgrid_cfg*, const void*, const dsu_sdf_mlp*,
-                                   const float*, int64_t, float, float, uint32_t, const float*,
-                                   const float*, const float*, const float*, float*, float*,
-                                   float*, float*, float*, void*, int64_t, void*);
-extern "C" int64_t dsu_sdf_fd_bwd_workspace_bytes_valu(const dsu_hashgrid_cfg*, int64_t);
-
-// Default mix (measured on MI355X, N = 262 144 ray-ordered samples, 4 active levels):
-//   forward:  VALU 0.22 ms vs MFMA 0.30 ms  -> VALU (gather-latency bound; 2 waves/SIMD help)
-//   backward: VALU 2.31 ms vs MFMA 1.60 ms  -> MFMA
-// DSU_SDF_IMPL=valu|mfma forces one implementation for everything (A/B runs, tests).
-// Default (measured round 2, N = 262 144 ray-ordered samples at the training step size, 4/5/6 levels):
-//   fused 0.60 / 0.72 / 0.85 ms, two kernels 0.54 / 0.61 / 0.71 ms -> two kernels.
-// DSU_BWD_SPLIT=0 selects the fused kernel.
-static bool bwd_split() {          // read per call: the variant tests run both forms in one process
-  return dsu_ab_int("DSU_BWD_SPLIT", 1) != 0;
-}
-
-static bool use_valu(bool forward) {
-  static int v = -1;
-  if (v < 0) v = dsu_ab_is("DSU_SDF_IMPL", "valu") ? 1 : (dsu_ab_is("DSU_SDF_IMPL", "mfma") ? 2 : 0);
-  return v == 1 || (v == 0 && forward);
-}
-
 extern "C" {
-
-#ifdef DSU_AB_SWITCHES
-int dsu_debug_sc_stats(unsigned long long* out48, int reset) {
-  if (hipMemcpyFromSymbol(out48, HIP_SYMBOL(dsu_sc_stat), 48 * sizeof(unsigned long long)) != hipSuccess)
-    return DSU_ELAUNCH;
-  if (reset) {
-    unsigned long long z[48] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(dsu_sc_stat), z, sizeof(z)) != hipSuccess) return DSU_ELAUNCH;
-  }
-  return DSU_OK;
-}
-int dsu_debug_sc_clocks(unsigned long long* out4096) {
-  return hipMemcpyFromSymbol(out4096, HIP_SYMBOL(dsu_sc_clk), 4096 * sizeof(unsigned long long)) == hipSuccess
-             ? DSU_OK : DSU_ELAUNCH;
-}
-#endif
-
-int dsu_sdf_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                const float* pts, int64_t n, float radius, uint32_t active_levels,
-                uint32_t n_out, float* out, void* stream) {
-  if (use_valu(true))
-    return dsu_sdf_fwd_valu(cfg, table_f16, mlp, pts, n, radius, active_levels, n_out, out, stream);
-  if (!cfg || !table_f16 || !mlp || (!pts && n) || (!out && n) || n < 0) return DSU_EINVAL;
-  if (!mlp->w0 || !mlp->b0 || !mlp->w1 || !mlp->b1) return DSU_EINVAL;
-  if (active_levels > cfg->n_levels) return DSU_EINVAL;
-  if (n_out != 1 && n_out != NOUT) return DSU_EUNSUP;
-  GridMeta m;
-  int rc = make_meta(cfg, &m);
-  if (rc) return rc;
-  if (n == 0) return DSU_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_capped_blocks(n, 256, 4096);
-  DSU_DISPATCH_NL(cfg->n_levels, {
-    if (n_out == 1)
-      sdf_fwd_mfma_kernel<NL, 1><<<dim3(blocks), dim3(256), 0, s>>>(
-          (const __half2*)table_f16, m, *mlp, pts, n, radius, active_levels, out);
-    else
-      sdf_fwd_mfma_kernel<NL, NOUT><<<dim3(blocks), dim3(256), 0, s>>>(
-          (const __half2*)table_f16, m, *mlp, pts, n, radius, active_levels, out);
-  });
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_sdf_fd_fwd_sorted(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, const int32_t* perm, int64_t n, float radius, float eps,
-                   uint32_t active_levels, float* sdf, float* grad, float* feature,
-                   float* laplace, void* enc_cache, void* stream) {
-  // the cache and the permuted write-back are features of the VALU kernel
-  if (use_valu(true) || enc_cache != nullptr || perm != nullptr)
-    return dsu_sdf_fd_fwd_valu(cfg, table_f16, mlp, pts, n, radius, eps, active_levels, sdf, grad,
-                               feature, laplace, enc_cache, perm, stream);
-  if (!cfg || !table_f16 || !mlp || (!pts && n) || (!sdf && n) || n < 0) return DSU_EINVAL;
-  if (!mlp->w0 || !mlp->b0 || !mlp->w1 || !mlp->b1) return DSU_EINVAL;
-  if (active_levels > cfg->n_levels || !(eps > 0.0f)) return DSU_EINVAL;
-  GridMeta m;
-  int rc = make_meta(cfg, &m);
-  if (rc) return rc;
-  if (n == 0) return DSU_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const float eps2 = (float)((double)eps * (double)eps);
-  const int blocks = dsu_capped_blocks(n, 256, 4096);
-  DSU_DISPATCH_NL(cfg->n_levels, {
-    sdf_fd_fwd_mfma_kernel<NL><<<dim3(blocks), dim3(256), 0, s>>>(
-        (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, sdf, grad,
-        feature, laplace);
-  });
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_sdf_fd_fwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
-                          float eps, uint32_t active_levels, float* sdf, float* grad,
-                          float* feature, float* laplace, void* enc_cache, void* stream) {
-  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               sdf, grad, feature, laplace, enc_cache, stream);
-}
-
-int dsu_sdf_fd_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, float* sdf, float* grad, float* feature,
-                   float* laplace, void* stream) {
-  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               sdf, grad, feature, laplace, nullptr, stream);
-}
 
 int64_t dsu_sdf_fd_enc_cache_bytes(int64_t n, uint32_t active_levels) {
   if (n < 0 || active_levels > DSU_MAX_LEVELS) return DSU_EINVAL;
@@ -2393,15 +1731,13 @@ int64_t dsu_sdf_fd_enc_cache_bytes(int64_t n, uint32_t active_levels) {
 }
 
 int64_t dsu_sdf_fd_bwd_workspace_bytes(const dsu_hashgrid_cfg* cfg, int64_t n) {
-  if (use_valu(false)) return dsu_sdf_fd_bwd_workspace_bytes_valu(cfg, n);
   if (!cfg || n < 0) return DSU_EINVAL;
   if (cfg->n_levels != 10 && cfg->n_levels != 12) return DSU_EUNSUP;
   const int blocks = dsu_capped_blocks(n, 256, BWD_MFMA_MAX_BLOCKS);
-  int64_t bytes = (int64_t)blocks * PART_STRIDE * sizeof(float);
-  // split form: + dIn of every (evaluation, point, level) as float2
+  // per-workgroup partial vectors + dIn of every (evaluation, point, level) as float2
   // (+ the scatter kernel's work counter behind it)
-  if (bwd_split()) bytes += (int64_t)7 * n * cfg->n_levels * (int64_t)sizeof(float2) + 256;
-  return bytes;
+  return (int64_t)blocks * PART_STRIDE * sizeof(float) +
+         (int64_t)7 * n * cfg->n_levels * (int64_t)sizeof(float2) + 256;
 }
 
 int dsu_sdf_fd_bwd_sorted(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
@@ -2428,6 +1764,10 @@ int dsu_sdf_fd_bwd_sorted_mid(const dsu_hashgrid_cfg* cfg, const void* table_f16
                                     stream);
 }
 
+// Two kernels on the stream: the MLP part (down to dIn, the gradient on the interpolated features)
+// and the scatter that turns dIn into table gradients.  (Measured round 2, N = 262 144 ray-ordered
+// samples at the training step size, 4/5/6 levels: one fused kernel 0.60 / 0.72 / 0.85 ms, two
+// kernels 0.54 / 0.61 / 0.71 ms.)
 int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f16,
                                const dsu_sdf_mlp* mlp, const float* pts, const int32_t* perm,
                                int64_t n, float radius, float eps, uint32_t active_levels,
@@ -2439,12 +1779,7 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
   if (extra && (!extra->partials || !extra->map || !extra->base || extra->nblocks < 0 ||
                 extra->n <= 0 || extra->stride < extra->n))
     return DSU_EINVAL;
-  if (extra && (use_valu(false) || !bwd_split() || n == 0)) return DSU_EUNSUP;
-  if (use_valu(false) && perm) return DSU_EUNSUP;
-  if (use_valu(false))
-    return dsu_sdf_fd_bwd_valu(cfg, table_f16, mlp, pts, n, radius, eps, active_levels, d_sdf,
-                               d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1, g_b1,
-                               workspace, workspace_bytes, stream);
+  if (extra && n == 0) return DSU_EUNSUP;
   if (!cfg || !table_f16 || !mlp || (!pts && n) || n < 0) return DSU_EINVAL;
   if (!mlp->w0 || !mlp->b0 || !mlp->w1 || !mlp->b1) return DSU_EINVAL;
   if (!grad_table || !g_w0 || !g_b0 || !g_w1 || !g_b1) return DSU_EINVAL;
@@ -2463,77 +1798,49 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
   const float eps2 = (float)((double)eps * (double)eps);
   // (the workspace is sized for two workgroups per CU; dsu_set_onewave_grid_cap may launch fewer)
   const int blocks = dsu_onewave_blocks(n, 256, BWD_MFMA_MAX_BLOCKS);
-  const int ablate = dsu_ab_int("DSU_BWD_ABLATE", 0);
-  if (bwd_split()) {
-    const size_t shm1 = (size_t)BWD_CACHE_OFF * sizeof(float);         // no gradient cache
-    const size_t shm2 = (size_t)SC_LDS_TOTAL * sizeof(float);
-    float2* dinbuf = reinterpret_cast<float2*>((char*)workspace +
-                                               (size_t)blocks * PART_STRIDE * sizeof(float));
-    // (dsu_set_scatter_grid_cap launches fewer workgroups — the items are handed out dynamically, so
-    // any count works; measured neutral with drawings in flight)
-    int sblocks = dsu_capped_blocks(n, SC_THREADS, SC_MAXBLOCKS);
-    if (dsu_scatter_grid_cap_value > 0 && sblocks > dsu_scatter_grid_cap_value) sblocks = dsu_scatter_grid_cap_value;
-    DSU_DISPATCH_NL(cfg->n_levels, {
-      auto k1 = enc_cache ? sdf_fd_bwd_mfma_kernel<NL, true, true>
-                          : sdf_fd_bwd_mfma_kernel<NL, true, false>;
-      auto k2 = sdf_fd_scatter_kernel<NL>;
-      DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, true, true>), shm1);
-      DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, true, false>), shm1);
-      DSU_ENSURE_DYN_LDS(k2, shm2);
-      // the lean / pipelined form of the MLP part (NL = 10, features from the cache, 4..7 active
-      // levels: the optimisation's schedule); anything else, and DSU_BWD_PIPE=0 in variant builds,
-      // takes the general kernel
-      bool piped = false;
-      if constexpr (NL == 10) {
-        static int use_pipe = -1;
-        if (use_pipe < 0) use_pipe = dsu_ab_int("DSU_BWD_PIPE", 1) != 0;
-        if (use_pipe && enc_cache && ablate == 0)
-          piped = launch_bwd_pipe<NL>(active_levels, blocks, s, *mlp, pts, n, radius, eps, eps2,
-                                      d_sdf, d_grad, d_feature, d_laplace, (float*)workspace,
-                                      (const __half2*)enc_cache, dinbuf, perm);
-      }
-      if (!piped)
-        k1<<<dim3(blocks), dim3(256), shm1, s>>>(
-            (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, d_sdf,
-            d_grad, d_feature, d_laplace, grad_table, (float*)workspace, (const __half2*)enc_cache,
-            dinbuf, perm, ablate);
-      // the MLP part fills every SIMD with two 256-register waves; what a caller wants to run
-      // beside the rest of the backward (two 96-register waves per SIMD) waits for this event
-      if (mid_event && hipEventRecord((hipEvent_t)mid_event, s) != hipSuccess) return DSU_ELAUNCH;
-      // same-cell run merge (DPP segmented sums over 16 lanes) only where neighbouring lanes of the
-      // Morton order can share a cell: DSU_SC_MERGE_LEVELS (default: all levels)
-      static int merge_lv = -1;
-      if (merge_lv < 0) merge_lv = dsu_ab_int("DSU_SC_MERGE_LEVELS", 64);
-      static int centre_acc = -1;      // DSU_SC_CENTRE=0: every evaluation emitted on its own (A/B)
-      if (centre_acc < 0) centre_acc = dsu_ab_int("DSU_SC_CENTRE", 1) != 0;
-      static int dense_lv = -1;        // DSU_SC_DENSE=0 (variant builds): every level through the cache
-      if (dense_lv < 0) dense_lv = dsu_ab_int("DSU_SC_DENSE", 1) != 0;
-      int* work_counter = reinterpret_cast<int*>(dinbuf + (size_t)7 * (size_t)n * cfg->n_levels);
-      // the partial sums ride in the scatter launch (its first workgroups): no launches of their own
-      const OwnReduce own{(const float*)workspace, blocks, g_w0, g_b0, g_w1, g_b1};
-      dsu_partial_reduce ext{};
-      if (extra) ext = *extra;
-      const int n_red = OWN_RED_BLOCKS + (extra ? dsu_red::blocks_of(ext) : 0);
-      k2<<<dim3(n_red + sblocks), dim3(SC_THREADS), shm2, s>>>(m, pts, n, radius, eps, active_levels,
-                                                              dinbuf, grad_table, merge_lv, centre_acc,
-                                                              dense_lv, work_counter, own, ext);
-    });
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
-  if (mid_event && hipEventRecord((hipEvent_t)mid_event, s) != hipSuccess) return DSU_ELAUNCH;
-  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
+  const size_t shm1 = (size_t)K1_LDS_F * sizeof(float);
+  const size_t shm2 = (size_t)SC_LDS_TOTAL * sizeof(float);
+  float2* dinbuf = reinterpret_cast<float2*>((char*)workspace +
+                                             (size_t)blocks * PART_STRIDE * sizeof(float));
+  // (dsu_set_scatter_grid_cap launches fewer workgroups — the items are handed out dynamically, so
+  // any count works; measured neutral with drawings in flight)
+  int sblocks = dsu_capped_blocks(n, SC_THREADS, SC_MAXBLOCKS);
+  if (dsu_scatter_grid_cap_value > 0 && sblocks > dsu_scatter_grid_cap_value) sblocks = dsu_scatter_grid_cap_value;
   DSU_DISPATCH_NL(cfg->n_levels, {
-    auto k0 = enc_cache ? sdf_fd_bwd_mfma_kernel<NL, false, true>
-                        : sdf_fd_bwd_mfma_kernel<NL, false, false>;
-    DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, false, true>), shm);
-    DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, false, false>), shm);
-    k0<<<dim3(blocks), dim3(256), shm, s>>>(
-        (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, d_sdf,
-        d_grad, d_feature, d_laplace, grad_table, (float*)workspace, (const __half2*)enc_cache,
-        nullptr, perm, ablate);
-    reduce_partials_mfma_kernel<NL><<<dim3(OWN_RED_BLOCKS), dim3(1024), 0, s>>>(
-        OwnReduce{(const float*)workspace, blocks, g_w0, g_b0, g_w1, g_b1});
+    auto k1 = enc_cache ? sdf_fd_bwd_mfma_kernel<NL, true> : sdf_fd_bwd_mfma_kernel<NL, false>;
+    auto k2 = sdf_fd_scatter_kernel<NL>;
+    DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, true>), shm1);
+    DSU_ENSURE_DYN_LDS((sdf_fd_bwd_mfma_kernel<NL, false>), shm1);
+    DSU_ENSURE_DYN_LDS(k2, shm2);
+    // the lean / pipelined form of the MLP part (NL = 10, features from the cache, 4..7 active
+    // levels: the optimisation's schedule); anything else takes the general kernel
+    bool piped = false;
+    if constexpr (NL == 10) {
+      if (enc_cache)
+        piped = launch_bwd_pipe<NL>(active_levels, blocks, s, *mlp, pts, n, radius, eps, eps2,
+                                    d_sdf, d_grad, d_feature, d_laplace, (float*)workspace,
+                                    (const __half2*)enc_cache, dinbuf, perm);
+    }
+    if (!piped)
+      k1<<<dim3(blocks), dim3(256), shm1, s>>>(
+          (const __half2*)table_f16, m, *mlp, pts, n, radius, eps, eps2, active_levels, d_sdf,
+          d_grad, d_feature, d_laplace, (float*)workspace, (const __half2*)enc_cache, dinbuf, perm);
+    // the MLP part fills every SIMD with two 256-register waves; what a caller wants to run
+    // beside the rest of the backward (two 96-register waves per SIMD) waits for this event
+    if (mid_event && hipEventRecord((hipEvent_t)mid_event, s) != hipSuccess) return DSU_ELAUNCH;
+    int* work_counter = reinterpret_cast<int*>(dinbuf + (size_t)7 * (size_t)n * cfg->n_levels);
+    // the partial sums ride in the scatter launch (its first workgroups): no launches of their own
+    const OwnReduce own{(const float*)workspace, blocks, g_w0, g_b0, g_w1, g_b1};
+    dsu_partial_reduce ext{};
+    if (extra) ext = *extra;
+    const int n_red = OWN_RED_BLOCKS + (extra ? dsu_red::blocks_of(ext) : 0);
+    // merge_levels = 64: the same-cell run merge (DPP segmented sums over 16 lanes) on every level;
+    // centre_acc = 1: offsets that stay in the centre's cell are summed into its emission;
+    // dense_levels = 1: items whose box of cells fits the LDS tile skip the hashed cache
+    k2<<<dim3(n_red + sblocks), dim3(SC_THREADS), shm2, s>>>(m, pts, n, radius, eps, active_levels,
+                                                            dinbuf, grad_table, /*merge_levels*/ 64,
+                                                            /*centre_acc*/ 1, /*dense_levels*/ 1,
+                                                            work_counter, own, ext);
   });
   DSU_CHECK_LAUNCH();
   return DSU_OK;
@@ -2561,17 +1868,5 @@ int dsu_sdf_fd_bwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu
                                d_sdf, d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1,
                                g_b1, workspace, workspace_bytes, nullptr, stream);
 }
-
-#ifdef DSU_BWD_PROF
-int dsu_debug_bwd_prof(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(dsu_bwd_prof), 16 * sizeof(unsigned long long)) != hipSuccess)
-    return DSU_ELAUNCH;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(dsu_bwd_prof), z, sizeof(z)) != hipSuccess) return DSU_ELAUNCH;
-  }
-  return DSU_OK;
-}
-#endif
 
 }  // extern "C"

@@ -369,25 +369,6 @@ def test_fused_sdf_matches_reference_volume_sdf_fixture(dev):
         np.testing.assert_allclose(s1.cpu().numpy(), gold[k + "forward_level"], rtol=0, atol=5e-6)
 
 
-def test_sdf_fd_bwd_fused_form_in_subprocess():
-    """The single-kernel form of the backward (DSU_BWD_SPLIT=0; the default is the two-kernel form)
-    is selected once per process, so it is checked in a child process.  The switch exists only in
-    variant builds of the library (-DDSU_AB_SWITCHES, loaded through DSU_HIP_LIB by tools/): with
-    the product library this test has nothing to select."""
-    import os, subprocess, sys
-    from drawingspinup_amd import _lib
-    if not _lib.lib().dsu_ab_switches():
-        pytest.skip("product library: no A/B switches compiled in")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DSU_BWD_SPLIT="0", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu",
-                        os.path.join(root, "tests", "test_gpu_hashgrid.py") + "::test_sdf_fd_bwd",
-                        os.path.join(root, "tests", "test_gpu_hashgrid.py")
-                        + "::test_sdf_fd_feature_cache_round_trip"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-
-
 def test_sdf_fd_bwd_rejects_resolutions_beyond_the_cell_key(dev):
     """The same-cell run merge packs cell coordinates into 10 bits each: a grid whose active levels
     exceed 1023 cells per axis must be refused, not silently aliased."""
@@ -466,7 +447,7 @@ def test_sorted_order_gives_the_same_forward_and_backward(dev, active):
 
 
 @pytest.mark.parametrize("kind", ["ray", "repeat"])
-def test_sdf_fd_bwd_on_samples_that_share_cells(dev, kind, monkeypatch):
+def test_sdf_fd_bwd_on_samples_that_share_cells(dev, kind):
     """Neighbouring lanes in the SAME cell (samples along a ray, repeated points): the same-cell
     run merge of the backward scatter against float64 autograd.  (Uniform random points never
     put two neighbouring lanes into one cell; a DPP move under a short-circuit's EXEC mask once
@@ -490,16 +471,12 @@ def test_sdf_fd_bwd_on_samples_that_share_cells(dev, kind, monkeypatch):
     _torch_fd_loss(tab64, mlp64, pts.numpy(), eps, active, radius, [x.double() for x in d]).backward()
     ref_t = tab64.grad.numpy()
     scale = np.abs(ref_t).max()
-    from drawingspinup_amd import _lib
-    # the fused single-kernel form only exists behind the variant builds' DSU_BWD_SPLIT switch
-    for split in (("1", "0") if _lib.lib().dsu_ab_switches() else ("1",)):
-        monkeypatch.setenv("DSU_BWD_SPLIT", split)
-        gt, gm = ops.sdf_fd_bwd(CFG, tab.to(dev), [m.to(dev) for m in mlp], pts.to(dev), radius, eps,
-                                active, *[x.to(dev) for x in d])
-        gt = gt.cpu().numpy().reshape(-1, 2)
-        assert np.array_equal(ref_t != 0, gt != 0)
-        np.testing.assert_allclose(gt, ref_t, rtol=1e-4, atol=1e-5 * scale)
-        for got, ref in zip(gm, mlp64):
-            r = ref.grad.numpy()
-            np.testing.assert_allclose(got.cpu().numpy(), r, rtol=1e-4,
-                                       atol=1e-5 * max(np.abs(r).max(), 1.0))
+    gt, gm = ops.sdf_fd_bwd(CFG, tab.to(dev), [m.to(dev) for m in mlp], pts.to(dev), radius, eps,
+                            active, *[x.to(dev) for x in d])
+    gt = gt.cpu().numpy().reshape(-1, 2)
+    assert np.array_equal(ref_t != 0, gt != 0)
+    np.testing.assert_allclose(gt, ref_t, rtol=1e-4, atol=1e-5 * scale)
+    for got, ref in zip(gm, mlp64):
+        r = ref.grad.numpy()
+        np.testing.assert_allclose(got.cpu().numpy(), r, rtol=1e-4,
+                                   atol=1e-5 * max(np.abs(r).max(), 1.0))

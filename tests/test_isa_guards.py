@@ -44,20 +44,17 @@ def test_weight_gradient_kernel_keeps_its_accumulators_in_place():
 def test_dominant_nsr_kernels_have_no_scratch():
     ks = _kernels("hashgrid_mfma.hip")
     hot = [k for k in ks if k.startswith("sdf_fd_bwd_mfma_kernel") or k.startswith("sdf_fd_scatter")]
-    assert len(hot) >= 5
+    assert len(hot) == 6       # the general MLP-part kernel <NL = 10 | 12, cache or not> + the scatter <10 | 12>
     for name in hot:
         md, ops = ks[name]
         assert md["scratch"] == 0 and md["vspill"] == 0, (name, md)
         assert sum(o.startswith("scratch_") for o in ops) == 0, name
         assert md["vgpr"] <= 512
-    # the production variant <NL=10, MLP part only (split), feature cache>: the gather path and its
-    # level metadata are compiled out (SGPR spills 130 -> 36 when that was introduced for the fused
-    # form, which is kept as an option and allowed a few more for the per-workgroup range scalars)
+    # <NL=10, feature cache>: the gather path and its level metadata are compiled out (SGPR spills
+    # 130 -> 36 when that was introduced, with a few more allowed for the per-workgroup range scalars)
     # (round 3: the two point halves as straight-line code with hand-placed load waits doubled the
     # scalars kept in vector lanes, 43 -> 87; measured faster all the same, profiles/round3_ab_k1_load_waits.txt)
-    md, _ = ks["sdf_fd_bwd_mfma_kernel<10,1,1>"]
-    assert md["sspill"] <= 96, md
-    md, _ = ks["sdf_fd_bwd_mfma_kernel<10,0,1>"]
+    md, _ = ks["sdf_fd_bwd_mfma_kernel<10,1>"]
     assert md["sspill"] <= 96, md
 
 

@@ -1,5 +1,5 @@
 """Geometry forward (dsu_sdf_fd_fwd_sorted) timed alone on fixed inputs, for A/B of variant
-libraries (DSU_HIP_LIB=...), including the ablated ones of tools/ab_fwd_variants.sh.
+libraries (DSU_HIP_LIB=...).
 
     fwd_phase_probe.py capture FILE   run the NSR optimisation on the synthetic sphere with the
                                       Python-sequenced step and save the forward's real inputs
