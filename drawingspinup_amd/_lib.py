@@ -168,6 +168,10 @@ _PROTOS = {
                       P, P],
     "dsu_raster_mask": [P, c_i64, c_f32, c_i32, P, P],
     "dsu_erode_ellipse_u8": [P, c_i32, c_i32, c_i32, P, P],
+    "dsu_mesh_render_ortho_workspace_bytes": [c_i32, c_i32],
+    "dsu_mesh_render_ortho": [c_i32, P, P, P, P, c_i32, c_i64, c_i64, C.c_double, C.c_double,
+                              C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
+    "dsu_pos_edge_u8": [P, c_i32, c_i32, c_i32, P, P],
     "dsu_point_bin_count": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P],
     "dsu_point_bin_fill": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
     "dsu_knn8_blend": [P, c_i64, P, P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],

@@ -1,0 +1,24 @@
+"""Frame rendering between reconstruction and stylisation: `<uid>/mesh/*.obj` -> the colour /
+position / edge frames of `<uid>/mesh/blender_render/<action>/` (3_style_translator/run_render.py +
+blender_animation.py), for the two actions that need no rig:
+
+    rest_pose      one frame of the rest mesh — the training input
+    rest_rotate    a turntable of the rest mesh — the reference's fallback when a character has no
+                   animation (run_render.py:81-82)
+
+For those the reference's Blender is an orthographic rasteriser of a vertex-coloured mesh, run once
+with the colours and once with the normalised positions (blender_animation.py:26-33,92-121);
+pos2edge (run_render.py:31-57) runs on the position pass.  Both passes, all frames and the edges
+run on the device (csrc/mesh_render.hip).  A caller-supplied (F,V,3) vertex animation is accepted
+as well: a skinned animation made elsewhere renders through the same path.
+
+Deviations from the reference (Blender itself is not here to compare against): a box filter over
+ss^2 sub-samples stands in for Blender's pixel filter; no view transform or tone curve is applied
+(the reference selects 'Standard'); the turntable's frame count lives in a .blend file that is not
+in the snapshot, so it is a parameter.
+"""
+from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
+                     read_obj, render_frames, rest_pose, rest_rotate)
+
+__all__ = ["DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
+           "read_obj", "render_frames", "rest_pose", "rest_rotate"]

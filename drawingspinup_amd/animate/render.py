@@ -1,0 +1,149 @@
+"""Host side of the frame rendering: OBJ reader, position colours, motions, the view rule, and the
+call into the device rasteriser (ops.mesh_render_ortho / ops.pos_edge_u8)."""
+import math
+
+import numpy as np
+import torch
+
+from .. import ops
+
+DEFAULT_SIZE = 512      # config_ortho.blend's resolution, as the 512 of blender_animation.py:72-77
+DEFAULT_SPAN = 1.35     # its ortho_scale (blender_animation.py:71,77; save_mesh's ortho_scale)
+MAX_SIZE = 2048
+
+
+def read_obj(path):
+    """Inverse of nsr/mesh.write_obj: `v x y z [r g b]` lines and 1-based triangular faces (`f a b c`,
+    `a/b/c` corners accepted).  Returns (verts (V,3) f64, faces (M,3) i64 0-based, colours (V,3) f32
+    or None when no vertex carries a colour)."""
+    verts, cols, faces = [], [], []
+    with open(path) as fh:
+        for line in fh:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                verts.append([float(x) for x in p[1:4]])
+                if len(p) >= 7:
+                    cols.append([float(x) for x in p[4:7]])
+            elif p[0] == "f":
+                if len(p) != 4:
+                    raise ValueError(f"{path}: only triangular faces are supported: {line.strip()!r}")
+                faces.append([int(c.split("/")[0]) - 1 for c in p[1:4]])
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if cols and len(cols) != len(verts):
+        raise ValueError(f"{path}: some vertices carry a colour and some do not")
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{path}: face index out of range")
+    return v, f, (np.asarray(cols, np.float32).reshape(-1, 3) if cols else None)
+
+
+def position_colours(verts):
+    """blender_animation.py:30-32: (v - min) / (max - min) per axis of the OBJ coordinates (an axis
+    without extent gives 0 rather than the reference's 0 / 0)."""
+    v = np.asarray(verts, np.float64)
+    lo, hi = v.min(0), v.max(0)
+    ext = hi - lo
+    return (v - lo) / np.where(ext > 0, ext, 1.0)
+
+
+def rest_pose(verts):
+    """(1,V,3): the rest mesh as it is."""
+    return np.asarray(verts, np.float64)[None].copy()
+
+
+def rest_rotate(verts, n_frames=24):
+    """(n_frames,V,3): one full turn about the vertical (y) axis through the origin; frame k is the
+    rest mesh turned by 2 pi k / n_frames (x right, y up, z towards the viewer: +x turns towards
+    the viewer first)."""
+    if n_frames < 1:
+        raise ValueError("n_frames >= 1")
+    v = np.asarray(verts, np.float64)
+    out = np.empty((n_frames,) + v.shape, np.float64)
+    for k in range(n_frames):
+        # exact quarter turns: cos / sin of k pi / 2 taken from the table, not from 1e-16 residues
+        q, r = divmod(4 * k, n_frames)
+        if r == 0:
+            c, s = [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)][q % 4]
+        else:
+            a = 2.0 * math.pi * k / n_frames
+            c, s = math.cos(a), math.sin(a)
+        out[k, :, 0] = c * v[:, 0] + s * v[:, 2]
+        out[k, :, 1] = v[:, 1]
+        out[k, :, 2] = -s * v[:, 0] + c * v[:, 2]
+    return out
+
+
+def motion_frames(verts, motion, n_frames=24):
+    """'rest_pose' | 'rest_rotate' | an (F,V,3) array -> (F,V,3) f64."""
+    if isinstance(motion, str):
+        if motion == "rest_pose":
+            return rest_pose(verts)
+        if motion == "rest_rotate":
+            return rest_rotate(verts, n_frames)
+        raise ValueError(f"unknown motion {motion!r} (rest_pose, rest_rotate or an (F,V,3) array)")
+    m = motion.detach().cpu().numpy() if torch.is_tensor(motion) else np.asarray(motion)
+    m = m.astype(np.float64)
+    if m.ndim != 3 or m.shape[1:] != (len(verts), 3) or m.shape[0] < 1:
+        raise ValueError(f"motion of shape {m.shape}, expected (F,{len(verts)},3)")
+    return m
+
+
+def frame_window(frames_xyz):
+    """The view rule of blender_animation.py:46-77 -> (cx, cy, size, span): the bounding box over
+    all frames, the window re-centred on it; when the larger of its width and height exceeds 1.35,
+    size = int(512 / 1.35 * ratio) rounded up to a multiple of 4 and span = 1.35 * size / 512,
+    otherwise 512 px across 1.35."""
+    p = np.asarray(frames_xyz, np.float64).reshape(-1, 3)
+    if not len(p):
+        return 0.0, 0.0, DEFAULT_SIZE, DEFAULT_SPAN
+    lo, hi = p.min(0), p.max(0)
+    cx, cy = float((hi[0] + lo[0]) / 2), float((hi[1] + lo[1]) / 2)
+    ratio = float(max(hi[0] - lo[0], hi[1] - lo[1]))
+    size, span = DEFAULT_SIZE, DEFAULT_SPAN
+    if ratio > DEFAULT_SPAN:
+        size = int(DEFAULT_SIZE / DEFAULT_SPAN * ratio)
+        if size % 4 > 0:
+            size = size + 4 - size % 4
+        if size > MAX_SIZE:
+            raise ValueError(f"the animation spans {ratio:.3f}: a {size} px window, above {MAX_SIZE}")
+        span = DEFAULT_SPAN * (size / DEFAULT_SIZE)
+    return cx, cy, size, span
+
+
+@torch.no_grad()
+def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24, device="cuda",
+                  window=None, want=()):
+    """Render the motion of one vertex-coloured mesh.  verts (V,3) in save_mesh's frame (x right, y
+    up, z front; the viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
+
+    rest_pose keeps the default camera (origin-centred, 512 px across 1.35: the exported character
+    fills the frame as in the reference); every other motion goes through frame_window.  `window`
+    (cx, cy, size, span) overrides both.
+
+    Returns a dict: color, pos (F,S,S,4) uint8 RGBA; edge (F,S,S) uint8 (255 = no edge); frames
+    (F,6,S,S) f32, the DatasetFullImages tensor with mask and pos on; size; span; centre; plus the
+    extra rasteriser outputs named in `want` (face_id, depth, pixels)."""
+    dev = torch.device(device)
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    v = to_np(verts).astype(np.float64).reshape(-1, 3)
+    f = to_np(faces).astype(np.int64).reshape(-1, 3)
+    c = to_np(colours).astype(np.float32).reshape(-1, 3)
+    if len(c) != len(v):
+        raise ValueError("one colour per vertex")
+    xyz = motion_frames(v, motion, n_frames)
+    if window is not None:
+        cx, cy, size, span = window
+    elif isinstance(motion, str) and motion == "rest_pose":
+        cx, cy, size, span = 0.0, 0.0, DEFAULT_SIZE, DEFAULT_SPAN
+    else:
+        cx, cy, size, span = frame_window(xyz)
+    screen = torch.from_numpy(xyz.astype(np.float32)).to(dev)
+    pos = torch.from_numpy(position_colours(v).astype(np.float32)).to(dev)
+    out = ops.mesh_render_ortho(screen, torch.from_numpy(f).to(dev), torch.from_numpy(c).to(dev), pos,
+                                cx, cy, span, size, ss, want=("color_u8", "pos_u8", "frames", *want))
+    res = {"color": out["color_u8"], "pos": out["pos_u8"], "edge": ops.pos_edge_u8(out["pos_u8"]),
+           "frames": out["frames"], "size": int(size), "span": float(span), "centre": (cx, cy)}
+    res.update({k: out[k] for k in want})
+    return res

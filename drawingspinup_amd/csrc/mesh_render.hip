@@ -1,0 +1,397 @@
+// Frame rendering between reconstruction and stylisation (3_style_translator/run_render.py +
+// blender_animation.py): the reference hands the exported OBJ to Blender, which for the rig-free
+// actions (rest_pose, rest_rotate) is an orthographic rasteriser of a vertex-coloured mesh, run
+// once with the colours and once with the normalised positions; run_render.py:31-57 (pos2edge)
+// then derives the edge map from the position pass.  Here: F frames of one mesh and both attribute
+// sets in one call, on the device (gfx950).
+//
+// The rule (include/dsu_hip.h states it in full; tests/frame_render_ref.py restates it in float64):
+//   * fine lattice N = S * ss; sample (R, C) at x = cx + ((C + 0.5) / N - 0.5) * span,
+//     y = cy - ((R + 0.5) / N - 0.5) * span (float64, this order);
+//   * coverage by the three edge functions of mesh_post.hip (float64 from the f32 vertices, both
+//     orientations, edges inclusive), area = w0 + w1 + w2 at the sample, area == 0 skipped;
+//   * z = (w0 za + w1 zb + w2 zc) / area rounded to f32: largest z wins, equal z -> lowest face;
+//   * per pixel: alpha = covered / ss^2, attribute = mean over the covered samples.
+//
+// Shape of the work: (frame, triangle) pairs are binned onto 16x16-pixel tiles (counting sort in
+// two launches around the caller's prefix sum, as zgrid_bin_kernel); one workgroup per (frame, tile)
+// keeps the tile's (16 ss)^2 sub-samples in LDS as one 64-bit key each — depth as an ordered
+// integer in the high word, the complemented face index in the low word — and walks the tile's
+// list with LDS atomicMax, so the winner does not depend on the order of the list.  The same
+// workgroup then resolves: no global atomics on the frame, no visibility buffer in HBM.
+// LDS: 32 KB of keys + 1 KB of lattice coordinates at ss = 4.
+#include "common.h"
+
+namespace {
+
+constexpr int RT_TILE = 16;   // output pixels per tile side
+
+struct RenderView {
+  double cx, cy, span;
+  int32_t S, ss, N, G;        // output side, sub-samples per pixel side, N = S ss, tiles per side
+};
+
+struct TriXY {
+  double ax, ay, bx, by, cx, cy;
+};
+
+// mesh_post.hip's edge functions: w0 weighs vertex a (edge b->c), w1 b (c->a), w2 c (a->b)
+__device__ __forceinline__ void edge_functions(const TriXY& t, double px, double py, double& w0,
+                                               double& w1, double& w2) {
+  w0 = (px - t.bx) * (t.cy - t.by) - (py - t.by) * (t.cx - t.bx);
+  w1 = (px - t.cx) * (t.ay - t.cy) - (py - t.cy) * (t.ax - t.cx);
+  w2 = (px - t.ax) * (t.by - t.ay) - (py - t.ay) * (t.bx - t.ax);
+}
+
+__device__ __forceinline__ bool covers(double w0, double w1, double w2) {
+  return (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
+}
+
+__device__ __forceinline__ double lattice_x(const RenderView& v, int C) {
+  return v.cx + (((double)C + 0.5) / (double)v.N - 0.5) * v.span;
+}
+__device__ __forceinline__ double lattice_y(const RenderView& v, int R) {
+  return v.cy - (((double)R + 0.5) / (double)v.N - 0.5) * v.span;
+}
+
+// The three vertex indices of face m, or false when one of them is outside [0, V).
+__device__ __forceinline__ bool face_vertices(const int32_t* __restrict__ faces, int64_t m, int64_t V,
+                                              int& ia, int& ib, int& ic) {
+  ia = faces[m * 3];
+  ib = faces[m * 3 + 1];
+  ic = faces[m * 3 + 2];
+  return ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V;
+}
+
+// Samples whose centre can lie inside the triangle's xy bounding box: floor / ceil of the bounds'
+// lattice coordinates, which already leaves up to one sample of margin on each side (the float64
+// rounding of the lattice formula is many orders below one sample).
+// false: non-finite vertex, or entirely outside the frame.  The range is clipped to the frame.
+__device__ __forceinline__ bool sample_range(const RenderView& v, const TriXY& t, int& c0, int& c1,
+                                             int& r0, int& r1) {
+  const double xmin = fmin(fmin(t.ax, t.bx), t.cx), xmax = fmax(fmax(t.ax, t.bx), t.cx);
+  const double ymin = fmin(fmin(t.ay, t.by), t.cy), ymax = fmax(fmax(t.ay, t.by), t.cy);
+  if (!(isfinite(xmin) && isfinite(xmax) && isfinite(ymin) && isfinite(ymax))) return false;
+  const double n = (double)v.N, lim = n + 4.0;
+  const double tc0 = ((xmin - v.cx) / v.span + 0.5) * n - 0.5, tc1 = ((xmax - v.cx) / v.span + 0.5) * n - 0.5;
+  const double tr0 = (0.5 - (ymax - v.cy) / v.span) * n - 0.5, tr1 = (0.5 - (ymin - v.cy) / v.span) * n - 0.5;
+  c0 = (int)floor(fmin(fmax(tc0, -4.0), lim));
+  c1 = (int)ceil(fmin(fmax(tc1, -4.0), lim));
+  r0 = (int)floor(fmin(fmax(tr0, -4.0), lim));
+  r1 = (int)ceil(fmin(fmax(tr1, -4.0), lim));
+  if (c1 < 0 || r1 < 0 || c0 > v.N - 1 || r0 > v.N - 1) return false;
+  c0 = max(c0, 0); r0 = max(r0, 0); c1 = min(c1, v.N - 1); r1 = min(r1, v.N - 1);
+  return true;
+}
+
+__device__ __forceinline__ TriXY load_xy(const float* __restrict__ sv, int ia, int ib, int ic) {
+  TriXY t;
+  t.ax = sv[(int64_t)ia * 3]; t.ay = sv[(int64_t)ia * 3 + 1];
+  t.bx = sv[(int64_t)ib * 3]; t.by = sv[(int64_t)ib * 3 + 1];
+  t.cx = sv[(int64_t)ic * 3]; t.cy = sv[(int64_t)ic * 3 + 1];
+  return t;
+}
+
+// MODE 0: counts[bin] += 1 for every tile the (frame, triangle) pair may touch;
+// MODE 1: items[offsets[bin] + cursor[bin]++] = triangle.  bin = (frame G + tile_row) G + tile_col.
+template <int MODE>
+__global__ __launch_bounds__(256) void render_bin_kernel(
+    const float* __restrict__ screen, const int32_t* __restrict__ faces, int32_t F, int64_t V,
+    int64_t M, RenderView view, int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
+    int32_t* __restrict__ items, int64_t n_items) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)F * M) return;
+  const int f = (int)(i / M);
+  const int64_t m = i - (int64_t)f * M;
+  int ia, ib, ic;
+  if (!face_vertices(faces, m, V, ia, ib, ic)) return;
+  const TriXY t = load_xy(screen + (int64_t)f * V * 3, ia, ib, ic);
+  int c0, c1, r0, r1;
+  if (!sample_range(view, t, c0, c1, r0, r1)) return;
+  const int T = RT_TILE * view.ss;
+  for (int ty = r0 / T; ty <= r1 / T; ++ty)
+    for (int tx = c0 / T; tx <= c1 / T; ++tx) {
+      const int bin = (f * view.G + ty) * view.G + tx;
+      const int k = atomicAdd(&counts[bin], 1);
+      if (MODE == 1) {
+        const int64_t at = (int64_t)offsets[bin] + k;
+        if (at >= 0 && at < n_items) items[at] = (int32_t)m;
+      }
+    }
+}
+
+// float -> unsigned with the same order (all finite values and infinities; never 0)
+__device__ __forceinline__ uint32_t ordered_bits(float z) {
+  const uint32_t u = __float_as_uint(z);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+__device__ __forceinline__ uint32_t quantise(double v) { return (uint32_t)(int)floor(v * 255.0 + 0.5); }
+
+struct RenderOut {
+  uint8_t* color_u8;    // (F,S,S,4)
+  uint8_t* pos_u8;      // (F,S,S,4)
+  int32_t* face_id;     // (F,N,N)
+  float* depth;         // (F,N,N)
+  float* frames;        // (F,6,S,S)
+  float* pixels;        // (F,S,S,8)
+};
+
+// One workgroup of four waves per (frame, tile).
+template <int SS>
+__global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
+    const float* __restrict__ screen, const int32_t* __restrict__ faces,
+    const float* __restrict__ colour, const float* __restrict__ pos, int64_t V, int64_t M,
+    RenderView view, const int32_t* __restrict__ offsets, const int32_t* __restrict__ items,
+    int64_t n_items, RenderOut out) {
+  constexpr int T = RT_TILE * SS;
+  __shared__ unsigned long long keys[T * T];
+  __shared__ double xs[T], ys[T];
+  const int tid = threadIdx.x;
+  const int bin = blockIdx.x;
+  const int f = bin / (view.G * view.G);
+  const int ty = (bin - f * view.G * view.G) / view.G, tx = bin - (f * view.G + ty) * view.G;
+  const int R0 = ty * T, C0 = tx * T;
+  const float* __restrict__ sv = screen + (int64_t)f * V * 3;
+  for (int s = tid; s < T * T; s += 256) keys[s] = 0ull;
+  if (tid < T) xs[tid] = lattice_x(view, C0 + tid);
+  else if (tid < 2 * T) ys[tid - T] = lattice_y(view, R0 + tid - T);
+  __syncthreads();
+
+  // ---- visibility: one triangle per wave, its lanes stride over the triangle's samples in the tile
+  const int wave = tid >> 6, lane = tid & 63;
+  const int64_t beg = offsets[bin], end = min((int64_t)offsets[bin + 1], n_items);
+  for (int64_t k = max(beg, (int64_t)0) + wave; k < end; k += 4) {
+    const int m = items[k];
+    if (m < 0 || m >= M) continue;
+    int ia, ib, ic;
+    if (!face_vertices(faces, m, V, ia, ib, ic)) continue;
+    const TriXY t = load_xy(sv, ia, ib, ic);
+    int c0, c1, r0, r1;
+    if (!sample_range(view, t, c0, c1, r0, r1)) continue;
+    c0 = max(c0, C0); r0 = max(r0, R0); c1 = min(c1, C0 + T - 1); r1 = min(r1, R0 + T - 1);
+    if (c1 < c0 || r1 < r0) continue;
+    const double za = sv[(int64_t)ia * 3 + 2], zb = sv[(int64_t)ib * 3 + 2], zc = sv[(int64_t)ic * 3 + 2];
+    const int w = c1 - c0 + 1, n = w * (r1 - r0 + 1);
+    const uint32_t low = ~(uint32_t)m;
+    for (int i = lane; i < n; i += 64) {
+      const int rr = i / w;
+      const int lr = r0 - R0 + rr, lc = c0 - C0 + (i - rr * w);
+      double w0, w1, w2;
+      edge_functions(t, xs[lc], ys[lr], w0, w1, w2);
+      const double area = w0 + w1 + w2;
+      if (area == 0.0 || !covers(w0, w1, w2)) continue;
+      float z = (float)((w0 * za + w1 * zb + w2 * zc) / area);
+      if (!(z == z)) continue;
+      if (z == 0.0f) z = 0.0f;                       // -0 and +0 are the same depth
+      atomicMax(&keys[lr * T + lc], ((unsigned long long)ordered_bits(z) << 32) | low);
+    }
+  }
+  __syncthreads();
+
+  // ---- per-sample outputs
+  if (out.face_id || out.depth) {
+    for (int s = tid; s < T * T; s += 256) {
+      const int lr = s / T, lc = s - lr * T;
+      const int R = R0 + lr, C = C0 + lc;
+      if (R >= view.N || C >= view.N) continue;
+      const unsigned long long key = keys[s];
+      const int64_t at = ((int64_t)f * view.N + R) * view.N + C;
+      if (out.face_id) out.face_id[at] = key ? (int32_t)~(uint32_t)key : -1;
+      if (out.depth) out.depth[at] = key ? ordered_float((uint32_t)(key >> 32)) : 0.0f;
+    }
+  }
+
+  // ---- resolve: one pixel per thread, its samples in row-major order
+  const int py = tid / RT_TILE, px = tid - py * RT_TILE;
+  const int Y = ty * RT_TILE + py, X = tx * RT_TILE + px;
+  if (Y >= view.S || X >= view.S) return;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int covered = 0;
+  uint32_t last = 0xffffffffu;
+  TriXY t = {};
+  float a0[6], a1[6], a2[6];
+#pragma unroll
+  for (int ch = 0; ch < 6; ++ch) a0[ch] = a1[ch] = a2[ch] = 0.0f;
+  for (int sy = 0; sy < SS; ++sy)
+    for (int sx = 0; sx < SS; ++sx) {
+      const int lr = py * SS + sy, lc = px * SS + sx;
+      const unsigned long long key = keys[lr * T + lc];
+      if (!key) continue;
+      const uint32_t m = ~(uint32_t)key;
+      if (m != last) {
+        int ia, ib, ic;
+        face_vertices(faces, m, V, ia, ib, ic);      // validated when the key was written
+        t = load_xy(sv, ia, ib, ic);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          a0[ch] = clamp01(colour[(int64_t)ia * 3 + ch]);
+          a1[ch] = clamp01(colour[(int64_t)ib * 3 + ch]);
+          a2[ch] = clamp01(colour[(int64_t)ic * 3 + ch]);
+          a0[3 + ch] = clamp01(pos[(int64_t)ia * 3 + ch]);
+          a1[3 + ch] = clamp01(pos[(int64_t)ib * 3 + ch]);
+          a2[3 + ch] = clamp01(pos[(int64_t)ic * 3 + ch]);
+        }
+        last = m;
+      }
+      double w0, w1, w2;
+      edge_functions(t, xs[lc], ys[lr], w0, w1, w2);
+      const double area = w0 + w1 + w2;
+#pragma unroll
+      for (int ch = 0; ch < 6; ++ch)
+        acc[ch] += (double)(float)((w0 * (double)a0[ch] + w1 * (double)a1[ch] + w2 * (double)a2[ch]) / area);
+      ++covered;
+    }
+  double v[6];
+#pragma unroll
+  for (int ch = 0; ch < 6; ++ch) v[ch] = covered ? acc[ch] / (double)covered : 0.0;
+  const double alpha = (double)covered / (double)(SS * SS);
+  const uint32_t a8 = quantise(alpha);
+  uint32_t q[6];
+#pragma unroll
+  for (int ch = 0; ch < 6; ++ch) q[ch] = quantise(v[ch]);
+  const int64_t pix = ((int64_t)f * view.S + Y) * view.S + X;
+  if (out.color_u8)
+    reinterpret_cast<uint32_t*>(out.color_u8)[pix] = q[0] | (q[1] << 8) | (q[2] << 16) | (a8 << 24);
+  if (out.pos_u8)
+    reinterpret_cast<uint32_t*>(out.pos_u8)[pix] = q[3] | (q[4] << 8) | (q[5] << 16) | (a8 << 24);
+  if (out.pixels) {
+    float4* p = reinterpret_cast<float4*>(out.pixels) + pix * 2;
+    p[0] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)alpha);
+    p[1] = make_float4((float)v[3], (float)v[4], (float)v[5], (float)alpha);
+  }
+  if (out.frames) {
+    // DatasetFullImages (entry/data.py): ToTensor = u8 / 255 in f32, Normalize(0.5, 0.5) on the
+    // colour and position channels, the mask as it is — from the uint8 values, like a PNG read back
+    const int64_t plane = (int64_t)view.S * view.S;
+    float* fr = out.frames + (int64_t)f * 6 * plane + (int64_t)Y * view.S + X;
+    fr[0] = ((float)q[0] / 255.0f - 0.5f) / 0.5f;
+    fr[plane] = ((float)q[1] / 255.0f - 0.5f) / 0.5f;
+    fr[2 * plane] = ((float)q[2] / 255.0f - 0.5f) / 0.5f;
+    fr[3 * plane] = (float)a8 / 255.0f;
+    fr[4 * plane] = ((float)q[3] / 255.0f - 0.5f) / 0.5f;
+    fr[5 * plane] = ((float)q[4] / 255.0f - 0.5f) / 0.5f;
+  }
+}
+
+// pos2edge (run_render.py:31-57) + the inversion of :120 on the RGBA8 position image: channels
+// u8 -> f32 / 255, every channel 2 where alpha8 < 255 (alpha < 1), 3x3 Sobel per channel in
+// float64 (cv2.Sobel(..., CV_64F, ksize=3), default border BORDER_REFLECT_101), magnitude, maximum
+// over the three colour channels, > 0.3 = edge; stored 255 - edge (255 = no edge).
+__device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+
+__global__ __launch_bounds__(256) void pos_edge_kernel(const uint8_t* __restrict__ pos_rgba, int32_t H,
+                                                       int32_t W, uint8_t* __restrict__ edge) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
+  if (x >= W) return;
+  const uint32_t* __restrict__ img = reinterpret_cast<const uint32_t*>(pos_rgba) + (int64_t)f * H * W;
+  uint32_t px[3][3];
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx)
+      px[dy][dx] = img[(int64_t)reflect101(y + dy - 1, H) * W + reflect101(x + dx - 1, W)];
+  double best = 0.0;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    double p[3][3];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const uint32_t w = px[dy][dx];
+        p[dy][dx] = (w >> 24) < 255u ? 2.0 : (double)((float)((w >> (8 * ch)) & 255u) / 255.0f);
+      }
+    const double gx = (p[0][2] - p[0][0]) + 2.0 * (p[1][2] - p[1][0]) + (p[2][2] - p[2][0]);
+    const double gy = (p[2][0] - p[0][0]) + 2.0 * (p[2][1] - p[0][1]) + (p[2][2] - p[0][2]);
+    best = fmax(best, sqrt(gx * gx + gy * gy));
+  }
+  edge[((int64_t)f * H + y) * W + x] = best > 0.3 ? 0 : 255;
+}
+
+bool view_ok(int32_t F, int32_t S, int32_t ss, double span) {
+  return F >= 1 && F <= 4096 && S >= 4 && S <= 2048 && S % 4 == 0 && (ss == 1 || ss == 2 || ss == 4) &&
+         span > 0.0 && span == span && span < 1e30;
+}
+
+int64_t bins_of(int32_t F, int32_t S) {
+  const int64_t G = (S + RT_TILE - 1) / RT_TILE;
+  return (int64_t)F * G * G;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size) {
+  if (n_frames < 1 || n_frames > 4096 || size < 4 || size > 2048 || size % 4) return DSU_EINVAL;
+  return (3 * bins_of(n_frames, size) + 1) * (int64_t)sizeof(int32_t);
+}
+
+int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
+                          const float* colour, const float* pos, int32_t n_frames, int64_t n_verts,
+                          int64_t n_faces, double cx, double cy, double span, int32_t size, int32_t ss,
+                          void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
+                          uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
+                          float* frames, float* pixels, void* stream) {
+  if (stage < DSU_RENDER_COUNT || stage > DSU_RENDER_RASTER) return DSU_EINVAL;
+  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
+      n_verts > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  const int64_t nb = bins_of(n_frames, size);
+  if (!workspace || workspace_bytes < (3 * nb + 1) * (int64_t)sizeof(int32_t)) return DSU_EINVAL;
+  if (n_faces && (!screen || !faces || n_verts == 0)) return DSU_EINVAL;
+  if (stage != DSU_RENDER_COUNT && n_items && !items) return DSU_EINVAL;
+  if (stage == DSU_RENDER_RASTER && n_faces && (!colour || !pos)) return DSU_EINVAL;
+  int32_t* counts = (int32_t*)workspace;
+  int32_t* offsets = counts + nb;            // nb + 1 entries, written by the caller between the stages
+  int32_t* cursor = offsets + nb + 1;
+  hipStream_t st = (hipStream_t)stream;
+  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
+  const int64_t pairs = (int64_t)n_frames * n_faces;
+  if (stage == DSU_RENDER_COUNT) {
+    if (hipMemsetAsync(counts, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
+    if (pairs)
+      render_bin_kernel<0><<<dsu_blocks_for(pairs, 256), 256, 0, st>>>(
+          screen, faces, n_frames, n_verts, n_faces, view, counts, nullptr, nullptr, 0);
+    DSU_CHECK_LAUNCH();
+    return DSU_OK;
+  }
+  if (stage == DSU_RENDER_FILL) {
+    if (hipMemsetAsync(cursor, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
+    if (pairs && n_items)
+      render_bin_kernel<1><<<dsu_blocks_for(pairs, 256), 256, 0, st>>>(
+          screen, faces, n_frames, n_verts, n_faces, view, cursor, offsets, items, n_items);
+    DSU_CHECK_LAUNCH();
+    return DSU_OK;
+  }
+  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
+#define DSU_RASTER(SS_)                                                                         \
+  mesh_raster_resolve_kernel<SS_><<<(unsigned)nb, 256, 0, st>>>(screen, faces, colour, pos, n_verts, \
+                                                                n_faces, view, offsets, items,   \
+                                                                n_faces ? n_items : 0, out)
+  if (ss == 1) DSU_RASTER(1);
+  else if (ss == 2) DSU_RASTER(2);
+  else DSU_RASTER(4);
+#undef DSU_RASTER
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_pos_edge_u8(const uint8_t* pos_rgba, int32_t n_frames, int32_t H, int32_t W, uint8_t* edge,
+                    void* stream) {
+  if (n_frames < 1 || n_frames > 65535 || H < 2 || W < 2 || H > 65535 || W > 16384 || !pos_rgba || !edge)
+    return DSU_EINVAL;
+  pos_edge_kernel<<<dim3((W + 255) / 256, H, n_frames), dim3(256), 0, (hipStream_t)stream>>>(pos_rgba, H,
+                                                                                             W, edge);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+}  // extern "C"

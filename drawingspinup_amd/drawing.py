@@ -4,8 +4,10 @@ stages handing tensors over in memory instead of PNG/OBJ files.
 
 Synthetic inputs: a 512x512 RGBA "drawing" (low-pass random colour inside an
 ellipse), random-init weights of the reference architectures.  Blender/Mixamo rigging between
-recon and stylisation is an external manual tool in the reference (README.md:183-186); the
-stylisation frames are synthetic colour / position / edge maps of the stated shapes.
+recon and stylisation is an external manual tool in the reference (README.md:183-186); by default
+the stylisation frames are synthetic colour / position / edge maps of the stated shapes.
+DrawingPipeline(frames="rendered") renders the reconstructed mesh instead, as the reference's
+rig-free `rest_rotate` action (drawingspinup_amd.animate): the frames then depend on the drawing.
 """
 import os
 import time
@@ -82,7 +84,11 @@ class DrawingPipeline:
 
     def __init__(self, device="cuda", seed=0, mv_steps=75, nsr_steps=3000, n_frames=24,
                  with_clip=True, export_resolution=512, with_mv=True, with_contour=True, mesh_post=True,
-                 with_matting=None, isnet_weights=None):
+                 with_matting=None, isnet_weights=None, frames="synthetic"):
+        if frames not in ("synthetic", "rendered"):
+            raise ValueError("frames: 'synthetic' or 'rendered'")
+        self.frames = frames                 # what stage 3 stylises: synthetic maps, or the mesh rendered
+        self.render_ss = 4                   # sub-samples per pixel side of the rendered frames
         self.device = torch.device(device)
         self.mv_steps, self.nsr_steps, self.n_frames = mv_steps, nsr_steps, n_frames
         self.style_batch = 4                 # frames per generator call
@@ -310,10 +316,31 @@ class DrawingPipeline:
             outs.append(torch.cat([to_image_space(s2), (x[:, 3:4] * 255).to(torch.uint8)], 1))
         return torch.cat(outs)
 
-    def run(self, seed):
-        drawing = synthetic_drawing(seed, device=self.device)
+    def render_mesh(self, mesh_post):
+        """run_render.py --test without animation files: the exported mesh as `rest_rotate`, n_frames
+        of a turntable -> (frames (n,6,S,S), edges (n,S,S) uint8), or None for an empty mesh."""
+        if mesh_post is None or not len(mesh_post["faces"]) or mesh_post["colors"] is None:
+            return None
+        from . import animate
+        r = animate.render_frames(mesh_post["verts"], mesh_post["faces"], mesh_post["colors"], "rest_rotate",
+                                  ss=self.render_ss, n_frames=self.n_frames, device=self.device)
+        return r["frames"], r["edge"]
+
+    def run(self, seed, drawing=None):
+        if drawing is None:
+            drawing = synthetic_drawing(seed, device=self.device)
         normals, colors = self.multiview(drawing, 123456 + seed)
+        self.last_mesh_post = None
         system, inside = self.reconstruct(normals, colors, drawing, 123456 + seed)
+        if self.frames == "rendered":
+            rendered = self.render_mesh(self.last_mesh_post)
+            if rendered is not None:
+                fr, edges = rendered
+                return {"views": colors, "inside_voxels": inside.sum(), "frames": self.stylize(fr, edges),
+                        "frame_source": "rendered", "rendered": fr}
         fr = synthetic_frames(seed, self.n_frames, device=self.device)
         frames = self.stylize(fr, synthetic_edges(fr))
-        return {"views": colors, "inside_voxels": inside.sum(), "frames": frames}
+        out = {"views": colors, "inside_voxels": inside.sum(), "frames": frames}
+        if self.frames == "rendered":
+            out["frame_source"] = "synthetic (the reconstruction gave an empty mesh)"
+        return out

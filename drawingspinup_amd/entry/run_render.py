@@ -1,0 +1,60 @@
+"""`python run_render.py --data_dir D --uid U [--test]` (3_style_translator/run_render.py:60-124)
+for the actions that need no rig: `<uid>/mesh/*.obj` ->
+`<uid>/mesh/blender_render/<action>/{color,pos,edge}/%04d.png`.
+
+Without --test the action is `rest_pose` (the training input); with it, `rest_rotate`, the
+reference's fallback for a character without animation files (run_render.py:78-82).  The
+reference starts Blender on a rigged FBX; here the OBJ is rendered on the device
+(drawingspinup_amd.animate).  Names start at 0001.png, as Blender's do and as
+DatasetPatches_M.load_image expects; color and pos are RGBA, edge is 8-bit grey.
+"""
+import argparse
+import glob
+import os
+import time
+
+from PIL import Image
+
+from .. import animate
+
+
+def write_frames(out_dir, rendered):
+    """color/ pos/ edge/ PNGs of one render_frames result."""
+    for sub in ("color", "pos", "edge"):
+        os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+    color, pos, edge = (rendered[k].cpu().numpy() for k in ("color", "pos", "edge"))
+    for i in range(color.shape[0]):
+        name = "%04d.png" % (i + 1)
+        Image.fromarray(color[i], "RGBA").save(os.path.join(out_dir, "color", name))
+        Image.fromarray(pos[i], "RGBA").save(os.path.join(out_dir, "pos", name))
+        Image.fromarray(edge[i], "L").save(os.path.join(out_dir, "edge", name))
+    return color.shape[0]
+
+
+def run(argv=None):
+    ap = argparse.ArgumentParser(description="frame rendering")
+    ap.add_argument("--data_dir", default="../dataset/AnimatedDrawings/preprocessed", help="data root")
+    ap.add_argument("--uid", default="0dd66be9d0534b93a092d8c4c4dfd30a", help="image uid")
+    ap.add_argument("--test", action="store_true", help="render the test action (rest_rotate)")
+    ap.add_argument("--frames", type=int, default=24, help="frames of the rest_rotate turntable")
+    ap.add_argument("--ss", type=int, default=4, choices=[1, 2, 4], help="sub-samples per pixel side")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
+    if not found:
+        raise FileNotFoundError(f"no OBJ under {os.path.join(args.data_dir, args.uid, 'mesh')}")
+    verts, faces, colours = animate.read_obj(found[0])
+    if colours is None:
+        raise ValueError(f"{found[0]} has no vertex colours")
+    action = "rest_rotate" if args.test else "rest_pose"
+    out_dir = os.path.join(args.data_dir, args.uid, "mesh", "blender_render", action)
+    start = time.time()
+    rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
+                                     device=args.device)
+    n = write_frames(out_dir, rendered)
+    print((time.time() - start) / n, n)
+    return out_dir, rendered
+
+
+if __name__ == "__main__":
+    run()

@@ -1343,3 +1343,93 @@ def knn8_blend(query_xy, known_xy, known_rgb):
                                ptr(known_rgb), k64.shape[0], x0, y0, cell, g, off, items, ptr(out),
                                stream()), "dsu_knn8_blend")
     return out
+
+
+# ------------------------------------------------------------------ frame rendering (csrc/mesh_render.hip)
+RENDER_COUNT, RENDER_FILL, RENDER_RASTER = 0, 1, 2
+
+
+class MeshRenderPlan:
+    """The binning half of dsu_mesh_render_ortho for one (screen, faces, window): (frame, triangle)
+    pairs counted per 16x16-pixel tile, the prefix sum (torch), the triangle ids filled in.
+    screen (F,V,3) f32, faces (M,3) i32 on the device; size a multiple of 4 (<= 2048), ss 1 | 2 | 4."""
+
+    def __init__(self, screen, faces, cx, cy, span, size, ss):
+        self.screen, self.faces = _f32c(screen), faces.to(torch.int32).contiguous()
+        if self.screen.dim() != 3 or self.screen.shape[2] != 3 or self.faces.dim() != 2:
+            raise ValueError("screen (F,V,3) and faces (M,3) expected")
+        self.F, self.V, self.M = self.screen.shape[0], self.screen.shape[1], self.faces.shape[0]
+        self.cx, self.cy, self.span = float(cx), float(cy), float(span)
+        self.size, self.ss = int(size), int(ss)
+        nbytes = lib().dsu_mesh_render_ortho_workspace_bytes(self.F, self.size)
+        if nbytes < 0:
+            check(int(nbytes), "dsu_mesh_render_ortho_workspace_bytes")
+        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.screen.device)
+        self.bins = (nbytes // 4 - 1) // 3
+        self.items = None
+
+    def _call(self, stage, colour=None, pos=None, outs=(None,) * 6):
+        items = self.items
+        check(lib().dsu_mesh_render_ortho(
+            stage, ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), ptr(colour), ptr(pos),
+            self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss,
+            ptr(self.workspace), self.workspace.numel() * 4, ptr(items),
+            0 if items is None else items.numel(), *[ptr(o) for o in outs], stream()),
+            "dsu_mesh_render_ortho")
+
+    def count(self):
+        self._call(RENDER_COUNT)
+
+    def scan(self):
+        nb = self.bins
+        self.workspace[nb] = 0
+        self.workspace[nb + 1:2 * nb + 1] = torch.cumsum(self.workspace[:nb], 0).to(torch.int32)
+        return int(self.workspace[2 * nb])
+
+    def fill(self, total):
+        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.screen.device)[:total]
+        self._call(RENDER_FILL)
+
+    def bin(self):
+        self.count()
+        self.fill(self.scan())
+        return self
+
+    def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames")):
+        """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
+        (F,S,S,4) uint8, face_id (F,N,N) i32, depth (F,N,N) f32, frames (F,6,S,S) f32, pixels
+        (F,S,S,8) f32."""
+        if self.items is None:
+            raise DsuError("MeshRenderPlan.raster before bin()")
+        F, S, N, dev = self.F, self.size, self.size * self.ss, self.screen.device
+        shapes = {"color_u8": ((F, S, S, 4), torch.uint8), "pos_u8": ((F, S, S, 4), torch.uint8),
+                  "face_id": ((F, N, N), torch.int32), "depth": ((F, N, N), torch.float32),
+                  "frames": ((F, 6, S, S), torch.float32), "pixels": ((F, S, S, 8), torch.float32)}
+        bad = [w for w in want if w not in shapes]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
+        colour, pos = _f32c(colour), _f32c(pos)
+        if colour.shape != (self.V, 3) or pos.shape != (self.V, 3):
+            raise ValueError("colour and pos must be (V,3)")
+        self._call(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
+        return out
+
+
+def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
+                      want=("color_u8", "pos_u8", "frames")):
+    """Orthographic render of F frames of one vertex-coloured mesh with two attribute sets
+    (include/dsu_hip.h, dsu_mesh_render_ortho): bin, then rasterise and resolve."""
+    return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want)
+
+
+def pos_edge_u8(pos_rgba):
+    """run_render.py's pos2edge, stored inverted: pos_rgba (F,H,W,4) uint8 -> (F,H,W) uint8, 255 =
+    no edge, 0 = edge."""
+    if pos_rgba.dim() != 4 or pos_rgba.shape[3] != 4:
+        raise ValueError("pos_rgba (F,H,W,4) expected")
+    F, H, W = pos_rgba.shape[:3]
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=pos_rgba.device)
+    check(lib().dsu_pos_edge_u8(ptr(pos_rgba, torch.uint8), F, H, W, ptr(out), stream()),
+          "dsu_pos_edge_u8")
+    return out

@@ -1021,6 +1021,62 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
                    int32_t g, const int32_t* offsets, const int32_t* items, float* out_rgb,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Frame rendering between reconstruction and stylisation (3_style_translator/run_render.py +
+ * blender_animation.py; csrc/mesh_render.hip): for the rig-free actions the reference's renderer
+ * is an orthographic rasteriser of a vertex-coloured mesh, run once with the colours and once with
+ * the normalised positions.  n_frames frames of one mesh, both attribute sets, in one call.
+ *
+ * Inputs: screen (n_frames, n_verts, 3) f32 per-frame vertices (x right, y up, z towards the
+ * viewer); faces (n_faces, 3) i32; colour, pos (n_verts, 3) f32, clamped to [0, 1]; the window
+ * centre (cx, cy) and world width span; output side `size` (a multiple of 4, at most 2048);
+ * ss in {1, 2, 4} sub-samples per pixel side.
+ *
+ * Rule.  Fine lattice N = size * ss: sample (R, C) sits at x = cx + ((C + 0.5) / N - 0.5) * span,
+ * y = cy - ((R + 0.5) / N - 0.5) * span, in float64 in this order (it depends on N only).  With the
+ * edge functions of dsu_zray_cast (float64 from the f32 vertices a, b, c)
+ *     w0 = (x - bx)(cy - by) - (y - by)(cx - bx),  w1 = (x - cx)(ay - cy) - (y - cy)(ax - cx),
+ *     w2 = (x - ax)(by - ay) - (y - ay)(bx - ax),  area = w0 + w1 + w2,
+ * a sample is covered when all three are >= 0 or all three are <= 0 and area != 0.  Its depth is
+ * z = (w0 za + w1 zb + w2 zc) / area rounded to f32; the largest z wins, equal z goes to the lowest
+ * face index.  The attributes of the winning face are (w0 va + w1 vb + w2 vc) / area per sample
+ * (rounded to f32).  Per pixel over its ss^2 samples: alpha = covered / ss^2, rgb = the float64
+ * mean over the covered samples in row-major order (straight alpha; 0 where nothing is covered),
+ * uint8 = floor(v * 255 + 0.5).  No products are fused.
+ *
+ * Outputs, each optional (NULL): color_u8, pos_u8 (n_frames, size, size, 4) RGBA; face_id
+ * (n_frames, N, N) i32, -1 = empty; depth (n_frames, N, N) f32, 0 where empty; frames
+ * (n_frames, 6, size, size) f32 = the DatasetFullImages tensor with mask and pos on, formed from the
+ * uint8 values ((u8 / 255 - 0.5) / 0.5 for colour rgb and pos rg, a8 / 255 for the mask: what a PNG
+ * round trip gives); pixels (n_frames, size, size, 8) f32 = colour rgb, alpha, pos rgb, alpha
+ * before quantisation.
+ *
+ * (frame, triangle) pairs are binned onto 16x16-pixel tiles by a counting sort around the
+ * caller's prefix sum, one stage per call on the same arguments:
+ *   DSU_RENDER_COUNT   counts per (frame, tile) bin -> workspace int32 [0, bins)
+ *   (caller)           exclusive prefix sum of the counts -> workspace int32 [bins, 2 bins + 1);
+ *                      its last entry is n_items, the length of `items` (int32, caller-owned)
+ *   DSU_RENDER_FILL    triangle ids into items
+ *   DSU_RENDER_RASTER  one workgroup per bin: visibility in LDS, resolve, all outputs
+ * bins = n_frames * ceil(size / 16)^2; workspace_bytes = (3 bins + 1) * 4. */
+#define DSU_RENDER_COUNT 0
+#define DSU_RENDER_FILL 1
+#define DSU_RENDER_RASTER 2
+int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size);
+int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
+                          const float* colour, const float* pos, int32_t n_frames, int64_t n_verts,
+                          int64_t n_faces, double cx, double cy, double span, int32_t size, int32_t ss,
+                          void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
+                          uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
+                          float* frames, float* pixels, void* stream);
+/* pos2edge (run_render.py:31-57) and the inversion of run_render.py:120 on RGBA8 position images
+ * (n_frames, H, W, 4): channels u8 -> f32 / 255, every channel 2 where alpha8 < 255, per-channel 3x3
+ * Sobel in float64 with reflect-101 borders, magnitude, maximum over the three colour channels,
+ * > 0.3 = edge.  edge (n_frames, H, W) uint8: 255 = no edge, 0 = edge — the edge PNG and the
+ * stylisation path's edge tensor at once. */
+int dsu_pos_edge_u8(const uint8_t* pos_rgba, int32_t n_frames, int32_t H, int32_t W, uint8_t* edge,
+                    void* stream);
+
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
  * triangles.  HOST function on HOST arrays (as in the reference, where trimesh hands the mesh to
