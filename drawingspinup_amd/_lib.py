@@ -172,6 +172,13 @@ _PROTOS = {
     "dsu_mesh_render_ortho": [c_i32, P, P, P, P, c_i32, c_i64, c_i64, C.c_double, C.c_double,
                               C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
     "dsu_pos_edge_u8": [P, c_i32, c_i32, c_i32, P, P],
+    "dsu_bone_visibility_workspace_bytes": [c_i32, c_i32, c_i32],
+    "dsu_bone_visibility": [c_i32, P, P, P, c_i64, c_i64, c_i32, P, C.c_double, C.c_double, C.c_double,
+                            C.c_double, c_i32, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P],
+    "dsu_spd_cg_block_workspace_bytes": [c_i64, c_i32],
+    "dsu_spd_cg_block": [P, P, P, c_i64, c_i64, c_i32, P, P, C.c_double, c_i32, P, c_i64,
+                         C.POINTER(c_i32), C.POINTER(C.c_double), P],
+    "dsu_skin_lbs": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P, P],
     "dsu_point_bin_count": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P],
     "dsu_point_bin_fill": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
     "dsu_knn8_blend": [P, c_i64, P, P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],

@@ -16,9 +16,20 @@ Deviations from the reference (Blender itself is not here to compare against): a
 ss^2 sub-samples stands in for Blender's pixel filter; no view transform or tone curve is applied
 (the reference selects 'Standard'); the turntable's frame count lives in a .blend file that is not
 in the snapshot, so it is a parameter.
+
+Rigged animations: `read_bvh` reads a skeleton and a motion clip, `bone_heat_weights` binds the mesh
+to the skeleton (distances, visibility and the solve on the device, csrc/mesh_skin.hip),
+`animate_mesh` skins every frame on the device and renders it through the same rasteriser.  The
+weighting follows the published bone-heat form, not Blender's source; the view box is taken over
+the deformed vertices where Blender uses the object's bound_box; there is no retargeting and no
+automatic joint placement (`fit_to_mesh` only scales and centres a skeleton); the 30 degree turn
+that blender_animation.py:17-18 applies to two named clips is not restated.  FBX is not read.
 """
 from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
                      read_obj, render_frames, rest_pose, rest_rotate)
+from .skeleton import Clip, Skeleton, fit_to_mesh, read_bvh, rest_clip, skinning_matrices
+from .skin import animate_mesh, bone_heat_weights
 
-__all__ = ["DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
+__all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "fit_to_mesh", "read_bvh", "rest_clip",
+           "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
            "read_obj", "render_frames", "rest_pose", "rest_rotate"]

@@ -30,6 +30,30 @@ __device__ __forceinline__ void reduce_block(const dsu_partial_reduce& r, int bl
   if (d >= 0) r.base[d] += s;
 }
 
+// The float64 form used by the block conjugate gradients (mesh_skin.hip): a workgroup of 256 threads
+// holds G groups of B column accumulators (thread t: column t % B, group t / B; threads past G B
+// idle).  Its partial per column is the sum over the groups in group order, written to dst[0, B);
+// the total of a column is the sum of the workgroups' partials in workgroup order.
+__device__ __forceinline__ void block_column_partials(double acc, double* red /* LDS, 256 doubles */, int B,
+                                                      int G, double* __restrict__ dst) {
+  const int t = threadIdx.x;
+  red[t] = t < G * B ? acc : 0.0;
+  __syncthreads();
+  if (t < B) {
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += red[g * B + t];
+    dst[t] = s;
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ double column_sum(const double* __restrict__ partials, int nblocks, int stride,
+                                             int col) {
+  double s = 0.0;
+  for (int b = 0; b < nblocks; ++b) s += partials[(size_t)b * stride + col];
+  return s;
+}
+
 __host__ __device__ inline int blocks_of(const dsu_partial_reduce& r) { return (r.n + 63) / 64; }
 
 }  // namespace dsu_red

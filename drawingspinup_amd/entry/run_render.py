@@ -5,7 +5,11 @@ for the actions that need no rig: `<uid>/mesh/*.obj` ->
 Without --test the action is `rest_pose` (the training input); with it, `rest_rotate`, the
 reference's fallback for a character without animation files (run_render.py:78-82).  The
 reference starts Blender on a rigged FBX; here the OBJ is rendered on the device
-(drawingspinup_amd.animate).  Names start at 0001.png, as Blender's do and as
+(drawingspinup_amd.animate).  With --test and BVH clips under `<uid>/mesh/bvh_files/`, each clip is an
+action named by its file stem (the reference loops over `fbx_files` the same way, run_render.py:
+79-82): the skeleton is scaled and centred on the mesh (animate.fit_to_mesh), the bone-heat weights
+are computed once and kept in `<uid>/mesh/skin_weights.npz`, and every clip is skinned and rendered
+on the device.  Names start at 0001.png, as Blender's do and as
 DatasetPatches_M.load_image expects; color and pos are RGBA, edge is 8-bit grey.
 """
 import argparse
@@ -13,9 +17,11 @@ import glob
 import os
 import time
 
+import numpy as np
 from PIL import Image
 
 from .. import animate
+from ..animate.skeleton import bvh_files
 
 
 def write_frames(out_dir, rendered):
@@ -29,6 +35,30 @@ def write_frames(out_dir, rendered):
         Image.fromarray(pos[i], "RGBA").save(os.path.join(out_dir, "pos", name))
         Image.fromarray(edge[i], "L").save(os.path.join(out_dir, "edge", name))
     return color.shape[0]
+
+
+def plan_actions(mesh_dir, test):
+    """[(action, bvh path or None)]: rest_pose for training; with --test one action per
+    `bvh_files/*.bvh`, or rest_rotate when there is none."""
+    if not test:
+        return [("rest_pose", None)]
+    clips = bvh_files(os.path.join(mesh_dir, "bvh_files"))
+    if not clips:
+        return [("rest_rotate", None)]
+    return [(os.path.splitext(os.path.basename(p))[0], p) for p in clips]
+
+
+def skin_weights(mesh_dir, verts, faces, skeleton, device):
+    """The bone-heat weights of the mesh for this skeleton, from `skin_weights.npz` when it holds
+    them (same joints, same vertex count), else computed and stored there."""
+    path = os.path.join(mesh_dir, "skin_weights.npz")
+    if os.path.exists(path):
+        with np.load(path) as z:
+            if list(z["joints"]) == list(skeleton.names) and len(z["influences"]) == len(verts):
+                return z["influences"], z["weights"]
+    infl, w = animate.bone_heat_weights(verts, faces, skeleton, device=device)
+    np.savez(path, influences=infl, weights=w, joints=np.asarray(skeleton.names))
+    return infl, w
 
 
 def run(argv=None):
@@ -46,13 +76,20 @@ def run(argv=None):
     verts, faces, colours = animate.read_obj(found[0])
     if colours is None:
         raise ValueError(f"{found[0]} has no vertex colours")
-    action = "rest_rotate" if args.test else "rest_pose"
-    out_dir = os.path.join(args.data_dir, args.uid, "mesh", "blender_render", action)
-    start = time.time()
-    rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
-                                     device=args.device)
-    n = write_frames(out_dir, rendered)
-    print((time.time() - start) / n, n)
+    mesh_dir = os.path.join(args.data_dir, args.uid, "mesh")
+    for action, clip_path in plan_actions(mesh_dir, args.test):
+        out_dir = os.path.join(mesh_dir, "blender_render", action)
+        start = time.time()
+        if clip_path is None:
+            rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
+                                             device=args.device)
+        else:
+            skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
+            weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
+            rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
+                                            ss=args.ss, device=args.device)
+        n = write_frames(out_dir, rendered)
+        print((time.time() - start) / n, n)
     return out_dir, rendered
 
 

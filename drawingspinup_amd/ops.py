@@ -1433,3 +1433,120 @@ def pos_edge_u8(pos_rgba):
     check(lib().dsu_pos_edge_u8(ptr(pos_rgba, torch.uint8), F, H, W, ptr(out), stream()),
           "dsu_pos_edge_u8")
     return out
+
+
+# ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
+SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
+
+
+class BoneVisibilityPlan:
+    """The binning half of dsu_bone_visibility: the triangles of one mesh counted per cell of a
+    uniform 3-D grid over the mesh and the bones, the prefix sum (torch), the ids filled in; and the
+    vertex order (by cell) that keeps a workgroup's segments together.
+    verts (V,3) f32, faces (M,3) i32, bones (B,2,3) f32 on the device."""
+
+    def __init__(self, verts, faces, bones, cells_per_axis=None):
+        import math
+        self.verts, self.faces = _f32c(verts), faces.to(torch.int32).contiguous()
+        self.bones = _f32c(bones)
+        if self.verts.dim() != 2 or self.verts.shape[1] != 3 or self.faces.dim() != 2 or \
+                self.faces.shape[1] != 3 or self.bones.dim() != 3 or self.bones.shape[1:] != (2, 3):
+            raise ValueError("verts (V,3), faces (M,3) and bones (B,2,3) expected")
+        self.V, self.M, self.B = self.verts.shape[0], self.faces.shape[0], self.bones.shape[0]
+        pts = torch.cat([self.verts, self.bones.reshape(-1, 3)], 0).to(torch.float64)
+        lo, hi = pts.amin(0).tolist(), pts.amax(0).tolist()
+        ext = [max(h - l, 0.0) for l, h in zip(lo, hi)]
+        longest = max(max(ext), 1e-9)
+        # about two triangles per occupied cell of a surface: cells ~ sqrt(M / 2) along the longest axis
+        n = cells_per_axis or int(min(128, max(4, math.sqrt(max(self.M, 1) / 2.0))))
+        self.cell = longest / n * (1.0 + 1e-6)
+        self.g = [int(min(256, max(1, math.ceil(e / self.cell)))) for e in ext]
+        self.lo = lo
+        nbytes = lib().dsu_bone_visibility_workspace_bytes(*self.g)
+        if nbytes < 0:
+            check(int(nbytes), "dsu_bone_visibility_workspace_bytes")
+        self.cells = self.g[0] * self.g[1] * self.g[2]
+        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.verts.device)
+        self.items = None
+        c = ((self.verts.to(torch.float64) - pts.new_tensor(lo)) / self.cell).floor().to(torch.int64)
+        c = torch.minimum(c.clamp_(min=0), torch.tensor(self.g, device=c.device) - 1)
+        key = (c[:, 2] * self.g[1] + c[:, 1]) * self.g[0] + c[:, 0]
+        self.order = torch.argsort(key, stable=True).to(torch.int32).contiguous()
+
+    def _call(self, stage, dist=None, visible=None):
+        items = self.items
+        check(lib().dsu_bone_visibility(
+            stage, ptr(self.verts, torch.float32), ptr(self.faces, torch.int32), ptr(self.bones, torch.float32),
+            self.V, self.M, self.B, ptr(self.order, torch.int32), self.lo[0], self.lo[1], self.lo[2],
+            self.cell, self.g[0], self.g[1], self.g[2], ptr(self.workspace), self.workspace.numel() * 4,
+            ptr(items), 0 if items is None else items.numel(), ptr(dist), ptr(visible), stream()),
+            "dsu_bone_visibility")
+
+    def bin(self):
+        nc = self.cells
+        self._call(SKIN_COUNT)
+        self.workspace[nc] = 0
+        self.workspace[nc + 1:2 * nc + 1] = torch.cumsum(self.workspace[:nc], 0).to(torch.int32)
+        total = int(self.workspace[2 * nc])
+        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.verts.device)[:total]
+        self._call(SKIN_FILL)
+        return self
+
+    def run(self):
+        if self.items is None:
+            raise DsuError("BoneVisibilityPlan.run before bin()")
+        dist = torch.empty((self.V, self.B), dtype=torch.float64, device=self.verts.device)
+        visible = torch.empty((self.V, self.B), dtype=torch.uint8, device=self.verts.device)
+        self._call(SKIN_RUN, dist, visible)
+        return dist, visible
+
+
+def bone_visibility(verts, faces, bones, cells_per_axis=None):
+    """For every (vertex, bone): the distance to the bone's segment (V,B) f64 and whether the open
+    segment vertex -> closest point is free of triangles (V,B) uint8 (include/dsu_hip.h,
+    dsu_bone_visibility)."""
+    return BoneVisibilityPlan(verts, faces, bones, cells_per_axis).bin().run()
+
+
+def spd_cg_block(rowptr, cols, vals, rhs, x0=None, tol=1e-10, max_iters=10000):
+    """Jacobi-preconditioned conjugate gradients in float64 for a symmetric positive definite CSR
+    matrix and all columns of rhs (n,B) at once (dsu_spd_cg_block).  Returns (x (n,B) f64,
+    iterations, final relative residuals (B,) as a numpy array)."""
+    import ctypes as C
+    import numpy as np
+    rhs = rhs.to(torch.float64).contiguous()
+    if rhs.dim() != 2:
+        raise ValueError("rhs (n,B) expected")
+    n, B = rhs.shape
+    rowptr, cols = rowptr.to(torch.int32).contiguous(), cols.to(torch.int32).contiguous()
+    vals = vals.to(torch.float64).contiguous()
+    if rowptr.numel() != n + 1 or cols.numel() != vals.numel():
+        raise ValueError("CSR arrays do not match rhs")
+    x = torch.zeros_like(rhs) if x0 is None else x0.to(torch.float64).clone().contiguous()
+    nbytes = lib().dsu_spd_cg_block_workspace_bytes(n, B)
+    if nbytes < 0:
+        check(int(nbytes), "dsu_spd_cg_block_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=rhs.device)
+    iters = C.c_int32(0)
+    res = np.zeros(B, np.float64)
+    check(lib().dsu_spd_cg_block(ptr(rowptr, torch.int32), ptr(cols, torch.int32), ptr(vals, torch.float64),
+                                 n, vals.numel(), B, ptr(rhs, torch.float64), ptr(x, torch.float64),
+                                 float(tol), int(max_iters), ptr(ws), ws.numel() * 8, C.byref(iters),
+                                 res.ctypes.data_as(C.POINTER(C.c_double)), stream()), "dsu_spd_cg_block")
+    return x, int(iters.value), res
+
+
+def skin_lbs(rest, influences, weights, matrices):
+    """Linear-blend skinning (dsu_skin_lbs): rest (V,3), influences (V,K) joint indices, weights
+    (V,K), matrices (F,J,3,4) -> (F,V,3) f32 on the device."""
+    rest, weights, matrices = _f32c(rest), _f32c(weights), _f32c(matrices)
+    influences = influences.to(torch.int32).contiguous()
+    if rest.dim() != 2 or rest.shape[1] != 3 or influences.dim() != 2 or weights.shape != influences.shape \
+            or influences.shape[0] != rest.shape[0] or matrices.dim() != 4 or matrices.shape[2:] != (3, 4):
+        raise ValueError("rest (V,3), influences / weights (V,K) and matrices (F,J,3,4) expected")
+    V, K = influences.shape
+    F, J = matrices.shape[:2]
+    out = torch.empty((F, V, 3), dtype=torch.float32, device=rest.device)
+    check(lib().dsu_skin_lbs(ptr(rest, torch.float32), ptr(influences, torch.int32), ptr(weights, torch.float32),
+                             ptr(matrices, torch.float32), V, K, F, J, ptr(out), stream()), "dsu_skin_lbs")
+    return out

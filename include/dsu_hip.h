@@ -1077,6 +1077,82 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
 int dsu_pos_edge_u8(const uint8_t* pos_rgba, int32_t n_frames, int32_t H, int32_t W, uint8_t* edge,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Rigging of the reconstructed mesh (blender_animation.py:38-44: the mesh is bound to the armature
+ * with Blender's automatic bone-heat weights and skinned per frame; csrc/mesh_skin.hip).  The
+ * weighting follows the published bone-heat form (Baran & Popovic, "Automatic rigging and animation
+ * of 3D characters", 2007), not Blender's source.  Host side: drawingspinup_amd/animate/skin.py.
+ *
+ * a. dsu_bone_visibility.  Inputs: verts (n_verts, 3) f32; faces (n_faces, 3) i32; bones
+ * (n_bones, 2, 3) f32, head a and tail b of each bone; order (n_verts) i32 or NULL: the vertex that
+ * thread k takes (a permutation; spatially sorted vertices keep a workgroup's segments together —
+ * the outputs do not depend on it).
+ *
+ * Rule, for vertex p (index i) and bone (a, b), everything in float64 from the f32 inputs, sums of
+ * three terms taken as (x + y) + z, no products are fused:
+ *     ab = b - a,  ap = p - a,  den = ab.ab,  num = ap.ab,
+ *     t = num / den clamped to [0, 1] (t = 0 when den is not > 0),
+ *     q = a + t ab (per coordinate),  e = q - p,  d = sqrt(e.e).
+ * With  [x, y, z] = (x0 (y1 z2 - y2 z1) + x1 (y2 z0 - y0 z2)) + x2 (y0 z1 - y1 z0)  for three vectors
+ * x, y, z (components 0, 1, 2), a triangle (u, v, w) none of whose three indices equals i crosses the
+ * open segment p -> q when, with A = u - p, B = v - p, C = w - p,
+ *     s1 = [A, B, C],  s2 = [u - q, v - q, w - q]:  (s1 > 0 and s2 < 0) or (s1 < 0 and s2 > 0)
+ *                                                   (both ends strictly off the plane, on opposite sides)
+ *     t1 = [e, A, B],  t2 = [e, B, C],  t3 = [e, C, A]:  all three >= 0 or all three <= 0
+ *                                                   (the closed triangle).
+ * visible = no such triangle.  A non-finite d gives visible = 0.  Triangles with an index outside
+ * [0, n_verts) are ignored.
+ * Outputs: dist (n_verts, n_bones) f64 = d; visible (n_verts, n_bones) u8.
+ *
+ * Triangles are binned on a uniform grid — cell (cx, cy, cz) = floor((x - x0) / cell) per axis,
+ * clamped to [0, g - 1], list index (cz gy + cy) gx + cx — into every cell their bounding box
+ * touches, by the counting sort of dsu_mesh_render_ortho, one stage per call on the same arguments:
+ *   DSU_SKIN_COUNT   counts per cell -> workspace int32 [0, cells)
+ *   (caller)         exclusive prefix sum -> workspace int32 [cells, 2 cells + 1); its last entry
+ *                    is n_items, the length of `items` (int32, caller-owned)
+ *   DSU_SKIN_FILL    triangle ids into items
+ *   DSU_SKIN_RUN     one workgroup per (256 vertices, bone): only the cells that the boxes of its
+ *                    segments touch are walked, 256 triangles at a time through LDS; a triangle
+ *                    whose box is apart from a segment's box is not tested against it (they have
+ *                    no point in common).
+ * cells = gx gy gz (each at most 256, at most 2^22 in all); workspace_bytes = (3 cells + 1) * 4. */
+#define DSU_SKIN_COUNT 0
+#define DSU_SKIN_FILL 1
+#define DSU_SKIN_RUN 2
+int64_t dsu_bone_visibility_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
+int dsu_bone_visibility(int32_t stage, const float* verts, const int32_t* faces, const float* bones,
+                        int64_t n_verts, int64_t n_faces, int32_t n_bones, const int32_t* order, double x0,
+                        double y0, double z0, double cell, int32_t gx, int32_t gy, int32_t gz,
+                        void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
+                        double* dist, uint8_t* visible, void* stream);
+/* c. The bone-heat system (L + M H) W = M H P (assembled on the host, once per character) for all
+ * bones at once: Jacobi-preconditioned conjugate gradients in float64 on a symmetric positive
+ * definite matrix in CSR form (rowptr (n + 1) i32, cols (nnz) i32, vals (nnz) f64: device arrays),
+ * rhs and x (n, n_rhs) f64 row-major (a matrix row reads n_rhs contiguous values per neighbour).
+ * x holds the starting guess on entry and the solution on return.  Every column runs its own
+ * recurrence (alpha = r.z / p.Ap, beta = r.z new / r.z old, z = r / diag; a diagonal that is not
+ * > 0 counts as 1; a row's products are added in the order of its entries); the inner products are
+ * fixed-order partial sums — per workgroup in row order, then over the workgroups in order — so
+ * two runs give the same bits.  After every iteration the relative residuals |r| / |b| of the
+ * recurrence (|b| = 0 counts as 1) are compared with tol: the solve stops when every column is
+ * <= tol, or after max_iters iterations.  out_iters (HOST int32) = iterations run; out_residuals
+ * (HOST, n_rhs f64) = the final relative residuals.  Synchronises the stream (one flag per
+ * iteration is read back).  n_rhs <= 256.
+ * workspace_bytes: three (n, n_rhs) vectors, the inverse diagonal and the partial sums. */
+int64_t dsu_spd_cg_block_workspace_bytes(int64_t n, int32_t n_rhs);
+int dsu_spd_cg_block(const int32_t* rowptr, const int32_t* cols, const double* vals, int64_t n, int64_t nnz,
+                     int32_t n_rhs, const double* rhs, double* x, double tol, int32_t max_iters,
+                     void* workspace, int64_t workspace_bytes, int32_t* out_iters, double* out_residuals,
+                     void* stream);
+/* Linear-blend skinning: rest (n_verts, 3) f32, influences (n_verts, K) i32 joint indices, weights
+ * (n_verts, K) f32, matrices (n_frames, n_joints, 3, 4) f32 = [R | t] per frame and joint ->
+ * out (n_frames, n_verts, 3) f32, the `screen` tensor of dsu_mesh_render_ortho:
+ *     y_k = ((R_c0 x + R_c1 y) + R_c2 z) + t_c per coordinate c,  out = sum_k w_k y_k,
+ * accumulated in f32 from 0 in the order k = 0 .. K-1, no products are fused.  An influence
+ * outside [0, n_joints) contributes nothing. */
+int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weights, const float* matrices,
+                 int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints, float* out, void* stream);
+
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
  * triangles.  HOST function on HOST arrays (as in the reference, where trimesh hands the mesh to
