@@ -12,11 +12,40 @@ DEFAULT_SPAN = 1.35     # its ortho_scale (blender_animation.py:71,77; save_mesh
 MAX_SIZE = 2048
 
 
+def _texture_path(obj_path, mtllib):
+    """The first readable map_Kd of the OBJ's material library, or None."""
+    import os
+    folder = os.path.dirname(os.path.abspath(obj_path))
+    mtl = os.path.join(folder, mtllib)
+    if not os.path.isfile(mtl):
+        return None
+    with open(mtl) as fh:
+        for line in fh:
+            p = line.split(None, 1)
+            if len(p) == 2 and p[0] == "map_Kd":
+                tex = os.path.join(folder, p[1].strip())
+                if os.path.isfile(tex):
+                    return tex
+    return None
+
+
+def sample_texture(image, uvs):
+    """Nearest sample of an (S,S,3) uint8 texture under the bake's convention (nsr/uv.py): image
+    row r, column c holds uv * S = (c, S - 1 - r).  -> (N,3) f32 in [0,1]."""
+    S = image.shape[0]
+    t = np.asarray(uvs, np.float64) * S
+    c = np.clip(np.floor(t[:, 0] + 0.5).astype(np.int64), 0, S - 1)
+    r = np.clip(S - 1 - np.floor(t[:, 1] + 0.5).astype(np.int64), 0, S - 1)
+    return (image[r, c, :3].astype(np.float32) / np.float32(255.0)).astype(np.float32)
+
+
 def read_obj(path):
     """Inverse of nsr/mesh.write_obj: `v x y z [r g b]` lines and 1-based triangular faces (`f a b c`,
     `a/b/c` corners accepted).  Returns (verts (V,3) f64, faces (M,3) i64 0-based, colours (V,3) f32
-    or None when no vertex carries a colour)."""
-    verts, cols, faces = [], [], []
+    or None when no vertex carries a colour).  A textured file (nsr/mesh.write_obj_textured: no
+    vertex colours, but `vt`, `mtllib` and a readable square `map_Kd`) returns the texture's nearest
+    sample at each vertex's uv instead — the first uv a vertex is used with, in file order."""
+    verts, cols, faces, vts, corners, mtllib = [], [], [], [], [], None
     with open(path) as fh:
         for line in fh:
             p = line.split()
@@ -26,17 +55,39 @@ def read_obj(path):
                 verts.append([float(x) for x in p[1:4]])
                 if len(p) >= 7:
                     cols.append([float(x) for x in p[4:7]])
+            elif p[0] == "vt":
+                vts.append([float(x) for x in p[1:3]])
+            elif p[0] == "mtllib" and mtllib is None and len(p) > 1:
+                mtllib = line.split(None, 1)[1].strip()
             elif p[0] == "f":
                 if len(p) != 4:
                     raise ValueError(f"{path}: only triangular faces are supported: {line.strip()!r}")
                 faces.append([int(c.split("/")[0]) - 1 for c in p[1:4]])
+                if vts:
+                    corners.append([int(c.split("/")[1]) - 1 if c.count("/") and c.split("/")[1] else -1
+                                    for c in p[1:4]])
     v = np.asarray(verts, np.float64).reshape(-1, 3)
     f = np.asarray(faces, np.int64).reshape(-1, 3)
     if cols and len(cols) != len(verts):
         raise ValueError(f"{path}: some vertices carry a colour and some do not")
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError(f"{path}: face index out of range")
-    return v, f, (np.asarray(cols, np.float32).reshape(-1, 3) if cols else None)
+    if cols:
+        return v, f, np.asarray(cols, np.float32).reshape(-1, 3)
+    tex = _texture_path(path, mtllib) if (vts and mtllib and len(corners) == len(faces)) else None
+    if tex is None:
+        return v, f, None
+    from PIL import Image
+    image = np.array(Image.open(tex).convert("RGB"))
+    vt = np.asarray(vts, np.float64).reshape(-1, 2)
+    ti = np.asarray(corners, np.int64).reshape(-1)
+    if image.shape[0] != image.shape[1] or (ti.size and (ti.min() < 0 or ti.max() >= len(vt))):
+        return v, f, None
+    vi = f.reshape(-1)
+    _, first = np.unique(vi, return_index=True)                        # first use of each vertex
+    colours = np.zeros((len(v), 3), np.float32)
+    colours[vi[first]] = sample_texture(image, vt[ti[first]])
+    return v, f, colours
 
 
 def position_colours(verts):

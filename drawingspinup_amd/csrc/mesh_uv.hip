@@ -1,0 +1,397 @@
+// UV export of the reconstructed mesh (the export_uv branch of save_mesh, mesh_utils.py:65-67 and
+// coloring_utils.py:140-167): axis-projection charts instead of xatlas, and the reference's
+// compute_interpolation_map as a rasteriser of the mesh's own triangles.  Host side:
+// drawingspinup_amd/nsr/uv.py; the rules are stated in full in include/dsu_hip.h and restated in
+// float64 numpy in tests/uv_ref.py.
+//
+//   dsu_uv_face_labels   one thread per face: normal, dominant-axis label, projected area
+//   dsu_uv_components    chart id = smallest face index of the component: every face takes the
+//                        minimum over its same-label neighbours and jumps twice along its own
+//                        pointer (chart[chart[m]]); only thread m writes chart[m], values only fall,
+//                        so in-place updates between the launches' barriers can only be ahead of a
+//                        synchronous sweep and the fixed point is the same
+//   dsu_uv_bake          COUNT / FILL / RASTER like dsu_mesh_render_ortho: faces counting-sorted
+//                        onto 16x16-texel tiles, one workgroup per tile and one thread per texel,
+//                        the tile's faces walked through LDS 256 at a time (15 KB: ten workgroups
+//                        fit a CU's LDS, the four waves of a workgroup cover the four SIMDs).  Every
+//                        thread keeps its own lowest covering face, so no atomics and no dependence
+//                        on the order of the tile's list
+//   dsu_uv_dilate        one gutter round per launch, integer arithmetic
+// No floating-point atomics anywhere: two runs give the same bits.
+#include "common.h"
+
+namespace {
+
+constexpr int UV_TILE = 16;
+constexpr int UV_BATCH = 256;
+
+__device__ __forceinline__ bool uv_face(const int32_t* __restrict__ faces, int64_t m, int64_t V, int& ia,
+                                        int& ib, int& ic) {
+  ia = faces[m * 3];
+  ib = faces[m * 3 + 1];
+  ic = faces[m * 3 + 2];
+  return ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V;
+}
+
+__global__ __launch_bounds__(256) void uv_face_labels_kernel(const float* __restrict__ verts,
+                                                             const int32_t* __restrict__ faces, int64_t V,
+                                                             int64_t M, double* __restrict__ normal,
+                                                             int32_t* __restrict__ label,
+                                                             double* __restrict__ area) {
+  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  int ia, ib, ic;
+  double n[3] = {0.0, 0.0, 0.0};
+  int lab = -1;
+  double ar = 0.0;
+  if (uv_face(faces, m, V, ia, ib, ic)) {
+    double a[3], e1[3], e2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      a[k] = verts[(int64_t)ia * 3 + k];
+      e1[k] = (double)verts[(int64_t)ib * 3 + k] - a[k];
+      e2[k] = (double)verts[(int64_t)ic * 3 + k] - a[k];
+    }
+    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    const double m0 = fabs(n[0]), m1 = fabs(n[1]), m2 = fabs(n[2]);
+    // a non-finite normal fails every comparison below and stays degenerate
+    if (m0 > 0.0 || m1 > 0.0 || m2 > 0.0) {
+      if (isfinite(m0) && isfinite(m1) && isfinite(m2)) {
+        int ax = 0;
+        double best = m0;
+        if (m1 > best) { ax = 1; best = m1; }
+        if (m2 > best) { ax = 2; best = m2; }
+        lab = 2 * ax + (n[ax] < 0.0 ? 1 : 0);
+        ar = 0.5 * best;
+      }
+    }
+    if (lab < 0) n[0] = n[1] = n[2] = 0.0;
+  }
+  normal[m * 3] = n[0];
+  normal[m * 3 + 1] = n[1];
+  normal[m * 3 + 2] = n[2];
+  label[m] = lab;
+  area[m] = ar;
+}
+
+// chart values are read while other threads lower them: every value ever stored is a face of the
+// same component, so either reading is valid
+__device__ __forceinline__ int32_t chart_load(const int32_t* p) {
+  return __atomic_load_n(p, __ATOMIC_RELAXED);
+}
+
+__global__ __launch_bounds__(256) void uv_components_round_kernel(const int32_t* __restrict__ adj,
+                                                                  const int32_t* __restrict__ label, int64_t M,
+                                                                  int32_t* chart, int32_t* flag) {
+  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const int32_t lab = label[m];
+  if (lab < 0) return;
+  const int32_t old = chart_load(chart + m);
+  int32_t c = old;
+  if (c < 0 || c > m) return;                        // not the caller's initial state: leave it
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const int32_t nb = adj[m * 3 + e];
+    if (nb < 0 || nb >= M || label[nb] != lab) continue;
+    const int32_t v = chart_load(chart + nb);
+    if (v >= 0 && v < c) c = v;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int32_t v = chart_load(chart + c);
+    if (v >= 0 && v < c) c = v;
+  }
+  if (c < old) {
+    __atomic_store_n(chart + m, c, __ATOMIC_RELAXED);
+    *flag = 1;
+  }
+}
+
+struct UvTri {
+  double ax, ay, bx, by, cx, cy;
+};
+
+// uv * size in float64 from the f32 uv
+__device__ __forceinline__ UvTri uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
+  UvTri t;
+  t.ax = (double)uvs[(int64_t)ia * 2] * S; t.ay = (double)uvs[(int64_t)ia * 2 + 1] * S;
+  t.bx = (double)uvs[(int64_t)ib * 2] * S; t.by = (double)uvs[(int64_t)ib * 2 + 1] * S;
+  t.cx = (double)uvs[(int64_t)ic * 2] * S; t.cy = (double)uvs[(int64_t)ic * 2 + 1] * S;
+  return t;
+}
+
+__device__ __forceinline__ void uv_edges(const UvTri& t, double px, double py, double& w0, double& w1,
+                                         double& w2) {
+  w0 = (t.cx - t.bx) * (py - t.by) - (t.cy - t.by) * (px - t.bx);
+  w1 = (t.ax - t.cx) * (py - t.cy) - (t.ay - t.cy) * (px - t.cx);
+  w2 = (t.bx - t.ax) * (py - t.ay) - (t.by - t.ay) * (px - t.ax);
+}
+
+// Texel range [x0, x1] x [y0, y1] (uv-texel coordinates, y up) of the samples the face can cover:
+// floor / ceil of its bounds, clipped to the atlas.  false: non-finite, or outside.
+__device__ __forceinline__ bool uv_range(const UvTri& t, int S, int& x0, int& x1, int& y0, int& y1) {
+  const double xmin = fmin(fmin(t.ax, t.bx), t.cx), xmax = fmax(fmax(t.ax, t.bx), t.cx);
+  const double ymin = fmin(fmin(t.ay, t.by), t.cy), ymax = fmax(fmax(t.ay, t.by), t.cy);
+  if (!(isfinite(xmin) && isfinite(xmax) && isfinite(ymin) && isfinite(ymax))) return false;
+  const double lim = (double)S + 4.0;
+  x0 = (int)floor(fmin(fmax(xmin, -4.0), lim));
+  x1 = (int)ceil(fmin(fmax(xmax, -4.0), lim));
+  y0 = (int)floor(fmin(fmax(ymin, -4.0), lim));
+  y1 = (int)ceil(fmin(fmax(ymax, -4.0), lim));
+  if (x1 < 0 || y1 < 0 || x0 > S - 1 || y0 > S - 1) return false;
+  x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, S - 1); y1 = min(y1, S - 1);
+  return true;
+}
+
+// MODE 0: counts[tile] += 1; MODE 1: items[offsets[tile] + cursor[tile]++] = face.  tile = ty G + tx.
+template <int MODE>
+__global__ __launch_bounds__(256) void uv_bin_kernel(const float* __restrict__ uvs,
+                                                     const int32_t* __restrict__ faces, int64_t V, int64_t M,
+                                                     int32_t S, int32_t G, int32_t* __restrict__ counts,
+                                                     const int32_t* __restrict__ offsets,
+                                                     int32_t* __restrict__ items, int64_t n_items) {
+  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  int ia, ib, ic;
+  if (!uv_face(faces, m, V, ia, ib, ic)) return;
+  const UvTri t = uv_tri(uvs, ia, ib, ic, (double)S);
+  int x0, x1, y0, y1;
+  if (!uv_range(t, S, x0, x1, y0, y1)) return;
+  for (int ty = y0 / UV_TILE; ty <= y1 / UV_TILE; ++ty)
+    for (int tx = x0 / UV_TILE; tx <= x1 / UV_TILE; ++tx) {
+      const int bin = ty * G + tx;
+      const int k = atomicAdd(&counts[bin], 1);
+      if (MODE == 1) {
+        const int64_t at = (int64_t)offsets[bin] + k;
+        if (at >= 0 && at < n_items) items[at] = (int32_t)m;
+      }
+    }
+}
+
+__device__ __forceinline__ uint8_t uv_quantise(double v) {
+  v = v * 255.0;
+  if (!(v == v)) return 0;                           // the reference's nan -> 0
+  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+  return (uint8_t)(int)v;                            // truncation, as astype(np.uint8)
+}
+
+__global__ __launch_bounds__(256) void uv_raster_kernel(
+    const float* __restrict__ uvs, const int32_t* __restrict__ faces, const float* __restrict__ colours,
+    const double* __restrict__ depth, int64_t V, int64_t M, int32_t S, int32_t G,
+    const int32_t* __restrict__ offsets, const int32_t* __restrict__ items, int64_t n_items,
+    uint8_t* __restrict__ image, int32_t* __restrict__ face_id, uint8_t* __restrict__ demote) {
+  __shared__ UvTri tri[UV_BATCH];
+  __shared__ double dep[UV_BATCH];
+  __shared__ int32_t idx[UV_BATCH];
+  const int tid = threadIdx.x;
+  const int bin = blockIdx.x;
+  const int ty = bin / G, tx = bin - ty * G;
+  const int x = tx * UV_TILE + (tid & (UV_TILE - 1)), y = ty * UV_TILE + tid / UV_TILE;
+  const bool live = x < S && y < S;
+  const double px = (double)x, py = (double)y;
+  int32_t lowest = -1;                               // lowest face covering the sample (edges inclusive)
+  int32_t front = -1;                                // front-most face strictly containing the sample
+  double front_depth = 0.0;
+  const int64_t beg = max((int64_t)offsets[bin], (int64_t)0), end = min((int64_t)offsets[bin + 1], n_items);
+  for (int64_t base = beg; base < end; base += UV_BATCH) {
+    const int n = (int)min((int64_t)UV_BATCH, end - base);
+    __syncthreads();
+    if (tid < n) {
+      const int32_t m = items[base + tid];
+      int ia, ib, ic;
+      int32_t keep = -1;
+      if (m >= 0 && m < M && uv_face(faces, m, V, ia, ib, ic)) {
+        tri[tid] = uv_tri(uvs, ia, ib, ic, (double)S);
+        dep[tid] = depth ? depth[m] : 0.0;
+        keep = m;
+      }
+      idx[tid] = keep;
+    }
+    __syncthreads();
+    if (!live) continue;
+    for (int k = 0; k < n; ++k) {
+      const int32_t m = idx[k];
+      if (m < 0) continue;
+      double w0, w1, w2;
+      uv_edges(tri[k], px, py, w0, w1, w2);
+      if (!(w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0)) continue;
+      if (!((w0 + w1) + w2 > 0.0)) continue;
+      if (lowest < 0 || m < lowest) lowest = m;
+      if (demote && w0 > 0.0 && w1 > 0.0 && w2 > 0.0) {
+        const double d = dep[k];
+        if (front < 0) {
+          front = m; front_depth = d;
+        } else if (d > front_depth || (d == front_depth && m < front)) {
+          demote[front] = 1;
+          front = m; front_depth = d;
+        } else {
+          demote[m] = 1;
+        }
+      }
+    }
+  }
+  if (!live) return;
+  const int64_t at = (int64_t)(S - 1 - y) * S + x;   // image row r samples uv * size = (c, size - 1 - r)
+  uint8_t q[3] = {0, 0, 0};
+  if (lowest >= 0) {
+    int ia, ib, ic;
+    uv_face(faces, lowest, V, ia, ib, ic);           // validated when it was staged
+    const UvTri t = uv_tri(uvs, ia, ib, ic, (double)S);
+    double w0, w1, w2;
+    uv_edges(t, px, py, w0, w1, w2);
+    const double area = (w0 + w1) + w2;
+    const double b0 = w0 / area, b1 = w1 / area, b2 = w2 / area;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      q[ch] = uv_quantise((b0 * (double)colours[(int64_t)ia * 3 + ch] + b1 * (double)colours[(int64_t)ib * 3 + ch]) +
+                          b2 * (double)colours[(int64_t)ic * 3 + ch]);
+  }
+  if (image) {
+    image[at * 3] = q[0];
+    image[at * 3 + 1] = q[1];
+    image[at * 3 + 2] = q[2];
+  }
+  if (face_id) face_id[at] = lowest;
+}
+
+__global__ __launch_bounds__(256) void uv_dilate_kernel(const uint8_t* __restrict__ img_in,
+                                                        const uint8_t* __restrict__ cov_in, int32_t S,
+                                                        uint8_t* __restrict__ img_out,
+                                                        uint8_t* __restrict__ cov_out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)S * S) return;
+  const int r = (int)(i / S), c = (int)(i - (int64_t)r * S);
+  uint32_t out[3] = {0, 0, 0};
+  uint8_t cov = cov_in[i] ? 1 : 0;
+  if (cov) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[ch] = img_in[i * 3 + ch];
+  } else {
+    uint32_t sum[3] = {0, 0, 0}, n = 0;
+    for (int dr = -1; dr <= 1; ++dr)
+      for (int dc = -1; dc <= 1; ++dc) {
+        const int rr = r + dr, cc = c + dc;
+        if ((dr == 0 && dc == 0) || rr < 0 || cc < 0 || rr >= S || cc >= S) continue;
+        const int64_t j = (int64_t)rr * S + cc;
+        if (!cov_in[j]) continue;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) sum[ch] += img_in[j * 3 + ch];
+        ++n;
+      }
+    if (n) {
+      cov = 1;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) out[ch] = (2u * sum[ch] + n) / (2u * n);
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) img_out[i * 3 + ch] = (uint8_t)out[ch];
+  cov_out[i] = cov;
+}
+
+bool uv_size_ok(int32_t size) { return size >= 1 && size <= 8192; }
+
+int64_t uv_tiles(int32_t size) {
+  const int64_t G = (size + UV_TILE - 1) / UV_TILE;
+  return G * G;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsu_uv_face_labels(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces,
+                       double* normal, int32_t* label, double* area, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_verts > (int64_t)1 << 30 || n_faces > (int64_t)1 << 30) return DSU_EINVAL;
+  if (n_faces == 0) return DSU_OK;
+  if (!verts || !faces || !normal || !label || !area || n_verts == 0) return DSU_EINVAL;
+  uv_face_labels_kernel<<<dsu_blocks_for(n_faces, 256), 256, 0, (hipStream_t)stream>>>(
+      verts, faces, n_verts, n_faces, normal, label, area);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_uv_components(const int32_t* adjacency, const int32_t* label, int64_t n_faces, int32_t* chart,
+                      int32_t* flag, int32_t check_every, int32_t max_rounds, int32_t* out_rounds,
+                      void* stream) {
+  if (n_faces < 0 || n_faces > (int64_t)1 << 30 || check_every < 1 || max_rounds < 1) return DSU_EINVAL;
+  if (out_rounds) *out_rounds = 0;
+  if (n_faces == 0) return DSU_OK;
+  if (!adjacency || !label || !chart || !flag) return DSU_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t rounds = 0, host_flag = 1;
+  while (host_flag && rounds < max_rounds) {
+    if (hipMemsetAsync(flag, 0, sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
+    for (int k = 0; k < check_every && rounds < max_rounds; ++k, ++rounds)
+      uv_components_round_kernel<<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(adjacency, label, n_faces,
+                                                                              chart, flag);
+    DSU_CHECK_LAUNCH();
+    if (hipMemcpyAsync(&host_flag, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return DSU_ELAUNCH;
+  }
+  if (out_rounds) *out_rounds = rounds;
+  return host_flag ? DSU_EUNSUP : DSU_OK;
+}
+
+int64_t dsu_uv_bake_workspace_bytes(int32_t size) {
+  if (!uv_size_ok(size)) return DSU_EINVAL;
+  return (3 * uv_tiles(size) + 1) * (int64_t)sizeof(int32_t);
+}
+
+int dsu_uv_bake(int32_t stage, const float* uvs, const int32_t* indices, const float* colours,
+                const double* depth, int64_t n_verts, int64_t n_faces, int32_t size, void* workspace,
+                int64_t workspace_bytes, int32_t* items, int64_t n_items, uint8_t* image, int32_t* face_id,
+                uint8_t* demote, void* stream) {
+  if (stage < DSU_UV_COUNT || stage > DSU_UV_RASTER || !uv_size_ok(size)) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_items < 0 || n_faces > (int64_t)1 << 30 || n_verts > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  const int64_t nb = uv_tiles(size);
+  if (!workspace || workspace_bytes < (3 * nb + 1) * (int64_t)sizeof(int32_t)) return DSU_EINVAL;
+  if (n_faces && (!uvs || !indices || n_verts == 0)) return DSU_EINVAL;
+  if (stage != DSU_UV_COUNT && n_items && !items) return DSU_EINVAL;
+  if (stage == DSU_UV_RASTER && ((n_faces && !colours) || (demote && !depth))) return DSU_EINVAL;
+  int32_t* counts = (int32_t*)workspace;
+  int32_t* offsets = counts + nb;                    // nb + 1 entries, written by the caller between the stages
+  int32_t* cursor = offsets + nb + 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t G = (size + UV_TILE - 1) / UV_TILE;
+  if (stage == DSU_UV_COUNT) {
+    if (hipMemsetAsync(counts, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
+    if (n_faces)
+      uv_bin_kernel<0><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(uvs, indices, n_verts, n_faces, size, G,
+                                                                     counts, nullptr, nullptr, 0);
+    DSU_CHECK_LAUNCH();
+    return DSU_OK;
+  }
+  if (stage == DSU_UV_FILL) {
+    if (hipMemsetAsync(cursor, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
+    if (n_faces && n_items)
+      uv_bin_kernel<1><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(uvs, indices, n_verts, n_faces, size, G,
+                                                                     cursor, offsets, items, n_items);
+    DSU_CHECK_LAUNCH();
+    return DSU_OK;
+  }
+  if (demote && n_faces && hipMemsetAsync(demote, 0, n_faces, st) != hipSuccess) return DSU_ELAUNCH;
+  uv_raster_kernel<<<(unsigned)nb, 256, 0, st>>>(uvs, indices, colours, depth, n_verts, n_faces, size, G,
+                                                 offsets, items, n_faces ? n_items : 0, image, face_id,
+                                                 demote);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_uv_dilate(const uint8_t* image_in, const uint8_t* covered_in, int32_t size, uint8_t* image_out,
+                  uint8_t* covered_out, void* stream) {
+  if (!uv_size_ok(size) || !image_in || !covered_in || !image_out || !covered_out || image_in == image_out ||
+      covered_in == covered_out)
+    return DSU_EINVAL;
+  uv_dilate_kernel<<<dsu_blocks_for((int64_t)size * size, 256), 256, 0, (hipStream_t)stream>>>(
+      image_in, covered_in, size, image_out, covered_out);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+}  // extern "C"

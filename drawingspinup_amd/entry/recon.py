@@ -126,7 +126,8 @@ def recon(uid, thinning, conf, dev):
     path = save_obj(os.path.join(out, name + ".obj"), mesh["verts"], mesh["faces"], mesh["vert_colors"],
                     ortho_scale=float(ex["ortho_scale"]), smoothing=bool(ex["smoothing"]),
                     shearing=bool(ex["shearing"]), color_back_projection=cbp,
-                    thinning={"mask": fm, "type": ex["thinning_type"]} if thinning else None)
+                    thinning={"mask": fm, "type": ex["thinning_type"]} if thinning else None,
+                    export_uv=bool(ex.get("export_uv", False)))
     torch.save(system.model.state_dict(), os.path.join(out, f"it{system.global_step}.ckpt"))
     return path
 

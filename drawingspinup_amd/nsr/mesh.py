@@ -850,9 +850,43 @@ def write_obj(path, verts, faces, colors=None):
     return path
 
 
+def write_obj_textured(path, verts, faces, uvs, image, name):
+    """The OBJ + MTL + PNG triple of a UV-mapped mesh (coloring_utils.uv_mapping + trimesh's export):
+    `<name>.obj` beside `path` with mtllib / usemtl, `v`, `vt` and `f a/a b/b c/c` (one uv per
+    vertex), `<name>.mtl` with SimpleMaterial's values (diffuse, ambient, specular 1, glossiness 0)
+    and map_Kd, `<name>.png`.  Returns the OBJ's path."""
+    from PIL import Image
+    folder = os.path.dirname(os.path.abspath(path))
+    os.makedirs(folder, exist_ok=True)
+    obj = os.path.join(folder, name + ".obj")
+    lines = ["mtllib %s.mtl\n" % name, "usemtl %s\n" % name]
+    for p in verts:
+        lines.append("v %.8f %.8f %.8f\n" % (p[0], p[1], p[2]))
+    for t in np.asarray(uvs, np.float64):
+        lines.append("vt %.9f %.9f\n" % (t[0], t[1]))
+    for t in np.asarray(faces) + 1:
+        lines.append("f %d/%d %d/%d %d/%d\n" % (t[0], t[0], t[1], t[1], t[2], t[2]))
+    with open(obj, "w") as fh:
+        fh.writelines(lines)
+    with open(os.path.join(folder, name + ".mtl"), "w") as fh:
+        fh.write("newmtl %s\nKa 1.00000000 1.00000000 1.00000000\nKd 1.00000000 1.00000000 1.00000000\n"
+                 "Ks 1.00000000 1.00000000 1.00000000\nNs 0.00000000\nmap_Kd %s.png\n" % (name, name))
+    Image.fromarray(np.ascontiguousarray(image, np.uint8)).save(os.path.join(folder, name + ".png"))
+    return obj
+
+
 def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
-             color_back_projection=None, thinning=None):
-    """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj."""
+             color_back_projection=None, thinning=None, export_uv=False, texture_size=1024):
+    """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj, or with export_uv
+    (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file."""
     out, fz, c = post_process_mesh(verts, faces, colors, ortho_scale, smoothing, shearing,
                                    color_back_projection, thinning)
+    if export_uv:
+        if c is None:
+            raise ValueError("export_uv needs vertex colours")
+        from .uv import uv_mapping
+        name = os.path.splitext(os.path.basename(path))[0]
+        m = uv_mapping(out, fz, c, name, size=int(texture_size),
+                       device=verts.device if verts.is_cuda else None)
+        return write_obj_textured(path, m["verts"], m["faces"], m["uvs"], m["image"], name)
     return write_obj(path, out, fz, c)

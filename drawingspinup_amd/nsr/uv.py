@@ -1,0 +1,233 @@
+"""The export_uv branch of save_mesh (mesh_utils.py:65-67, coloring_utils.py:140-167) without
+xatlas: axis-projection charts, shelf packing, and the reference's compute_interpolation_map as a
+rasteriser of the mesh's own triangles.
+
+    parametrize(verts, faces)            -> (vmapping, indices, uvs), as xatlas.parametrize
+    bake_vertex_colours(uvs, indices, c) -> (size, size, 3) uint8, as compute_interpolation_map
+    uv_mapping(v, faces, colours, name)  -> the textured mesh, as coloring_utils.uv_mapping
+
+Labels, charts, the atlas raster and the gutter fill run on the device (csrc/mesh_uv.hip, rules in
+include/dsu_hip.h); projection and packing are numpy on the host.
+
+Charts.  A face's label is its normal's dominant axis and sign; a chart is a connected component
+of faces that share a manifold edge and a label, its id the smallest face index in it.  No label
+relaxation is shipped, so every face keeps |n_axis| >= |n| / sqrt(3): MIN_COS.  A chart is
+projected along its axis, the two other axes ordered so that its faces are counter-clockwise in
+uv; one scale (texels per unit length) serves all charts.  A chart that overlaps itself in
+projection is split: the atlas is rasterised, of the faces strictly containing one sample point
+all but the front-most (largest coordinate sum along the viewing side of the axis; lowest index on
+a tie) are demoted to label + 6, and charts, packing and raster are redone — the check therefore
+always runs at the layout that is returned.  After SPLIT_ROUNDS demotions a face still in conflict
+becomes a chart of its own.
+
+Texel convention: the reference's, image row r / column c samples uv * size = (c, size - 1 - r).
+That is half a texel away from the texel-centre convention most viewers assume; the gutter fill
+around every chart is what makes the difference harmless (a bilinear fetch near a chart's border
+reads filled texels, never the empty atlas).
+"""
+import math
+
+import numpy as np
+import torch
+
+MIN_COS = 1.0 / math.sqrt(3.0)
+SPLIT_ROUNDS = 8
+SHRINK = 0.9            # the scale's factor per packing retry
+FILL_TARGET = 0.6       # first scale: the charts' projected area over the atlas area
+
+
+# ------------------------------------------------------------------ host parts
+def shelf_pack(wh, ids, size, gutter):
+    """Boxes (C,2) whole texels (w, h), sorted by (h descending, id), placed left to right on
+    shelves from the bottom: boxes `gutter` apart and `gutter` from the border.  -> (C,2) int64
+    origins (x0, y0) in the input's order, or None when they do not fit."""
+    wh = np.asarray(wh, np.int64).reshape(-1, 2)
+    ids = np.asarray(ids, np.int64)
+    out = np.zeros_like(wh)
+    x = y = int(gutter)
+    shelf = 0
+    for k in np.lexsort((ids, -wh[:, 1])):
+        w, h = int(wh[k, 0]), int(wh[k, 1])
+        if w + 2 * gutter > size:
+            return None
+        if x + w + gutter > size:
+            y += shelf + gutter
+            x, shelf = int(gutter), 0
+        if y + h + gutter > size:
+            return None
+        out[k] = (x, y)
+        x += w + gutter
+        shelf = max(shelf, h)
+    return out
+
+
+def _axes(label):
+    """(axis, u axis, v axis, viewing sign) per base label 0..5; a degenerate face (-1) uses axis 0."""
+    lab = np.where(label < 0, 0, label)
+    a = lab // 2
+    neg = (lab % 2) == 1
+    ua, va = (a + 1) % 3, (a + 2) % 3
+    return a, np.where(neg, va, ua), np.where(neg, ua, va), np.where(neg, -1.0, 1.0)
+
+
+def face_depths(verts, faces, label):
+    """Per face: the sum of its three coordinates along its axis, (a + b) + c in float64, times the
+    viewing sign — larger is nearer the side the chart is seen from."""
+    v = np.asarray(verts, np.float32).astype(np.float64)
+    a, _, _, sg = _axes(label)
+    rows = np.arange(len(faces))
+    p = v[faces][rows, :, a]                                           # (M,3)
+    return sg * ((p[:, 0] + p[:, 1]) + p[:, 2])
+
+
+def layout(verts, faces, label, chart, size, gutter, scale=None):
+    """Projection + packing for given labels and chart ids -> (vmapping, indices, uvs, info)."""
+    v = np.asarray(verts, np.float32).astype(np.float64)
+    M = len(faces)
+    ids, face_slot = np.unique(chart, return_inverse=True)
+    Cn = len(ids)
+    first = np.zeros(Cn, np.int64)
+    first[face_slot[::-1]] = np.arange(M)[::-1]                        # any face of the chart: the lowest
+    clabel = label[first]
+    # one new vertex per (old vertex, chart), ordered by (old vertex, chart id)
+    corner_v = faces.reshape(-1)
+    corner_c = np.repeat(chart, 3)
+    key, inv = np.unique(corner_v * np.int64(max(M, 1)) + corner_c, return_inverse=True)
+    vmapping = key // max(M, 1)
+    vchart = key - vmapping * max(M, 1)
+    indices = inv.reshape(M, 3).astype(np.int64)
+    vslot = np.searchsorted(ids, vchart)
+    _, ua, va, _ = _axes(clabel)
+    flat = clabel < 0                                                  # degenerate: a point
+    pu = np.where(flat[vslot], 0.0, v[vmapping, ua[vslot]])
+    pv = np.where(flat[vslot], 0.0, v[vmapping, va[vslot]])
+    lo_u, lo_v = np.full(Cn, np.inf), np.full(Cn, np.inf)
+    hi_u, hi_v = np.full(Cn, -np.inf), np.full(Cn, -np.inf)
+    np.minimum.at(lo_u, vslot, pu); np.minimum.at(lo_v, vslot, pv)
+    np.maximum.at(hi_u, vslot, pu); np.maximum.at(hi_v, vslot, pv)
+    ext = np.stack([hi_u - lo_u, hi_v - lo_v], 1) if Cn else np.zeros((0, 2))
+    if scale is None:
+        e1, e2 = v[faces[:, 1]] - v[faces[:, 0]], v[faces[:, 2]] - v[faces[:, 0]]
+        n = np.cross(e1, e2)
+        a, _, _, _ = _axes(label)
+        total = 0.5 * float(np.abs(n[np.arange(M), a])[label >= 0].sum()) if M else 0.0
+        scale = math.sqrt(FILL_TARGET * size * size / total) if total > 0 else 1.0
+    retries = 0
+    while True:
+        wh = np.ceil(ext * scale).astype(np.int64) + 1                 # samples x0 .. x0 + ceil(extent s)
+        origin = shelf_pack(wh, ids, size, gutter)
+        if origin is not None:
+            break
+        scale *= SHRINK
+        retries += 1
+        if retries > 400:
+            raise ValueError(f"{Cn} charts do not fit a {size}x{size} atlas with gutter {gutter}")
+    U = (pu - lo_u[vslot]) * scale + origin[vslot, 0]
+    W = (pv - lo_v[vslot]) * scale + origin[vslot, 1]
+    uvs = (np.stack([U, W], 1) / float(size)).astype(np.float32)
+    a, _, _, _ = _axes(clabel)
+    info = {"face_chart": chart.astype(np.int64), "chart_ids": ids, "chart_axis": a,
+            "chart_sign": np.where(clabel < 0, 0, clabel % 2), "chart_rect": np.concatenate([origin, wh], 1),
+            "scale": float(scale), "min_cos": MIN_COS, "pack_retries": retries}
+    return vmapping, indices, uvs, info
+
+
+# ------------------------------------------------------------------ device parts
+class DeviceBackend:
+    """The four kernels behind the interface parametrize / bake_vertex_colours use (tests/uv_ref.py
+    has the float64 numpy one)."""
+
+    def __init__(self, device=None):
+        self.dev = torch.device(device if device is not None else "cuda")
+
+    def labels(self, verts, faces):
+        from .. import ops
+        self.faces = torch.from_numpy(np.ascontiguousarray(faces)).to(self.dev)
+        n, lab, ar = ops.uv_face_labels(torch.from_numpy(np.ascontiguousarray(verts, np.float32)).to(self.dev),
+                                        self.faces)
+        self.adjacency = ops.face_adjacency(self.faces)
+        return n.cpu().numpy(), lab.cpu().numpy().astype(np.int64), ar.cpu().numpy()
+
+    def components(self, faces, comp_label):
+        from .. import ops
+        chart, rounds = ops.uv_components(self.adjacency, torch.from_numpy(comp_label.astype(np.int32)).to(self.dev))
+        return chart.cpu().numpy().astype(np.int64), rounds
+
+    def bake(self, uvs, indices, colours, size, depth=None):
+        from .. import ops
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.dev)
+        img, fid, dem = ops.uv_bake(t(uvs, np.float32), t(indices, np.int32), t(colours, np.float32), size,
+                                    None if depth is None else t(depth, np.float64))
+        return img, fid, (None if dem is None else dem.cpu().numpy())
+
+    def dilate(self, image, covered, rounds):
+        from .. import ops
+        return ops.uv_dilate(image, covered, rounds)[0]
+
+    @staticmethod
+    def to_numpy(a):
+        return a.cpu().numpy()
+
+
+def parametrize(verts, faces, size=1024, gutter=2, return_info=False, device=None, scale=None, backend=None):
+    """xatlas.parametrize's contract: vmapping (V',) int64 — new vertex k is old vertex vmapping[k];
+    indices (M,3) int64 with vmapping[indices] == faces; uvs (V',2) float32 in [0,1].  `scale`
+    (texels per unit length) overrides the first scale tried.  With return_info also the dict
+    described in the module's header (face_chart, chart_ids / _axis / _sign / _rect (x0, y0, w, h
+    in uv texels, y up), scale, min_cos, split_rounds, isolated_faces, component_rounds)."""
+    verts = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3))
+    faces = np.ascontiguousarray(np.asarray(faces, np.int64).reshape(-1, 3))
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError("face index out of range")
+    be = backend if backend is not None else DeviceBackend(device)
+    normal, base, area = be.labels(verts, faces)
+    comp = base.copy()
+    depth = face_depths(verts, faces, base)
+    split_rounds = isolated = 0
+    comp_rounds = []
+    zeros = None
+    for _ in range(SPLIT_ROUNDS + len(faces) + 2):
+        chart, rounds = be.components(faces, comp)
+        comp_rounds.append(int(rounds))
+        vmapping, indices, uvs, info = layout(verts, faces, base, chart, size, gutter, scale)
+        if zeros is None or len(zeros) != len(vmapping):
+            zeros = np.zeros((len(vmapping), 3), np.float32)
+        demote = be.bake(uvs, indices, zeros, size, depth)[2]
+        hit = np.nonzero(demote)[0] if len(faces) else np.zeros(0, np.int64)
+        if len(hit) == 0:
+            break
+        if split_rounds < SPLIT_ROUNDS:
+            comp[hit] += 6
+            split_rounds += 1
+        else:
+            comp[hit] = -2                                             # joins nothing: a chart of its own
+            isolated += len(hit)
+    else:
+        raise RuntimeError("uv charts still overlap after the split loop")
+    info.update(split_rounds=split_rounds, isolated_faces=isolated, component_rounds=comp_rounds,
+                label=base, normal=normal, area=area)
+    return (vmapping, indices, uvs, info) if return_info else (vmapping, indices, uvs)
+
+
+def bake_vertex_colours(uvs, indices, colours, size=1024, gutter=2, device=None, backend=None,
+                        return_maps=False):
+    """compute_interpolation_map on the mesh's own triangles: (size, size, 3) uint8, `gutter` rounds
+    of fill around the charts, 0 where nothing reaches.  return_maps: also face_id (size, size)
+    int32 before the fill, -1 where no face covers the sample."""
+    be = backend if backend is not None else DeviceBackend(device)
+    img, fid, _ = be.bake(np.asarray(uvs, np.float32), np.asarray(indices, np.int64),
+                          np.asarray(colours, np.float32).reshape(-1, 3), int(size))
+    out = be.dilate(img, fid >= 0, int(gutter)) if gutter > 0 else img
+    out = be.to_numpy(out)
+    return (out, be.to_numpy(fid)) if return_maps else out
+
+
+def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=None, backend=None):
+    """coloring_utils.uv_mapping: parametrise, duplicate the vertices per chart, bake the colours.
+    Returns the textured mesh as a dict (verts (V',3) f64, faces (M,3) i64, uvs (V',2) f32, image
+    (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference."""
+    v_np = np.asarray(v_np, np.float64).reshape(-1, 3)
+    vmapping, indices, uvs = parametrize(v_np, faces, size, gutter, device=device, backend=backend)
+    image = bake_vertex_colours(uvs, indices, np.asarray(vert_colors, np.float32)[vmapping], size, gutter,
+                                device=device, backend=backend)
+    return {"verts": v_np[vmapping], "faces": indices, "uvs": uvs, "image": image, "name": save_name}

@@ -1435,6 +1435,144 @@ def pos_edge_u8(pos_rgba):
     return out
 
 
+# ------------------------------------------------------------------ uv export (csrc/mesh_uv.hip)
+UV_COUNT, UV_FILL, UV_RASTER = 0, 1, 2
+
+
+def uv_face_labels(verts, faces):
+    """dsu_uv_face_labels: verts (V,3) f32, faces (M,3) on the device -> normal (M,3) f64, label (M)
+    i32 (2 axis + (n_axis < 0), -1 = degenerate), area (M) f64 projected along the axis."""
+    verts, faces = _f32c(verts), faces.to(torch.int32).contiguous()
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("verts (V,3) and faces (M,3) expected")
+    M, dev = faces.shape[0], verts.device
+    normal = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    label = torch.empty(M, dtype=torch.int32, device=dev)
+    area = torch.empty(M, dtype=torch.float64, device=dev)
+    check(lib().dsu_uv_face_labels(ptr(verts, torch.float32), ptr(faces, torch.int32), verts.shape[0], M,
+                                   ptr(normal), ptr(label), ptr(area), stream()), "dsu_uv_face_labels")
+    return normal, label, area
+
+
+def face_adjacency(faces):
+    """(M,3) i32 on the faces' device: the face across edge (a,b), (b,c), (c,a); -1 on a boundary
+    edge and on an edge used by more than two faces (torch sorts: plumbing for dsu_uv_components)."""
+    f = faces.to(torch.int64)
+    M = f.shape[0]
+    if M == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=f.device)
+    a, b = f, f[:, [1, 2, 0]]
+    nv = int(f.max()) + 1
+    key = (torch.minimum(a, b) * nv + torch.maximum(a, b)).reshape(-1)      # slot = 3 face + edge
+    skey, order = torch.sort(key, stable=True)
+    first = torch.ones_like(skey, dtype=torch.bool)
+    first[1:] = skey[1:] != skey[:-1]
+    group = torch.cumsum(first.to(torch.int64), 0) - 1
+    size = torch.bincount(group)[group]
+    pos = torch.arange(len(skey), device=f.device) - torch.nonzero(first).reshape(-1)[group]
+    partner = torch.where(pos == 0, torch.roll(order, -1), torch.roll(order, 1))
+    adj = torch.full((3 * M,), -1, dtype=torch.int64, device=f.device)
+    two = size == 2
+    adj[order[two]] = torch.div(partner[two], 3, rounding_mode="floor")
+    return adj.reshape(M, 3).to(torch.int32).contiguous()
+
+
+def uv_components(adjacency, label, check_every=4, max_rounds=1 << 20):
+    """dsu_uv_components -> (chart (M) i32: the smallest face index of each face's component,
+    rounds launched)."""
+    adjacency, label = adjacency.to(torch.int32).contiguous(), label.to(torch.int32).contiguous()
+    M, dev = label.shape[0], label.device
+    if adjacency.shape != (M, 3):
+        raise ValueError("adjacency (M,3) and label (M) expected")
+    chart = torch.arange(M, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    rounds = C.c_int32(0)
+    check(lib().dsu_uv_components(ptr(adjacency, torch.int32), ptr(label, torch.int32), M, ptr(chart),
+                                  ptr(flag), int(check_every), int(max_rounds), C.byref(rounds), stream()),
+          "dsu_uv_components")
+    return chart, int(rounds.value)
+
+
+class UvBakePlan:
+    """The binning half of dsu_uv_bake for one (uvs, indices, size): faces counted per 16x16-texel
+    tile, the prefix sum (torch), the ids filled in.  uvs (V,2) f32, indices (M,3) on the device."""
+
+    def __init__(self, uvs, indices, size):
+        self.uvs, self.indices = _f32c(uvs), indices.to(torch.int32).contiguous()
+        if self.uvs.dim() != 2 or self.uvs.shape[1] != 2 or self.indices.dim() != 2 or self.indices.shape[1] != 3:
+            raise ValueError("uvs (V,2) and indices (M,3) expected")
+        self.V, self.M, self.size = self.uvs.shape[0], self.indices.shape[0], int(size)
+        nbytes = lib().dsu_uv_bake_workspace_bytes(self.size)
+        if nbytes < 0:
+            check(int(nbytes), "dsu_uv_bake_workspace_bytes")
+        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.uvs.device)
+        self.bins = (nbytes // 4 - 1) // 3
+        self.items = None
+
+    def _call(self, stage, colours=None, depth=None, outs=(None, None, None)):
+        items = self.items
+        check(lib().dsu_uv_bake(stage, ptr(self.uvs, torch.float32), ptr(self.indices, torch.int32),
+                                ptr(colours), ptr(depth), self.V, self.M, self.size, ptr(self.workspace),
+                                self.workspace.numel() * 4, ptr(items), 0 if items is None else items.numel(),
+                                *[ptr(o) for o in outs], stream()), "dsu_uv_bake")
+
+    def count(self):
+        self._call(UV_COUNT)
+
+    def scan(self):
+        nb = self.bins
+        self.workspace[nb] = 0
+        self.workspace[nb + 1:2 * nb + 1] = torch.cumsum(self.workspace[:nb], 0).to(torch.int32)
+        return int(self.workspace[2 * nb])
+
+    def fill(self, total):
+        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.uvs.device)[:total]
+        self._call(UV_FILL)
+
+    def bin(self):
+        self.count()
+        self.fill(self.scan())
+        return self
+
+    def raster(self, colours, depth=None):
+        """-> image (S,S,3) u8, face_id (S,S) i32, demote (M) u8 (None without depth)."""
+        if self.items is None:
+            raise DsuError("UvBakePlan.raster before bin()")
+        S, dev = self.size, self.uvs.device
+        colours = _f32c(colours)
+        if colours.shape != (self.V, 3):
+            raise ValueError("colours must be (V',3)")
+        image = torch.empty((S, S, 3), dtype=torch.uint8, device=dev)
+        face_id = torch.empty((S, S), dtype=torch.int32, device=dev)
+        demote = None
+        if depth is not None:
+            depth = depth.to(torch.float64).contiguous()
+            if depth.shape != (self.M,):
+                raise ValueError("depth must be (M,)")
+            demote = torch.empty(self.M, dtype=torch.uint8, device=dev)
+        self._call(UV_RASTER, colours, depth, (image, face_id, demote))
+        return image, face_id, demote
+
+
+def uv_bake(uvs, indices, colours, size, depth=None):
+    """dsu_uv_bake (include/dsu_hip.h): bin, then rasterise.  No gutter fill: see uv_dilate."""
+    return UvBakePlan(uvs, indices, size).bin().raster(colours, depth)
+
+
+def uv_dilate(image, covered, rounds):
+    """`rounds` launches of dsu_uv_dilate, double-buffered -> (image (S,S,3) u8, covered (S,S) u8)."""
+    image, covered = image.contiguous(), covered.to(torch.uint8).contiguous()
+    S = image.shape[0]
+    if image.shape != (S, S, 3) or covered.shape != (S, S) or image.dtype != torch.uint8:
+        raise ValueError("image (S,S,3) uint8 and covered (S,S) expected")
+    for _ in range(int(rounds)):
+        img2, cov2 = torch.empty_like(image), torch.empty_like(covered)
+        check(lib().dsu_uv_dilate(ptr(image, torch.uint8), ptr(covered, torch.uint8), S, ptr(img2), ptr(cov2),
+                                  stream()), "dsu_uv_dilate")
+        image, covered = img2, cov2
+    return image, covered
+
+
 # ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
 SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
 

@@ -1153,6 +1153,85 @@ int dsu_spd_cg_block(const int32_t* rowptr, const int32_t* cols, const double* v
 int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weights, const float* matrices,
                  int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * UV export (the export_uv branch of save_mesh, mesh_utils.py:65-67; coloring_utils.py:140-167;
+ * csrc/mesh_uv.hip).  The reference parametrises with xatlas and bakes the vertex colours with
+ * scipy's griddata; here the charts are axis projections and the bake rasterises the mesh's own
+ * triangles.  Host side (projection, packing, the split loop): drawingspinup_amd/nsr/uv.py.
+ * Everything below is float64 from the f32 inputs, no products are fused, and no kernel uses a
+ * floating-point atomic: two runs give the same bits.
+ *
+ * a. dsu_uv_face_labels.  verts (n_verts, 3) f32, faces (n_faces, 3) i32.  With e1 = b - a,
+ * e2 = c - a:  n = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,  e1x e2y - e1y e2x);
+ * axis = argmax |n_c| (the lowest axis on a tie);  label = 2 axis + (n_axis < 0);
+ * area = |n_axis| / 2, the area of the face projected along its axis.  A face whose normal is zero
+ * or not finite, or with an index outside [0, n_verts), gets n = 0, label = -1, area = 0.
+ * Outputs: normal (n_faces, 3) f64, label (n_faces) i32, area (n_faces) f64.
+ * (|n_axis| >= |n| / sqrt(3) follows from the argmax: the `min_cos` of the parametrisation.)
+ *
+ * b. dsu_uv_components.  adjacency (n_faces, 3) i32: the face across edge (a,b), (b,c), (c,a), or
+ * -1 where the edge is on a boundary or used by more than two faces; label (n_faces) i32.  Two
+ * faces are joined when they are adjacent and carry the same label >= 0; a face with a negative
+ * label joins nothing.  chart (n_faces) i32 holds chart[m] = m on entry and the smallest face index
+ * of m's component on return.  One round = every face takes the minimum of its own value and its
+ * joined neighbours' values, then twice replaces its value c by chart[c] (pointer jumping); a face
+ * that lowered its value raises `flag` (device int32).  Rounds are launched check_every at a time;
+ * after each group the flag is read back (the stream is synchronised) and the loop ends when no
+ * face changed, or after max_rounds rounds (then DSU_EUNSUP).  out_rounds (HOST int32) = rounds
+ * launched.  Values only fall and only thread m writes chart[m], so the in-place rounds are never
+ * behind a synchronous sweep; on a strip numbered along its length the distance covered at least
+ * doubles per round.
+ *
+ * c. dsu_uv_bake.  uvs (n_verts, 2) f32 in [0, 1]; indices (n_faces, 3) i32; colours (n_verts, 3)
+ * f32; depth (n_faces) f64 or NULL.  Texel convention of compute_interpolation_map (points =
+ * tcoords * shape, X = arange, Y = flip(arange)): image row r, column c samples the point
+ * (x, y) = (c, size - 1 - r) of uv * size — NOT the half-texel centre.  Vertex positions are
+ * (double)u * size, (double)v * size.  With
+ *     w0 = (cx - bx)(y - by) - (cy - by)(x - bx),  w1 = (ax - cx)(y - cy) - (ay - cy)(x - cx),
+ *     w2 = (bx - ax)(y - ay) - (by - ay)(x - ax),  area = (w0 + w1) + w2
+ * (positive inside a counter-clockwise face: the sign opposite to dsu_mesh_render_ortho's),
+ * a face covers the sample when w0 >= 0, w1 >= 0, w2 >= 0 and area > 0 (counter-clockwise faces
+ * only; a face with an index outside [0, n_verts) or a non-finite uv covers nothing).  The lowest
+ * covering face index wins: face_id (size, size) i32, -1 where no face covers.  Its colour is
+ *     ((w0 / area) c_a + (w1 / area) c_b) + (w2 / area) c_c   per channel, summed as written,
+ * uint8 = the value * 255 clipped to [0, 255] and truncated (NaN -> 0): image (size, size, 3) u8,
+ * 0 where uncovered.  demote (n_faces) u8 or NULL (needs depth): a face STRICTLY contains the
+ * sample when w0, w1, w2 > 0; among the faces strictly containing one sample the one with the
+ * largest depth (the lowest index on a tie) is in front, every other one gets demote = 1; faces
+ * never behind another stay 0.  (The packing keeps charts apart, so two such faces belong to one
+ * chart: the chart overlaps itself there.)
+ * Faces are binned onto 16x16-texel tiles (tile (ty, tx) holds x in [16 tx, 16 tx + 15], y
+ * likewise; bin = ty G + tx, G = ceil(size / 16)) by the counting sort of dsu_mesh_render_ortho:
+ *   DSU_UV_COUNT    counts per tile -> workspace int32 [0, tiles)
+ *   (caller)        exclusive prefix sum -> workspace int32 [tiles, 2 tiles + 1); its last entry is
+ *                   n_items, the length of `items` (int32, caller-owned)
+ *   DSU_UV_FILL     face ids into items
+ *   DSU_UV_RASTER   one workgroup per tile, one thread per texel, the tile's faces through LDS 256
+ *                   at a time; every thread keeps its own winners, so the outputs do not depend on
+ *                   the order of the lists
+ * size <= 8192; workspace_bytes = (3 tiles + 1) * 4.
+ *
+ * d. dsu_uv_dilate: one round of the gutter fill.  image_in (size, size, 3) u8, covered_in
+ * (size, size) u8.  A covered texel is copied.  An uncovered texel with at least one covered
+ * texel among its eight neighbours inside the image takes, per channel, the rounded mean
+ * (2 sum + n) / (2 n) in integer arithmetic over those n neighbours and is covered in the output;
+ * any other texel is 0 and uncovered.  In and out must be different buffers. */
+#define DSU_UV_COUNT 0
+#define DSU_UV_FILL 1
+#define DSU_UV_RASTER 2
+int dsu_uv_face_labels(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces,
+                       double* normal, int32_t* label, double* area, void* stream);
+int dsu_uv_components(const int32_t* adjacency, const int32_t* label, int64_t n_faces, int32_t* chart,
+                      int32_t* flag, int32_t check_every, int32_t max_rounds, int32_t* out_rounds,
+                      void* stream);
+int64_t dsu_uv_bake_workspace_bytes(int32_t size);
+int dsu_uv_bake(int32_t stage, const float* uvs, const int32_t* indices, const float* colours,
+                const double* depth, int64_t n_verts, int64_t n_faces, int32_t size, void* workspace,
+                int64_t workspace_bytes, int32_t* items, int64_t n_items, uint8_t* image, int32_t* face_id,
+                uint8_t* demote, void* stream);
+int dsu_uv_dilate(const uint8_t* image_in, const uint8_t* covered_in, int32_t size, uint8_t* image_out,
+                  uint8_t* covered_out, void* stream);
+
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
  * triangles.  HOST function on HOST arrays (as in the reference, where trimesh hands the mesh to
