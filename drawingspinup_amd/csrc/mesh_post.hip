@@ -5,8 +5,8 @@
 // The reference answers them with three CPU / third-party pieces:
 //   * mesh_raycast.raycast(source, (0,0,+-1), mesh=triangles) once per vertex in Python loops —
 //     every ray is parallel to z, so the query is two-dimensional: which triangles cover (x, y),
-//     and at which z.  Here: triangles are binned on a uniform xy grid (counting sort, two
-//     kernels around the caller's prefix sum) and a ray only visits its cell's list.
+//     and at which z.  Here: triangles are binned on a uniform xy grid (the counting sort of
+//     bin_sort.h) and a ray only visits its cell's list.
 //   * pytorch3d's MeshRasterizer used as a silhouette renderer (MaskRenderer.render:
 //     zbuf > -1) — one kernel that marks the pixel centres every triangle covers.
 //   * scipy cKDTree k-nearest neighbours in xy (interpolate_rgb) — the same grid, searched ring
@@ -20,6 +20,8 @@
 // (self_vertex >= 0) meets the triangles incident to that vertex at distance exactly 0 — the
 // reference relies on that (`farthest_result['distance'] == 0` = "nothing in front of me").
 #include "common.h"
+#include "bin_sort.h"
+#include "mesh_geom.h"
 
 namespace {
 
@@ -33,26 +35,33 @@ __device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g)
   return min(max(c, 0), g - 1);
 }
 
-// MODE 0: counts[cell] += 1 per overlapped cell; MODE 1: items[offsets[cell] + cursor[cell]++] = face
-template <int MODE>
-__global__ __launch_bounds__(256) void zgrid_bin_kernel(const float* __restrict__ tris, int64_t nf,
-                                                        ZGrid gr, int32_t* __restrict__ counts,
-                                                        const int32_t* __restrict__ offsets,
-                                                        int32_t* __restrict__ items) {
-  const int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (f >= nf) return;
-  const float* t = tris + f * 9;
-  const float xmin = fminf(fminf(t[0], t[3]), t[6]), xmax = fmaxf(fmaxf(t[0], t[3]), t[6]);
-  const float ymin = fminf(fminf(t[1], t[4]), t[7]), ymax = fmaxf(fmaxf(t[1], t[4]), t[7]);
-  const int cx0 = cell_of(xmin, gr.x0, gr.inv_cell, gr.g), cx1 = cell_of(xmax, gr.x0, gr.inv_cell, gr.g);
-  const int cy0 = cell_of(ymin, gr.y0, gr.inv_cell, gr.g), cy1 = cell_of(ymax, gr.y0, gr.inv_cell, gr.g);
-  for (int cy = cy0; cy <= cy1; ++cy)
-    for (int cx = cx0; cx <= cx1; ++cx) {
-      const int c = cy * gr.g + cx;
-      const int k = atomicAdd(&counts[c], 1);
-      if (MODE == 1) items[offsets[c] + k] = (int32_t)f;
-    }
-}
+// bin_sort.h source: triangle f goes to every cell its xy box overlaps
+struct TriangleCells {
+  const float* __restrict__ tris;
+  ZGrid gr;
+  __device__ __forceinline__ int32_t id(int64_t f) const { return (int32_t)f; }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t f, Emit emit) const {
+    const float* t = tris + f * 9;
+    const float xmin = fminf(fminf(t[0], t[3]), t[6]), xmax = fmaxf(fmaxf(t[0], t[3]), t[6]);
+    const float ymin = fminf(fminf(t[1], t[4]), t[7]), ymax = fmaxf(fmaxf(t[1], t[4]), t[7]);
+    const int cx0 = cell_of(xmin, gr.x0, gr.inv_cell, gr.g), cx1 = cell_of(xmax, gr.x0, gr.inv_cell, gr.g);
+    const int cy0 = cell_of(ymin, gr.y0, gr.inv_cell, gr.g), cy1 = cell_of(ymax, gr.y0, gr.inv_cell, gr.g);
+    for (int cy = cy0; cy <= cy1; ++cy)
+      for (int cx = cx0; cx <= cx1; ++cx) emit(cy * gr.g + cx);
+  }
+};
+
+// bin_sort.h source: point i goes to its cell (the k-NN search's bins)
+struct PointCells {
+  const float* __restrict__ xy;
+  ZGrid gr;
+  __device__ __forceinline__ int32_t id(int64_t i) const { return (int32_t)i; }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t i, Emit emit) const {
+    emit(cell_of(xy[i * 2 + 1], gr.y0, gr.inv_cell, gr.g) * gr.g + cell_of(xy[i * 2], gr.x0, gr.inv_cell, gr.g));
+  }
+};
 
 // one ray per thread
 __global__ __launch_bounds__(256) void zray_cast_kernel(
@@ -75,15 +84,12 @@ __global__ __launch_bounds__(256) void zray_cast_kernel(
     if (sv >= 0 && (faces[f * 3] == sv || faces[f * 3 + 1] == sv || faces[f * 3 + 2] == sv)) {
       th = 0.0f;                               // incident triangle: met at the origin itself
     } else {
-      const double px = ox, py = oy;
-      const double ax = t[0], ay = t[1], bx = t[3], by = t[4], cx = t[6], cy = t[7];
-      const double w0 = (px - bx) * (cy - by) - (py - by) * (cx - bx);   // edge b->c, weight of a
-      const double w1 = (px - cx) * (ay - cy) - (py - cy) * (ax - cx);   // edge c->a, weight of b
-      const double w2 = (px - ax) * (by - ay) - (py - ay) * (bx - ax);   // edge a->b, weight of c
+      const TriXY xy{t[0], t[1], t[3], t[4], t[6], t[7]};
+      double w0, w1, w2;
+      edge_functions(xy, ox, oy, w0, w1, w2);
       const double area = w0 + w1 + w2;
       if (area == 0.0) continue;
-      const bool inside = (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
-      if (!inside) continue;
+      if (!covers(w0, w1, w2)) continue;
       const double z = (w0 * (double)t[2] + w1 * (double)t[5] + w2 * (double)t[8]) / area;
       th = (float)((z - (double)oz) * (double)sign);
       if (!(th >= 0.0f)) continue;
@@ -109,13 +115,12 @@ __global__ __launch_bounds__(256) void raster_mask_kernel(const float* __restric
   const int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (f >= nf) return;
   const float* t = tris + f * 9;
-  const double ax = (double)t[0] * scale, ay = (double)t[1] * scale;
-  const double bx = (double)t[3] * scale, by = (double)t[4] * scale;
-  const double cx = (double)t[6] * scale, cy = (double)t[7] * scale;
-  const double area = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+  const TriXY xy{(double)t[0] * scale, (double)t[1] * scale, (double)t[3] * scale,
+                 (double)t[4] * scale, (double)t[6] * scale, (double)t[7] * scale};
+  const double area = (xy.bx - xy.ax) * (xy.cy - xy.ay) - (xy.by - xy.ay) * (xy.cx - xy.ax);
   if (area == 0.0) return;
-  const double xmin = fmin(fmin(ax, bx), cx), xmax = fmax(fmax(ax, bx), cx);
-  const double ymin = fmin(fmin(ay, by), cy), ymax = fmax(fmax(ay, by), cy);
+  const double xmin = fmin(fmin(xy.ax, xy.bx), xy.cx), xmax = fmax(fmax(xy.ax, xy.bx), xy.cx);
+  const double ymin = fmin(fmin(xy.ay, xy.by), xy.cy), ymax = fmax(fmax(xy.ay, xy.by), xy.cy);
   // x = (2c + 1) / res - 1  ->  c = ((x + 1) res - 1) / 2 ;  y = 1 - (2r + 1) / res  ->  r = ((1 - y) res - 1) / 2
   int c0 = (int)ceil(((xmin + 1.0) * res - 1.0) * 0.5), c1 = (int)floor(((xmax + 1.0) * res - 1.0) * 0.5);
   int r0 = (int)ceil(((1.0 - ymax) * res - 1.0) * 0.5), r1 = (int)floor(((1.0 - ymin) * res - 1.0) * 0.5);
@@ -124,11 +129,9 @@ __global__ __launch_bounds__(256) void raster_mask_kernel(const float* __restric
     const double py = 1.0 - (2.0 * r + 1.0) / res;
     for (int c = c0; c <= c1; ++c) {
       const double px = (2.0 * c + 1.0) / res - 1.0;
-      const double w0 = (px - bx) * (cy - by) - (py - by) * (cx - bx);
-      const double w1 = (px - cx) * (ay - cy) - (py - cy) * (ax - cx);
-      const double w2 = (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-      if ((w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0))
-        mask[(size_t)r * res + c] = 255;
+      double w0, w1, w2;
+      edge_functions(xy, px, py, w0, w1, w2);
+      if (covers(w0, w1, w2)) mask[(size_t)r * res + c] = 255;
     }
   }
 }
@@ -220,19 +223,6 @@ __global__ __launch_bounds__(128) void knn_blend_kernel(const double* __restrict
   for (int ch = 0; ch < 3; ++ch) out_rgb[i * 3 + ch] = wsum > 0.0 ? (float)(acc[ch] / wsum) : 0.0f;
 }
 
-// point bins for the k-NN search: MODE as above
-template <int MODE>
-__global__ __launch_bounds__(256) void point_bin_kernel(const float* __restrict__ xy, int64_t n, ZGrid gr,
-                                                        int32_t* __restrict__ counts,
-                                                        const int32_t* __restrict__ offsets,
-                                                        int32_t* __restrict__ items) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int c = cell_of(xy[i * 2 + 1], gr.y0, gr.inv_cell, gr.g) * gr.g + cell_of(xy[i * 2], gr.x0, gr.inv_cell, gr.g);
-  const int k = atomicAdd(&counts[c], 1);
-  if (MODE == 1) items[offsets[c] + k] = (int32_t)i;
-}
-
 bool grid_ok(float cell, int32_t g) { return cell > 0.0f && g >= 1 && g <= 4096; }
 
 }  // namespace
@@ -244,8 +234,7 @@ int dsu_zgrid_count(const float* tris, int64_t n_faces, float x0, float y0, floa
   if (n_faces < 0 || !grid_ok(cell, g) || !counts || (n_faces && !tris)) return DSU_EINVAL;
   if (n_faces == 0) return DSU_OK;
   const ZGrid gr{x0, y0, 1.0f / cell, g};
-  zgrid_bin_kernel<0><<<dsu_blocks_for(n_faces, 256), 256, 0, (hipStream_t)stream>>>(
-      tris, n_faces, gr, counts, nullptr, nullptr);
+  dsu_bin::launch<0>(TriangleCells{tris, gr}, n_faces, counts, nullptr, nullptr, 0, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
@@ -256,8 +245,8 @@ int dsu_zgrid_fill(const float* tris, int64_t n_faces, float x0, float y0, float
     return DSU_EINVAL;
   if (n_faces == 0) return DSU_OK;
   const ZGrid gr{x0, y0, 1.0f / cell, g};
-  zgrid_bin_kernel<1><<<dsu_blocks_for(n_faces, 256), 256, 0, (hipStream_t)stream>>>(
-      tris, n_faces, gr, cursor, offsets, items);
+  dsu_bin::launch<1>(TriangleCells{tris, gr}, n_faces, cursor, offsets, items, dsu_bin::NO_LIMIT,
+                     (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
@@ -304,8 +293,7 @@ int dsu_point_bin_count(const float* xy, int64_t n, float x0, float y0, float ce
   if (n < 0 || !grid_ok(cell, g) || !counts || (n && !xy)) return DSU_EINVAL;
   if (n == 0) return DSU_OK;
   const ZGrid gr{x0, y0, 1.0f / cell, g};
-  point_bin_kernel<0><<<dsu_blocks_for(n, 256), 256, 0, (hipStream_t)stream>>>(xy, n, gr, counts,
-                                                                               nullptr, nullptr);
+  dsu_bin::launch<0>(PointCells{xy, gr}, n, counts, nullptr, nullptr, 0, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
@@ -315,8 +303,7 @@ int dsu_point_bin_fill(const float* xy, int64_t n, float x0, float y0, float cel
   if (n < 0 || !grid_ok(cell, g) || !offsets || !cursor || (n && (!xy || !items))) return DSU_EINVAL;
   if (n == 0) return DSU_OK;
   const ZGrid gr{x0, y0, 1.0f / cell, g};
-  point_bin_kernel<1><<<dsu_blocks_for(n, 256), 256, 0, (hipStream_t)stream>>>(xy, n, gr, cursor,
-                                                                               offsets, items);
+  dsu_bin::launch<1>(PointCells{xy, gr}, n, cursor, offsets, items, dsu_bin::NO_LIMIT, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

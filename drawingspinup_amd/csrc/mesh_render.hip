@@ -8,19 +8,21 @@
 // The rule (include/dsu_hip.h states it in full; tests/frame_render_ref.py restates it in float64):
 //   * fine lattice N = S * ss; sample (R, C) at x = cx + ((C + 0.5) / N - 0.5) * span,
 //     y = cy - ((R + 0.5) / N - 0.5) * span (float64, this order);
-//   * coverage by the three edge functions of mesh_post.hip (float64 from the f32 vertices, both
+//   * coverage by the three edge functions of mesh_geom.h (float64 from the f32 vertices, both
 //     orientations, edges inclusive), area = w0 + w1 + w2 at the sample, area == 0 skipped;
 //   * z = (w0 za + w1 zb + w2 zc) / area rounded to f32: largest z wins, equal z -> lowest face;
 //   * per pixel: alpha = covered / ss^2, attribute = mean over the covered samples.
 //
-// Shape of the work: (frame, triangle) pairs are binned onto 16x16-pixel tiles (counting sort in
-// two launches around the caller's prefix sum, as zgrid_bin_kernel); one workgroup per (frame, tile)
+// Shape of the work: (frame, triangle) pairs are binned onto 16x16-pixel tiles (the counting sort
+// of bin_sort.h); one workgroup per (frame, tile)
 // keeps the tile's (16 ss)^2 sub-samples in LDS as one 64-bit key each — depth as an ordered
 // integer in the high word, the complemented face index in the low word — and walks the tile's
 // list with LDS atomicMax, so the winner does not depend on the order of the list.  The same
 // workgroup then resolves: no global atomics on the frame, no visibility buffer in HBM.
 // LDS: 32 KB of keys + 1 KB of lattice coordinates at ss = 4.
 #include "common.h"
+#include "bin_sort.h"
+#include "mesh_geom.h"
 
 namespace {
 
@@ -31,36 +33,11 @@ struct RenderView {
   int32_t S, ss, N, G;        // output side, sub-samples per pixel side, N = S ss, tiles per side
 };
 
-struct TriXY {
-  double ax, ay, bx, by, cx, cy;
-};
-
-// mesh_post.hip's edge functions: w0 weighs vertex a (edge b->c), w1 b (c->a), w2 c (a->b)
-__device__ __forceinline__ void edge_functions(const TriXY& t, double px, double py, double& w0,
-                                               double& w1, double& w2) {
-  w0 = (px - t.bx) * (t.cy - t.by) - (py - t.by) * (t.cx - t.bx);
-  w1 = (px - t.cx) * (t.ay - t.cy) - (py - t.cy) * (t.ax - t.cx);
-  w2 = (px - t.ax) * (t.by - t.ay) - (py - t.ay) * (t.bx - t.ax);
-}
-
-__device__ __forceinline__ bool covers(double w0, double w1, double w2) {
-  return (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
-}
-
 __device__ __forceinline__ double lattice_x(const RenderView& v, int C) {
   return v.cx + (((double)C + 0.5) / (double)v.N - 0.5) * v.span;
 }
 __device__ __forceinline__ double lattice_y(const RenderView& v, int R) {
   return v.cy - (((double)R + 0.5) / (double)v.N - 0.5) * v.span;
-}
-
-// The three vertex indices of face m, or false when one of them is outside [0, V).
-__device__ __forceinline__ bool face_vertices(const int32_t* __restrict__ faces, int64_t m, int64_t V,
-                                              int& ia, int& ib, int& ic) {
-  ia = faces[m * 3];
-  ib = faces[m * 3 + 1];
-  ic = faces[m * 3 + 2];
-  return ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V;
 }
 
 // Samples whose centre can lie inside the triangle's xy bounding box: floor / ceil of the bounds'
@@ -69,9 +46,9 @@ __device__ __forceinline__ bool face_vertices(const int32_t* __restrict__ faces,
 // false: non-finite vertex, or entirely outside the frame.  The range is clipped to the frame.
 __device__ __forceinline__ bool sample_range(const RenderView& v, const TriXY& t, int& c0, int& c1,
                                              int& r0, int& r1) {
+  if (!finite_xy(t)) return false;
   const double xmin = fmin(fmin(t.ax, t.bx), t.cx), xmax = fmax(fmax(t.ax, t.bx), t.cx);
   const double ymin = fmin(fmin(t.ay, t.by), t.cy), ymax = fmax(fmax(t.ay, t.by), t.cy);
-  if (!(isfinite(xmin) && isfinite(xmax) && isfinite(ymin) && isfinite(ymax))) return false;
   const double n = (double)v.N, lim = n + 4.0;
   const double tc0 = ((xmin - v.cx) / v.span + 0.5) * n - 0.5, tc1 = ((xmax - v.cx) / v.span + 0.5) * n - 0.5;
   const double tr0 = (0.5 - (ymax - v.cy) / v.span) * n - 0.5, tr1 = (0.5 - (ymin - v.cy) / v.span) * n - 0.5;
@@ -92,33 +69,28 @@ __device__ __forceinline__ TriXY load_xy(const float* __restrict__ sv, int ia, i
   return t;
 }
 
-// MODE 0: counts[bin] += 1 for every tile the (frame, triangle) pair may touch;
-// MODE 1: items[offsets[bin] + cursor[bin]++] = triangle.  bin = (frame G + tile_row) G + tile_col.
-template <int MODE>
-__global__ __launch_bounds__(256) void render_bin_kernel(
-    const float* __restrict__ screen, const int32_t* __restrict__ faces, int32_t F, int64_t V,
-    int64_t M, RenderView view, int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
-    int32_t* __restrict__ items, int64_t n_items) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= (int64_t)F * M) return;
-  const int f = (int)(i / M);
-  const int64_t m = i - (int64_t)f * M;
-  int ia, ib, ic;
-  if (!face_vertices(faces, m, V, ia, ib, ic)) return;
-  const TriXY t = load_xy(screen + (int64_t)f * V * 3, ia, ib, ic);
-  int c0, c1, r0, r1;
-  if (!sample_range(view, t, c0, c1, r0, r1)) return;
-  const int T = RT_TILE * view.ss;
-  for (int ty = r0 / T; ty <= r1 / T; ++ty)
-    for (int tx = c0 / T; tx <= c1 / T; ++tx) {
-      const int bin = (f * view.G + ty) * view.G + tx;
-      const int k = atomicAdd(&counts[bin], 1);
-      if (MODE == 1) {
-        const int64_t at = (int64_t)offsets[bin] + k;
-        if (at >= 0 && at < n_items) items[at] = (int32_t)m;
-      }
-    }
-}
+// bin_sort.h source: pair i = frame M + triangle goes to every tile the triangle may touch in that
+// frame, stored as the triangle.  bin = (frame G + tile_row) G + tile_col.
+struct FrameTriangleTiles {
+  const float* __restrict__ screen;
+  const int32_t* __restrict__ faces;
+  int64_t V, M;
+  RenderView view;
+  __device__ __forceinline__ int32_t id(int64_t i) const { return (int32_t)(i - (int64_t)(int)(i / M) * M); }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t i, Emit emit) const {
+    const int f = (int)(i / M);
+    const int64_t m = i - (int64_t)f * M;
+    int ia, ib, ic;
+    if (!face_indices(faces, m, V, ia, ib, ic)) return;
+    const TriXY t = load_xy(screen + (int64_t)f * V * 3, ia, ib, ic);
+    int c0, c1, r0, r1;
+    if (!sample_range(view, t, c0, c1, r0, r1)) return;
+    const int T = RT_TILE * view.ss;
+    for (int ty = r0 / T; ty <= r1 / T; ++ty)
+      for (int tx = c0 / T; tx <= c1 / T; ++tx) emit((f * view.G + ty) * view.G + tx);
+  }
+};
 
 // float -> unsigned with the same order (all finite values and infinities; never 0)
 __device__ __forceinline__ uint32_t ordered_bits(float z) {
@@ -170,7 +142,7 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
     const int m = items[k];
     if (m < 0 || m >= M) continue;
     int ia, ib, ic;
-    if (!face_vertices(faces, m, V, ia, ib, ic)) continue;
+    if (!face_indices(faces, m, V, ia, ib, ic)) continue;
     const TriXY t = load_xy(sv, ia, ib, ic);
     int c0, c1, r0, r1;
     if (!sample_range(view, t, c0, c1, r0, r1)) continue;
@@ -226,7 +198,7 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
       const uint32_t m = ~(uint32_t)key;
       if (m != last) {
         int ia, ib, ic;
-        face_vertices(faces, m, V, ia, ib, ic);      // validated when the key was written
+        face_indices(faces, m, V, ia, ib, ic);      // validated when the key was written
         t = load_xy(sv, ia, ib, ic);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -330,7 +302,7 @@ extern "C" {
 
 int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size) {
   if (n_frames < 1 || n_frames > 4096 || size < 4 || size > 2048 || size % 4) return DSU_EINVAL;
-  return (3 * bins_of(n_frames, size) + 1) * (int64_t)sizeof(int32_t);
+  return dsu_bin::bytes(bins_of(n_frames, size));
 }
 
 int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
@@ -345,32 +317,16 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
       n_verts > (int64_t)1 << 30)
     return DSU_EINVAL;
   const int64_t nb = bins_of(n_frames, size);
-  if (!workspace || workspace_bytes < (3 * nb + 1) * (int64_t)sizeof(int32_t)) return DSU_EINVAL;
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
   if (n_faces && (!screen || !faces || n_verts == 0)) return DSU_EINVAL;
   if (stage != DSU_RENDER_COUNT && n_items && !items) return DSU_EINVAL;
   if (stage == DSU_RENDER_RASTER && n_faces && (!colour || !pos)) return DSU_EINVAL;
-  int32_t* counts = (int32_t*)workspace;
-  int32_t* offsets = counts + nb;            // nb + 1 entries, written by the caller between the stages
-  int32_t* cursor = offsets + nb + 1;
   hipStream_t st = (hipStream_t)stream;
   RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
-  const int64_t pairs = (int64_t)n_frames * n_faces;
-  if (stage == DSU_RENDER_COUNT) {
-    if (hipMemsetAsync(counts, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (pairs)
-      render_bin_kernel<0><<<dsu_blocks_for(pairs, 256), 256, 0, st>>>(
-          screen, faces, n_frames, n_verts, n_faces, view, counts, nullptr, nullptr, 0);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
-  if (stage == DSU_RENDER_FILL) {
-    if (hipMemsetAsync(cursor, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (pairs && n_items)
-      render_bin_kernel<1><<<dsu_blocks_for(pairs, 256), 256, 0, st>>>(
-          screen, faces, n_frames, n_verts, n_faces, view, cursor, offsets, items, n_items);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
+  if (stage != DSU_RENDER_RASTER)
+    return dsu_bin::run_stage(stage, FrameTriangleTiles{screen, faces, n_verts, n_faces, view},
+                              (int64_t)n_frames * n_faces, workspace, nb, items, n_items, st);
+  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
   const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
 #define DSU_RASTER(SS_)                                                                         \
   mesh_raster_resolve_kernel<SS_><<<(unsigned)nb, 256, 0, st>>>(screen, faces, colour, pos, n_verts, \

@@ -10,8 +10,8 @@
 // The rules (include/dsu_hip.h states them in full; tests/skin_ref.py restates them in float64).
 //
 // Shape of the visibility work (the hot one: V * B segments against M triangles): triangles are
-// binned on a uniform 3-D grid by the cells their bounding box touches (counting sort in two
-// launches around the caller's prefix sum, as render_bin_kernel).  One workgroup takes 256
+// binned on a uniform 3-D grid by the cells their bounding box touches (the counting sort of
+// bin_sort.h).  One workgroup takes 256
 // vertices (in the caller's order: sorted by cell, so that they are neighbours) and ONE bone:
 // their segments run side by side, so the union of their boxes is slim.  The workgroup walks the
 // rows of cells of that union box — a row along x is one contiguous range of the item list —
@@ -21,6 +21,8 @@
 // cells is tested several times; the answer is an OR, so the order and the repeats do not matter.
 // The walk stops as soon as every segment of the workgroup is blocked.
 #include "common.h"
+#include "bin_sort.h"
+#include "mesh_geom.h"
 #include "partial_reduce.h"
 
 namespace {
@@ -37,47 +39,32 @@ __device__ __forceinline__ int cell_of(double x, double lo, double cell, int g) 
   return (int)fmin(fmax(t, 0.0), (double)(g - 1));
 }
 
-__device__ __forceinline__ bool face_ok(const int32_t* __restrict__ faces, int64_t m, int64_t V, int& ia,
-                                        int& ib, int& ic) {
-  ia = faces[m * 3];
-  ib = faces[m * 3 + 1];
-  ic = faces[m * 3 + 2];
-  return ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V;
-}
-
-// MODE 0: counts[cell] += 1 for every cell the triangle's box touches; MODE 1: items filled.
-// cell = (cz gy + cy) gx + cx.
-template <int MODE>
-__global__ __launch_bounds__(256) void skin_bin_kernel(const float* __restrict__ verts,
-                                                       const int32_t* __restrict__ faces, int64_t V,
-                                                       int64_t M, SkinGrid g, int32_t* __restrict__ counts,
-                                                       const int32_t* __restrict__ offsets,
-                                                       int32_t* __restrict__ items, int64_t n_items) {
-  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  int ia, ib, ic;
-  if (!face_ok(faces, m, V, ia, ib, ic)) return;
-  int lo[3], hi[3];
-  const double o[3] = {g.x0, g.y0, g.z0};
-  const int n[3] = {g.gx, g.gy, g.gz};
+// bin_sort.h source: triangle m goes to every cell its 3-D box touches.  cell = (cz gy + cy) gx + cx.
+struct TriangleCells3 {
+  const float* __restrict__ verts;
+  const int32_t* __restrict__ faces;
+  int64_t V;
+  SkinGrid g;
+  __device__ __forceinline__ int32_t id(int64_t m) const { return (int32_t)m; }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t m, Emit emit) const {
+    int ia, ib, ic;
+    if (!face_indices(faces, m, V, ia, ib, ic)) return;
+    int lo[3], hi[3];
+    const double o[3] = {g.x0, g.y0, g.z0};
+    const int n[3] = {g.gx, g.gy, g.gz};
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double u = verts[(int64_t)ia * 3 + a], v = verts[(int64_t)ib * 3 + a], w = verts[(int64_t)ic * 3 + a];
-    if (!(isfinite(u) && isfinite(v) && isfinite(w))) return;
-    lo[a] = cell_of(fmin(fmin(u, v), w), o[a], g.cell, n[a]);
-    hi[a] = cell_of(fmax(fmax(u, v), w), o[a], g.cell, n[a]);
+    for (int a = 0; a < 3; ++a) {
+      const double u = verts[(int64_t)ia * 3 + a], v = verts[(int64_t)ib * 3 + a], w = verts[(int64_t)ic * 3 + a];
+      if (!(isfinite(u) && isfinite(v) && isfinite(w))) return;
+      lo[a] = cell_of(fmin(fmin(u, v), w), o[a], g.cell, n[a]);
+      hi[a] = cell_of(fmax(fmax(u, v), w), o[a], g.cell, n[a]);
+    }
+    for (int cz = lo[2]; cz <= hi[2]; ++cz)
+      for (int cy = lo[1]; cy <= hi[1]; ++cy)
+        for (int cx = lo[0]; cx <= hi[0]; ++cx) emit((cz * g.gy + cy) * g.gx + cx);
   }
-  for (int cz = lo[2]; cz <= hi[2]; ++cz)
-    for (int cy = lo[1]; cy <= hi[1]; ++cy)
-      for (int cx = lo[0]; cx <= hi[0]; ++cx) {
-        const int c = (cz * g.gy + cy) * g.gx + cx;
-        const int k = atomicAdd(&counts[c], 1);
-        if (MODE == 1) {
-          const int64_t at = (int64_t)offsets[c] + k;
-          if (at >= 0 && at < n_items) items[at] = (int32_t)m;
-        }
-      }
-}
+};
 
 // ------------------------------------------------------------------ distance and visibility
 // a . (b x c), in this order; no products are fused (-ffp-contract=off)
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(256) void bone_visibility_kernel(
         int ia = -1, ib = -1, ic = -1;
         if (k < end) {
           const int m = items[k];
-          if (m >= 0 && m < M && face_ok(faces, m, V, ia, ib, ic)) {
+          if (m >= 0 && m < M && face_indices(faces, m, V, ia, ib, ic)) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
               tc[a][tid] = verts[(int64_t)ia * 3 + a];
@@ -409,7 +396,7 @@ extern "C" {
 
 int64_t dsu_bone_visibility_workspace_bytes(int32_t gx, int32_t gy, int32_t gz) {
   if (!grid_ok(gx, gy, gz)) return DSU_EINVAL;
-  return (3 * (int64_t)gx * gy * gz + 1) * (int64_t)sizeof(int32_t);
+  return dsu_bin::bytes((int64_t)gx * gy * gz);
 }
 
 int dsu_bone_visibility(int32_t stage, const float* verts, const int32_t* faces, const float* bones,
@@ -423,31 +410,16 @@ int dsu_bone_visibility(int32_t stage, const float* verts, const int32_t* faces,
       n_bones < 1 || n_bones > 65535 || n_verts * n_bones > (int64_t)1 << 31)
     return DSU_EINVAL;
   const int64_t nc = (int64_t)gx * gy * gz;
-  if (!workspace || workspace_bytes < (3 * nc + 1) * (int64_t)sizeof(int32_t)) return DSU_EINVAL;
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nc)) return DSU_EINVAL;
   if (!verts || (n_faces && !faces)) return DSU_EINVAL;
   if (stage != DSU_SKIN_COUNT && n_items && !items) return DSU_EINVAL;
   if (stage == DSU_SKIN_RUN && (!bones || !dist || !visible)) return DSU_EINVAL;
-  int32_t* counts = (int32_t*)workspace;
-  int32_t* offsets = counts + nc;            // nc + 1 entries, written by the caller between the stages
-  int32_t* cursor = offsets + nc + 1;
   hipStream_t st = (hipStream_t)stream;
   const SkinGrid g{x0, y0, z0, cell, gx, gy, gz};
-  if (stage == DSU_SKIN_COUNT) {
-    if (hipMemsetAsync(counts, 0, nc * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (n_faces)
-      skin_bin_kernel<0><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(verts, faces, n_verts, n_faces, g,
-                                                                       counts, nullptr, nullptr, 0);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
-  if (stage == DSU_SKIN_FILL) {
-    if (hipMemsetAsync(cursor, 0, nc * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (n_faces && n_items)
-      skin_bin_kernel<1><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(verts, faces, n_verts, n_faces, g,
-                                                                       cursor, offsets, items, n_items);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
+  if (stage != DSU_SKIN_RUN)
+    return dsu_bin::run_stage(stage, TriangleCells3{verts, faces, n_verts, g}, n_faces, workspace, nc, items,
+                              n_items, st);
+  const int32_t* offsets = dsu_bin::split(workspace, nc).offsets;
   bone_visibility_kernel<<<dim3((unsigned)dsu_blocks_for(n_verts, 256), (unsigned)n_bones), dim3(256), 0, st>>>(
       verts, faces, bones, n_verts, n_faces, n_bones, order, g, offsets, items, n_faces ? n_items : 0, dist,
       visible);

@@ -10,8 +10,8 @@
 //                        pointer (chart[chart[m]]); only thread m writes chart[m], values only fall,
 //                        so in-place updates between the launches' barriers can only be ahead of a
 //                        synchronous sweep and the fixed point is the same
-//   dsu_uv_bake          COUNT / FILL / RASTER like dsu_mesh_render_ortho: faces counting-sorted
-//                        onto 16x16-texel tiles, one workgroup per tile and one thread per texel,
+//   dsu_uv_bake          COUNT / FILL / RASTER: faces counting-sorted onto 16x16-texel tiles
+//                        (bin_sort.h), one workgroup per tile and one thread per texel,
 //                        the tile's faces walked through LDS 256 at a time (15 KB: ten workgroups
 //                        fit a CU's LDS, the four waves of a workgroup cover the four SIMDs).  Every
 //                        thread keeps its own lowest covering face, so no atomics and no dependence
@@ -19,19 +19,13 @@
 //   dsu_uv_dilate        one gutter round per launch, integer arithmetic
 // No floating-point atomics anywhere: two runs give the same bits.
 #include "common.h"
+#include "bin_sort.h"
+#include "mesh_geom.h"
 
 namespace {
 
 constexpr int UV_TILE = 16;
 constexpr int UV_BATCH = 256;
-
-__device__ __forceinline__ bool uv_face(const int32_t* __restrict__ faces, int64_t m, int64_t V, int& ia,
-                                        int& ib, int& ic) {
-  ia = faces[m * 3];
-  ib = faces[m * 3 + 1];
-  ic = faces[m * 3 + 2];
-  return ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V;
-}
 
 __global__ __launch_bounds__(256) void uv_face_labels_kernel(const float* __restrict__ verts,
                                                              const int32_t* __restrict__ faces, int64_t V,
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(256) void uv_face_labels_kernel(const float* __rest
   double n[3] = {0.0, 0.0, 0.0};
   int lab = -1;
   double ar = 0.0;
-  if (uv_face(faces, m, V, ia, ib, ic)) {
+  if (face_indices(faces, m, V, ia, ib, ic)) {
     double a[3], e1[3], e2[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -110,20 +104,18 @@ __global__ __launch_bounds__(256) void uv_components_round_kernel(const int32_t*
   }
 }
 
-struct UvTri {
-  double ax, ay, bx, by, cx, cy;
-};
-
 // uv * size in float64 from the f32 uv
-__device__ __forceinline__ UvTri uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
-  UvTri t;
+__device__ __forceinline__ TriXY uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
+  TriXY t;
   t.ax = (double)uvs[(int64_t)ia * 2] * S; t.ay = (double)uvs[(int64_t)ia * 2 + 1] * S;
   t.bx = (double)uvs[(int64_t)ib * 2] * S; t.by = (double)uvs[(int64_t)ib * 2 + 1] * S;
   t.cx = (double)uvs[(int64_t)ic * 2] * S; t.cy = (double)uvs[(int64_t)ic * 2 + 1] * S;
   return t;
 }
 
-__device__ __forceinline__ void uv_edges(const UvTri& t, double px, double py, double& w0, double& w1,
+// Not mesh_geom.h's edge_functions: the operands are in the other order, every value is the exact
+// negation of the shared form, and uv_raster_kernel accepts this orientation only.
+__device__ __forceinline__ void uv_edges(const TriXY& t, double px, double py, double& w0, double& w1,
                                          double& w2) {
   w0 = (t.cx - t.bx) * (py - t.by) - (t.cy - t.by) * (px - t.bx);
   w1 = (t.ax - t.cx) * (py - t.cy) - (t.ay - t.cy) * (px - t.cx);
@@ -132,10 +124,10 @@ __device__ __forceinline__ void uv_edges(const UvTri& t, double px, double py, d
 
 // Texel range [x0, x1] x [y0, y1] (uv-texel coordinates, y up) of the samples the face can cover:
 // floor / ceil of its bounds, clipped to the atlas.  false: non-finite, or outside.
-__device__ __forceinline__ bool uv_range(const UvTri& t, int S, int& x0, int& x1, int& y0, int& y1) {
+__device__ __forceinline__ bool uv_range(const TriXY& t, int S, int& x0, int& x1, int& y0, int& y1) {
+  if (!finite_xy(t)) return false;
   const double xmin = fmin(fmin(t.ax, t.bx), t.cx), xmax = fmax(fmax(t.ax, t.bx), t.cx);
   const double ymin = fmin(fmin(t.ay, t.by), t.cy), ymax = fmax(fmax(t.ay, t.by), t.cy);
-  if (!(isfinite(xmin) && isfinite(xmax) && isfinite(ymin) && isfinite(ymax))) return false;
   const double lim = (double)S + 4.0;
   x0 = (int)floor(fmin(fmax(xmin, -4.0), lim));
   x1 = (int)ceil(fmin(fmax(xmax, -4.0), lim));
@@ -146,30 +138,24 @@ __device__ __forceinline__ bool uv_range(const UvTri& t, int S, int& x0, int& x1
   return true;
 }
 
-// MODE 0: counts[tile] += 1; MODE 1: items[offsets[tile] + cursor[tile]++] = face.  tile = ty G + tx.
-template <int MODE>
-__global__ __launch_bounds__(256) void uv_bin_kernel(const float* __restrict__ uvs,
-                                                     const int32_t* __restrict__ faces, int64_t V, int64_t M,
-                                                     int32_t S, int32_t G, int32_t* __restrict__ counts,
-                                                     const int32_t* __restrict__ offsets,
-                                                     int32_t* __restrict__ items, int64_t n_items) {
-  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  int ia, ib, ic;
-  if (!uv_face(faces, m, V, ia, ib, ic)) return;
-  const UvTri t = uv_tri(uvs, ia, ib, ic, (double)S);
-  int x0, x1, y0, y1;
-  if (!uv_range(t, S, x0, x1, y0, y1)) return;
-  for (int ty = y0 / UV_TILE; ty <= y1 / UV_TILE; ++ty)
-    for (int tx = x0 / UV_TILE; tx <= x1 / UV_TILE; ++tx) {
-      const int bin = ty * G + tx;
-      const int k = atomicAdd(&counts[bin], 1);
-      if (MODE == 1) {
-        const int64_t at = (int64_t)offsets[bin] + k;
-        if (at >= 0 && at < n_items) items[at] = (int32_t)m;
-      }
-    }
-}
+// bin_sort.h source: face m goes to every tile its texel range touches.  tile = ty G + tx.
+struct FaceTexelTiles {
+  const float* __restrict__ uvs;
+  const int32_t* __restrict__ faces;
+  int64_t V;
+  int32_t S, G;
+  __device__ __forceinline__ int32_t id(int64_t m) const { return (int32_t)m; }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t m, Emit emit) const {
+    int ia, ib, ic;
+    if (!face_indices(faces, m, V, ia, ib, ic)) return;
+    const TriXY t = uv_tri(uvs, ia, ib, ic, (double)S);
+    int x0, x1, y0, y1;
+    if (!uv_range(t, S, x0, x1, y0, y1)) return;
+    for (int ty = y0 / UV_TILE; ty <= y1 / UV_TILE; ++ty)
+      for (int tx = x0 / UV_TILE; tx <= x1 / UV_TILE; ++tx) emit(ty * G + tx);
+  }
+};
 
 __device__ __forceinline__ uint8_t uv_quantise(double v) {
   v = v * 255.0;
@@ -183,7 +169,7 @@ __global__ __launch_bounds__(256) void uv_raster_kernel(
     const double* __restrict__ depth, int64_t V, int64_t M, int32_t S, int32_t G,
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ items, int64_t n_items,
     uint8_t* __restrict__ image, int32_t* __restrict__ face_id, uint8_t* __restrict__ demote) {
-  __shared__ UvTri tri[UV_BATCH];
+  __shared__ TriXY tri[UV_BATCH];
   __shared__ double dep[UV_BATCH];
   __shared__ int32_t idx[UV_BATCH];
   const int tid = threadIdx.x;
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(256) void uv_raster_kernel(
       const int32_t m = items[base + tid];
       int ia, ib, ic;
       int32_t keep = -1;
-      if (m >= 0 && m < M && uv_face(faces, m, V, ia, ib, ic)) {
+      if (m >= 0 && m < M && face_indices(faces, m, V, ia, ib, ic)) {
         tri[tid] = uv_tri(uvs, ia, ib, ic, (double)S);
         dep[tid] = depth ? depth[m] : 0.0;
         keep = m;
@@ -238,8 +224,8 @@ __global__ __launch_bounds__(256) void uv_raster_kernel(
   uint8_t q[3] = {0, 0, 0};
   if (lowest >= 0) {
     int ia, ib, ic;
-    uv_face(faces, lowest, V, ia, ib, ic);           // validated when it was staged
-    const UvTri t = uv_tri(uvs, ia, ib, ic, (double)S);
+    face_indices(faces, lowest, V, ia, ib, ic);           // validated when it was staged
+    const TriXY t = uv_tri(uvs, ia, ib, ic, (double)S);
     double w0, w1, w2;
     uv_edges(t, px, py, w0, w1, w2);
     const double area = (w0 + w1) + w2;
@@ -339,7 +325,7 @@ int dsu_uv_components(const int32_t* adjacency, const int32_t* label, int64_t n_
 
 int64_t dsu_uv_bake_workspace_bytes(int32_t size) {
   if (!uv_size_ok(size)) return DSU_EINVAL;
-  return (3 * uv_tiles(size) + 1) * (int64_t)sizeof(int32_t);
+  return dsu_bin::bytes(uv_tiles(size));
 }
 
 int dsu_uv_bake(int32_t stage, const float* uvs, const int32_t* indices, const float* colours,
@@ -350,31 +336,16 @@ int dsu_uv_bake(int32_t stage, const float* uvs, const int32_t* indices, const f
   if (n_verts < 0 || n_faces < 0 || n_items < 0 || n_faces > (int64_t)1 << 30 || n_verts > (int64_t)1 << 30)
     return DSU_EINVAL;
   const int64_t nb = uv_tiles(size);
-  if (!workspace || workspace_bytes < (3 * nb + 1) * (int64_t)sizeof(int32_t)) return DSU_EINVAL;
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
   if (n_faces && (!uvs || !indices || n_verts == 0)) return DSU_EINVAL;
   if (stage != DSU_UV_COUNT && n_items && !items) return DSU_EINVAL;
   if (stage == DSU_UV_RASTER && ((n_faces && !colours) || (demote && !depth))) return DSU_EINVAL;
-  int32_t* counts = (int32_t*)workspace;
-  int32_t* offsets = counts + nb;                    // nb + 1 entries, written by the caller between the stages
-  int32_t* cursor = offsets + nb + 1;
   hipStream_t st = (hipStream_t)stream;
   const int32_t G = (size + UV_TILE - 1) / UV_TILE;
-  if (stage == DSU_UV_COUNT) {
-    if (hipMemsetAsync(counts, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (n_faces)
-      uv_bin_kernel<0><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(uvs, indices, n_verts, n_faces, size, G,
-                                                                     counts, nullptr, nullptr, 0);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
-  if (stage == DSU_UV_FILL) {
-    if (hipMemsetAsync(cursor, 0, nb * sizeof(int32_t), st) != hipSuccess) return DSU_ELAUNCH;
-    if (n_faces && n_items)
-      uv_bin_kernel<1><<<dsu_blocks_for(n_faces, 256), 256, 0, st>>>(uvs, indices, n_verts, n_faces, size, G,
-                                                                     cursor, offsets, items, n_items);
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
+  if (stage != DSU_UV_RASTER)
+    return dsu_bin::run_stage(stage, FaceTexelTiles{uvs, indices, n_verts, size, G}, n_faces, workspace, nb,
+                              items, n_items, st);
+  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
   if (demote && n_faces && hipMemsetAsync(demote, 0, n_faces, st) != hipSuccess) return DSU_ELAUNCH;
   uv_raster_kernel<<<(unsigned)nb, 256, 0, st>>>(uvs, indices, colours, depth, n_verts, n_faces, size, G,
                                                  offsets, items, n_faces ? n_items : 0, image, face_id,

@@ -1345,11 +1345,52 @@ def knn8_blend(query_xy, known_xy, known_rgb):
     return out
 
 
+# ------------------------------------------------------------------ binning of the staged mesh entry points
+class _BinnedPlan:
+    """The binning half of a staged entry point (csrc/bin_sort.h): stage 0 counts the items per bin
+    into the workspace, the prefix sum is taken here (torch), stage 1 fills the ids in.  A subclass
+    calls _alloc() from its constructor and states its entry point's argument list in _stage()."""
+
+    def _alloc(self, nbytes, name, device):
+        if nbytes < 0:
+            check(int(nbytes), name)
+        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+        self.bins = (nbytes // 4 - 1) // 3          # counts (bins) | offsets (bins + 1) | cursor (bins)
+        self.items = None
+
+    def _bin_args(self):
+        """workspace, workspace_bytes, items, n_items of the entry point."""
+        items = self.items
+        return (ptr(self.workspace), self.workspace.numel() * 4, ptr(items),
+                0 if items is None else items.numel())
+
+    def _stage(self, stage, *args):
+        raise NotImplementedError
+
+    def count(self):
+        self._stage(0)                              # = RENDER_COUNT = UV_COUNT = SKIN_COUNT
+
+    def scan(self):
+        nb = self.bins
+        self.workspace[nb] = 0
+        self.workspace[nb + 1:2 * nb + 1] = torch.cumsum(self.workspace[:nb], 0).to(torch.int32)
+        return int(self.workspace[2 * nb])
+
+    def fill(self, total):
+        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.workspace.device)[:total]
+        self._stage(1)                              # = RENDER_FILL = UV_FILL = SKIN_FILL
+
+    def bin(self):
+        self.count()
+        self.fill(self.scan())
+        return self
+
+
 # ------------------------------------------------------------------ frame rendering (csrc/mesh_render.hip)
 RENDER_COUNT, RENDER_FILL, RENDER_RASTER = 0, 1, 2
 
 
-class MeshRenderPlan:
+class MeshRenderPlan(_BinnedPlan):
     """The binning half of dsu_mesh_render_ortho for one (screen, faces, window): (frame, triangle)
     pairs counted per 16x16-pixel tile, the prefix sum (torch), the triangle ids filled in.
     screen (F,V,3) f32, faces (M,3) i32 on the device; size a multiple of 4 (<= 2048), ss 1 | 2 | 4."""
@@ -1361,39 +1402,14 @@ class MeshRenderPlan:
         self.F, self.V, self.M = self.screen.shape[0], self.screen.shape[1], self.faces.shape[0]
         self.cx, self.cy, self.span = float(cx), float(cy), float(span)
         self.size, self.ss = int(size), int(ss)
-        nbytes = lib().dsu_mesh_render_ortho_workspace_bytes(self.F, self.size)
-        if nbytes < 0:
-            check(int(nbytes), "dsu_mesh_render_ortho_workspace_bytes")
-        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.screen.device)
-        self.bins = (nbytes // 4 - 1) // 3
-        self.items = None
+        self._alloc(lib().dsu_mesh_render_ortho_workspace_bytes(self.F, self.size),
+                    "dsu_mesh_render_ortho_workspace_bytes", self.screen.device)
 
-    def _call(self, stage, colour=None, pos=None, outs=(None,) * 6):
-        items = self.items
+    def _stage(self, stage, colour=None, pos=None, outs=(None,) * 6):
         check(lib().dsu_mesh_render_ortho(
             stage, ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), ptr(colour), ptr(pos),
             self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss,
-            ptr(self.workspace), self.workspace.numel() * 4, ptr(items),
-            0 if items is None else items.numel(), *[ptr(o) for o in outs], stream()),
-            "dsu_mesh_render_ortho")
-
-    def count(self):
-        self._call(RENDER_COUNT)
-
-    def scan(self):
-        nb = self.bins
-        self.workspace[nb] = 0
-        self.workspace[nb + 1:2 * nb + 1] = torch.cumsum(self.workspace[:nb], 0).to(torch.int32)
-        return int(self.workspace[2 * nb])
-
-    def fill(self, total):
-        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.screen.device)[:total]
-        self._call(RENDER_FILL)
-
-    def bin(self):
-        self.count()
-        self.fill(self.scan())
-        return self
+            *self._bin_args(), *[ptr(o) for o in outs], stream()), "dsu_mesh_render_ortho")
 
     def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames")):
         """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
@@ -1412,7 +1428,7 @@ class MeshRenderPlan:
         colour, pos = _f32c(colour), _f32c(pos)
         if colour.shape != (self.V, 3) or pos.shape != (self.V, 3):
             raise ValueError("colour and pos must be (V,3)")
-        self._call(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
+        self._stage(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
         return out
 
 
@@ -1493,7 +1509,7 @@ def uv_components(adjacency, label, check_every=4, max_rounds=1 << 20):
     return chart, int(rounds.value)
 
 
-class UvBakePlan:
+class UvBakePlan(_BinnedPlan):
     """The binning half of dsu_uv_bake for one (uvs, indices, size): faces counted per 16x16-texel
     tile, the prefix sum (torch), the ids filled in.  uvs (V,2) f32, indices (M,3) on the device."""
 
@@ -1502,37 +1518,13 @@ class UvBakePlan:
         if self.uvs.dim() != 2 or self.uvs.shape[1] != 2 or self.indices.dim() != 2 or self.indices.shape[1] != 3:
             raise ValueError("uvs (V,2) and indices (M,3) expected")
         self.V, self.M, self.size = self.uvs.shape[0], self.indices.shape[0], int(size)
-        nbytes = lib().dsu_uv_bake_workspace_bytes(self.size)
-        if nbytes < 0:
-            check(int(nbytes), "dsu_uv_bake_workspace_bytes")
-        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.uvs.device)
-        self.bins = (nbytes // 4 - 1) // 3
-        self.items = None
+        self._alloc(lib().dsu_uv_bake_workspace_bytes(self.size), "dsu_uv_bake_workspace_bytes",
+                    self.uvs.device)
 
-    def _call(self, stage, colours=None, depth=None, outs=(None, None, None)):
-        items = self.items
+    def _stage(self, stage, colours=None, depth=None, outs=(None, None, None)):
         check(lib().dsu_uv_bake(stage, ptr(self.uvs, torch.float32), ptr(self.indices, torch.int32),
-                                ptr(colours), ptr(depth), self.V, self.M, self.size, ptr(self.workspace),
-                                self.workspace.numel() * 4, ptr(items), 0 if items is None else items.numel(),
+                                ptr(colours), ptr(depth), self.V, self.M, self.size, *self._bin_args(),
                                 *[ptr(o) for o in outs], stream()), "dsu_uv_bake")
-
-    def count(self):
-        self._call(UV_COUNT)
-
-    def scan(self):
-        nb = self.bins
-        self.workspace[nb] = 0
-        self.workspace[nb + 1:2 * nb + 1] = torch.cumsum(self.workspace[:nb], 0).to(torch.int32)
-        return int(self.workspace[2 * nb])
-
-    def fill(self, total):
-        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.uvs.device)[:total]
-        self._call(UV_FILL)
-
-    def bin(self):
-        self.count()
-        self.fill(self.scan())
-        return self
 
     def raster(self, colours, depth=None):
         """-> image (S,S,3) u8, face_id (S,S) i32, demote (M) u8 (None without depth)."""
@@ -1550,7 +1542,7 @@ class UvBakePlan:
             if depth.shape != (self.M,):
                 raise ValueError("depth must be (M,)")
             demote = torch.empty(self.M, dtype=torch.uint8, device=dev)
-        self._call(UV_RASTER, colours, depth, (image, face_id, demote))
+        self._stage(UV_RASTER, colours, depth, (image, face_id, demote))
         return image, face_id, demote
 
 
@@ -1577,7 +1569,7 @@ def uv_dilate(image, covered, rounds):
 SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
 
 
-class BoneVisibilityPlan:
+class BoneVisibilityPlan(_BinnedPlan):
     """The binning half of dsu_bone_visibility: the triangles of one mesh counted per cell of a
     uniform 3-D grid over the mesh and the bones, the prefix sum (torch), the ids filled in; and the
     vertex order (by cell) that keeps a workgroup's segments together.
@@ -1600,42 +1592,27 @@ class BoneVisibilityPlan:
         self.cell = longest / n * (1.0 + 1e-6)
         self.g = [int(min(256, max(1, math.ceil(e / self.cell)))) for e in ext]
         self.lo = lo
-        nbytes = lib().dsu_bone_visibility_workspace_bytes(*self.g)
-        if nbytes < 0:
-            check(int(nbytes), "dsu_bone_visibility_workspace_bytes")
-        self.cells = self.g[0] * self.g[1] * self.g[2]
-        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.verts.device)
-        self.items = None
+        self._alloc(lib().dsu_bone_visibility_workspace_bytes(*self.g), "dsu_bone_visibility_workspace_bytes",
+                    self.verts.device)
+        self.cells = self.bins
         c = ((self.verts.to(torch.float64) - pts.new_tensor(lo)) / self.cell).floor().to(torch.int64)
         c = torch.minimum(c.clamp_(min=0), torch.tensor(self.g, device=c.device) - 1)
         key = (c[:, 2] * self.g[1] + c[:, 1]) * self.g[0] + c[:, 0]
         self.order = torch.argsort(key, stable=True).to(torch.int32).contiguous()
 
-    def _call(self, stage, dist=None, visible=None):
-        items = self.items
+    def _stage(self, stage, dist=None, visible=None):
         check(lib().dsu_bone_visibility(
             stage, ptr(self.verts, torch.float32), ptr(self.faces, torch.int32), ptr(self.bones, torch.float32),
             self.V, self.M, self.B, ptr(self.order, torch.int32), self.lo[0], self.lo[1], self.lo[2],
-            self.cell, self.g[0], self.g[1], self.g[2], ptr(self.workspace), self.workspace.numel() * 4,
-            ptr(items), 0 if items is None else items.numel(), ptr(dist), ptr(visible), stream()),
+            self.cell, self.g[0], self.g[1], self.g[2], *self._bin_args(), ptr(dist), ptr(visible), stream()),
             "dsu_bone_visibility")
-
-    def bin(self):
-        nc = self.cells
-        self._call(SKIN_COUNT)
-        self.workspace[nc] = 0
-        self.workspace[nc + 1:2 * nc + 1] = torch.cumsum(self.workspace[:nc], 0).to(torch.int32)
-        total = int(self.workspace[2 * nc])
-        self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.verts.device)[:total]
-        self._call(SKIN_FILL)
-        return self
 
     def run(self):
         if self.items is None:
             raise DsuError("BoneVisibilityPlan.run before bin()")
         dist = torch.empty((self.V, self.B), dtype=torch.float64, device=self.verts.device)
         visible = torch.empty((self.V, self.B), dtype=torch.uint8, device=self.verts.device)
-        self._call(SKIN_RUN, dist, visible)
+        self._stage(SKIN_RUN, dist, visible)
         return dist, visible
 
 
