@@ -177,6 +177,8 @@ _PROTOS = {
     "dsu_uv_bake_workspace_bytes": [c_i32],
     "dsu_uv_bake": [c_i32, P, P, P, P, c_i64, c_i64, c_i32, P, c_i64, P, c_i64, P, P, P, P],
     "dsu_uv_dilate": [P, P, c_i32, P, P, P],
+    "dsu_uv_project": [P, P, P, c_i64, c_i64, c_i32, P, P, c_f32, c_f32, c_f32, c_i32, P, P, P, P, P, P, c_i32,
+                       C.c_double, P, P, P],
     "dsu_bone_visibility_workspace_bytes": [c_i32, c_i32, c_i32],
     "dsu_bone_visibility": [c_i32, P, P, P, c_i64, c_i64, c_i32, P, C.c_double, C.c_double, C.c_double,
                             C.c_double, c_i32, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P],

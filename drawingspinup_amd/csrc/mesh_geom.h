@@ -33,3 +33,32 @@ __device__ __forceinline__ void edge_functions(const TriXY& t, double px, double
 __device__ __forceinline__ bool covers(double w0, double w1, double w2) {
   return (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
 }
+
+// Uniform xy grid of the z-parallel queries (mesh_post.hip builds it, mesh_uv.hip reads it too).
+struct ZGrid {
+  float x0, y0, inv_cell;
+  int32_t g;   // cells per axis
+};
+
+__device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g) {
+  int c = (int)floorf((v - v0) * inv_cell);
+  return min(max(c, 0), g - 1);
+}
+
+// uv * size in float64 from the f32 uv
+__device__ __forceinline__ TriXY uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
+  TriXY t;
+  t.ax = (double)uvs[(int64_t)ia * 2] * S; t.ay = (double)uvs[(int64_t)ia * 2 + 1] * S;
+  t.bx = (double)uvs[(int64_t)ib * 2] * S; t.by = (double)uvs[(int64_t)ib * 2 + 1] * S;
+  t.cx = (double)uvs[(int64_t)ic * 2] * S; t.cy = (double)uvs[(int64_t)ic * 2 + 1] * S;
+  return t;
+}
+
+// The atlas raster's edge functions.  Not edge_functions above: the operands are in the other order,
+// every value is the exact negation of that form, and the uv kernels accept this orientation only.
+__device__ __forceinline__ void uv_edges(const TriXY& t, double px, double py, double& w0, double& w1,
+                                         double& w2) {
+  w0 = (t.cx - t.bx) * (py - t.by) - (t.cy - t.by) * (px - t.bx);
+  w1 = (t.ax - t.cx) * (py - t.cy) - (t.ay - t.cy) * (px - t.cx);
+  w2 = (t.bx - t.ax) * (py - t.ay) - (t.by - t.ay) * (px - t.ax);
+}

@@ -25,16 +25,6 @@
 
 namespace {
 
-struct ZGrid {
-  float x0, y0, inv_cell;
-  int32_t g;   // cells per axis
-};
-
-__device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g) {
-  int c = (int)floorf((v - v0) * inv_cell);
-  return min(max(c, 0), g - 1);
-}
-
 // bin_sort.h source: triangle f goes to every cell its xy box overlaps
 struct TriangleCells {
   const float* __restrict__ tris;

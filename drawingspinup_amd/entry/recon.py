@@ -44,6 +44,8 @@ def parse(argv=None):
     ap.add_argument("--face_count", type=int, default=None)
     ap.add_argument("--resolution", type=int, default=None, help="model.geometry.isosurface.resolution")
     ap.add_argument("--thinning_type", default=None, choices=["double", "front", "back"])
+    ap.add_argument("--texture_source", default=None, choices=["vertex", "drawings"],
+                    help="export.texture_source: what export.export_uv bakes into the atlas")
     for name in ("remeshing", "thinning", "smoothing", "shearing", "color_back_projection"):
         _bool_flag(ap, name)
     ap.add_argument("overrides", nargs="*", help="OmegaConf-style dotlist, e.g. trainer.max_steps=100")
@@ -56,7 +58,8 @@ def parse(argv=None):
                            ("face_count", geo, "face_count"), ("remeshing", geo, "remeshing"),
                            ("thinning", ex, "thinning"), ("smoothing", ex, "smoothing"),
                            ("shearing", ex, "shearing"), ("thinning_type", ex, "thinning_type"),
-                           ("color_back_projection", ex, "color_back_projection")):
+                           ("color_back_projection", ex, "color_back_projection"),
+                           ("texture_source", ex, "texture_source")):
         if getattr(args, key) is not None:
             dst[name] = getattr(args, key)
     if args.max_steps is not None:
@@ -65,6 +68,12 @@ def parse(argv=None):
         sch["gamma"] = C.exp_lr_gamma(args.max_steps, conf["system"]["constant_steps"])
     if args.resolution is not None:
         geo["isosurface"]["resolution"] = args.resolution
+    source = ex.get("texture_source", "vertex")
+    if source not in ("vertex", "drawings"):
+        ap.error(f"export.texture_source must be 'vertex' or 'drawings', not {source!r}")
+    if source == "drawings" and not (ex.get("export_uv", False) and ex["color_back_projection"]):
+        # refused here, before hours of optimisation, not by save_obj after them
+        ap.error("texture_source 'drawings' needs export.export_uv=true and export.color_back_projection on")
     return args, conf
 
 
@@ -127,7 +136,8 @@ def recon(uid, thinning, conf, dev):
                     ortho_scale=float(ex["ortho_scale"]), smoothing=bool(ex["smoothing"]),
                     shearing=bool(ex["shearing"]), color_back_projection=cbp,
                     thinning={"mask": fm, "type": ex["thinning_type"]} if thinning else None,
-                    export_uv=bool(ex.get("export_uv", False)))
+                    export_uv=bool(ex.get("export_uv", False)),
+                    texture_source=str(ex.get("texture_source", "vertex")))
     torch.save(system.model.state_dict(), os.path.join(out, f"it{system.global_step}.ckpt"))
     return path
 

@@ -774,7 +774,7 @@ def nearest_vertex_colors(old_verts, new_verts, colors):
 
 
 def post_process_mesh(verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
-                      color_back_projection=None, thinning=None):
+                      color_back_projection=None, thinning=None, return_projection_frame=False):
     """save_mesh (mesh_utils.py:25-73) up to the file write: halve, swap to the front-facing
     convention (x right, y up, z front), [thinning], [Laplacian smoothing], [colour back-projection
     | nearest-vertex colour transfer], [shear], ortho_scale.  Returns (verts (N,3) f64, faces (M,3)
@@ -785,7 +785,9 @@ def post_process_mesh(verts, faces, colors=None, ortho_scale=1.35, smoothing=Fal
     the nearest-vertex transfer (mesh_utils.py:48-53).  thinning: dict(mask=(res,res) uint8
     character mask, type='double' | 'front' | 'back') runs nsr/thinning.thinning_processing
     (mesh_utils.py:38-39) first; the nearest-vertex colour transfer then reads the thinned
-    vertices, as the reference's does."""
+    vertices, as the reference's does.  return_projection_frame: a fourth value, the vertices
+    (N,3) f64 as color_projection sees them — after thinning and smoothing, before shear and
+    ortho_scale (what nsr/uv.bake_drawings projects the drawings from)."""
     if torch.is_tensor(verts) and verts.is_cuda and thinning is None and \
             (colors is None or color_back_projection is not None):
         # everything stays on the device (the export path: smoothing by Jacobi sweeps, colour
@@ -801,9 +803,11 @@ def post_process_mesh(verts, faces, colors=None, ortho_scale=1.35, smoothing=Fal
             cbp = color_back_projection
             c = color_projection(out.contiguous(), fd, cbp["color_front"], cbp["mask_front"],
                                  cbp["color_back"], res=cbp["color_front"].shape[0]).float().cpu().numpy()
+        frame = out
         if shearing and out.shape[0]:
             out = shear_transformation_device(out)
-        return (out * ortho_scale).cpu().numpy(), fd.cpu().numpy(), c
+        res = ((out * ortho_scale).cpu().numpy(), fd.cpu().numpy(), c)
+        return res + (frame.cpu().numpy(),) if return_projection_frame else res
     v = verts.detach().cpu().numpy().astype(np.float64) * 0.5
     old = np.zeros_like(v)
     old[:, 0], old[:, 1], old[:, 2] = v[:, 0], v[:, 2], -v[:, 1]
@@ -827,9 +831,11 @@ def post_process_mesh(verts, faces, colors=None, ortho_scale=1.35, smoothing=Fal
         c = color_projection(torch.from_numpy(np.ascontiguousarray(out)).to(dev),
                              torch.from_numpy(fz).to(dev), cbp["color_front"], cbp["mask_front"],
                              cbp["color_back"], res=cbp["color_front"].shape[0]).float().cpu().numpy()
+    frame = out
     if shearing and len(out):
         out = shear_transformation(out)
-    return out * ortho_scale, fz, c
+    res = (out * ortho_scale, fz, c)
+    return res + (np.asarray(frame, np.float64),) if return_projection_frame else res
 
 
 def write_obj(path, verts, faces, colors=None):
@@ -876,17 +882,28 @@ def write_obj_textured(path, verts, faces, uvs, image, name):
 
 
 def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
-             color_back_projection=None, thinning=None, export_uv=False, texture_size=1024):
+             color_back_projection=None, thinning=None, export_uv=False, texture_size=1024,
+             texture_source="vertex"):
     """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj, or with export_uv
-    (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file."""
-    out, fz, c = post_process_mesh(verts, faces, colors, ortho_scale, smoothing, shearing,
-                                   color_back_projection, thinning)
+    (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file.
+    texture_source: "vertex" bakes the vertex colours (the reference's texture); "drawings" (an
+    extension, needs export_uv and color_back_projection) projects the front / back drawings of
+    color_back_projection into the atlas texel by texel, the vertex colours filling what neither
+    drawing sees (nsr/uv.bake_drawings)."""
+    if texture_source not in ("vertex", "drawings"):
+        raise ValueError("texture_source must be 'vertex' or 'drawings'")
+    drawings = texture_source == "drawings"
+    if drawings and not (export_uv and color_back_projection is not None):
+        raise ValueError("texture_source='drawings' needs export_uv=True and the color_back_projection images")
+    out, fz, c, *frame = post_process_mesh(verts, faces, colors, ortho_scale, smoothing, shearing,
+                                           color_back_projection, thinning, return_projection_frame=drawings)
     if export_uv:
         if c is None:
             raise ValueError("export_uv needs vertex colours")
         from .uv import uv_mapping
         name = os.path.splitext(os.path.basename(path))[0]
+        projection = dict(color_back_projection, positions=frame[0]) if drawings else None
         m = uv_mapping(out, fz, c, name, size=int(texture_size),
-                       device=verts.device if verts.is_cuda else None)
+                       device=verts.device if verts.is_cuda else None, projection=projection)
         return write_obj_textured(path, m["verts"], m["faces"], m["uvs"], m["image"], name)
     return write_obj(path, out, fz, c)

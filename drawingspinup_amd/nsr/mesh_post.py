@@ -43,12 +43,23 @@ def get_color_from_image(pc, color_map, back=False):
     return color_map[yi, xi]
 
 
+def _rgba(color_u8, eroded_u8):
+    return torch.cat([color_u8, eroded_u8[:, :, None]], 2).to(torch.float32) / 255.0
+
+
 def load_color(color_u8, mask_u8, ksize=19):
     """coloring_utils.py:61-65 without the file reads: erode the mask with the 19x19 ellipse, stack
     as alpha, float32 / 255."""
-    mask = ops.erode_ellipse_u8(mask_u8.contiguous(), ksize)
-    rgba = torch.cat([color_u8, mask[:, :, None]], 2)
-    return rgba.to(torch.float32) / 255.0
+    return _rgba(color_u8, ops.erode_ellipse_u8(mask_u8.contiguous(), ksize))
+
+
+def projection_masks(verts, faces, mask_front_u8, res=2048, ksize=19):
+    """The two masks color_projection reads its drawings under (coloring_utils.py:99-100, :61-64,
+    :119): the front mask cut to the mesh's own silhouette and eroded with the ksize ellipse, and the
+    same for the back view from the cut mask mirrored in x.  -> (front, back) (res,res) uint8."""
+    mask_front = torch.minimum(mask_front_u8, render_mask(verts, faces, res, 2.0))
+    return (ops.erode_ellipse_u8(mask_front.contiguous(), ksize),
+            ops.erode_ellipse_u8(mask_front.flip(1).contiguous(), ksize))
 
 
 @torch.no_grad()
@@ -67,17 +78,16 @@ def color_projection(verts, faces, color_front_u8, mask_front_u8, color_back_u8,
     all_ids = torch.arange(V, dtype=torch.int32, device=dev)
     vert_colors = torch.zeros(V, 4, dtype=torch.float64, device=dev)
 
-    mask_front = torch.minimum(mask_front_u8, render_mask(verts, faces, res, 2.0))
+    eroded_front, eroded_back = projection_masks(verts, faces, mask_front_u8, res)
     # front: vertices whose pixel is inside the eroded mask and that nothing covers from +z
-    col = get_color_from_image(verts, load_color(color_front_u8, mask_front))
+    col = get_color_from_image(verts, _rgba(color_front_u8, eroded_front))
     cand = torch.nonzero(col[:, 3] > 0)[:, 0]
     cnt, _, _, t_far, _ = ops.zray_cast(grid, faces_i, v32[cand], +1, all_ids[cand].contiguous())
     ok = (cnt > 0) & (t_far == 0)
     vert_colors[cand[ok]] = col[cand[ok]].to(torch.float64)
     # back: the still uncoloured ones, mirrored mask / image, nothing behind them along -z
-    mask_back = mask_front.flip(1)
     rest = torch.nonzero(vert_colors[:, 3] == 0)[:, 0]
-    col = get_color_from_image(verts[rest], load_color(color_back_u8, mask_back.contiguous()), True)
+    col = get_color_from_image(verts[rest], _rgba(color_back_u8, eroded_back), True)
     keep = col[:, 3] > 0
     cand, col = rest[keep], col[keep]
     cnt, _, _, t_far, _ = ops.zray_cast(grid, faces_i, v32[cand], -1, all_ids[cand].contiguous())

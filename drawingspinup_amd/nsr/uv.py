@@ -4,6 +4,8 @@ rasteriser of the mesh's own triangles.
 
     parametrize(verts, faces)            -> (vmapping, indices, uvs), as xatlas.parametrize
     bake_vertex_colours(uvs, indices, c) -> (size, size, 3) uint8, as compute_interpolation_map
+    bake_drawings(uvs, indices, p, ...)  -> the same atlas with the input drawings projected into
+                                            it texel by texel (an extension, see below)
     uv_mapping(v, faces, colours, name)  -> the textured mesh, as coloring_utils.uv_mapping
 
 Labels, charts, the atlas raster and the gutter fill run on the device (csrc/mesh_uv.hip, rules in
@@ -24,6 +26,14 @@ Texel convention: the reference's, image row r / column c samples uv * size = (c
 That is half a texel away from the texel-centre convention most viewers assume; the gutter fill
 around every chart is what makes the difference harmless (a bilinear fetch near a chart's border
 reads filled texels, never the empty atlas).
+
+Drawings.  The vertex-colour bake holds no more detail than the vertices do.  bake_drawings asks,
+per texel, which pixel of the front or back drawing the texel's surface point sees — the question
+nsr/mesh_post.color_projection asks per vertex (same frame, same masks, same nearest-pixel read) —
+and keeps the vertex-colour bake where neither view sees it (dsu_uv_project in include/dsu_hip.h
+has the rule in full).  What remains visible of the composition: a seam where projected and
+fallback texels meet, nearest-pixel sampling (no bilinear or area filter), and a fallback band along
+the silhouette as wide as the erosion of the masks (19 pixels of the 2048^2 drawings).
 """
 import math
 
@@ -34,6 +44,18 @@ MIN_COS = 1.0 / math.sqrt(3.0)
 SPLIT_ROUNDS = 8
 SHRINK = 0.9            # the scale's factor per packing retry
 FILL_TARGET = 0.6       # first scale: the charts' projected area over the atlas area
+# Occluders closer than this in front of a texel's point are ignored (projection frame units, the
+# mesh inside [-0.5, 0.5]).  Lower bound: z is float32, one rounding is ~6e-8 here, and a neighbour
+# across a shared edge or a fold meets the point at a depth difference of that order, which must
+# not count as cover.  Upper bound: two layers of the surface that really hide one another are at
+# least one voxel of the marching-cubes lattice apart, ~1e-3 at resolution 512; a tolerance near
+# that would let the rear layer read the drawing through the front one.  1e-4 is a tenth of a voxel
+# and three decades above the rounding.  The choice rests on that reasoning: on the smooth
+# ~50 000-face probe mesh the sweep of tools/uv_project_probe.py (`tolerance_sweep` in
+# profiles/uv_project_probe.json) moves 3 of 334 085 covered texels between 0 and 1e-5 and none
+# between 1e-5, 1e-4 and 1e-3, so that mesh does not tell the candidates apart; a marching-cubes
+# mesh with thin folds has not been swept.
+Z_TOLERANCE = 1e-4
 
 
 # ------------------------------------------------------------------ host parts
@@ -134,8 +156,8 @@ def layout(verts, faces, label, chart, size, gutter, scale=None):
 
 # ------------------------------------------------------------------ device parts
 class DeviceBackend:
-    """The four kernels behind the interface parametrize / bake_vertex_colours use (tests/uv_ref.py
-    has the float64 numpy one)."""
+    """The kernels behind the interface parametrize / bake_vertex_colours / bake_drawings use
+    (tests/uv_ref.py and tests/uv_project_ref.py have the float64 numpy one)."""
 
     def __init__(self, device=None):
         self.dev = torch.device(device if device is not None else "cuda")
@@ -164,9 +186,26 @@ class DeviceBackend:
         from .. import ops
         return ops.uv_dilate(image, covered, rounds)[0]
 
+    def project(self, uvs, indices, positions, face_id, color_front, mask_front, color_back, z_tolerance,
+                erode, cells_per_axis=None):
+        """Mask preparation as color_projection's + dsu_uv_project -> image (S,S,3) u8, source (S,S) u8."""
+        from .. import ops
+        from .mesh_post import projection_masks
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(_host(a), dt)).to(self.dev)
+        pos, ind = t(positions, np.float32), t(indices, np.int64)
+        cf, mf, cb = (torch.as_tensor(a).to(self.dev, torch.uint8).contiguous()
+                      for a in (color_front, mask_front, color_back))
+        front, back = projection_masks(pos, ind, mf, res=cf.shape[0], ksize=int(erode))
+        return ops.uv_project(t(uvs, np.float32), ind, pos, face_id, cf, front, cb, back, z_tolerance,
+                              cells_per_axis=cells_per_axis)
+
     @staticmethod
     def to_numpy(a):
         return a.cpu().numpy()
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
 def parametrize(verts, faces, size=1024, gutter=2, return_info=False, device=None, scale=None, backend=None):
@@ -222,12 +261,47 @@ def bake_vertex_colours(uvs, indices, colours, size=1024, gutter=2, device=None,
     return (out, be.to_numpy(fid)) if return_maps else out
 
 
-def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=None, backend=None):
+def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_back_u8, fallback_colours,
+                  size=1024, gutter=2, z_tolerance=Z_TOLERANCE, erode=19, device=None, backend=None,
+                  return_maps=False):
+    """The atlas with the drawings projected into it: positions (V',3) are the atlas vertices in
+    color_projection's frame (x right, y up, z front, inside [-0.5, 0.5]: after thinning and
+    smoothing, before shear and ortho_scale), color_*_u8 (res,res,3) and mask_front_u8 (res,res) the
+    images color_projection takes (arrays or tensors).  The masks are prepared as there (cut to the
+    mesh's silhouette, eroded with the `erode` ellipse, mirrored for the back view); a texel that
+    neither view sees keeps the vertex-colour bake of fallback_colours (V',3); the gutter fill runs
+    over the composition.  return_maps: also face_id (size,size) i32 and source (size,size) u8
+    (0 fallback, 1 front, 2 back)."""
+    be = backend if backend is not None else DeviceBackend(device)
+    uvs, indices = np.asarray(uvs, np.float32), np.asarray(indices, np.int64)
+    img, fid, _ = be.bake(uvs, indices, np.asarray(fallback_colours, np.float32).reshape(-1, 3), int(size))
+    proj, src = be.project(uvs, indices, np.asarray(_host(positions), np.float32).reshape(-1, 3), fid,
+                           color_front_u8, mask_front_u8, color_back_u8, float(z_tolerance), int(erode))
+    where = torch.where if torch.is_tensor(src) else np.where
+    out = where((src > 0)[..., None], proj, img)
+    if gutter > 0:
+        out = be.dilate(out, fid >= 0, int(gutter))
+    out = be.to_numpy(out)
+    return (out, be.to_numpy(fid), be.to_numpy(src)) if return_maps else out
+
+
+def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=None, backend=None,
+               projection=None):
     """coloring_utils.uv_mapping: parametrise, duplicate the vertices per chart, bake the colours.
     Returns the textured mesh as a dict (verts (V',3) f64, faces (M,3) i64, uvs (V',2) f32, image
-    (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference."""
+    (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference.
+    projection: dict(positions (V,3) in the order of v_np and in color_projection's frame,
+    color_front, mask_front, color_back[, z_tolerance, erode]) bakes with bake_drawings, the vertex
+    colours being the fallback; None = the vertex colours alone."""
     v_np = np.asarray(v_np, np.float64).reshape(-1, 3)
     vmapping, indices, uvs = parametrize(v_np, faces, size, gutter, device=device, backend=backend)
-    image = bake_vertex_colours(uvs, indices, np.asarray(vert_colors, np.float32)[vmapping], size, gutter,
-                                device=device, backend=backend)
+    colours = np.asarray(vert_colors, np.float32)[vmapping]
+    if projection is None:
+        image = bake_vertex_colours(uvs, indices, colours, size, gutter, device=device, backend=backend)
+    else:
+        pr = projection
+        image = bake_drawings(uvs, indices, _host(pr["positions"]).reshape(-1, 3)[vmapping], pr["color_front"],
+                              pr["mask_front"], pr["color_back"], colours, size, gutter,
+                              z_tolerance=pr.get("z_tolerance", Z_TOLERANCE), erode=pr.get("erode", 19),
+                              device=device, backend=backend)
     return {"verts": v_np[vmapping], "faces": indices, "uvs": uvs, "image": image, "name": save_name}

@@ -1565,6 +1565,40 @@ def uv_dilate(image, covered, rounds):
     return image, covered
 
 
+def uv_project(uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
+               z_tolerance, grid=None, cells_per_axis=None):
+    """dsu_uv_project (include/dsu_hip.h): which pixel of the front / back drawing every atlas texel
+    sees.  uvs (V',2) f32, indices (M,3), positions (V',3) f32 in color_projection's frame, face_id
+    (S,S) i32 from uv_bake, color_* (res,res,3) u8 and the eroded masks (res,res) u8, all on the
+    device.  `grid`: the ZGrid over positions[indices], built here when absent (`cells_per_axis`
+    overrides its resolution).  -> image (S,S,3) u8, source (S,S) u8 (0 none, 1 front, 2 back)."""
+    uvs, positions = _f32c(uvs), _f32c(positions)
+    indices = indices.to(torch.int32).contiguous()
+    V, M, S, dev = uvs.shape[0], indices.shape[0], face_id.shape[0], uvs.device
+    if uvs.shape != (V, 2) or positions.shape != (V, 3) or indices.shape != (M, 3) or face_id.shape != (S, S):
+        raise ValueError("uvs (V',2), positions (V',3), indices (M,3) and face_id (S,S) expected")
+    res = color_front.shape[0]
+    for img, shape in ((color_front, (res, res, 3)), (color_back, (res, res, 3)), (mask_front, (res, res)),
+                       (mask_back, (res, res))):
+        if tuple(img.shape) != shape or img.dtype != torch.uint8:
+            raise ValueError("drawings (res,res,3) and masks (res,res) must be uint8 of one resolution")
+    if grid is None and M:
+        tris = positions[indices.long()].contiguous()
+        xy = tris[..., :2].reshape(-1, 2)
+        xy = xy[torch.isfinite(xy).all(1)]                   # a non-finite vertex must not set the extent
+        lo, hi = (xy.amin(0).tolist(), xy.amax(0).tolist()) if xy.shape[0] else ([0.0, 0.0], [0.0, 0.0])
+        grid = ZGrid(tris, lo, hi, cells_per_axis=cells_per_axis)
+    image = torch.empty((S, S, 3), dtype=torch.uint8, device=dev)
+    source = torch.empty((S, S), dtype=torch.uint8, device=dev)
+    gargs = (ptr(grid.data, torch.float32),) + grid.args() if M else (None, 0.0, 0.0, 1.0, 1, None, None)
+    check(lib().dsu_uv_project(ptr(uvs), ptr(indices), ptr(positions), V, M, S,
+                               ptr(face_id.contiguous(), torch.int32), *gargs,
+                               ptr(color_front.contiguous()), ptr(mask_front.contiguous()),
+                               ptr(color_back.contiguous()), ptr(mask_back.contiguous()), res,
+                               float(z_tolerance), ptr(image), ptr(source), stream()), "dsu_uv_project")
+    return image, source
+
+
 # ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
 SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
 

@@ -1215,7 +1215,42 @@ int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weig
  * (size, size) u8.  A covered texel is copied.  An uncovered texel with at least one covered
  * texel among its eight neighbours inside the image takes, per channel, the rounded mean
  * (2 sum + n) / (2 n) in integer arithmetic over those n neighbours and is covered in the output;
- * any other texel is 0 and uncovered.  In and out must be different buffers. */
+ * any other texel is 0 and uncovered.  In and out must be different buffers.
+ *
+ * e. dsu_uv_project: per-texel back-projection of the front and back drawings into the atlas (an
+ * extension: the reference projects the drawings onto the vertices only, coloring_utils.py:91-138).
+ * The atlas is (uvs, indices, size) and face_id (size, size) i32 as dsu_uv_bake wrote it; positions
+ * (n_verts, 3) f32 are the atlas vertices in color_projection's frame (x right, y up, z front,
+ * inside [-0.5, 0.5]); tris (n_faces, 3, 3) f32 = positions[indices] with its z-parallel grid (x0,
+ * y0, cell, g, offsets, items) exactly as dsu_zray_cast takes it; per view a colour image (res,
+ * res, 3) u8 and an eroded mask (res, res) u8.  Outputs image (size, size, 3) u8 and source (size,
+ * size) u8: 0 = not projected (image 0), 1 = front, 2 = back.  One thread per texel, one workgroup
+ * per 16x16 tile.  Everything in float64 from the f32 inputs, in this operand order:
+ *   1. the texel (row r, column c) with m = face_id >= 0 (a face with an index outside [0, n_verts)
+ *      projects nothing) samples (x, y) = (c, size - 1 - r); w0, w1, w2 and area as in c. above,
+ *      b_i = w_i / area.
+ *   2. p = (b0 Pa + b1 Pb) + b2 Pc per coordinate, Pa, Pb, Pc the positions of m's vertices.  A
+ *      non-finite p projects nothing.
+ *   3. the front view (sign +1) is tested, then the back view (sign -1); the first that passes
+ *      gives source and colour.  A view passes when
+ *      facing:      ((Pbx - Pax)(Pcy - Pay) - (Pby - Pay)(Pcx - Pax)) sign > 0;
+ *      pixel:       X = rint((+-px + 0.5)(res - 1)), px negated for the back view,
+ *                   Y = rint((-py + 0.5)(res - 1)), half to even, both clamped to [0, res - 1]
+ *                   (get_color_from_image, coloring_utils.py:67-86); mask[Y][X] > 0;
+ *      unoccluded:  the grid cell of ((float)px, (float)py) is walked; for every listed triangle
+ *                   f != m with dsu_zray_cast's edge functions e0, e1, e2 at (px, py),
+ *                   ar = (e0 + e1) + e2 != 0 and (all e >= 0 or all e <= 0):
+ *                   z_f = ((e0 z0 + e1 z1) + e2 z2) / ar; the texel is occluded when
+ *                   (z_f - pz) sign > z_tolerance for any such f.
+ *   4. the colour is the drawing's uint8 pixel [Y][X] of that view, copied.
+ * No atomics: two runs give the same bits.  A triangle that covers (px, py) has a box that
+ * contains the float casts, so the result does not depend on the grid's resolution.
+ * DSU_EINVAL before any launch: size outside 1..8192, res outside 1..16384, g outside 1..4096,
+ * cell <= 0 or not finite, x0 or y0 not finite, z_tolerance negative or not finite, n_verts or
+ * n_faces negative or above 2^30, image or source NULL; and, with n_faces > 0, n_verts == 0 or any
+ * other pointer NULL.  n_faces == 0: DSU_OK, image and source zeroed, the other pointers unread.
+ * The mesh must be wound outward in this frame (as marching cubes leaves it): the facing test reads
+ * the winding, and a mesh wound inward projects nothing its views can see. */
 #define DSU_UV_COUNT 0
 #define DSU_UV_FILL 1
 #define DSU_UV_RASTER 2
@@ -1231,6 +1266,11 @@ int dsu_uv_bake(int32_t stage, const float* uvs, const int32_t* indices, const f
                 uint8_t* demote, void* stream);
 int dsu_uv_dilate(const uint8_t* image_in, const uint8_t* covered_in, int32_t size, uint8_t* image_out,
                   uint8_t* covered_out, void* stream);
+int dsu_uv_project(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                   int64_t n_faces, int32_t size, const int32_t* face_id, const float* tris, float x0, float y0,
+                   float cell, int32_t g, const int32_t* offsets, const int32_t* items, const uint8_t* color_front,
+                   const uint8_t* mask_front, const uint8_t* color_back, const uint8_t* mask_back, int32_t res,
+                   double z_tolerance, uint8_t* image, uint8_t* source, void* stream);
 
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`

@@ -1,0 +1,241 @@
+"""Float64 numpy restatement of dsu_uv_project (include/dsu_hip.h, UV export e.), independent of
+csrc/mesh_uv.hip: the texel's point from the atlas barycentrics, the facing / pixel / mask tests
+and a brute-force occluder search over ALL triangles (no grid: a triangle that covers the point
+is in the point's cell whatever the grid, so the device's answer must not depend on it).  The
+raster itself is tests/uv_ref.py's.  RefBackend plugs the restatement into
+drawingspinup_amd.nsr.uv.bake_drawings / uv_mapping.  Also the synthetic drawings and the cases the
+host and GPU tests share."""
+import functools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import uv_ref as R  # noqa: E402
+
+FRAGILE_REL = R.FRAGILE_REL
+RES = 256                     # the tests' drawings
+BBOX_PAD = 1e-6               # candidate filter of the occluder search, far above any rounding
+
+
+# ------------------------------------------------------------------ drawings and masks
+def drawings(res=RES):
+    """front, back (res,res,3) u8.  r = column mod 256, g = row mod 256, b = a one-pixel checker; the
+    back drawing is the front one with its channels permuted.  Nothing in it is symmetric: a
+    wrong mirror, flip or row / column swap changes the bytes."""
+    row, col = np.meshgrid(np.arange(res), np.arange(res), indexing="ij")
+    front = np.stack([col % 256, row % 256, 255 * ((row + col) & 1)], -1).astype(np.uint8)
+    return front, np.ascontiguousarray(front[..., [2, 0, 1]])
+
+
+def disc_masks(res=RES):
+    """front, back (res,res) u8: a disc of radius 0.45 res about (res / 2, res / 2), and its mirror
+    image in x (not the same set: the centre is not the image's)."""
+    row, col = np.meshgrid(np.arange(res), np.arange(res), indexing="ij")
+    inside = 400 * ((row - res // 2) ** 2 + (col - res // 2) ** 2) <= 81 * res * res
+    front = np.where(inside, 255, 0).astype(np.uint8)
+    return front, np.ascontiguousarray(front[:, ::-1])
+
+
+def prepare_masks(positions, indices, mask_front, erode):
+    """nsr/mesh_post.projection_masks with the oracle's stand-ins for pytorch3d's silhouette and
+    cv2.erode (oracle/mesh_post_ref.py)."""
+    from oracle import mesh_post_ref as O
+    mask_front = np.asarray(mask_front, np.uint8)
+    sil = O.MaskRenderer(mask_front.shape[0]).render(np.asarray(positions, np.float32) * np.float32(2.0), indices)
+    cut = np.minimum(mask_front, sil)
+    el = O.getStructuringElement(O.MORPH_ELLIPSE, (int(erode), int(erode)))
+    return O.erode(cut, el), O.erode(O.flip(cut, 1), el)
+
+
+# ------------------------------------------------------------------ the rule
+def project(uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back, z_tolerance,
+            bake_fragile=None):
+    """-> image (S,S,3) u8, source (S,S) u8, fragile (S,S) bool.  The masks are the prepared ones.
+    fragile: bake_fragile (uv_ref.bake's), or an occluder's edge function within FRAGILE_REL of
+    zero relative to its area and not exactly zero (where taking it as zero makes the triangle
+    cover the point, and the triangle is an occluder: in front by the tolerance), or
+    |(z_f - p_z) sign - z_tolerance| <= 1e-9 for a covering triangle, or a
+    pixel coordinate within 1e-9 of a half-integer, or the facing component within 1e-12 of zero
+    relative to the normal's length.  A facing component that IS zero is not fragile: it is a
+    difference of two products that round to the same number in both implementations (no fused
+    product on either side), and the lattice case is full of them."""
+    S = face_id.shape[0]
+    uv = np.asarray(uvs, np.float32).astype(np.float64) * float(S)
+    P = np.asarray(positions, np.float32).astype(np.float64)
+    ind = np.asarray(indices, np.int64)
+    res = color_front.shape[0]
+    image = np.zeros((S, S, 3), np.uint8)
+    source = np.zeros((S, S), np.uint8)
+    fragile = np.zeros((S, S), bool) if bake_fragile is None else np.array(bake_fragile, bool)
+    fid = np.asarray(face_id, np.int64)
+    valid = np.zeros(len(ind), bool)
+    if len(ind):
+        valid = (ind.min(1) >= 0) & (ind.max(1) < len(P))
+    live = (fid >= 0) & (fid < len(ind))
+    live[live] = valid[fid[live]]
+    rows, cols = np.nonzero(live)
+    if len(rows) == 0:
+        return image, source, fragile
+    m = fid[rows, cols]
+    px, py = cols.astype(np.float64), (S - 1 - rows).astype(np.float64)
+    ia, ib, ic = ind[m, 0], ind[m, 1], ind[m, 2]
+    with np.errstate(all="ignore"):
+        w0, w1, w2 = R._edges((uv[ia, 0], uv[ia, 1], uv[ib, 0], uv[ib, 1], uv[ic, 0], uv[ic, 1]), px, py)
+        area = (w0 + w1) + w2
+        b0, b1, b2 = w0 / area, w1 / area, w2 / area
+        Pa, Pb, Pc = P[ia], P[ib], P[ic]
+        p = (b0[:, None] * Pa + b1[:, None] * Pb) + b2[:, None] * Pc
+        finite = np.isfinite(p).all(1)
+        e1, e2 = Pb - Pa, Pc - Pa
+        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        nlen = np.sqrt(np.sum(np.cross(e1, e2) ** 2, 1))
+        span = float(res - 1)
+        sign = np.where(nz > 0, 1.0, -1.0)
+        facing = finite & (nz * sign > 0)                                  # nz == 0 or NaN: neither view
+        X = np.where(sign > 0, p[:, 0], -p[:, 0])
+        X, Y = (X + 0.5) * span, (-p[:, 1] + 0.5) * span
+        near_half = (np.abs(np.abs(X - np.floor(X)) - 0.5) <= 1e-9) | (np.abs(np.abs(Y - np.floor(Y)) - 0.5) <= 1e-9)
+        safe = np.where(facing, X, 0.0), np.where(facing, Y, 0.0)
+        xi = np.clip(np.rint(safe[0]), 0, span).astype(np.int64)           # rint: half to even
+        yi = np.clip(np.rint(safe[1]), 0, span).astype(np.int64)
+    front = sign > 0
+    mask = np.where(front, np.asarray(mask_front)[yi, xi], np.asarray(mask_back)[yi, xi])
+    cand = facing & (mask > 0)
+    frag = finite & (nz != 0) & (np.abs(nz) <= 1e-12 * nlen)
+    frag |= facing & near_half
+    # occluders: every triangle against the candidates inside its padded box
+    occluded = np.zeros(len(m), bool)
+    T = P[ind[valid]]                                                      # (F,3,3): the grid's triangles
+    face_no = np.nonzero(valid)[0]
+    idx = np.nonzero(cand)[0]
+    qx, qy, qz, qs, qm = p[idx, 0], p[idx, 1], p[idx, 2], sign[idx], m[idx]
+    order = np.argsort(qx, kind="stable")
+    sx = qx[order]
+    for f, t in zip(face_no, T):
+        (ax, ay, az), (bx, by, bz), (cx, cy, cz) = t
+        if not np.all(np.isfinite(t[:, :2])):
+            continue
+        lo, hi = np.searchsorted(sx, [min(ax, bx, cx) - BBOX_PAD, max(ax, bx, cx) + BBOX_PAD])
+        k = order[lo:hi]
+        k = k[(qy[k] >= min(ay, by, cy) - BBOX_PAD) & (qy[k] <= max(ay, by, cy) + BBOX_PAD) & (qm[k] != f)]
+        if len(k) == 0:
+            continue
+        x, y = qx[k], qy[k]
+        f0 = (x - bx) * (cy - by) - (y - by) * (cx - bx)
+        f1 = (x - cx) * (ay - cy) - (y - cy) * (ax - cx)
+        f2 = (x - ax) * (by - ay) - (y - ay) * (bx - ax)
+        ar = (f0 + f1) + f2
+        if not np.any(ar != 0):
+            continue
+        covers = ((f0 >= 0) & (f1 >= 0) & (f2 >= 0)) | ((f0 <= 0) & (f1 <= 0) & (f2 <= 0))
+        covers &= ar != 0
+        with np.errstate(all="ignore"):
+            d = (((f0 * az + f1 * bz) + f2 * cz) / ar - qz[k]) * qs[k]
+        occluded[idx[k[covers & (d > z_tolerance)]]] = True
+        tiny = np.abs(ar) * FRAGILE_REL
+        n0, n1, n2 = [(np.abs(w) <= tiny) & (w != 0) for w in (f0, f1, f2)]
+        z0, z1, z2 = np.where(n0, 0.0, f0), np.where(n1, 0.0, f1), np.where(n2, 0.0, f2)
+        would = ((z0 >= 0) & (z1 >= 0) & (z2 >= 0)) | ((z0 <= 0) & (z1 <= 0) & (z2 <= 0))
+        # an OCCLUDER's edge: a triangle that is not in front by the tolerance changes nothing by
+        # covering or not (the neighbour across the texel's own edge, met at d ~ 1e-17, is the usual one)
+        in_front = d > z_tolerance - 1e-9
+        edge = (n0 | n1 | n2) & would & (ar != 0) & in_front
+        depth = (covers | edge) & (np.abs(d - z_tolerance) <= 1e-9)
+        risky = edge | depth
+        frag[idx[k[risky]]] = True
+    ok = cand & ~occluded
+    src = np.where(ok, np.where(front, 1, 2), 0).astype(np.uint8)
+    col = np.where(front[:, None], np.asarray(color_front)[yi, xi], np.asarray(color_back)[yi, xi])
+    source[rows, cols] = src
+    image[rows, cols] = np.where(ok[:, None], col, 0)
+    fragile[rows, cols] |= frag
+    return image, source, fragile
+
+
+class RefBackend(R.RefBackend):
+    """uv_ref.RefBackend + project.  masks: prepared (front, back) masks that stand in for the mask
+    preparation (the GPU tests hand over the device's own); None = prepare_masks.  After a call,
+    .fragile holds the fragile texels of the last bake + project."""
+
+    def __init__(self, masks=None):
+        self.masks = masks
+        self.fragile = self._bake_fragile = None
+
+    def bake(self, uvs, indices, colours, size, depth=None):
+        out = R.bake(uvs, indices, colours, size, depth)
+        self._bake_fragile = out[3]
+        return out[:3]
+
+    def project(self, uvs, indices, positions, face_id, color_front, mask_front, color_back, z_tolerance, erode,
+                cells_per_axis=None):
+        host = lambda a: np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+        front, back = self.masks if self.masks is not None else \
+            prepare_masks(positions, indices, host(mask_front), erode)
+        image, source, self.fragile = project(uvs, indices, positions, face_id, host(color_front), host(front),
+                                              host(color_back), host(back), z_tolerance, self._bake_fragile)
+        return image, source
+
+
+# ------------------------------------------------------------------ cases
+def into_frame(name, verts, faces):
+    """The test meshes inside color_projection's [-0.5, 0.5] frame, float32.  The lattice cube goes to
+    [1/8, 3/8]^2 x [-1/8, 1/8] by powers of two, so every quantity of the rule stays exact, and off
+    x = 0 and y = 0, the only places where (x + 1/2)(res - 1) is a half-integer for a dyadic x.
+    A mesh wound inside out (negative signed volume: the torus) is mirrored in z, which turns its
+    faces outward: the facing test reads the winding."""
+    v = np.asarray(verts, np.float64)
+    if name == "lattice":
+        return (v * 0.25 + np.array([0.125, 0.125, -0.125])).astype(np.float32)
+    lo, hi = v.min(0), v.max(0)
+    v = (v - 0.5 * (lo + hi)) * (0.9 / (hi - lo).max())
+    t = v[np.asarray(faces, np.int64)]
+    if np.einsum("ij,ij->", t[:, 0], np.cross(t[:, 1], t[:, 2])) < 0:
+        v = v * np.array([1.0, 1.0, -1.0])
+    return v.astype(np.float32)
+
+
+# (mesh, atlas size) as tests/test_gpu_uv.py's bake cases: 64 with 4728 faces = the arm in front of
+# the body; torus = two layers and a hole; helicoid = several layers over one (x, y); 100 = not a
+# multiple of the tile; lattice = exact
+CASES = [("body_and_arm", 64), ("torus", 256), ("helicoid", 128), ("character", 100), ("lattice", 128)]
+CLOSED = {"body_and_arm", "torus", "character", "lattice"}
+Z_TOL = 1e-4                  # the cases' tolerance (= nsr.uv.Z_TOLERANCE, asserted by the host test)
+
+
+SIL_ERODE = 5                 # the silhouette masks' erosion: the 19 of the 2048^2 drawings, at 256^2
+MASK_KINDS = ("disc", "silhouette")
+
+
+def fixed(name, size):
+    """What a case's device run and its restatement share: the atlas of uv_ref.reference(name, size),
+    positions in the frame, the synthetic drawings."""
+    r = R.reference(name, size)
+    cf, cb = drawings()
+    return {"uvs": r["uvs"], "indices": r["indices"], "face_id": r["face_id"], "bake_fragile": r["fragile"],
+            "positions": into_frame(name, r["verts"], r["faces"])[r["vmapping"]], "color_front": cf,
+            "color_back": cb, "size": size}
+
+
+def restate(c, masks, z_tolerance):
+    """fixed() + the masks, the tolerance and the restatement's image / source / fragile, read-only."""
+    image, source, fragile = project(c["uvs"], c["indices"], c["positions"], c["face_id"], c["color_front"],
+                                     masks[0], c["color_back"], masks[1], z_tolerance, c["bake_fragile"])
+    out = dict(c, mask_front=masks[0], mask_back=masks[1], image=image, source=source, fragile=fragile,
+               z_tolerance=z_tolerance)
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(name, size, z_tolerance=Z_TOL, masks="disc"):
+    """A case computed once.  masks: "disc", or "silhouette" = the mesh's own silhouette eroded by
+    SIL_ERODE as bake_drawings prepares it, here with the oracle's stand-ins (the GPU tests hand
+    restate() the device's own instead)."""
+    c = fixed(name, size)
+    full = np.full((RES, RES), 255, np.uint8)
+    m = disc_masks() if masks == "disc" else prepare_masks(c["positions"], c["indices"], full, SIL_ERODE)
+    return restate(c, m, z_tolerance)
