@@ -171,6 +171,9 @@ _PROTOS = {
     "dsu_mesh_render_ortho_workspace_bytes": [c_i32, c_i32],
     "dsu_mesh_render_ortho": [c_i32, P, P, P, P, c_i32, c_i64, c_i64, C.c_double, C.c_double,
                               C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
+    "dsu_mesh_render_ortho_textured": [P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i64, c_i64, C.c_double,
+                                       C.c_double, C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P,
+                                       P, P, P, P],
     "dsu_pos_edge_u8": [P, c_i32, c_i32, c_i32, P, P],
     "dsu_uv_face_labels": [P, P, c_i64, c_i64, P, P, P, P],
     "dsu_uv_components": [P, P, c_i64, P, P, c_i32, c_i32, C.POINTER(c_i32), P],

@@ -17,6 +17,11 @@ ss^2 sub-samples stands in for Blender's pixel filter; no view transform or tone
 (the reference selects 'Standard'); the turntable's frame count lives in a .blend file that is not
 in the snapshot, so it is a parameter.
 
+Textured frames: `read_obj_textured` keeps a textured export's uvs and atlas, and `render_frames` /
+`animate_mesh` with `texture=` and `uvs=` sample the atlas inside the rasteriser's resolve, per
+sub-sample (nearest or bilinear; no mip-mapping, no seam blending), where Blender reads `map_Kd`.
+Without them the colour frames interpolate the vertex colours, as before.
+
 Rigged animations: `read_bvh` reads a skeleton and a motion clip, `bone_heat_weights` binds the mesh
 to the skeleton (distances, visibility and the solve on the device, csrc/mesh_skin.hip),
 `animate_mesh` skins every frame on the device and renders it through the same rasteriser.  The
@@ -26,10 +31,10 @@ automatic joint placement (`fit_to_mesh` only scales and centres a skeleton); th
 that blender_animation.py:17-18 applies to two named clips is not restated.  FBX is not read.
 """
 from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
-                     read_obj, render_frames, rest_pose, rest_rotate)
+                     read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
 from .skeleton import Clip, Skeleton, fit_to_mesh, read_bvh, rest_clip, skinning_matrices
 from .skin import animate_mesh, bone_heat_weights
 
 __all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "fit_to_mesh", "read_bvh", "rest_clip",
            "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
-           "read_obj", "render_frames", "rest_pose", "rest_rotate"]
+           "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate"]

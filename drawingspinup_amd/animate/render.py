@@ -90,6 +90,65 @@ def read_obj(path):
     return v, f, colours
 
 
+def read_obj_textured(path):
+    """The textured triple of nsr/mesh.write_obj_textured, whole: (verts (V',3) f64, faces (M,3) i64
+    0-based, uvs (V',2) f32, image (T,T,3) uint8).  A corner's `v` and `vt` indices may differ: the
+    mesh then gets one vertex per distinct (v, vt) pair, in the order of first use; a file whose
+    corners all read `a/a` (one uv per vertex, write_obj_textured's) comes back as it is.  ValueError when the file has
+    no `vt` on every corner, no readable square `map_Kd`, or an index out of range."""
+    verts, vts, corners, mtllib = [], [], [], None
+    with open(path) as fh:
+        for line in fh:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                verts.append([float(x) for x in p[1:4]])
+            elif p[0] == "vt":
+                vts.append([float(x) for x in p[1:3]])
+            elif p[0] == "mtllib" and mtllib is None and len(p) > 1:
+                mtllib = line.split(None, 1)[1].strip()
+            elif p[0] == "f":
+                if len(p) != 4:
+                    raise ValueError(f"{path}: only triangular faces are supported: {line.strip()!r}")
+                for c in p[1:4]:
+                    q = c.split("/")
+                    if len(q) < 2 or not q[1]:
+                        raise ValueError(f"{path}: no texture coordinates (vt) on face corner {c!r}")
+                    corners.append((int(q[0]) - 1, int(q[1]) - 1))
+    if not vts:
+        raise ValueError(f"{path}: no texture coordinates (vt)")
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    vt = np.asarray(vts, np.float64).reshape(-1, 2)
+    cn = np.asarray(corners, np.int64).reshape(-1, 2)
+    if cn.size and (cn[:, 0].min() < 0 or cn[:, 0].max() >= len(v)):
+        raise ValueError(f"{path}: face index out of range")
+    if cn.size and (cn[:, 1].min() < 0 or cn[:, 1].max() >= len(vt)):
+        raise ValueError(f"{path}: vt index out of range")
+    tex = _texture_path(path, mtllib) if mtllib else None
+    if tex is None:
+        raise ValueError(f"{path}: no readable map_Kd texture")
+    from PIL import Image
+    try:
+        image = np.array(Image.open(tex).convert("RGB"))
+    except OSError as e:
+        raise ValueError(f"{path}: map_Kd {tex} is not a readable image ({e})")
+    if image.shape[0] != image.shape[1]:
+        raise ValueError(f"{path}: map_Kd {tex} is not square ({image.shape[1]} x {image.shape[0]})")
+    if len(v) == len(vt) and np.array_equal(cn[:, 0], cn[:, 1]):
+        return v, cn[:, 0].reshape(-1, 3).copy(), vt.astype(np.float32), image      # one uv per vertex already
+    index, pairs = {}, []
+    faces = np.empty(len(cn), np.int64)
+    for k, pair in enumerate(map(tuple, cn.tolist())):
+        at = index.get(pair)
+        if at is None:
+            at = index[pair] = len(pairs)
+            pairs.append(pair)
+        faces[k] = at
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    return v[pairs[:, 0]], faces.reshape(-1, 3), vt[pairs[:, 1]].astype(np.float32), image
+
+
 def position_colours(verts):
     """blender_animation.py:30-32: (v - min) / (max - min) per axis of the OBJ coordinates (an axis
     without extent gives 0 rather than the reference's 0 / 0)."""
@@ -163,11 +222,44 @@ def frame_window(frames_xyz):
     return cx, cy, size, span
 
 
+def _texture_args(texture, uvs, texture_filter, n_verts, dev):
+    """The uv / texture / filter keywords of ops.mesh_render_ortho from a host or device texture
+    (T,T,3|4) uint8 and uvs (V,2), or {} without a texture."""
+    if (texture is None) != (uvs is None):
+        raise ValueError("texture and uvs come together or not at all")
+    if texture is None:
+        return {}
+    if texture_filter not in ops.TEXTURE_FILTERS:
+        raise ValueError(f"texture_filter must be one of {sorted(ops.TEXTURE_FILTERS)}")
+    to_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    uv = to_t(uvs).to(dev, torch.float32).reshape(-1, 2)
+    if len(uv) != n_verts:
+        raise ValueError("one uv per vertex")
+    return {"uv": uv, "texture": to_t(texture).to(dev), "filter": texture_filter}
+
+
+def _vertex_colours(colours, n_verts, textured):
+    """(V,3) f32 vertex colours; None is allowed (and stays None) when a texture gives the colour."""
+    if colours is None and textured:
+        return None
+    if colours is None:
+        raise ValueError("vertex colours or a texture are needed")
+    c = (colours.detach().cpu().numpy() if torch.is_tensor(colours) else np.asarray(colours))
+    c = c.astype(np.float32).reshape(-1, 3)
+    if len(c) != n_verts:
+        raise ValueError("one colour per vertex")
+    return c
+
+
 @torch.no_grad()
 def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24, device="cuda",
-                  window=None, want=()):
-    """Render the motion of one vertex-coloured mesh.  verts (V,3) in save_mesh's frame (x right, y
-    up, z front; the viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
+                  window=None, want=(), texture=None, uvs=None, texture_filter="bilinear"):
+    """Render the motion of one mesh.  verts (V,3) in save_mesh's frame (x right, y up, z front; the
+    viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
+
+    texture (T,T,3|4) uint8 with uvs (V,2) (read_obj_textured's) renders the colour frames from the
+    texture, sampled per sub-sample with texture_filter "bilinear" or "nearest"; colours may then be
+    None.  The position and edge frames do not depend on it.
 
     rest_pose keeps the default camera (origin-centred, 512 px across 1.35: the exported character
     fills the frame as in the reference); every other motion goes through frame_window.  `window`
@@ -180,9 +272,8 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    c = to_np(colours).astype(np.float32).reshape(-1, 3)
-    if len(c) != len(v):
-        raise ValueError("one colour per vertex")
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev)
+    c = _vertex_colours(colours, len(v), bool(tex))
     xyz = motion_frames(v, motion, n_frames)
     if window is not None:
         cx, cy, size, span = window
@@ -192,8 +283,8 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
         cx, cy, size, span = frame_window(xyz)
     screen = torch.from_numpy(xyz.astype(np.float32)).to(dev)
     pos = torch.from_numpy(position_colours(v).astype(np.float32)).to(dev)
-    out = ops.mesh_render_ortho(screen, torch.from_numpy(f).to(dev), torch.from_numpy(c).to(dev), pos,
-                                cx, cy, span, size, ss, want=("color_u8", "pos_u8", "frames", *want))
+    out = ops.mesh_render_ortho(screen, torch.from_numpy(f).to(dev), None if c is None else torch.from_numpy(c).to(dev),
+                                pos, cx, cy, span, size, ss, want=("color_u8", "pos_u8", "frames", *want), **tex)
     res = {"color": out["color_u8"], "pos": out["pos_u8"], "edge": ops.pos_edge_u8(out["pos_u8"]),
            "frames": out["frames"], "size": int(size), "span": float(span), "centre": (cx, cy)}
     res.update({k: out[k] for k in want})

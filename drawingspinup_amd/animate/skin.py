@@ -13,7 +13,7 @@ import torch
 
 from .. import ops
 from ..nsr.thinning import _weld, cotmatrix
-from .render import frame_window, position_colours
+from .render import _texture_args, _vertex_colours, frame_window, position_colours
 from .skeleton import skinning_matrices
 
 NEAR = 1e-4          # bones within (1 + NEAR) of the nearest visible one share a vertex's heat
@@ -138,20 +138,21 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 
 
 @torch.no_grad()
-def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=()):
-    """Render a skinned animation of one vertex-coloured mesh: weights (bone heat unless given as
-    (influences, weights)), linear-blend skinning on the device, then the rasteriser of
-    render_frames.  The skinned vertices never leave the device; the window is frame_window's rule
-    on their bounding box over all frames (Blender uses the object's bound_box).
+def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
+                 texture=None, uvs=None, texture_filter="bilinear"):
+    """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
+    weights)), linear-blend skinning on the device, then the rasteriser of render_frames.  The
+    skinned vertices never leave the device; the window is frame_window's rule on their bounding
+    box over all frames (Blender uses the object's bound_box).  texture, uvs, texture_filter: as in
+    render_frames (colours may be None with a texture).
 
     Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor."""
     dev = torch.device(device)
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    c = to_np(colours).astype(np.float32).reshape(-1, 3)
-    if len(c) != len(v):
-        raise ValueError("one colour per vertex")
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev)
+    c = _vertex_colours(colours, len(v), bool(tex))
     if weights is None:
         weights = bone_heat_weights(v, f, skeleton, K=K, device=device)
     infl, w = (to_np(a) for a in weights)
@@ -162,8 +163,8 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     box = torch.stack([screen.amin((0, 1)), screen.amax((0, 1))]).cpu().numpy()
     cx, cy, size, span = frame_window(box)
     pos = torch.from_numpy(position_colours(v).astype(np.float32)).to(dev)
-    out = ops.mesh_render_ortho(screen, torch.from_numpy(f).to(dev), torch.from_numpy(c).to(dev), pos,
-                                cx, cy, span, size, ss, want=("color_u8", "pos_u8", "frames", *want))
+    out = ops.mesh_render_ortho(screen, torch.from_numpy(f).to(dev), None if c is None else torch.from_numpy(c).to(dev),
+                                pos, cx, cy, span, size, ss, want=("color_u8", "pos_u8", "frames", *want), **tex)
     res = {"color": out["color_u8"], "pos": out["pos_u8"], "edge": ops.pos_edge_u8(out["pos_u8"]),
            "frames": out["frames"], "size": int(size), "span": float(span), "centre": (cx, cy),
            "vertices": screen}

@@ -20,6 +20,12 @@
 // list with LDS atomicMax, so the winner does not depend on the order of the list.  The same
 // workgroup then resolves: no global atomics on the frame, no visibility buffer in HBM.
 // LDS: 32 KB of keys + 1 KB of lattice coordinates at ss = 4.
+//
+// Textured frames (dsu_mesh_render_ortho_textured): the same visibility, and in the resolve the three
+// colour channels of a sample come from the UV atlas — the face's uvs interpolated with the sample's
+// edge functions, then a nearest or bilinear read of the RGBA8 texture under the bake's convention
+// (image row r, column c holds uv T = (c, T - 1 - r)).  The texels are read through L2: neighbouring
+// samples share them.  The position pass is untouched.
 #include "common.h"
 #include "bin_sort.h"
 #include "mesh_geom.h"
@@ -114,16 +120,55 @@ struct RenderOut {
   float* pixels;        // (F,S,S,8)
 };
 
-// One workgroup of four waves per (frame, tile).
-template <int SS>
-__global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
+// The atlas of the textured resolve: uv (V,2) f32, texels (T,T) RGBA8 as one 32-bit word each.
+struct RenderTexture {
+  const float* __restrict__ uv;
+  const uint32_t* __restrict__ texels;
+  int32_t T;
+};
+
+constexpr int TEX_NONE = -1, TEX_NEAREST = 0, TEX_BILINEAR = 1;
+
+__device__ __forceinline__ float texel_channel(uint32_t p, int ch) { return (float)((p >> (8 * ch)) & 255u); }
+
+// Colour of one sample from the atlas (include/dsu_hip.h, the textured rule): tx, ty = uv T.
+template <int TEX>
+__device__ __forceinline__ void sample_atlas(const RenderTexture& tex, double tx, double ty, float rgb[3]) {
+  const double top = (double)(tex.T - 1);
+  if (!isfinite(tx)) tx = 0.0;
+  if (!isfinite(ty)) ty = 0.0;
+  if constexpr (TEX == TEX_NEAREST) {
+    const int c = (int)fmin(fmax(floor(tx + 0.5), 0.0), top);
+    const int r = (int)fmin(fmax(top - floor(ty + 0.5), 0.0), top);
+    const uint32_t p = tex.texels[(int64_t)r * tex.T + c];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rgb[ch] = texel_channel(p, ch) / 255.0f;
+  } else {
+    const double x = fmin(fmax(tx, 0.0), top), y = fmin(fmax(top - ty, 0.0), top);
+    const int c0 = (int)floor(x), r0 = (int)floor(y);
+    const int c1 = min(c0 + 1, tex.T - 1), r1 = min(r0 + 1, tex.T - 1);
+    const double fx = x - (double)c0, fy = y - (double)r0;
+    const uint32_t p00 = tex.texels[(int64_t)r0 * tex.T + c0], p01 = tex.texels[(int64_t)r0 * tex.T + c1];
+    const uint32_t p10 = tex.texels[(int64_t)r1 * tex.T + c0], p11 = tex.texels[(int64_t)r1 * tex.T + c1];
+    const double k00 = (1.0 - fx) * (1.0 - fy), k01 = fx * (1.0 - fy), k10 = (1.0 - fx) * fy, k11 = fx * fy;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      rgb[ch] = (float)((k00 * (double)texel_channel(p00, ch) + k01 * (double)texel_channel(p01, ch) +
+                         k10 * (double)texel_channel(p10, ch) + k11 * (double)texel_channel(p11, ch)) / 255.0);
+  }
+}
+
+// One workgroup of four waves per (frame, tile).  TEX: where the colour channels of a sample come
+// from — TEX_NONE the vertex colours, TEX_NEAREST / TEX_BILINEAR the atlas.
+template <int SS, int TEX>
+__device__ __forceinline__ void raster_resolve_tile(
+    unsigned long long* keys, double* xs, double* ys,
     const float* __restrict__ screen, const int32_t* __restrict__ faces,
     const float* __restrict__ colour, const float* __restrict__ pos, int64_t V, int64_t M,
-    RenderView view, const int32_t* __restrict__ offsets, const int32_t* __restrict__ items,
-    int64_t n_items, RenderOut out) {
+    const RenderView& view, const int32_t* __restrict__ offsets, const int32_t* __restrict__ items,
+    int64_t n_items, const RenderTexture& tex, const RenderOut& out) {
   constexpr int T = RT_TILE * SS;
-  __shared__ unsigned long long keys[T * T];
-  __shared__ double xs[T], ys[T];
+  constexpr int CH0 = TEX == TEX_NONE ? 0 : 3;   // first interpolated channel
   const int tid = threadIdx.x;
   const int bin = blockIdx.x;
   const int f = bin / (view.G * view.G);
@@ -190,6 +235,7 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
   float a0[6], a1[6], a2[6];
 #pragma unroll
   for (int ch = 0; ch < 6; ++ch) a0[ch] = a1[ch] = a2[ch] = 0.0f;
+  float ua = 0.0f, va = 0.0f, ub = 0.0f, vb = 0.0f, uc = 0.0f, vc = 0.0f;
   for (int sy = 0; sy < SS; ++sy)
     for (int sx = 0; sx < SS; ++sx) {
       const int lr = py * SS + sy, lc = px * SS + sx;
@@ -202,20 +248,35 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
         t = load_xy(sv, ia, ib, ic);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-          a0[ch] = clamp01(colour[(int64_t)ia * 3 + ch]);
-          a1[ch] = clamp01(colour[(int64_t)ib * 3 + ch]);
-          a2[ch] = clamp01(colour[(int64_t)ic * 3 + ch]);
+          if constexpr (TEX == TEX_NONE) {
+            a0[ch] = clamp01(colour[(int64_t)ia * 3 + ch]);
+            a1[ch] = clamp01(colour[(int64_t)ib * 3 + ch]);
+            a2[ch] = clamp01(colour[(int64_t)ic * 3 + ch]);
+          }
           a0[3 + ch] = clamp01(pos[(int64_t)ia * 3 + ch]);
           a1[3 + ch] = clamp01(pos[(int64_t)ib * 3 + ch]);
           a2[3 + ch] = clamp01(pos[(int64_t)ic * 3 + ch]);
+        }
+        if constexpr (TEX != TEX_NONE) {
+          ua = tex.uv[(int64_t)ia * 2]; va = tex.uv[(int64_t)ia * 2 + 1];
+          ub = tex.uv[(int64_t)ib * 2]; vb = tex.uv[(int64_t)ib * 2 + 1];
+          uc = tex.uv[(int64_t)ic * 2]; vc = tex.uv[(int64_t)ic * 2 + 1];
         }
         last = m;
       }
       double w0, w1, w2;
       edge_functions(t, xs[lc], ys[lr], w0, w1, w2);
       const double area = w0 + w1 + w2;
+      if constexpr (TEX != TEX_NONE) {
+        const double u = (w0 * (double)ua + w1 * (double)ub + w2 * (double)uc) / area;
+        const double v = (w0 * (double)va + w1 * (double)vb + w2 * (double)vc) / area;
+        float rgb[3];
+        sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, rgb);
 #pragma unroll
-      for (int ch = 0; ch < 6; ++ch)
+        for (int ch = 0; ch < 3; ++ch) acc[ch] += (double)rgb[ch];
+      }
+#pragma unroll
+      for (int ch = CH0; ch < 6; ++ch)
         acc[ch] += (double)(float)((w0 * (double)a0[ch] + w1 * (double)a1[ch] + w2 * (double)a2[ch]) / area);
       ++covered;
     }
@@ -249,6 +310,31 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
     fr[4 * plane] = ((float)q[3] / 255.0f - 0.5f) / 0.5f;
     fr[5 * plane] = ((float)q[4] / 255.0f - 0.5f) / 0.5f;
   }
+}
+
+template <int SS>
+__global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
+    const float* __restrict__ screen, const int32_t* __restrict__ faces,
+    const float* __restrict__ colour, const float* __restrict__ pos, int64_t V, int64_t M,
+    RenderView view, const int32_t* __restrict__ offsets, const int32_t* __restrict__ items,
+    int64_t n_items, RenderOut out) {
+  constexpr int T = RT_TILE * SS;
+  __shared__ unsigned long long keys[T * T];
+  __shared__ double xs[T], ys[T];
+  raster_resolve_tile<SS, TEX_NONE>(keys, xs, ys, screen, faces, colour, pos, V, M, view, offsets, items,
+                                    n_items, RenderTexture{nullptr, nullptr, 0}, out);
+}
+
+template <int SS, int FILTER>
+__global__ __launch_bounds__(256) void mesh_raster_resolve_textured_kernel(
+    const float* __restrict__ screen, const int32_t* __restrict__ faces, const float* __restrict__ pos,
+    int64_t V, int64_t M, RenderView view, const int32_t* __restrict__ offsets,
+    const int32_t* __restrict__ items, int64_t n_items, RenderTexture tex, RenderOut out) {
+  constexpr int T = RT_TILE * SS;
+  __shared__ unsigned long long keys[T * T];
+  __shared__ double xs[T], ys[T];
+  raster_resolve_tile<SS, FILTER>(keys, xs, ys, screen, faces, nullptr, pos, V, M, view, offsets, items,
+                                  n_items, tex, out);
 }
 
 // pos2edge (run_render.py:31-57) + the inversion of :120 on the RGBA8 position image: channels
@@ -335,6 +421,46 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
   if (ss == 1) DSU_RASTER(1);
   else if (ss == 2) DSU_RASTER(2);
   else DSU_RASTER(4);
+#undef DSU_RASTER
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, const float* colour,
+                                   const float* pos, const float* uv, const uint8_t* texture,
+                                   int32_t tex_size, int32_t filter, int32_t n_frames, int64_t n_verts,
+                                   int64_t n_faces, double cx, double cy, double span, int32_t size,
+                                   int32_t ss, void* workspace, int64_t workspace_bytes, int32_t* items,
+                                   int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id,
+                                   float* depth, float* frames, float* pixels, void* stream) {
+  (void)colour;                                          // the atlas replaces the vertex colours
+  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
+      n_verts > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  if (!uv || !texture || tex_size < 1 || tex_size > 8192 || (filter != 0 && filter != 1)) return DSU_EINVAL;
+  if ((uintptr_t)texture % 4) return DSU_EINVAL;         // a texel is one 32-bit load
+  const int64_t nb = bins_of(n_frames, size);
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
+  if (n_faces && (!screen || !faces || !pos || n_verts == 0)) return DSU_EINVAL;
+  if (n_items && !items) return DSU_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
+  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
+  const RenderTexture tex{uv, reinterpret_cast<const uint32_t*>(texture), tex_size};
+  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
+#define DSU_RASTER(SS_, F_)                                                                     \
+  mesh_raster_resolve_textured_kernel<SS_, F_><<<(unsigned)nb, 256, 0, st>>>(                    \
+      screen, faces, pos, n_verts, n_faces, view, offsets, items, n_faces ? n_items : 0, tex, out)
+  if (filter == TEX_NEAREST) {
+    if (ss == 1) DSU_RASTER(1, TEX_NEAREST);
+    else if (ss == 2) DSU_RASTER(2, TEX_NEAREST);
+    else DSU_RASTER(4, TEX_NEAREST);
+  } else {
+    if (ss == 1) DSU_RASTER(1, TEX_BILINEAR);
+    else if (ss == 2) DSU_RASTER(2, TEX_BILINEAR);
+    else DSU_RASTER(4, TEX_BILINEAR);
+  }
 #undef DSU_RASTER
   DSU_CHECK_LAUNCH();
   return DSU_OK;

@@ -11,6 +11,11 @@ action named by its file stem (the reference loops over `fbx_files` the same way
 are computed once and kept in `<uid>/mesh/skin_weights.npz`, and every clip is skinned and rendered
 on the device.  Names start at 0001.png, as Blender's do and as
 DatasetPatches_M.load_image expects; color and pos are RGBA, edge is 8-bit grey.
+
+`--texture atlas` renders the colour frames of a textured export (save_obj(export_uv=True): OBJ +
+MTL + PNG) from its atlas, sampled per sub-sample in the rasteriser (`--texture_filter bilinear` or
+`nearest`), as the reference's Blender reads `map_Kd`; the default `--texture vertex` renders vertex
+colours (for a textured export: the atlas's nearest texel at each vertex).
 """
 import argparse
 import glob
@@ -68,26 +73,35 @@ def run(argv=None):
     ap.add_argument("--test", action="store_true", help="render the test action (rest_rotate)")
     ap.add_argument("--frames", type=int, default=24, help="frames of the rest_rotate turntable")
     ap.add_argument("--ss", type=int, default=4, choices=[1, 2, 4], help="sub-samples per pixel side")
+    ap.add_argument("--texture", default="vertex", choices=["vertex", "atlas"],
+                    help="colour source: vertex colours, or the OBJ's map_Kd atlas sampled per sub-sample")
+    ap.add_argument("--texture_filter", default="bilinear", choices=["bilinear", "nearest"],
+                    help="how --texture atlas samples the atlas")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
     if not found:
         raise FileNotFoundError(f"no OBJ under {os.path.join(args.data_dir, args.uid, 'mesh')}")
-    verts, faces, colours = animate.read_obj(found[0])
-    if colours is None:
-        raise ValueError(f"{found[0]} has no vertex colours")
+    tex = {}
+    if args.texture == "atlas":
+        verts, faces, uvs, image = animate.read_obj_textured(found[0])     # refuses an untextured OBJ
+        colours, tex = None, dict(texture=image, uvs=uvs, texture_filter=args.texture_filter)
+    else:
+        verts, faces, colours = animate.read_obj(found[0])
+        if colours is None:
+            raise ValueError(f"{found[0]} has no vertex colours")
     mesh_dir = os.path.join(args.data_dir, args.uid, "mesh")
     for action, clip_path in plan_actions(mesh_dir, args.test):
         out_dir = os.path.join(mesh_dir, "blender_render", action)
         start = time.time()
         if clip_path is None:
             rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
-                                             device=args.device)
+                                             device=args.device, **tex)
         else:
             skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
             weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
-                                            ss=args.ss, device=args.device)
+                                            ss=args.ss, device=args.device, **tex)
         n = write_frames(out_dir, rendered)
         print((time.time() - start) / n, n)
     return out_dir, rendered

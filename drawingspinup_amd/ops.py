@@ -1411,12 +1411,19 @@ class MeshRenderPlan(_BinnedPlan):
             self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss,
             *self._bin_args(), *[ptr(o) for o in outs], stream()), "dsu_mesh_render_ortho")
 
-    def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames")):
+    def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames"), uv=None, texture=None,
+               filter="bilinear"):
         """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
         (F,S,S,4) uint8, face_id (F,N,N) i32, depth (F,N,N) f32, frames (F,6,S,S) f32, pixels
-        (F,S,S,8) f32."""
+        (F,S,S,8) f32.
+
+        With uv (V,2) f32 and texture (T,T,3) or (T,T,4) uint8 (both or neither) the colour of every
+        sample comes from the texture (dsu_mesh_render_ortho_textured; filter "bilinear" or
+        "nearest") and `colour` may be None; without them this is the vertex-colour call."""
         if self.items is None:
             raise DsuError("MeshRenderPlan.raster before bin()")
+        if (uv is None) != (texture is None):
+            raise ValueError("uv and texture come together or not at all")
         F, S, N, dev = self.F, self.size, self.size * self.ss, self.screen.device
         shapes = {"color_u8": ((F, S, S, 4), torch.uint8), "pos_u8": ((F, S, S, 4), torch.uint8),
                   "face_id": ((F, N, N), torch.int32), "depth": ((F, N, N), torch.float32),
@@ -1424,19 +1431,53 @@ class MeshRenderPlan(_BinnedPlan):
         bad = [w for w in want if w not in shapes]
         if bad:
             raise ValueError(f"unknown outputs {bad}")
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
-        colour, pos = _f32c(colour), _f32c(pos)
-        if colour.shape != (self.V, 3) or pos.shape != (self.V, 3):
+        pos = _f32c(pos)
+        if pos.shape != (self.V, 3):
             raise ValueError("colour and pos must be (V,3)")
-        self._stage(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
+        if texture is None:
+            colour = _f32c(colour)
+            if colour.shape != (self.V, 3):
+                raise ValueError("colour and pos must be (V,3)")
+            out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
+            self._stage(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
+            return out
+        if filter not in TEXTURE_FILTERS:
+            raise ValueError(f"filter must be one of {sorted(TEXTURE_FILTERS)}")
+        uv, rgba = _f32c(uv), texture_rgba(texture)
+        if uv.shape != (self.V, 2):
+            raise ValueError("uv must be (V,2)")
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
+        check(lib().dsu_mesh_render_ortho_textured(
+            ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), None, ptr(pos), ptr(uv),
+            ptr(rgba, torch.uint8), rgba.shape[0], TEXTURE_FILTERS[filter], self.F, self.V, self.M,
+            self.cx, self.cy, self.span, self.size, self.ss, *self._bin_args(),
+            *[ptr(out.get(k)) for k in shapes], stream()), "dsu_mesh_render_ortho_textured")
         return out
 
 
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}
+
+
+def texture_rgba(texture):
+    """(T,T,3) or (T,T,4) uint8 on the device -> the contiguous (T,T,4) RGBA8 texture of
+    dsu_mesh_render_ortho_textured (an opaque alpha is added to three channels; four are kept)."""
+    if not torch.is_tensor(texture) or texture.dtype != torch.uint8 or texture.dim() != 3 or \
+            texture.shape[0] != texture.shape[1] or texture.shape[2] not in (3, 4) or texture.shape[0] < 1:
+        raise ValueError("texture (T,T,3) or (T,T,4) uint8 expected")
+    if texture.shape[2] == 4:
+        return texture.contiguous()
+    rgba = torch.full((*texture.shape[:2], 4), 255, dtype=torch.uint8, device=texture.device)
+    rgba[..., :3] = texture
+    return rgba
+
+
 def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
-                      want=("color_u8", "pos_u8", "frames")):
-    """Orthographic render of F frames of one vertex-coloured mesh with two attribute sets
-    (include/dsu_hip.h, dsu_mesh_render_ortho): bin, then rasterise and resolve."""
-    return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want)
+                      want=("color_u8", "pos_u8", "frames"), uv=None, texture=None, filter="bilinear"):
+    """Orthographic render of F frames of one mesh with two attribute sets (include/dsu_hip.h,
+    dsu_mesh_render_ortho): bin, then rasterise and resolve.  The colours are the vertex colours,
+    or with uv and texture the texture's (dsu_mesh_render_ortho_textured)."""
+    return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want, uv, texture,
+                                                                              filter)
 
 
 def pos_edge_u8(pos_rgba):

@@ -1069,6 +1069,38 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
                           void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
                           uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
                           float* frames, float* pixels, void* stream);
+/* Textured frames: the RASTER stage of dsu_mesh_render_ortho with the colour of every sample taken
+ * from a UV atlas instead of the vertex colours (the reference's Blender reads the OBJ's map_Kd).
+ * Binning is dsu_mesh_render_ortho's COUNT and FILL on the same arguments and the same workspace.
+ *
+ * Additional inputs: uv (n_verts, 2) f32; texture (tex_size, tex_size, 4) uint8 RGBA, 4-byte
+ * aligned (a texel is one 32-bit load; the fourth byte is not read); 1 <= tex_size <= 8192;
+ * filter 0 = nearest, 1 = bilinear.  colour is not read and may be NULL.
+ *
+ * Rule.  Visibility, depth, alpha, the position pass, frames, the layout of pixels and everything
+ * downstream of pos_u8 are dsu_mesh_render_ortho's: the texture enters through the three colour
+ * channels and in no other way.  For a covered sample whose winner is face (a, b, c), with w0, w1,
+ * w2 and area as above and the vertex uvs widened from f32 to float64:
+ *     u = (w0 ua + w1 ub + w2 uc) / area,  v likewise,  tx = u T,  ty = v T  (T = tex_size);
+ *     a non-finite tx or ty is taken as 0.
+ * The texel convention is the bake's (dsu_uv_bake): image row r, column c holds uv T = (c, T - 1 - r).
+ *   nearest:   c = clamp(floor(tx + 0.5), 0, T - 1),  r = clamp(T - 1 - floor(ty + 0.5), 0, T - 1),
+ *              channel = (float)u8 / 255.0f.
+ *   bilinear:  x = clamp(tx, 0, T - 1),  y = clamp(T - 1 - ty, 0, T - 1),  c0 = floor(x),
+ *              c1 = min(c0 + 1, T - 1),  r0, r1 likewise from y,  fx = x - c0,  fy = y - r0,
+ *              channel = (((1 - fx)(1 - fy)) p00 + (fx (1 - fy)) p01 + ((1 - fx) fy) p10 + (fx fy) p11) / 255
+ *              in float64, summed left to right (p01 = row r0, column c1; p10 = row r1, column c0),
+ *              rounded to f32.  T = 1 is legal.
+ * The per-sample value goes where the interpolated vertex colour goes: accumulated in float64 over
+ * the pixel's covered samples in row-major order, divided by their count, uint8 = floor(v 255 + 0.5).
+ * No mip-mapping or area sampling: a texture much finer than the sample lattice aliases. */
+int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, const float* colour,
+                                   const float* pos, const float* uv, const uint8_t* texture,
+                                   int32_t tex_size, int32_t filter, int32_t n_frames, int64_t n_verts,
+                                   int64_t n_faces, double cx, double cy, double span, int32_t size,
+                                   int32_t ss, void* workspace, int64_t workspace_bytes, int32_t* items,
+                                   int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id,
+                                   float* depth, float* frames, float* pixels, void* stream);
 /* pos2edge (run_render.py:31-57) and the inversion of run_render.py:120 on RGBA8 position images
  * (n_frames, H, W, 4): channels u8 -> f32 / 255, every channel 2 where alpha8 < 255, per-channel 3x3
  * Sobel in float64 with reflect-101 borders, magnitude, maximum over the three colour channels,
