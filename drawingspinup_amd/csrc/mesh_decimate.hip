@@ -66,17 +66,44 @@ struct Quadric {
     return v.x * (a00 * v.x + 2 * a01 * v.y + 2 * a02 * v.z) + v.y * (a11 * v.y + 2 * a12 * v.z) +
            a22 * v.z * v.z + 2 * (b0 * v.x + b1 * v.y + b2 * v.z) + c;
   }
-  // minimiser -A^-1 b when A is well conditioned relative to its own scale
-  bool minimum(V3& out) const {
+  // minimiser -A^-1 b when A is well conditioned relative to its own scale, as o + d with
+  // A d = -(b + A o) for a point o near the answer (the edge's midpoint), by elimination with
+  // partial pivoting.  Not the cofactor inverse: on a near-planar quadric (eigenvalues l1 >> l2 of
+  // A) every 2x2 minor cancels to ~l1 l2 with rounding eps l1^2, which puts a factor l1 / l2 on top
+  // of the eps cond(A) |x| a stable solve loses — 8e-8 on marching-cubes vertices at |x| ~ 20,
+  // cond(A) = 3e4.  About o the right-hand side is small, so what is left is eps cond(A) |x| from
+  // its rounding.  The determinant still decides whether to solve at all.
+  struct Row4 {
+    double c[4];
+  };
+  static void swap_if(Row4& a, Row4& b, bool s) {
+    if (s) std::swap(a, b);
+  }
+  static void eliminate(Row4& r, const Row4& piv, int col) {
+    const double f = r.c[col] / piv.c[col];
+    for (int k = 0; k < 4; ++k) r.c[k] -= f * piv.c[k];
+  }
+  bool minimum(V3 o, V3& out) const {
     const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
     const double det = a00 * c00 + a01 * c01 + a02 * c02;
     const double tr = a00 + a11 + a22;
     if (!(tr > 0.0) || !(fabs(det) > 1e-9 * tr * tr * tr)) return false;
-    const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-    const double inv = -1.0 / det;
-    out.x = inv * (c00 * b0 + c01 * b1 + c02 * b2);
-    out.y = inv * (c01 * b0 + c11 * b1 + c12 * b2);
-    out.z = inv * (c02 * b0 + c12 * b1 + c22 * b2);
+    Row4 r0 = {{a00, a01, a02, -(b0 + (a00 * o.x + a01 * o.y + a02 * o.z))}};
+    Row4 r1 = {{a01, a11, a12, -(b1 + (a01 * o.x + a11 * o.y + a12 * o.z))}};
+    Row4 r2 = {{a02, a12, a22, -(b2 + (a02 * o.x + a12 * o.y + a22 * o.z))}};
+    swap_if(r0, r1, fabs(r1.c[0]) > fabs(r0.c[0]));
+    swap_if(r0, r2, fabs(r2.c[0]) > fabs(r0.c[0]));
+    if (!(fabs(r0.c[0]) > 0.0)) return false;
+    eliminate(r1, r0, 0);
+    eliminate(r2, r0, 0);
+    swap_if(r1, r2, fabs(r2.c[1]) > fabs(r1.c[1]));
+    if (!(fabs(r1.c[1]) > 0.0)) return false;
+    eliminate(r2, r1, 1);
+    if (!(fabs(r2.c[2]) > 0.0)) return false;
+    const double z = r2.c[3] / r2.c[2];
+    const double y = (r1.c[3] - r1.c[2] * z) / r1.c[1];
+    const double x = (r0.c[3] - r0.c[1] * y - r0.c[2] * z) / r0.c[0];
+    out = {o.x + x, o.y + y, o.z + z};
     return true;
   }
 };
@@ -124,10 +151,10 @@ struct Mesh {
 void edge_target(const Mesh& m, int32_t v0, int32_t v1, double& cost, V3& vbar) {
   Quadric q = m.q[v0];
   q.add(m.q[v1]);
-  if (q.minimum(vbar)) {
+  const V3 mid = (m.v[v0] + m.v[v1]) * 0.5;
+  if (q.minimum(mid, vbar)) {
     // a minimiser far outside the edge's neighbourhood means the conditioning test was too kind
     const double len = norm(m.v[v1] - m.v[v0]);
-    const V3 mid = (m.v[v0] + m.v[v1]) * 0.5;
     if (norm(vbar - mid) <= 4.0 * len) {
       cost = q.eval(vbar);
       return;

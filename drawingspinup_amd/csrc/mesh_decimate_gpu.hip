@@ -69,18 +69,40 @@ __device__ inline double quad_eval(const Quad& a, D3 v) {
          v.y * (a.q[3] * v.y + 2 * a.q[4] * v.z) + a.q[5] * v.z * v.z +
          2 * (a.q[6] * v.x + a.q[7] * v.y + a.q[8] * v.z) + a.q[9];
 }
-__device__ inline bool quad_minimum(const Quad& a, D3& out) {
+// mesh_decimate.hip: Quadric::minimum (same arithmetic: see there why it is not the cofactor inverse)
+struct Row4 {
+  double c[4];
+};
+__device__ inline void row_swap_if(Row4& a, Row4& b, bool s) {
+  if (s) { const Row4 t = a; a = b; b = t; }
+}
+__device__ inline void row_eliminate(Row4& r, const Row4& piv, int col) {
+  const double f = r.c[col] / piv.c[col];
+  for (int k = 0; k < 4; ++k) r.c[k] -= f * piv.c[k];
+}
+__device__ inline bool quad_minimum(const Quad& a, D3 o, D3& out) {
   const double a00 = a.q[0], a01 = a.q[1], a02 = a.q[2], a11 = a.q[3], a12 = a.q[4], a22 = a.q[5];
   const double b0 = a.q[6], b1 = a.q[7], b2 = a.q[8];
   const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
   const double det = a00 * c00 + a01 * c01 + a02 * c02;
   const double tr = a00 + a11 + a22;
   if (!(tr > 0.0) || !(fabs(det) > 1e-9 * tr * tr * tr)) return false;
-  const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-  const double inv = -1.0 / det;
-  out.x = inv * (c00 * b0 + c01 * b1 + c02 * b2);
-  out.y = inv * (c01 * b0 + c11 * b1 + c12 * b2);
-  out.z = inv * (c02 * b0 + c12 * b1 + c22 * b2);
+  Row4 r0 = {{a00, a01, a02, -(b0 + (a00 * o.x + a01 * o.y + a02 * o.z))}};
+  Row4 r1 = {{a01, a11, a12, -(b1 + (a01 * o.x + a11 * o.y + a12 * o.z))}};
+  Row4 r2 = {{a02, a12, a22, -(b2 + (a02 * o.x + a12 * o.y + a22 * o.z))}};
+  row_swap_if(r0, r1, fabs(r1.c[0]) > fabs(r0.c[0]));
+  row_swap_if(r0, r2, fabs(r2.c[0]) > fabs(r0.c[0]));
+  if (!(fabs(r0.c[0]) > 0.0)) return false;
+  row_eliminate(r1, r0, 0);
+  row_eliminate(r2, r0, 0);
+  row_swap_if(r1, r2, fabs(r2.c[1]) > fabs(r1.c[1]));
+  if (!(fabs(r1.c[1]) > 0.0)) return false;
+  row_eliminate(r2, r1, 1);
+  if (!(fabs(r2.c[2]) > 0.0)) return false;
+  const double z = r2.c[3] / r2.c[2];
+  const double y = (r1.c[3] - r1.c[2] * z) / r1.c[1];
+  const double x = (r0.c[3] - r0.c[1] * y - r0.c[2] * z) / r0.c[0];
+  out = {o.x + x, o.y + y, o.z + z};
   return true;
 }
 
@@ -109,9 +131,9 @@ __device__ inline void edge_target(const Mesh& m, int32_t v0, int32_t v1, double
   const Quad q1 = ldQ(m, v1);
   for (int i = 0; i < 10; ++i) q.q[i] += q1.q[i];
   const D3 p0 = ldP(m, v0), p1 = ldP(m, v1);
-  if (quad_minimum(q, vbar)) {
+  const D3 mid = (p0 + p1) * 0.5;
+  if (quad_minimum(q, mid, vbar)) {
     const double len = norm3(p1 - p0);
-    const D3 mid = (p0 + p1) * 0.5;
     if (norm3(vbar - mid) <= 4.0 * len) {
       cost = quad_eval(q, vbar);
       return;

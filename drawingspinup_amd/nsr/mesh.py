@@ -528,17 +528,51 @@ PARALLEL_STOP, PARALLEL_FLOOR, PARALLEL_MIN_FACES = 1.25, 1.0, 20000
 last_remesh_stats = {}
 
 
+def _decimate_parallel(verts, faces, stop_faces, floor_faces, boundary_weight, keep_manifold, max_rounds, workspace):
+    import ctypes as C
+    from .. import _lib, ops
+    dev = verts.device
+    v = verts.detach().to(torch.float64).contiguous().clone()
+    f = faces.detach().to(dev, torch.int32).contiguous().clone()
+    nv, n_faces = v.shape[0], int(f.shape[0])
+    lib = _lib.lib()
+    ws_bytes = int(lib.dsu_mesh_decimate_parallel_workspace_bytes(nv, n_faces))
+    if ws_bytes < 0:
+        raise ops.DsuError("dsu_mesh_decimate_parallel_workspace_bytes: unsupported size")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.dtype == torch.uint8 and ws.device == dev and ws.dim() == 1 and ws.is_contiguous(), \
+        "workspace: a contiguous 1-D uint8 tensor on the device of verts"
+    quad = torch.empty(nv, 10, dtype=torch.float64, device=dev)
+    out_nf = C.c_int64(0)
+    stats = (C.c_int32 * 3)()
+    ops.check(lib.dsu_mesh_decimate_parallel(
+        v.data_ptr(), nv, f.data_ptr(), n_faces, int(stop_faces), int(floor_faces), float(boundary_weight),
+        0 if keep_manifold else 1, int(max_rounds), quad.data_ptr(), C.byref(out_nf), stats, ws.data_ptr(),
+        int(ws.numel()), torch.cuda.current_stream(dev).cuda_stream), "dsu_mesh_decimate_parallel")
+    return v, f[:out_nf.value], quad, list(stats)
+
+
+def decimate_parallel(verts, faces, stop_faces, floor_faces, boundary_weight=1.0, keep_manifold=True,
+                      max_rounds=200, workspace=None):
+    """The device rounds alone (`dsu_mesh_decimate_parallel`) on device tensors of any size:
+    -> (verts (n_verts,3) float64, live faces (m,3) int32, quadrics (n_verts,10) float64, stats
+    (3,) int32 = rounds, collapses, rejected), device tensors over all n_verts in the C ABI's
+    indexing (collapsed vertices keep their rows; no live face names them).  The inputs are not
+    modified.  `workspace`: a uint8 device tensor to use instead of a fresh allocation."""
+    v, f, quad, stats = _decimate_parallel(verts, faces, stop_faces, floor_faces, boundary_weight, keep_manifold,
+                                           max_rounds, workspace)
+    return v, f, quad, torch.tensor(stats, dtype=torch.int32, device=v.device)
+
+
 def remesh(verts, faces, face_count, boundary_weight=1.0, keep_manifold=True):
     """mesh_utils.py:10-22 (`trimesh.simplify_quadratic_decimation(face_count)` -> Open3D's quadric
     decimation): (N,3) float verts, (M,3) int faces -> (verts float64, faces int64) numpy arrays,
     collapsed until the face count is <= face_count (or no admissible collapse is left).
     Device tensors (the export path: 1-3 M triangles from the 512^3 marching cubes): rounds of
-    independent collapses on the GPU down to 1.25 x face_count (`dsu_mesh_decimate_parallel`), then
+    independent collapses on the GPU down to 1.25 x face_count (`decimate_parallel`), then
     the serial queue for the last stretch.  Host arrays: the serial queue alone
     (`dsu_mesh_decimate_quadric`; restated from the published method — trimesh / Open3D are absent:
     unpinned, see the kernel files' headers for what is kept and what is added)."""
-    import ctypes as C
-    from .. import _lib, ops
     on_device = torch.is_tensor(verts) and verts.is_cuda
     n_faces = int(faces.shape[0])
     if not on_device or n_faces <= max(PARALLEL_MIN_FACES, PARALLEL_STOP * face_count):
@@ -547,27 +581,11 @@ def remesh(verts, faces, face_count, boundary_weight=1.0, keep_manifold=True):
         f = np.ascontiguousarray(np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces)
                                  .astype(np.int32))
         return _remesh_host(v, f, face_count, boundary_weight, keep_manifold)
-    dev = verts.device
-    v = verts.detach().to(torch.float64).contiguous().clone()
-    f = faces.detach().to(dev, torch.int32).contiguous().clone()
-    nv = v.shape[0]
-    lib = _lib.lib()
-    ws_bytes = int(lib.dsu_mesh_decimate_parallel_workspace_bytes(nv, n_faces))
-    if ws_bytes < 0:
-        raise ops.DsuError("dsu_mesh_decimate_parallel_workspace_bytes: unsupported size")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    quad = torch.empty(nv, 10, dtype=torch.float64, device=dev)
-    out_nf = C.c_int64(0)
-    stats = (C.c_int32 * 3)()
-    ops.check(lib.dsu_mesh_decimate_parallel(
-        v.data_ptr(), nv, f.data_ptr(), n_faces, int(PARALLEL_STOP * face_count),
-        int(PARALLEL_FLOOR * face_count), float(boundary_weight), 0 if keep_manifold else 1, 200,
-        quad.data_ptr(), C.byref(out_nf), stats, ws.data_ptr(), ws_bytes,
-        torch.cuda.current_stream(dev).cuda_stream), "dsu_mesh_decimate_parallel")
-    f = f[:out_nf.value]
+    v, f, quad, stats = _decimate_parallel(verts, faces, int(PARALLEL_STOP * face_count),
+                                           int(PARALLEL_FLOOR * face_count), boundary_weight, keep_manifold, 200, None)
     # only the vertices still in use travel to the host
     used, inv = torch.unique(f.reshape(-1).long(), return_inverse=True)
-    last_remesh_stats.update(input_faces=n_faces, device_faces=int(out_nf.value), rounds=int(stats[0]),
+    last_remesh_stats.update(input_faces=n_faces, device_faces=int(f.shape[0]), rounds=int(stats[0]),
                              collapses=int(stats[1]), rejected=int(stats[2]))
     hv = np.ascontiguousarray(v[used].cpu().numpy())
     hq = np.ascontiguousarray(quad[used].cpu().numpy())

@@ -30,12 +30,25 @@ def _target(Q, v0, v1):
     return costs[k], cands[k]
 
 
-def decimate(verts, faces, target_faces, boundary_weight=1.0, keep_manifold=True):
+_ORDER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2), (0, 3), (1, 3), (2, 3), (3, 3))
+
+
+def decimate(verts, faces, target_faces, boundary_weight=1.0, keep_manifold=True, quadrics=None,
+             return_quadrics=False):
+    """`quadrics`: (n_verts, 10) in the library's layout a00 a01 a02 a11 a12 a22 b0 b1 b2 c — the
+    queue starts from them and adds no face or boundary plane of its own, as
+    dsu_mesh_decimate_quadric_q does.  `return_quadrics`: also return the accumulated 4x4 quadric of
+    every output vertex."""
     v = [np.array(p, np.float64) for p in verts]
     f = [list(map(int, t)) for t in faces if len(set(map(int, t))) == 3]
     Q = [np.zeros((4, 4)) for _ in v]
     cnt = {}
-    for t in f:
+    if quadrics is not None:
+        for q, row in zip(Q, np.asarray(quadrics, np.float64)):
+            for k, (i, j) in enumerate(_ORDER):
+                q[i, j] = q[j, i] = row[k]
+        boundary_weight = 0.0
+    for t in [] if quadrics is not None else f:
         cr = np.cross(v[t[1]] - v[t[0]], v[t[2]] - v[t[0]])
         l = np.linalg.norm(cr)
         if l > 0:
@@ -119,5 +132,7 @@ def decimate(verts, faces, target_faces, boundary_weight=1.0, keep_manifold=True
                     if i != v0:
                         orient[tuple(sorted((v0, i)))] = v0
     used = sorted({i for t in f for i in t})
+    if return_quadrics:
+        return np.array([v[i] for i in used]), f, used, [Q[i] for i in used]
     return np.array([v[i] for i in used]), f, used
 
