@@ -270,6 +270,8 @@ _PROTOS = {
     "dsu_groupnorm_nhwc_f16": [P, P, P, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, P, P, P],
     "dsu_layernorm_f16": [P, P, P, c_i64, c_i32, c_f32, P, P],
     "dsu_geglu_f16": [P, c_i64, c_i32, P, P],
+    "dsu_cfg_model_input": [P, P, c_i32, c_i64, P, P],
+    "dsu_ddim_cfg_step": [P, P, P, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, P, P],
     "dsu_deform_tap_table_bytes": [c_i32, c_i32],
     "dsu_deform_tap_table": [P, c_i32, c_i32, P, P],
     "dsu_conv2d_wgrad_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32],

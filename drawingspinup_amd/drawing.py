@@ -84,13 +84,14 @@ class DrawingPipeline:
 
     def __init__(self, device="cuda", seed=0, mv_steps=75, nsr_steps=3000, n_frames=24,
                  with_clip=True, export_resolution=512, with_mv=True, with_contour=True, mesh_post=True,
-                 with_matting=None, isnet_weights=None, frames="synthetic"):
+                 with_matting=None, isnet_weights=None, guidance_scale=1.0, frames="synthetic"):
         if frames not in ("synthetic", "rendered"):
             raise ValueError("frames: 'synthetic' or 'rendered'")
         self.frames = frames                 # what stage 3 stylises: synthetic maps, or the mesh rendered
         self.render_ss = 4                   # sub-samples per pixel side of the rendered frames
         self.device = torch.device(device)
         self.mv_steps, self.nsr_steps, self.n_frames = mv_steps, nsr_steps, n_frames
+        self.guidance_scale = guidance_scale  # the multi-view pipeline's; 1.0 (the shipped YAML) = no guidance
         self.style_batch = 4                 # frames per generator call
         self.time_substages = False          # bench.py: split the NSR stage into fit / export (the
         #                                      synchronisations are the CURRENT STREAM's: several drawings
@@ -183,7 +184,7 @@ class DrawingPipeline:
         img = (small[..., :3] * small[..., 3:4] + (1.0 - small[..., 3:4])).permute(2, 0, 1)[None]
         imgs_in = img.expand(12, -1, -1, -1).contiguous()
         g = torch.Generator(device=self.device).manual_seed(seed)
-        out = self.mv(imgs_in, generator=g, guidance_scale=1.0, output_type="pt", eta=1.0,
+        out = self.mv(imgs_in, generator=g, guidance_scale=self.guidance_scale, output_type="pt", eta=1.0,
                       num_inference_steps=self.mv_steps)
         return out[:6], out[6:]
 

@@ -9,6 +9,18 @@ definitions.  Same call signature for the arguments mv.py uses (mv.py:79-86):
              num_images_per_prompt=1, eta=1.0, num_inference_steps=75)
 plus `latents=` / `step_noise=` to inject the random draws (tests; RNG streams differ between
 CUDA and HIP).
+
+guidance_scale == 1.0 (the shipped YAML) is the loop without classifier-free guidance.  Any other
+value runs the reference's guided branch (:164-180, :290-294, :465-477): the batch becomes
+[unconditional: 6 normal, 6 colour | conditional: 6 normal, 6 colour] — zero image embedding and zero
+image latents in the unconditional half, camera embedding duplicated (`cfg_conditioning`) — the UNet
+runs on 2B rows, and `uncond + g (cond - uncond)` goes into the scheduler step.  Initial latents,
+per-step noise and the callback's latents keep B rows.  Around the UNet call the step is two HIP
+kernels: ops.cfg_model_input (the 2B-row input) and ops.ddim_cfg_step (guidance + DDIM step in
+double, one rounding to f16; the reference rounds the guided prediction to f16 first).  The
+reference's joint attention still halves the batch (transformer_mv2d.py:878-883), so with guidance
+it couples every unconditional row with its conditional twin instead of normal with colour;
+unet._seg_table reproduces that (PARITY.md, documented deviations).
 """
 import math
 
@@ -101,6 +113,17 @@ class DDIMScheduler:
                                              device=model_output.device, dtype=model_output.dtype)
             prev = prev + std * variance_noise.float()
         return prev.to(sample.dtype)
+
+    def step_scalars(self, timestep, eta=0.0):
+        """sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), std of `step` as host floats (f32 values: the
+        arithmetic `step` does on its 0-d f32 tensors), for ops.ddim_cfg_step."""
+        t = int(timestep)
+        prev_t = t - self.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        variance = ((1 - a_prev) / (1 - a_t)) * (1 - a_t / a_prev)
+        std = eta * variance ** 0.5
+        return float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_prev ** 0.5), float(std)
 
 
 # ----------------------------------------------------------------------------------- VAE
@@ -255,6 +278,16 @@ DEFAULT_CAMERA_EMBEDDING = torch.tensor(      # pipeline_mvdiffusion_image.py:13
     dtype=torch.float16)
 
 
+def cfg_conditioning(image_embeddings, image_latents, camera):
+    """The conditioning of the guided batch, unconditional half first (pipeline_mvdiffusion_image.py
+    :164-170, :179-180, :290-294): (B,1,768) -> (2B,1,768) with a zero "negative" embedding,
+    (B,4,h,w) -> (2B,4,h,w) with zero image latents, the sin|cos camera embedding (B,10) -> (2B,10)
+    duplicated.  Pure torch, any device / dtype."""
+    return (torch.cat([torch.zeros_like(image_embeddings), image_embeddings]),
+            torch.cat([torch.zeros_like(image_latents), image_latents]),
+            torch.cat([camera, camera], dim=0))
+
+
 class MVDiffusionImagePipeline:
     def __init__(self, unet, vae, image_encoder, scheduler=None, num_views=6):
         self.unet, self.vae, self.image_encoder = unet, vae, image_encoder
@@ -262,7 +295,23 @@ class MVDiffusionImagePipeline:
         self.num_views = num_views
         self.vae_scale_factor = 8
         self.use_graph = False        # True: replay the UNet step from a captured HIP graph (see _unet_step)
-        self._graph = None
+        self._graphs = {}             # shapes -> capture, most recently replayed last (see drop_graphs)
+
+    @property
+    def _graph(self):
+        """The capture replayed last, or None.  `pipe._graph = None` drops every capture."""
+        return next(reversed(self._graphs.values()), None)
+
+    @_graph.setter
+    def _graph(self, value):
+        assert value is None, "captures are made by _unet_step; assign None to drop them"
+        self.drop_graphs()
+
+    def drop_graphs(self):
+        """Forget every captured UNet step (B rows, and 2B rows with guidance): the next call under
+        `use_graph` captures again.  To be called after the UNet's weights change — a capture holds
+        the pointers of the tensors the UNet derives from them — or to give the captures' memory back."""
+        self._graphs.clear()
 
     @property
     def device(self):
@@ -296,17 +345,18 @@ class MVDiffusionImagePipeline:
         and ~600 launches each.  With `use_graph` set the forward is captured once into a HIP graph
         (static input/output buffers) and replayed: bit-identical output, but measured no faster
         on MI355X (the step is GPU-bound: 14.8 ms either way) and the capture costs ~2.7 s, so
-        eager is the default."""
+        eager is the default.  One capture per set of shapes is kept (12 rows, and 24 with guidance),
+        so a pipeline that alternates between them replays both."""
         if not self.use_graph:
             return self.unet(model_in, t, image_embeddings, cam)
-        g = self._graph
         key = (tuple(model_in.shape), tuple(image_embeddings.shape), tuple(cam.shape))
-        if g is None or g["key"] != key:
+        g = self._graphs.pop(key, None)
+        if g is None:
             g = {"key": key, "x": torch.empty_like(model_in), "t": torch.zeros(1, device=model_in.device,
                                                                            dtype=t.dtype),
                  "emb": torch.empty_like(image_embeddings), "cam": torch.empty_like(cam),
                  "graph": None, "out": None}
-            self._graph = g
+        self._graphs[key] = g                    # (re-)inserted last: the one `_graph` shows
         g["x"].copy_(model_in)
         g["t"].copy_(t.reshape(1))
         g["emb"].copy_(image_embeddings)
@@ -318,12 +368,49 @@ class MVDiffusionImagePipeline:
                 for _ in range(2):                       # warm-up outside the capture
                     self.unet(g["x"], g["t"], g["emb"], g["cam"])
             torch.cuda.current_stream().wait_stream(side)
+            # the UNet keeps its cross-attention term per context tensor and version: written again,
+            # the context misses that cache, and the capture holds the term's kernels and output
+            # instead of pointing at the warm-up's tensor (stale for the next image, and freed as
+            # soon as a capture of other shapes replaces the cache entry)
+            g["emb"].copy_(image_embeddings)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 g["out"] = self.unet(g["x"], g["t"], g["emb"], g["cam"])
             g["graph"] = graph
         g["graph"].replay()
         return g["out"]
+
+    def _guided_loop(self, latents, image_embeddings, image_latents, cam, guidance_scale, eta,
+                     generator, step_noise, callback):
+        """pipeline_mvdiffusion_image.py:463-486 with do_classifier_free_guidance: the UNet on
+        [uncond | cond] rows, then guidance and the scheduler step.  Epsilon prediction (the shipped
+        scheduler config): ops.cfg_model_input and ops.ddim_cfg_step around the UNet call;
+        v_prediction: the same step in torch ops through `scheduler.step`."""
+        sch = self.scheduler
+        dev, dt = latents.device, latents.dtype
+        latents = latents.contiguous()
+        fused = isinstance(sch, DDIMScheduler) and sch.prediction_type == "epsilon"
+        image_embeddings, image_latents2, cam = cfg_conditioning(image_embeddings, image_latents, cam)
+        for i, t in enumerate(sch.timesteps):
+            if fused:
+                model_in = ops.cfg_model_input(latents, image_latents)
+            else:
+                model_in = torch.cat([torch.cat([latents] * 2), image_latents2], dim=1)
+            noise_pred = self._unet_step(model_in, t, image_embeddings, cam)
+            vn = None if step_noise is None else step_noise[i].to(dev, dt)
+            t_host = sch.timesteps_host[i] if hasattr(sch, "timesteps_host") else t
+            if fused:
+                if eta > 0 and vn is None:      # as `step` draws it: in the guided prediction's shape, B rows
+                    vn = torch.randn(latents.shape, generator=generator, device=dev, dtype=dt)
+                latents = ops.ddim_cfg_step(noise_pred, latents, vn.contiguous() if eta > 0 else None,
+                                            guidance_scale, *sch.step_scalars(t_host, eta))
+            else:
+                uncond, cond = noise_pred.chunk(2)
+                latents = sch.step(uncond + guidance_scale * (cond - uncond), t_host, latents, eta=eta,
+                                   generator=generator, variance_noise=vn)
+            if callback is not None:
+                callback(i, t, latents)
+        return latents
 
     def prepare_camera_embedding(self, camera_embedding):
         ce = camera_embedding.to(dtype=torch.float16, device=self.device)
@@ -333,8 +420,8 @@ class MVDiffusionImagePipeline:
     def __call__(self, image, camera_embedding=None, height=256, width=256,
                  num_inference_steps=75, guidance_scale=1.0, num_images_per_prompt=1, eta=1.0,
                  generator=None, latents=None, output_type="pt", step_noise=None, callback=None):
-        assert guidance_scale == 1.0 and num_images_per_prompt == 1, \
-            "mv.py runs without classifier-free guidance (mv.py:81-83)"
+        assert num_images_per_prompt == 1, "mv.py asks for one image per prompt (mv.py:84)"
+        do_cfg = guidance_scale != 1.0                                 # pipeline :413
         dev, dt = self.device, torch.float16
         image = image.to(dev)
         B = image.shape[0]
@@ -348,16 +435,20 @@ class MVDiffusionImagePipeline:
         if latents is None:
             latents = torch.randn(shape, generator=generator, device=dev, dtype=dt)
         latents = latents.to(dev, dt) * self.scheduler.init_noise_sigma
-        for i, t in enumerate(self.scheduler.timesteps):
-            model_in = torch.cat([latents, image_latents], dim=1)
-            noise_pred = self._unet_step(model_in, t, image_embeddings, cam)
-            vn = None if step_noise is None else step_noise[i].to(dev, dt)
-            # the host copy of the schedule: int(device tensor) was one blocking read-back per step
-            t_host = self.scheduler.timesteps_host[i] if hasattr(self.scheduler, "timesteps_host") else t
-            latents = self.scheduler.step(noise_pred, t_host, latents, eta=eta, generator=generator,
-                                          variance_noise=vn)
-            if callback is not None:
-                callback(i, t, latents)
+        if do_cfg:
+            latents = self._guided_loop(latents, image_embeddings, image_latents, cam, guidance_scale,
+                                        eta, generator, step_noise, callback)
+        else:
+            for i, t in enumerate(self.scheduler.timesteps):
+                model_in = torch.cat([latents, image_latents], dim=1)
+                noise_pred = self._unet_step(model_in, t, image_embeddings, cam)
+                vn = None if step_noise is None else step_noise[i].to(dev, dt)
+                # the host copy of the schedule: int(device tensor) was one blocking read-back per step
+                t_host = self.scheduler.timesteps_host[i] if hasattr(self.scheduler, "timesteps_host") else t
+                latents = self.scheduler.step(noise_pred, t_host, latents, eta=eta, generator=generator,
+                                              variance_noise=vn)
+                if callback is not None:
+                    callback(i, t, latents)
         if output_type == "latent":
             return latents
         img = self.vae.decode(latents / self.vae.scaling_factor)

@@ -433,16 +433,18 @@ def _time_projections(self, temb_act):
     _, w, b, sizes = hit
     out = ops.linear_f16(temb_act.contiguous(), w, b)                   # (B, sum O)
     B, total = out.shape
-    idx = self.__dict__.get("_dsu_tproj_idx")
-    if idx is None or idx[0] != (B, total, str(out.device)):
+    # one index tensor per batch size, kept for the module's life: a captured HIP graph holds the
+    # pointer of the one it was captured with (the pipeline keeps a capture per set of shapes)
+    idx_cache = self.__dict__.setdefault("_dsu_tproj_idx", {})
+    idx = idx_cache.get((B, total, str(out.device)))
+    if idx is None:
         cols, rows = torch.arange(total), torch.arange(B)
         parts, c0 = [], 0
         for o in sizes:                      # block i, packed: rows of (B, o) one after the other
             parts.append((rows[:, None] * total + cols[None, c0:c0 + o]).reshape(-1))
             c0 += o
-        idx = ((B, total, str(out.device)), torch.cat(parts).to(out.device))
-        self.__dict__["_dsu_tproj_idx"] = idx
-    flat = out.reshape(-1).index_select(0, idx[1])                       # ONE gather for all blocks
+        idx = idx_cache[(B, total, str(out.device))] = torch.cat(parts).to(out.device)
+    flat = out.reshape(-1).index_select(0, idx)                       # ONE gather for all blocks
     res, off = {}, 0
     for m, o in zip(blocks, sizes):
         res[id(m)] = flat[off:off + B * o].view(B, o)

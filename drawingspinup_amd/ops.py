@@ -1203,6 +1203,35 @@ def geglu_f16(h):
     return out
 
 
+# ------------------------------------------------------------------ classifier-free guidance (mv pipeline)
+def cfg_model_input(latents, image_latents):
+    """latents, image_latents (B,C,h,w) f16 -> the guided UNet input (2B,2C,h,w):
+    rows 0..B-1 [latents | 0], rows B..2B-1 [latents | image_latents]."""
+    assert latents.dim() == 4 and latents.shape == image_latents.shape
+    B, Cc, h, w = latents.shape
+    f16 = torch.float16
+    out = torch.empty((2 * B, 2 * Cc, h, w), dtype=f16, device=latents.device)
+    check(lib().dsu_cfg_model_input(ptr(latents, f16), ptr(image_latents, f16), B, Cc * h * w,
+                                    ptr(out), stream()), "dsu_cfg_model_input")
+    return out
+
+
+def ddim_cfg_step(noise_pred, latents, variance_noise, guidance_scale, sqrt_a_t, sqrt_1m_a_t,
+                  sqrt_a_prev, std):
+    """noise_pred (2B,C,h,w) f16 (unconditional rows first), latents (B,C,h,w) f16, variance_noise
+    (B,C,h,w) f16 or None -> the next latents (B,C,h,w) f16: guidance u + g (c - u) and the DDIM
+    step (epsilon prediction) in double, rounded to f16 once (include/dsu_hip.h has the rule)."""
+    assert noise_pred.shape == (2 * latents.shape[0],) + tuple(latents.shape[1:])
+    assert variance_noise is None or variance_noise.shape == latents.shape
+    f16 = torch.float16
+    out = torch.empty_like(latents, memory_format=torch.contiguous_format)
+    check(lib().dsu_ddim_cfg_step(ptr(noise_pred, f16), ptr(latents, f16), ptr(variance_noise, f16),
+                                  latents.numel(), float(guidance_scale), float(sqrt_a_t),
+                                  float(sqrt_1m_a_t), float(sqrt_a_prev), float(std), ptr(out),
+                                  stream()), "dsu_ddim_cfg_step")
+    return out
+
+
 # ------------------------------------------------------------------ fused NeuS shading / compositing
 def shade_prep_fwd(grad, feature):
     grad, feature = _f32c(grad), _f32c(feature)

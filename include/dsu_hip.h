@@ -781,6 +781,39 @@ int dsu_layernorm_f16(const void* x, const void* gamma, const void* beta, int64_
  * h (rows, 2*D) f16 = proj output; out[r][j] = h[r][j] * gelu_erf(h[r][D+j]). */
 int dsu_geglu_f16(const void* h, int64_t rows, int32_t D, void* out, void* stream);
 
+/* Classifier-free guidance around the UNet call of MVDiffusionImagePipeline.__call__
+ * (2_charactor_reconstructor/mvdiffusion/pipelines/pipeline_mvdiffusion_image.py, guidance_scale != 1).
+ *
+ * dsu_cfg_model_input — the UNet input of one step (:180 and :465-468: `cat([latents] * 2)`,
+ * `cat([.., cat([zeros_like(image_latents), image_latents])], dim=1)`) in one pass:
+ *   latents, image_latents (B, row_elems) f16, row_elems = C*h*w of one latent (C = 4);
+ *   out (2B, 2*row_elems) f16: rows 0..B-1 = [latents[b] | 0], rows B..2B-1 =
+ *   [latents[b] | image_latents[b]].  out must not alias an input.  Any row_elems >= 0.
+ *
+ * dsu_ddim_cfg_step — guidance (:476-477) and DDIMScheduler.step (diffusers 0.19.3, epsilon
+ * prediction, clip_sample False) in one pass over n = B*C*h*w elements:
+ *   noise_pred (2n) f16 = the UNet output, unconditional rows first; latents (n) f16;
+ *   variance_noise (n) f16 or NULL (NULL: no noise term, whatever std_dev is);
+ *   sqrt_a_t = sqrt(alphas_cumprod[t]), sqrt_1m_a_t = sqrt(1 - alphas_cumprod[t]),
+ *   sqrt_a_prev = sqrt(alphas_cumprod[t_prev]), std_dev = eta * sqrt(variance): the host's, as f32.
+ *   Per element, from the f16 inputs and the f32 scalars, in this operand order:
+ *     n    = u + g * (c - u)                        u = noise_pred[i], c = noise_pred[n + i]
+ *     x0   = (x - sqrt_1m_a_t * n) / sqrt_a_t       x = latents[i]
+ *     prev = sqrt_a_prev * x0 + dir * n             dir = sqrt(1 - sqrt_a_prev^2 - std_dev^2)
+ *     prev = prev + std_dev * variance_noise[i]
+ *     out[i] = (f16)prev                            the only rounding to f16
+ *   evaluated in double, so that out is the rounding of the rule's exact value to within the f16
+ *   conversion: the two terms of prev are of order 1 each and can cancel, and f32 roundings of them
+ *   (~1e-7) would exceed the f16 spacing of a result near zero (6e-8).  (The reference forms n in
+ *   f16 on its GPU and rounds it before the step, whose arithmetic is f32; here n is not rounded.)
+ *   DSU_EINVAL: sqrt_a_t <= 0, std_dev < 0, a radicand below -1e-6 (between that and 0: dir = 0),
+ *   out aliasing an input.  Any n >= 0. */
+int dsu_cfg_model_input(const void* latents, const void* image_latents, int32_t B,
+                        int64_t row_elems, void* out, void* stream);
+int dsu_ddim_cfg_step(const void* noise_pred, const void* latents, const void* variance_noise,
+                      int64_t n, float guidance_scale, float sqrt_a_t, float sqrt_1m_a_t,
+                      float sqrt_a_prev, float std_dev, void* out, void* stream);
+
 /* cv2.inpaint(img, mask, radius, cv2.INPAINT_TELEA) on an 8-bit 3-channel HOST image
  * (1_lama_contour_remover/predict.py:63: the predicted contour pixels and the background are
  * filled from the character's own pixels).  Host code, as in the reference: fast marching is a
