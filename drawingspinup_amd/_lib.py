@@ -174,6 +174,13 @@ _PROTOS = {
     "dsu_mesh_render_ortho_textured": [P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i64, c_i64, C.c_double,
                                        C.c_double, C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P,
                                        P, P, P, P],
+    "dsu_mip_levels": [c_i32],
+    "dsu_mip_pyramid_texels": [c_i32],
+    "dsu_mip_workspace_bytes": [c_i32],
+    "dsu_mip_pyramid_build": [P, P, c_i32, c_i32, P, P, c_i64, P],
+    "dsu_mesh_render_ortho_mip": [P, P, P, P, P, P, c_i32, c_i32, c_i64, c_i64, C.c_double, C.c_double,
+                                  C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
+    "dsu_mip_sample_host": [P, c_i32, P, P, P, c_i64, P],
     "dsu_pos_edge_u8": [P, c_i32, c_i32, c_i32, P, P],
     "dsu_uv_face_labels": [P, P, c_i64, c_i64, P, P, P, P],
     "dsu_uv_components": [P, P, c_i64, P, P, c_i32, c_i32, C.POINTER(c_i32), P],
@@ -306,7 +313,7 @@ _PROTOS = {
 # return types that are neither an error code nor a byte count
 _RESTYPES = {"dsu_nsr_driver_destroy": None, "dsu_nsr_driver_terms": c_vp,
              "dsu_nsr_driver_adam_moments": c_vp,
-             "dsu_conv_x3_packed_elems": C.c_int64}
+             "dsu_conv_x3_packed_elems": C.c_int64, "dsu_mip_pyramid_texels": C.c_int64}
 
 _lib = None
 

@@ -19,7 +19,9 @@ in the snapshot, so it is a parameter.
 
 Textured frames: `read_obj_textured` keeps a textured export's uvs and atlas, and `render_frames` /
 `animate_mesh` with `texture=` and `uvs=` sample the atlas inside the rasteriser's resolve, per
-sub-sample (nearest or bilinear; no mip-mapping, no seam blending), where Blender reads `map_Kd`.
+sub-sample (nearest, bilinear, or trilinear on the atlas's mip pyramid — `texture_filter="trilinear"`,
+isotropic, for an atlas finer than the sample lattice; no anisotropic filtering, no seam blending),
+where Blender reads `map_Kd`.
 Without them the colour frames interpolate the vertex colours, as before.
 
 Rigged animations: `read_bvh` reads a skeleton and a motion clip, `bone_heat_weights` binds the mesh

@@ -222,11 +222,18 @@ def frame_window(frames_xyz):
     return cx, cy, size, span
 
 
-def _texture_args(texture, uvs, texture_filter, n_verts, dev):
+MIP_COVERAGE = ("faces", "all")
+
+
+def _texture_args(texture, uvs, texture_filter, n_verts, dev, faces=None, mip_coverage="faces"):
     """The uv / texture / filter keywords of ops.mesh_render_ortho from a host or device texture
-    (T,T,3|4) uint8 and uvs (V,2), or {} without a texture."""
-    if (texture is None) != (uvs is None):
-        raise ValueError("texture and uvs come together or not at all")
+    (T,T,3|4) uint8 and uvs (V,2), or {} without a texture.  texture_filter "trilinear" adds the
+    texture's mip pyramid, built here once for all frames: mip_coverage "faces" averages only the
+    texels the uv faces (M,3) cover, "all" every texel."""
+    if mip_coverage not in MIP_COVERAGE:
+        raise ValueError(f"mip_coverage must be one of {list(MIP_COVERAGE)}")
+    if (texture is None) != (uvs is None) or (texture is None and texture_filter == ops.MIP_TRILINEAR):
+        raise ValueError("texture and uvs come together or not at all (texture_filter 'trilinear' needs both)")
     if texture is None:
         return {}
     if texture_filter not in ops.TEXTURE_FILTERS:
@@ -235,7 +242,16 @@ def _texture_args(texture, uvs, texture_filter, n_verts, dev):
     uv = to_t(uvs).to(dev, torch.float32).reshape(-1, 2)
     if len(uv) != n_verts:
         raise ValueError("one uv per vertex")
-    return {"uv": uv, "texture": to_t(texture).to(dev), "filter": texture_filter}
+    tex = {"uv": uv, "texture": to_t(texture).to(dev), "filter": texture_filter}
+    if texture_filter == ops.MIP_TRILINEAR:
+        covered = None
+        if mip_coverage == "faces":
+            # the bake's own coverage rule (dsu_uv_bake): counter-clockwise uv faces only
+            idx = to_t(faces).to(dev).reshape(-1, 3)
+            T = tex["texture"].shape[0]
+            covered = ops.uv_bake(uv, idx, torch.zeros(n_verts, 3, device=dev), T)[1] >= 0
+        tex["pyramid"] = ops.mip_pyramid(tex["texture"], covered)
+    return tex
 
 
 def _vertex_colours(colours, n_verts, textured):
@@ -253,13 +269,20 @@ def _vertex_colours(colours, n_verts, textured):
 
 @torch.no_grad()
 def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24, device="cuda",
-                  window=None, want=(), texture=None, uvs=None, texture_filter="bilinear"):
+                  window=None, want=(), texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces"):
     """Render the motion of one mesh.  verts (V,3) in save_mesh's frame (x right, y up, z front; the
     viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
 
     texture (T,T,3|4) uint8 with uvs (V,2) (read_obj_textured's) renders the colour frames from the
-    texture, sampled per sub-sample with texture_filter "bilinear" or "nearest"; colours may then be
-    None.  The position and edge frames do not depend on it.
+    texture, sampled per sub-sample with texture_filter "bilinear", "nearest" or "trilinear"; colours
+    may then be None.  The position and edge frames do not depend on it.  "trilinear" reads the
+    texture's mip pyramid (ops.mip_pyramid, built once per call): where a sub-sample spans more than a
+    texel — ss 1 or 2, a 2048^2 atlas, a character that fills part of the window — the two nearest
+    levels are blended instead of skipping texels.  mip_coverage says which texels the coarser levels
+    average: "faces" (default) those a uv face covers under the bake's rule (ops.uv_bake: counter-
+    clockwise uv faces only), so the background of the atlas does not bleed into the charts; "all"
+    every texel — the choice for a foreign OBJ whose charts are mirrored (clockwise in uv), which
+    "faces" would count as uncovered.
 
     rest_pose keeps the default camera (origin-centred, 512 px across 1.35: the exported character
     fills the frame as in the reference); every other motion goes through frame_window.  `window`
@@ -272,7 +295,7 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    tex = _texture_args(texture, uvs, texture_filter, len(v), dev)
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
     c = _vertex_colours(colours, len(v), bool(tex))
     xyz = motion_frames(v, motion, n_frames)
     if window is not None:

@@ -139,19 +139,19 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 
 @torch.no_grad()
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
-                 texture=None, uvs=None, texture_filter="bilinear"):
+                 texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces"):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
     weights)), linear-blend skinning on the device, then the rasteriser of render_frames.  The
     skinned vertices never leave the device; the window is frame_window's rule on their bounding
-    box over all frames (Blender uses the object's bound_box).  texture, uvs, texture_filter: as in
-    render_frames (colours may be None with a texture).
+    box over all frames (Blender uses the object's bound_box).  texture, uvs, texture_filter,
+    mip_coverage: as in render_frames (colours may be None with a texture).
 
     Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor."""
     dev = torch.device(device)
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    tex = _texture_args(texture, uvs, texture_filter, len(v), dev)
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
     c = _vertex_colours(colours, len(v), bool(tex))
     if weights is None:
         weights = bone_heat_weights(v, f, skeleton, K=K, device=device)

@@ -26,9 +26,15 @@
 // edge functions, then a nearest or bilinear read of the RGBA8 texture under the bake's convention
 // (image row r, column c holds uv T = (c, T - 1 - r)).  The texels are read through L2: neighbouring
 // samples share them.  The position pass is untouched.
+//
+// Mip-mapped frames (dsu_mesh_render_ortho_mip): the atlas is the pyramid of mesh_mip.hip and a sample
+// blends the bilinear reads of two neighbouring levels (mip_sample.h).  The view is orthographic and
+// uv is affine on a face, so the level is constant per (frame, face): it is computed where the
+// face's attributes are loaded.  The two levels of a face lie near each other in the buffer.
 #include "common.h"
 #include "bin_sort.h"
 #include "mesh_geom.h"
+#include "mip_sample.h"
 
 namespace {
 
@@ -127,7 +133,7 @@ struct RenderTexture {
   int32_t T;
 };
 
-constexpr int TEX_NONE = -1, TEX_NEAREST = 0, TEX_BILINEAR = 1;
+constexpr int TEX_NONE = -1, TEX_NEAREST = 0, TEX_BILINEAR = 1, TEX_TRILINEAR = 2;
 
 __device__ __forceinline__ float texel_channel(uint32_t p, int ch) { return (float)((p >> (8 * ch)) & 255u); }
 
@@ -159,7 +165,8 @@ __device__ __forceinline__ void sample_atlas(const RenderTexture& tex, double tx
 }
 
 // One workgroup of four waves per (frame, tile).  TEX: where the colour channels of a sample come
-// from — TEX_NONE the vertex colours, TEX_NEAREST / TEX_BILINEAR the atlas.
+// from — TEX_NONE the vertex colours, TEX_NEAREST / TEX_BILINEAR the atlas, TEX_TRILINEAR its pyramid
+// (tex.texels is then the pyramid buffer, tex.T the side of level 0).
 template <int SS, int TEX>
 __device__ __forceinline__ void raster_resolve_tile(
     unsigned long long* keys, double* xs, double* ys,
@@ -236,6 +243,8 @@ __device__ __forceinline__ void raster_resolve_tile(
 #pragma unroll
   for (int ch = 0; ch < 6; ++ch) a0[ch] = a1[ch] = a2[ch] = 0.0f;
   float ua = 0.0f, va = 0.0f, ub = 0.0f, vb = 0.0f, uc = 0.0f, vc = 0.0f;
+  int lod_k = 0, lod_at = 0;                        // TEX_TRILINEAR: the face's level, its texel offset
+  double lod_t = 0.0;                               // and the weight of level lod_k + 1
   for (int sy = 0; sy < SS; ++sy)
     for (int sx = 0; sx < SS; ++sx) {
       const int lr = py * SS + sy, lc = px * SS + sx;
@@ -262,6 +271,12 @@ __device__ __forceinline__ void raster_resolve_tile(
           ub = tex.uv[(int64_t)ib * 2]; vb = tex.uv[(int64_t)ib * 2 + 1];
           uc = tex.uv[(int64_t)ic * 2]; vc = tex.uv[(int64_t)ic * 2 + 1];
         }
+        if constexpr (TEX == TEX_TRILINEAR) {
+          const double rho = dsu_mip::footprint(t.ax, t.ay, t.bx, t.by, t.cx, t.cy, ua, va, ub, vb, uc, vc,
+                                                tex.T, view.span / (double)view.N);
+          dsu_mip::lod(rho, dsu_mip::levels(tex.T), lod_k, lod_t);
+          lod_at = (int)dsu_mip::level_offset(tex.T, lod_k);
+        }
         last = m;
       }
       double w0, w1, w2;
@@ -271,7 +286,10 @@ __device__ __forceinline__ void raster_resolve_tile(
         const double u = (w0 * (double)ua + w1 * (double)ub + w2 * (double)uc) / area;
         const double v = (w0 * (double)va + w1 * (double)vb + w2 * (double)vc) / area;
         float rgb[3];
-        sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, rgb);
+        if constexpr (TEX == TEX_TRILINEAR)
+          dsu_mip::sample(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, lod_k, lod_t, lod_at, rgb);
+        else
+          sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, rgb);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) acc[ch] += (double)rgb[ch];
       }
@@ -461,6 +479,39 @@ int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, co
     else if (ss == 2) DSU_RASTER(2, TEX_BILINEAR);
     else DSU_RASTER(4, TEX_BILINEAR);
   }
+#undef DSU_RASTER
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_mesh_render_ortho_mip(const float* screen, const int32_t* faces, const float* colour,
+                              const float* pos, const float* uv, const uint8_t* pyramid, int32_t tex_size,
+                              int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
+                              double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
+                              int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
+                              int32_t* face_id, float* depth, float* frames, float* pixels, void* stream) {
+  (void)colour;                                          // the atlas replaces the vertex colours
+  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
+      n_verts > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  if (!uv || !pyramid || tex_size < 1 || tex_size > dsu_mip::MAX_T) return DSU_EINVAL;
+  if ((uintptr_t)pyramid % 4) return DSU_EINVAL;         // a texel is one 32-bit load
+  const int64_t nb = bins_of(n_frames, size);
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
+  if (n_faces && (!screen || !faces || !pos || n_verts == 0)) return DSU_EINVAL;
+  if (n_items && !items) return DSU_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
+  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
+  const RenderTexture tex{uv, reinterpret_cast<const uint32_t*>(pyramid), tex_size};
+  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
+#define DSU_RASTER(SS_)                                                                         \
+  mesh_raster_resolve_textured_kernel<SS_, TEX_TRILINEAR><<<(unsigned)nb, 256, 0, st>>>(         \
+      screen, faces, pos, n_verts, n_faces, view, offsets, items, n_faces ? n_items : 0, tex, out)
+  if (ss == 1) DSU_RASTER(1);
+  else if (ss == 2) DSU_RASTER(2);
+  else DSU_RASTER(4);
 #undef DSU_RASTER
   DSU_CHECK_LAUNCH();
   return DSU_OK;

@@ -13,9 +13,12 @@ on the device.  Names start at 0001.png, as Blender's do and as
 DatasetPatches_M.load_image expects; color and pos are RGBA, edge is 8-bit grey.
 
 `--texture atlas` renders the colour frames of a textured export (save_obj(export_uv=True): OBJ +
-MTL + PNG) from its atlas, sampled per sub-sample in the rasteriser (`--texture_filter bilinear` or
-`nearest`), as the reference's Blender reads `map_Kd`; the default `--texture vertex` renders vertex
-colours (for a textured export: the atlas's nearest texel at each vertex).
+MTL + PNG) from its atlas, sampled per sub-sample in the rasteriser (`--texture_filter bilinear`,
+`nearest` or `trilinear`), as the reference's Blender reads `map_Kd`; the default `--texture vertex`
+renders vertex colours (for a textured export: the atlas's nearest texel at each vertex).
+`--texture_filter trilinear` reads the atlas's mip pyramid, so an atlas finer than the sample lattice
+does not alias; `--mip_coverage faces` (default) builds it from the texels the uv faces cover, `all`
+from every texel (an OBJ from elsewhere with mirrored charts).
 """
 import argparse
 import glob
@@ -75,8 +78,10 @@ def run(argv=None):
     ap.add_argument("--ss", type=int, default=4, choices=[1, 2, 4], help="sub-samples per pixel side")
     ap.add_argument("--texture", default="vertex", choices=["vertex", "atlas"],
                     help="colour source: vertex colours, or the OBJ's map_Kd atlas sampled per sub-sample")
-    ap.add_argument("--texture_filter", default="bilinear", choices=["bilinear", "nearest"],
+    ap.add_argument("--texture_filter", default="bilinear", choices=["bilinear", "nearest", "trilinear"],
                     help="how --texture atlas samples the atlas")
+    ap.add_argument("--mip_coverage", default="faces", choices=["faces", "all"],
+                    help="texels the mip levels of --texture_filter trilinear average: those the uv faces cover, or all")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
@@ -86,6 +91,8 @@ def run(argv=None):
     if args.texture == "atlas":
         verts, faces, uvs, image = animate.read_obj_textured(found[0])     # refuses an untextured OBJ
         colours, tex = None, dict(texture=image, uvs=uvs, texture_filter=args.texture_filter)
+        if args.texture_filter == "trilinear":
+            tex["mip_coverage"] = args.mip_coverage
     else:
         verts, faces, colours = animate.read_obj(found[0])
         if colours is None:

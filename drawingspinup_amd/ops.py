@@ -1441,18 +1441,21 @@ class MeshRenderPlan(_BinnedPlan):
             *self._bin_args(), *[ptr(o) for o in outs], stream()), "dsu_mesh_render_ortho")
 
     def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames"), uv=None, texture=None,
-               filter="bilinear"):
+               filter="bilinear", pyramid=None):
         """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
         (F,S,S,4) uint8, face_id (F,N,N) i32, depth (F,N,N) f32, frames (F,6,S,S) f32, pixels
         (F,S,S,8) f32.
 
         With uv (V,2) f32 and texture (T,T,3) or (T,T,4) uint8 (both or neither) the colour of every
         sample comes from the texture (dsu_mesh_render_ortho_textured; filter "bilinear" or
-        "nearest") and `colour` may be None; without them this is the vertex-colour call."""
+        "nearest") and `colour` may be None; without them this is the vertex-colour call.
+        filter "trilinear" reads the texture's mip pyramid (dsu_mesh_render_ortho_mip): `pyramid`, a
+        MipPyramid of this texture from mip_pyramid(), or None to build it here with every texel
+        covered and the default gutter."""
         if self.items is None:
             raise DsuError("MeshRenderPlan.raster before bin()")
-        if (uv is None) != (texture is None):
-            raise ValueError("uv and texture come together or not at all")
+        if (uv is None) != (texture is None) or (texture is None and (filter == MIP_TRILINEAR or pyramid is not None)):
+            raise ValueError("uv and texture come together or not at all (and a trilinear read needs both)")
         F, S, N, dev = self.F, self.size, self.size * self.ss, self.screen.device
         shapes = {"color_u8": ((F, S, S, 4), torch.uint8), "pos_u8": ((F, S, S, 4), torch.uint8),
                   "face_id": ((F, N, N), torch.int32), "depth": ((F, N, N), torch.float32),
@@ -1476,6 +1479,19 @@ class MeshRenderPlan(_BinnedPlan):
         if uv.shape != (self.V, 2):
             raise ValueError("uv must be (V,2)")
         out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
+        if filter == MIP_TRILINEAR:
+            if pyramid is None:
+                pyramid = mip_pyramid(rgba)
+            if not isinstance(pyramid, MipPyramid) or pyramid.T != rgba.shape[0] or pyramid.buffer.device != dev:
+                raise ValueError("pyramid must be the MipPyramid of this texture, on the mesh's device")
+            check(lib().dsu_mesh_render_ortho_mip(
+                ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), None, ptr(pos), ptr(uv),
+                ptr(pyramid.buffer, torch.uint8), pyramid.T, self.F, self.V, self.M,
+                self.cx, self.cy, self.span, self.size, self.ss, *self._bin_args(),
+                *[ptr(out.get(k)) for k in shapes], stream()), "dsu_mesh_render_ortho_mip")
+            return out
+        if pyramid is not None:
+            raise ValueError("a pyramid goes with filter 'trilinear'")
         check(lib().dsu_mesh_render_ortho_textured(
             ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), None, ptr(pos), ptr(uv),
             ptr(rgba, torch.uint8), rgba.shape[0], TEXTURE_FILTERS[filter], self.F, self.V, self.M,
@@ -1484,7 +1500,8 @@ class MeshRenderPlan(_BinnedPlan):
         return out
 
 
-TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}
+MIP_TRILINEAR = "trilinear"
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1, MIP_TRILINEAR: 2}
 
 
 def texture_rgba(texture):
@@ -1500,13 +1517,55 @@ def texture_rgba(texture):
     return rgba
 
 
+class MipPyramid:
+    """The mip pyramid of one atlas (dsu_mip_pyramid_build): buffer (dsu_mip_pyramid_texels(T), 4) uint8 on
+    the device, T the side of level 0, L the number of levels."""
+
+    def __init__(self, buffer, T, L):
+        self.buffer, self.T, self.L = buffer, int(T), int(L)
+
+    def size(self, k):
+        """T_k = ceil(T / 2^k)."""
+        if not 0 <= k < self.L:
+            raise IndexError(f"level {k} of {self.L}")
+        return (self.T + (1 << k) - 1) >> k
+
+    def level(self, k):
+        """(T_k, T_k, 4) uint8 view of level k."""
+        at = sum(self.size(j) ** 2 for j in range(k))
+        return self.buffer[at:at + self.size(k) ** 2].view(self.size(k), self.size(k), 4)
+
+
+def mip_pyramid(texture, covered=None, gutter=2):
+    """dsu_mip_pyramid_build (include/dsu_hip.h, "Mip-mapped frames"): texture (T,T,3|4) uint8 on the
+    device; covered (T,T) bool / uint8 or None = every texel covered; `gutter` dilation rounds per level
+    above 0 -> MipPyramid.  Level 0 is the texture (with an opaque alpha where it had three channels)."""
+    rgba = texture_rgba(texture)
+    T, dev = rgba.shape[0], rgba.device
+    if covered is not None:
+        if not torch.is_tensor(covered) or covered.shape != (T, T) or covered.device != dev:
+            raise ValueError("covered (T,T) on the texture's device expected")
+        covered = covered.to(torch.uint8).contiguous()
+    texels = int(lib().dsu_mip_pyramid_texels(T))
+    wbytes = int(lib().dsu_mip_workspace_bytes(T))
+    if texels < 0 or wbytes < 0:
+        check(min(texels, wbytes), "dsu_mip_pyramid_texels")
+    buffer = torch.empty((texels, 4), dtype=torch.uint8, device=dev)
+    work = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib().dsu_mip_pyramid_build(ptr(rgba, torch.uint8), ptr(covered), T, int(gutter), ptr(buffer), ptr(work),
+                                      work.numel(), stream()), "dsu_mip_pyramid_build")
+    return MipPyramid(buffer, T, int(lib().dsu_mip_levels(T)))
+
+
 def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
-                      want=("color_u8", "pos_u8", "frames"), uv=None, texture=None, filter="bilinear"):
+                      want=("color_u8", "pos_u8", "frames"), uv=None, texture=None, filter="bilinear",
+                      pyramid=None):
     """Orthographic render of F frames of one mesh with two attribute sets (include/dsu_hip.h,
     dsu_mesh_render_ortho): bin, then rasterise and resolve.  The colours are the vertex colours,
-    or with uv and texture the texture's (dsu_mesh_render_ortho_textured)."""
+    or with uv and texture the texture's (dsu_mesh_render_ortho_textured; filter "trilinear":
+    dsu_mesh_render_ortho_mip on `pyramid`, built from the texture when None)."""
     return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want, uv, texture,
-                                                                              filter)
+                                                                              filter, pyramid)
 
 
 def pos_edge_u8(pos_rgba):

@@ -1126,7 +1126,9 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
  *              rounded to f32.  T = 1 is legal.
  * The per-sample value goes where the interpolated vertex colour goes: accumulated in float64 over
  * the pixel's covered samples in row-major order, divided by their count, uint8 = floor(v 255 + 0.5).
- * No mip-mapping or area sampling: a texture much finer than the sample lattice aliases. */
+ * These two filters read level 0 only: a texture much finer than the sample lattice aliases under
+ * them.  dsu_mesh_render_ortho_mip below is the filtered read; there is no area or anisotropic
+ * sampling. */
 int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, const float* colour,
                                    const float* pos, const float* uv, const uint8_t* texture,
                                    int32_t tex_size, int32_t filter, int32_t n_frames, int64_t n_verts,
@@ -1134,6 +1136,73 @@ int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, co
                                    int32_t ss, void* workspace, int64_t workspace_bytes, int32_t* items,
                                    int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id,
                                    float* depth, float* frames, float* pixels, void* stream);
+/* Mip-mapped frames: the pyramid of the atlas (csrc/mesh_mip.hip) and the trilinear read of it in
+ * the resolve (csrc/mesh_render.hip; the arithmetic of both sides is csrc/mip_sample.h).
+ *
+ * a. The pyramid.  texture (T, T, 4) RGBA8 as above, 1 <= T <= 8192, any T; covered (T, T) u8 or
+ * NULL = every texel is covered.  Levels: T_0 = T, T_k = ceil(T_{k-1} / 2), L = the number of levels
+ * down to and including size 1 (dsu_mip_levels).  Storage: one RGBA8 buffer, level k at texel offset
+ * sum_{j<k} T_j^2; dsu_mip_pyramid_texels(T) texels in all.
+ *   Level 0 is the input byte for byte (its alpha is not rewritten; pyramid == texture skips the copy).
+ *   Level k >= 1, reduction: texel (r, c) owns the level-0 rows [2^k r, 2^k (r + 1)) clipped to
+ *   [0, T) and the columns likewise.  n = the covered level-0 texels of the block, sum_ch their
+ *   channel sum.  n > 0: the texel is covered and channel = (2 sum_ch + n) / (2 n) in integer
+ *   arithmetic (round half up, the form of dsu_uv_dilate's mean).  The means come from the exact sums,
+ *   not from rounded children: every level hands (sum_r, sum_g, sum_b, n), 64 bits each (255 4^13
+ *   does not fit 32), to the next; one thread per output texel adds its 2 x 2 children, and the
+ *   clipped edge of an odd level is absent children, not zeros.
+ *   Level k >= 1, gutter: `gutter` rounds (0..64; the export's 2) of exactly dsu_uv_dilate's rule on
+ *   the covered / uncovered texels of that level.  A texel still uncovered is 0.  The alpha byte is
+ *   255 where the texel is covered after the rounds and 0 otherwise; sampling never reads alpha.
+ * No atomics: two builds give the same bytes.  workspace (16-byte aligned):
+ * dsu_mip_workspace_bytes(T) = 32 (T_1^2 + T_2^2) + 4 T_1^2 for T > 1 — the sums of two consecutive
+ * levels and one spare level image for the gutter rounds (T = 8192: 704 MB; T = 1024: 11 MB) —, 0
+ * (workspace may be NULL) for T = 1.  DSU_EINVAL before any launch: T or gutter out of range,
+ * texture or pyramid NULL or not 4-byte aligned, workspace NULL, short or misaligned.
+ *
+ * b. dsu_mesh_render_ortho_mip: dsu_mesh_render_ortho_textured with the pyramid buffer in place of
+ * `texture` and no `filter`.  Visibility, depth, alpha, the position pass, frames and pixels are
+ * untouched; tx, ty of a sample are formed as there.
+ *   Level of detail.  The view is orthographic and uv is affine on a face, so the texel footprint
+ *   of one sub-sample is constant per (frame, face).  Float64 from the f32 screen vertices a, b, c
+ *   and the f32 uvs, in this operand order, no products fused:
+ *       e1 = b - a,  e2 = c - a (screen x, y);
+ *       p1 = (ub - ua) T,  q1 = (vb - va) T;  p2, q2 likewise from c;
+ *       det = e1x e2y - e1y e2x;   h = span / N, the sample spacing;
+ *       dpx = (p1 e2y - p2 e1y) / det,  dpy = (p2 e1x - p1 e2x) / det;  dqx, dqy likewise from q;
+ *       gx = dpx dpx + dqx dqx,  gy = dpy dpy + dqy dqy;
+ *       rho = sqrt((h h) (gx > gy ? gx : gy))       (IEEE sqrt; det == 0: rho = 0).
+ *   rho not finite or !(rho > 1): k = 0, t = 0.  Otherwise k = floor(log2 rho), read from the
+ *   exponent (ilogb; no transcendental call); k >= L - 1: k = L - 1, t = 0; otherwise
+ *   t = rho 2^-k - 1 (ldexp, exact), t in [0, 1).
+ *   Sample.  x_0 = tx, y_0 = (T - 1) - ty (non-finite tx, ty -> 0 first).  At level j:
+ *   x_j = (x_0 - (2^j - 1) / 2) / 2^j, y_j likewise — a level-j texel sits at the centre of its block
+ *   of level-0 sample points under the bake's point convention —, clamped to [0, T_j - 1].  B_j is
+ *   the bilinear filter's four-term expression at level j, same operand order, float64, not divided
+ *   and not rounded.  channel = (float)(((1 - t) B_k + t B_{k+1}) / 255), one rounding to f32; with
+ *   t = 0 level k + 1 is not read and channel = (float)(B_k / 255): at k = 0, t = 0 this is the
+ *   bilinear rule bit for bit.
+ * Deviations from the textbook filter.  The blend weight is linear in rho inside an octave where
+ * log2 rho would be the usual choice (they differ by at most 0.086 of a level); in exchange the rule
+ * is reproducible bit for bit on the host.  rho is the isotropic (max) rule: a face seen edge-on is
+ * blurred along both axes.  No anisotropic filtering.
+ *
+ * c. dsu_mip_sample_host: HOST function on HOST arrays — the sampling above (level and weight from
+ * rho[i], then the sample at tx[i], ty[i]) evaluated on the CPU by the text the kernel compiles:
+ * rgb_out (n, 3) f32. */
+int32_t dsu_mip_levels(int32_t tex_size);
+int64_t dsu_mip_pyramid_texels(int32_t tex_size);
+int64_t dsu_mip_workspace_bytes(int32_t tex_size);
+int dsu_mip_pyramid_build(const uint8_t* texture, const uint8_t* covered, int32_t tex_size, int32_t gutter,
+                          uint8_t* pyramid, void* workspace, int64_t workspace_bytes, void* stream);
+int dsu_mesh_render_ortho_mip(const float* screen, const int32_t* faces, const float* colour,
+                              const float* pos, const float* uv, const uint8_t* pyramid, int32_t tex_size,
+                              int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
+                              double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
+                              int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
+                              int32_t* face_id, float* depth, float* frames, float* pixels, void* stream);
+int dsu_mip_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tx, const double* ty,
+                        const double* rho, int64_t n, float* rgb_out);
 /* pos2edge (run_render.py:31-57) and the inversion of run_render.py:120 on RGBA8 position images
  * (n_frames, H, W, 4): channels u8 -> f32 / 255, every channel 2 where alpha8 < 255, per-channel 3x3
  * Sobel in float64 with reflect-101 borders, magnitude, maximum over the three colour channels,
