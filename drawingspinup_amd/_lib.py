@@ -196,6 +196,8 @@ _PROTOS = {
     "dsu_spd_cg_block": [P, P, P, c_i64, c_i64, c_i32, P, P, C.c_double, c_i32, P, c_i64,
                          C.POINTER(c_i32), C.POINTER(C.c_double), P],
     "dsu_skin_lbs": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P, P],
+    "dsu_skin_dqs": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P, P],
+    "dsu_skin_dqs_host": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P],
     "dsu_point_bin_count": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P],
     "dsu_point_bin_fill": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
     "dsu_knn8_blend": [P, c_i64, P, P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],

@@ -31,12 +31,16 @@ weighting follows the published bone-heat form, not Blender's source; the view b
 the deformed vertices where Blender uses the object's bound_box; there is no retargeting and no
 automatic joint placement (`fit_to_mesh` only scales and centres a skeleton); the 30 degree turn
 that blender_animation.py:17-18 applies to two named clips is not restated.  FBX is not read.
+`animate_mesh(skinning="dual_quaternion")` blends unit dual quaternions instead of matrices (Blender's
+"Preserve Volume"; `dual_quaternions` makes the table), and `resample_clip` brings a clip to another
+frame rate (slerp of the local rotations).
 """
 from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
                      read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
-from .skeleton import Clip, Skeleton, fit_to_mesh, read_bvh, rest_clip, skinning_matrices
+from .skeleton import (Clip, Skeleton, dual_quaternions, fit_to_mesh, quaternion_rotations, read_bvh, resample_clip,
+                       rest_clip, rotation_quaternions, skinning_matrices)
 from .skin import animate_mesh, bone_heat_weights
 
-__all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "fit_to_mesh", "read_bvh", "rest_clip",
-           "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
+__all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "dual_quaternions", "fit_to_mesh",
+           "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
            "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate"]

@@ -79,6 +79,10 @@ class Clip:
     def n_frames(self):
         return len(self.translations)
 
+    def resample(self, frame_time):
+        """This clip at another frame time (resample_clip)."""
+        return resample_clip(self, frame_time)
+
 
 def rest_clip(skeleton, n_frames=1):
     """The clip that leaves the skeleton in its rest pose."""
@@ -226,6 +230,130 @@ def skinning_matrices(skeleton, clip):
     out[..., :3] = Rw
     out[..., 3] = tw - np.einsum("fjab,jb->fja", Rw, rest)
     return out
+
+
+def rotation_quaternions(R):
+    """(...,3,3) rotations -> (...,4) unit quaternions (w, x, y, z) with w >= 0 (w = 0: the first
+    non-zero component positive).  The branch is chosen by the largest of the trace and the diagonal
+    entries (Shepperd), so that a rotation near 180 degrees keeps its digits."""
+    R = np.asarray(R, np.float64)
+    if R.shape[-2:] != (3, 3):
+        raise ValueError("rotations (...,3,3) expected")
+    m = R.reshape(-1, 3, 3)
+    d0, d1, d2 = m[:, 0, 0], m[:, 1, 1], m[:, 2, 2]
+    branch = np.stack([d0 + d1 + d2, d0, d1, d2], 1).argmax(1)
+    q = np.empty((len(m), 4))
+    for b in range(4):
+        i = np.flatnonzero(branch == b)
+        if not len(i):
+            continue
+        a = m[i]
+        if b == 0:
+            s = 2.0 * np.sqrt(np.maximum(1.0 + a[:, 0, 0] + a[:, 1, 1] + a[:, 2, 2], 0.0))          # 4 w
+            q[i] = np.stack([s / 4.0, (a[:, 2, 1] - a[:, 1, 2]) / s, (a[:, 0, 2] - a[:, 2, 0]) / s,
+                             (a[:, 1, 0] - a[:, 0, 1]) / s], 1)
+        elif b == 1:
+            s = 2.0 * np.sqrt(np.maximum(1.0 + a[:, 0, 0] - a[:, 1, 1] - a[:, 2, 2], 0.0))          # 4 x
+            q[i] = np.stack([(a[:, 2, 1] - a[:, 1, 2]) / s, s / 4.0, (a[:, 0, 1] + a[:, 1, 0]) / s,
+                             (a[:, 0, 2] + a[:, 2, 0]) / s], 1)
+        elif b == 2:
+            s = 2.0 * np.sqrt(np.maximum(1.0 + a[:, 1, 1] - a[:, 0, 0] - a[:, 2, 2], 0.0))          # 4 y
+            q[i] = np.stack([(a[:, 0, 2] - a[:, 2, 0]) / s, (a[:, 0, 1] + a[:, 1, 0]) / s, s / 4.0,
+                             (a[:, 1, 2] + a[:, 2, 1]) / s], 1)
+        else:
+            s = 2.0 * np.sqrt(np.maximum(1.0 + a[:, 2, 2] - a[:, 0, 0] - a[:, 1, 1], 0.0))          # 4 z
+            q[i] = np.stack([(a[:, 1, 0] - a[:, 0, 1]) / s, (a[:, 0, 2] + a[:, 2, 0]) / s,
+                             (a[:, 1, 2] + a[:, 2, 1]) / s, s / 4.0], 1)
+    q = q / np.sqrt((q * q).sum(1, keepdims=True))
+    q = q + 0.0                                                      # -0 -> +0
+    lead = np.take_along_axis(q, (q != 0.0).argmax(1)[:, None], 1)   # the first non-zero component
+    return np.where(lead < 0.0, -q, q).reshape(R.shape[:-2] + (4,)) + 0.0
+
+
+def quaternion_rotations(q):
+    """(...,4) unit quaternions (w, x, y, z) -> (...,3,3) rotations; the inverse of
+    rotation_quaternions."""
+    q = np.asarray(q, np.float64)
+    if q.shape[-1] != 4:
+        raise ValueError("quaternions (...,4) expected")
+    w, x, y, z = (q[..., c] for c in range(4))
+    R = np.empty(q.shape[:-1] + (3, 3))
+    R[..., 0, 0] = 1.0 - 2.0 * (y * y + z * z)
+    R[..., 0, 1] = 2.0 * (x * y - w * z)
+    R[..., 0, 2] = 2.0 * (x * z + w * y)
+    R[..., 1, 0] = 2.0 * (x * y + w * z)
+    R[..., 1, 1] = 1.0 - 2.0 * (x * x + z * z)
+    R[..., 1, 2] = 2.0 * (y * z - w * x)
+    R[..., 2, 0] = 2.0 * (x * z - w * y)
+    R[..., 2, 1] = 2.0 * (y * z + w * x)
+    R[..., 2, 2] = 1.0 - 2.0 * (x * x + y * y)
+    return R
+
+
+def dual_quaternions(matrices):
+    """(F,J,3,4) rigid transforms [R | t] -> (F,J,8) float64 [r_w r_x r_y r_z | d_w d_x d_y d_z]: the
+    unit rotation quaternion r of R and the dual part d = 1/2 (0, t) (x) r — the table of
+    ops.skin_dqs.  ValueError when a matrix is not rigid (|R^T R - I| above 1e-9, or det < 0):
+    skinning_matrices is rigid by construction, so this guards matrices made elsewhere."""
+    m = np.asarray(matrices, np.float64)
+    if m.ndim != 4 or m.shape[2:] != (3, 4):
+        raise ValueError("matrices (F,J,3,4) expected")
+    R, t = m[..., :3], m[..., 3]
+    if m.size:
+        err = np.abs(np.swapaxes(R, -1, -2) @ R - np.eye(3)).max()
+        if not err <= 1e-9 or not (np.linalg.det(R) > 0.0).all():
+            raise ValueError(f"dual quaternions need rigid transforms (|R^T R - I| = {err:.3e}, "
+                             f"smallest determinant {np.linalg.det(R).min():.3f})")
+    r = rotation_quaternions(R)
+    w, v = r[..., :1], r[..., 1:]
+    out = np.empty(m.shape[:2] + (8,))
+    out[..., :4] = r
+    out[..., 4] = -0.5 * (t * v).sum(-1)
+    out[..., 5:] = 0.5 * (w * t + np.cross(t, v))
+    return out + 0.0                                                 # -0 -> +0
+
+
+SLERP_LINEAR_BELOW = 1e-8       # radians: below this angle two quaternions are lerped and normalised
+
+
+def resample_clip(clip, frame_time):
+    """The clip at the times k frame_time, k = 0 .. floor(T / frame_time), T = (F - 1)
+    clip.frame_time.  The root translations are interpolated linearly; every joint's local rotation
+    by slerp between the two neighbouring frames, along the shorter arc (the quaternions' signs are
+    aligned first; below an angle of 1e-8 they are lerped and normalised).  A time that coincides
+    with a source frame (its quotient by clip.frame_time is an integer in float64) copies that
+    frame unchanged, so the clip's own frame_time returns equal arrays.  A one-frame clip is
+    returned as it is."""
+    ft = float(frame_time)
+    if not (ft > 0.0 and math.isfinite(ft)):
+        raise ValueError("frame_time must be positive")
+    F = clip.n_frames
+    if F <= 1:
+        return clip
+    # in units of the clip's frames: time k ft is frame k ratio, and T / ft = (F - 1) / ratio.  The own
+    # rate (ratio 1) and whole multiples of it give whole frames exactly
+    ratio = ft / clip.frame_time
+    n = int(math.floor((F - 1) / ratio)) + 1
+    u = np.arange(n) * ratio
+    i0 = np.minimum(np.floor(u).astype(np.int64), F - 1)
+    i1 = np.minimum(i0 + 1, F - 1)
+    a = u - i0
+    exact = a == 0.0
+    tr = (1.0 - a)[:, None] * clip.translations[i0] + a[:, None] * clip.translations[i1]
+    q0, q1 = rotation_quaternions(clip.rotations[i0]), rotation_quaternions(clip.rotations[i1])
+    dot = (q0 * q1).sum(-1, keepdims=True)
+    q1 = np.where(dot < 0.0, -q1, q1)
+    theta = np.arccos(np.clip(np.abs(dot), 0.0, 1.0))
+    al = a[:, None, None]
+    small = theta < SLERP_LINEAR_BELOW
+    st = np.where(small, 1.0, np.sin(theta))
+    k0 = np.where(small, 1.0 - al, np.sin((1.0 - al) * theta) / st)
+    k1 = np.where(small, al, np.sin(al * theta) / st)
+    q = k0 * q0 + k1 * q1
+    rot = quaternion_rotations(q / np.sqrt((q * q).sum(-1, keepdims=True)))
+    tr[exact] = clip.translations[i0[exact]]
+    rot[exact] = clip.rotations[i0[exact]]
+    return Clip(tr, rot, ft)
 
 
 def bvh_files(folder):

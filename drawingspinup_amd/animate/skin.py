@@ -14,8 +14,9 @@ import torch
 from .. import ops
 from ..nsr.thinning import _weld, cotmatrix
 from .render import _texture_args, _vertex_colours, frame_window, position_colours
-from .skeleton import skinning_matrices
+from .skeleton import dual_quaternions, skinning_matrices
 
+SKINNING = ("linear", "dual_quaternion")
 NEAR = 1e-4          # bones within (1 + NEAR) of the nearest visible one share a vertex's heat
 D_FLOOR = 1e-6       # d_i is taken no smaller than this fraction of the bounding-box diagonal
 
@@ -139,14 +140,19 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 
 @torch.no_grad()
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
-                 texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces"):
+                 texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear"):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
-    weights)), linear-blend skinning on the device, then the rasteriser of render_frames.  The
-    skinned vertices never leave the device; the window is frame_window's rule on their bounding
-    box over all frames (Blender uses the object's bound_box).  texture, uvs, texture_filter,
-    mip_coverage: as in render_frames (colours may be None with a texture).
+    weights)), skinning on the device, then the rasteriser of render_frames.  skinning: "linear"
+    blends the joints' matrices (ops.skin_lbs, Blender's default), "dual_quaternion" their unit dual
+    quaternions (ops.skin_dqs, Blender's "Preserve Volume": a twisted or bent limb keeps its
+    radius); the weights are the same for both.  The skinned vertices never leave the device; the
+    window is frame_window's rule on their bounding box over all frames (Blender uses the object's
+    bound_box).  texture, uvs, texture_filter, mip_coverage: as in render_frames (colours may be None
+    with a texture).
 
     Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor."""
+    if skinning not in SKINNING:
+        raise ValueError(f"skinning {skinning!r}: one of {SKINNING}")
     dev = torch.device(device)
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
@@ -156,10 +162,13 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     if weights is None:
         weights = bone_heat_weights(v, f, skeleton, K=K, device=device)
     infl, w = (to_np(a) for a in weights)
-    mats = skinning_matrices(skeleton, clip).astype(np.float32)
-    screen = ops.skin_lbs(torch.from_numpy(v.astype(np.float32)).to(dev),
-                          torch.from_numpy(infl.astype(np.int32)).to(dev),
-                          torch.from_numpy(w.astype(np.float32)).to(dev), torch.from_numpy(mats).to(dev))
+    rest, ti, tw = (torch.from_numpy(a).to(dev) for a in (v.astype(np.float32), infl.astype(np.int32),
+                                                          w.astype(np.float32)))
+    if skinning == "linear":
+        mats = skinning_matrices(skeleton, clip).astype(np.float32)
+        screen = ops.skin_lbs(rest, ti, tw, torch.from_numpy(mats).to(dev))
+    else:
+        screen = ops.skin_dqs(rest, ti, tw, torch.from_numpy(dual_quaternions(skinning_matrices(skeleton, clip))).to(dev))
     box = torch.stack([screen.amin((0, 1)), screen.amax((0, 1))]).cpu().numpy()
     cx, cy, size, span = frame_window(box)
     pos = torch.from_numpy(position_colours(v).astype(np.float32)).to(dev)

@@ -6,6 +6,8 @@
 //                         open segment vertex -> closest point is crossed by a triangle
 //   dsu_spd_cg_block      (L + M H) W = M H P, all bones at once: Jacobi-preconditioned CG, float64
 //   dsu_skin_lbs          out[f, v] = sum_k w_k (R_k x + t_k)
+//   dsu_skin_dqs          out[f, v] = the rigid transform of the blended unit dual quaternion
+//                         (dqs_blend.h; dsu_skin_dqs_host runs the same text on host arrays)
 //
 // The rules (include/dsu_hip.h states them in full; tests/skin_ref.py restates them in float64).
 //
@@ -24,6 +26,7 @@
 #include "bin_sort.h"
 #include "mesh_geom.h"
 #include "partial_reduce.h"
+#include "dqs_blend.h"
 
 namespace {
 
@@ -385,6 +388,30 @@ __global__ __launch_bounds__(256) void skin_lbs_kernel(const float* __restrict__
   out[i * 3 + 2] = oz;
 }
 
+// ------------------------------------------------------------------ dual-quaternion skinning
+// One thread per (frame, vertex), vertex fastest: the 12 B stores of a wave are contiguous, a wave's
+// influences and weights are contiguous rows, and the frame's table (J * 64 B) is shared by every
+// thread of the frame and stays in L2.
+__global__ __launch_bounds__(256) void skin_dqs_kernel(const float* __restrict__ rest,
+                                                       const int32_t* __restrict__ infl,
+                                                       const float* __restrict__ wts,
+                                                       const double* __restrict__ dq, int64_t V, int32_t K,
+                                                       int32_t F, int32_t J, float* __restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)F * V) return;
+  const int64_t f = i / V, v = i - f * V;
+  float o[3];
+  dsu_dqs::blend(infl + v * K, wts + v * K, K, dq + f * J * 8, J, rest[v * 3], rest[v * 3 + 1], rest[v * 3 + 2], o);
+  out[i * 3] = o[0];
+  out[i * 3 + 1] = o[1];
+  out[i * 3 + 2] = o[2];
+}
+
+bool skin_shape_ok(int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints) {
+  return !(n_verts < 0 || K < 1 || K > 4096 || n_frames < 1 || n_frames > 65535 || n_joints < 1 ||
+           (int64_t)n_frames * n_verts > (int64_t)1 << 31 || n_verts * K > (int64_t)1 << 31);
+}
+
 bool grid_ok(int32_t gx, int32_t gy, int32_t gz) {
   return gx >= 1 && gy >= 1 && gz >= 1 && gx <= 256 && gy <= 256 && gz <= 256 &&
          (int64_t)gx * gy * gz <= (int64_t)1 << 22;
@@ -489,6 +516,32 @@ int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weig
   skin_lbs_kernel<<<dsu_blocks_for(total, 256), 256, 0, (hipStream_t)stream>>>(
       rest, influences, weights, matrices, n_verts, K, n_frames, n_joints, out);
   DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_skin_dqs(const float* rest, const int32_t* influences, const float* weights, const double* dualquats,
+                 int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints, float* out, void* stream) {
+  if (!skin_shape_ok(n_verts, K, n_frames, n_joints)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  if (!rest || !influences || !weights || !dualquats || !out) return DSU_EINVAL;
+  const int64_t total = (int64_t)n_frames * n_verts;
+  skin_dqs_kernel<<<dsu_blocks_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+      rest, influences, weights, dualquats, n_verts, K, n_frames, n_joints, out);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+// HOST: the same blend (dqs_blend.h) on host arrays.
+int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float* weights,
+                      const double* dualquats, int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints,
+                      float* out) {
+  if (!skin_shape_ok(n_verts, K, n_frames, n_joints)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  if (!rest || !influences || !weights || !dualquats || !out) return DSU_EINVAL;
+  for (int64_t f = 0; f < n_frames; ++f)
+    for (int64_t v = 0; v < n_verts; ++v)
+      dsu_dqs::blend(influences + v * K, weights + v * K, K, dualquats + f * n_joints * 8, n_joints, rest[v * 3],
+                     rest[v * 3 + 1], rest[v * 3 + 2], out + (f * n_verts + v) * 3);
   return DSU_OK;
 }
 

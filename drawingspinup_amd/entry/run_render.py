@@ -19,6 +19,12 @@ renders vertex colours (for a textured export: the atlas's nearest texel at each
 `--texture_filter trilinear` reads the atlas's mip pyramid, so an atlas finer than the sample lattice
 does not alias; `--mip_coverage faces` (default) builds it from the texels the uv faces cover, `all`
 from every texel (an OBJ from elsewhere with mirrored charts).
+
+For the BVH actions, `--skinning dual_quaternion` blends the joints' unit dual quaternions instead of
+their matrices (Blender's "Preserve Volume"; the default `linear` is Blender's default and the
+reference's), and `--fps N` resamples each clip to 1 / N s per frame after it is fitted to the mesh
+(default: the clip's own rate).  The cached weights serve both blends.  rest_pose and rest_rotate
+have no skeleton and ignore both.
 """
 import argparse
 import glob
@@ -82,8 +88,14 @@ def run(argv=None):
                     help="how --texture atlas samples the atlas")
     ap.add_argument("--mip_coverage", default="faces", choices=["faces", "all"],
                     help="texels the mip levels of --texture_filter trilinear average: those the uv faces cover, or all")
+    ap.add_argument("--skinning", default="linear", choices=list(animate.skin.SKINNING),
+                    help="blend of the BVH actions: the joints' matrices, or their dual quaternions (preserve volume)")
+    ap.add_argument("--fps", type=float, default=None,
+                    help="resample each BVH clip to this many frames per second (default: the clip's own rate)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    if args.fps is not None and not args.fps > 0:
+        ap.error("--fps must be positive")
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
     if not found:
         raise FileNotFoundError(f"no OBJ under {os.path.join(args.data_dir, args.uid, 'mesh')}")
@@ -107,8 +119,10 @@ def run(argv=None):
         else:
             skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
             weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
+            if args.fps is not None:
+                clip = animate.resample_clip(clip, 1.0 / args.fps)
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
-                                            ss=args.ss, device=args.device, **tex)
+                                            ss=args.ss, device=args.device, skinning=args.skinning, **tex)
         n = write_frames(out_dir, rendered)
         print((time.time() - start) / n, n)
     return out_dir, rendered

@@ -1828,3 +1828,20 @@ def skin_lbs(rest, influences, weights, matrices):
     check(lib().dsu_skin_lbs(ptr(rest, torch.float32), ptr(influences, torch.int32), ptr(weights, torch.float32),
                              ptr(matrices, torch.float32), V, K, F, J, ptr(out), stream()), "dsu_skin_lbs")
     return out
+
+
+def skin_dqs(rest, influences, weights, dualquats):
+    """Dual-quaternion skinning (dsu_skin_dqs): rest (V,3), influences (V,K) joint indices, weights
+    (V,K), dualquats (F,J,8) float64 (animate.dual_quaternions) -> (F,V,3) f32 on the device."""
+    rest, weights = _f32c(rest), _f32c(weights)
+    influences = influences.to(torch.int32).contiguous()
+    dualquats = dualquats.to(torch.float64).contiguous()
+    if rest.dim() != 2 or rest.shape[1] != 3 or influences.dim() != 2 or weights.shape != influences.shape \
+            or influences.shape[0] != rest.shape[0] or dualquats.dim() != 3 or dualquats.shape[2] != 8:
+        raise ValueError("rest (V,3), influences / weights (V,K) and dualquats (F,J,8) expected")
+    V, K = influences.shape
+    F, J = dualquats.shape[:2]
+    out = torch.empty((F, V, 3), dtype=torch.float32, device=rest.device)
+    check(lib().dsu_skin_dqs(ptr(rest, torch.float32), ptr(influences, torch.int32), ptr(weights, torch.float32),
+                             ptr(dualquats, torch.float64), V, K, F, J, ptr(out), stream()), "dsu_skin_dqs")
+    return out

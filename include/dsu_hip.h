@@ -1286,6 +1286,49 @@ int dsu_spd_cg_block(const int32_t* rowptr, const int32_t* cols, const double* v
  * outside [0, n_joints) contributes nothing. */
 int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weights, const float* matrices,
                  int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints, float* out, void* stream);
+/* Dual-quaternion skinning ("Preserve Volume" of Blender's armature modifier; Kavan et al.,
+ * "Geometric skinning with approximate dual quaternion blending", 2008): where linear blending
+ * averages matrices — a vertex shared half and half by two joints that differ by a turn of theta
+ * lands at cos(theta / 2) of its distance from the axis —, this blends unit dual quaternions and
+ * applies the rigid transform of the normalised blend, so the distance is kept.  An extension of
+ * the reference (blender_animation.py leaves Blender's linear default on); csrc/dqs_blend.h holds
+ * the text, compiled for the kernel and for the host entry.
+ *
+ * rest, influences, weights, out: as dsu_skin_lbs.  dualquats (n_frames, n_joints, 8) FLOAT64 =
+ * [r_w r_x r_y r_z | d_w d_x d_y d_z] per frame and joint: a unit rotation quaternion r and the dual
+ * part d = 1/2 (0, t) (x) r of the joint's rigid skinning transform [R | t] (float64: the table is
+ * n_frames n_joints 64 B, the arithmetic is float64 anyway, and an f32 table alone would cost about
+ * 13 f32 ulps against the rigid transform).
+ *
+ * Rule per (frame, vertex), everything in float64 from the f32 / f64 inputs, sums of four terms
+ * taken as ((a + b) + c) + d, no products are fused:
+ *   1. k = 0 .. K-1 in order; an influence outside [0, n_joints) or with a weight that is not > 0
+ *      contributes nothing.  The first contributing influence is the pivot, r_p its rotation.
+ *   2. dot_k = ((r_k.w r_p.w + r_k.x r_p.x) + r_k.y r_p.y) + r_k.z r_p.z;  s_k = -1 if dot_k < 0,
+ *      else +1 (q and -q are the same transform; the pivot itself gets +1).
+ *   3. b_c = b_c + (s_k w_k) q_k,c for the 8 components c, accumulated from 0.
+ *   4. n2 = ((b_0 b_0 + b_1 b_1) + b_2 b_2) + b_3 b_3.  Unless n2 > 0 and finite, out = rest (no
+ *      contributing influence, rotations that cancel, NaN in a rotation part).
+ *   5. n = sqrt(n2);  r = b_0..3 / n,  d = b_4..7 / n  (component by component).
+ *   6. t = 2 ((r_w d_v - d_w r_v) + r_v x d_v)  with  (u x v)_x = u_y v_z - u_z v_y  (cyclic); the d_w
+ *      term removes the part of the blended dual that is no longer orthogonal to r.
+ *   7. a = r_v x x,  c = r_v x a,  x' = (x + (2 r_w) a) + 2 c  per coordinate.
+ *   8. out = (float)(x' + t), the one rounding to f32.
+ * The rotation is applied in this form, not as a 3x3 matrix built from r, because under identity
+ * transforms the blend is (W, 0, 0, 0 | 0): r_v = 0, d = 0 and x' = x + 0 + 0 exactly — the skinned
+ * rest mesh is the rest mesh bit for bit for any positive weights (dsu_skin_lbs: only at K = 1).
+ * Negating any table entry, the pivot's included, leaves the output bits unchanged.
+ * Kernel: one thread per (frame, vertex), vertex fastest, 256 threads; no LDS, no atomics: two runs
+ * give the same bits.  Skinning transforms here are rigid, so Blender's separate treatment of bone
+ * scale does not arise; the known bulge of dual-quaternion blending on the outside of a sharp bend
+ * is not corrected.
+ * dsu_skin_dqs_host: HOST function on HOST arrays, the same text evaluated on the CPU.
+ * Both return -1 on a null pointer with work to do and 0 for n_verts = 0. */
+int dsu_skin_dqs(const float* rest, const int32_t* influences, const float* weights, const double* dualquats,
+                 int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints, float* out, void* stream);
+int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float* weights,
+                      const double* dualquats, int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints,
+                      float* out);
 
 /* ------------------------------------------------------------------------------------
  * UV export (the export_uv branch of save_mesh, mesh_utils.py:65-67; coloring_utils.py:140-167;

@@ -1,14 +1,21 @@
 """Time the rigging steps (csrc/mesh_skin.hip) on a synthetic ~50 000-face character with 25 bones
 and 120 frames: triangle binning, distances + visibility, the bone-heat solve (with its iteration
-count), skinning, and the render of the same 120 frames; plus the compiler's register / LDS / spill
+count), skinning (linear-blend and dual-quaternion), and the render of the same 120 frames; plus the compiler's register / LDS / spill
 figures of the three kernels and, with --accuracy, the differences from the float64 reference
 (tests/skin_ref.py) on the three test meshes that the GPU tests' bars are set from.
 
     python tools/skin_probe.py [--runs 10] [--frames 120] [--accuracy] [--out profiles/skin_probe.json]
 
-Needs a GPU: there is no fallback.
+Kernel times of the two skinning kernels come from a trace of the same run, taken from outside and
+merged afterwards (the second command needs no GPU):
+
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/skin_probe.py ...
+    python tools/skin_probe.py --merge-trace DIR [--out profiles/skin_probe.json]
+
+The probe itself needs a GPU: there is no fallback.
 """
 import argparse
+import csv
 import importlib.util
 import json
 import os
@@ -114,7 +121,8 @@ def kernel_resources():
     md, out = isa.metadata(txt), {}
     for name, _ in isa.bodies(txt):
         short = isa.demangle_short(name)
-        if short in ("bone_visibility_kernel", "cg_spmv_kernel", "cg_update_kernel", "cg_direction_kernel", "skin_lbs_kernel"):
+        if short in ("bone_visibility_kernel", "cg_spmv_kernel", "cg_update_kernel", "cg_direction_kernel", "skin_lbs_kernel",
+                     "skin_dqs_kernel"):
             m = md[name]
             out[short] = {"vgpr": m["vgpr"], "sgpr": m["sgpr"], "lds_bytes": m["lds"], "scratch_bytes": m["scratch"],
                           "vgpr_spills": m["vspill"], "sgpr_spills": m["sspill"], "threads": 256}
@@ -148,14 +156,44 @@ def accuracy(dev):
     return out
 
 
+def merge_trace(folder, out):
+    """Median duration of skin_lbs_kernel and skin_dqs_kernel in the *kernel_trace.csv files under
+    `folder` (one traced run of this probe), and their ratio, into the probe's JSON."""
+    ns = {"skin_lbs_kernel": [], "skin_dqs_kernel": []}
+    for dp, _, fs in os.walk(folder):
+        for name in fs:
+            if not name.endswith("kernel_trace.csv"):
+                continue
+            with open(os.path.join(dp, name), newline="") as fh:
+                for row in csv.DictReader(fh):
+                    for k in ns:
+                        if k in row.get("Kernel_Name", ""):
+                            ns[k].append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+    if not all(ns.values()):
+        raise SystemExit(f"no launches of {[k for k, v in ns.items() if not v]} in the traces under {folder}")
+    with open(out) as fh:
+        res = json.load(fh)
+    us = {k: {"median_us": statistics.median(v) / 1e3, "min_us": min(v) / 1e3, "max_us": max(v) / 1e3, "launches": len(v)}
+          for k, v in ns.items()}
+    res["skinning_kernel_trace"] = dict(us, dqs_over_lbs=us["skin_dqs_kernel"]["median_us"] / us["skin_lbs_kernel"]["median_us"],
+                                        bytes_written_per_launch=12 * res["frames"] * res["verts"],
+                                        note="rocprofv3 --kernel-trace of the run that wrote this file")
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res["skinning_kernel_trace"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--merge-trace", metavar="DIR", help="read a kernel trace of an earlier run into --out; no GPU needed")
     ap.add_argument("--frames", type=int, default=120)
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--scale", type=float, default=1.0, help="mesh resolution factor (1.0: ~50 000 faces)")
     ap.add_argument("--accuracy", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "skin_probe.json"))
     a = ap.parse_args()
+    if a.merge_trace:
+        return merge_trace(a.merge_trace, a.out)
     if not torch.cuda.is_available():
         raise SystemExit("skin_probe needs a GPU")
     dev = torch.device("cuda:0")
@@ -184,6 +222,9 @@ def main():
     mats = torch.from_numpy(animate.skinning_matrices(sk, clip).astype(np.float32)).to(dev)
     ti, tw = torch.from_numpy(infl).to(dev), torch.from_numpy(w).to(dev)
     t_skin = timed(lambda: ops.skin_lbs(tv, ti, tw, mats), a.runs)
+    dq = torch.from_numpy(animate.dual_quaternions(animate.skinning_matrices(sk, clip))).to(dev)
+    t_dqs = timed(lambda: ops.skin_dqs(tv, ti, tw, dq), a.runs)
+    apart = (ops.skin_dqs(tv, ti, tw, dq) - ops.skin_lbs(tv, ti, tw, mats)).norm(dim=-1)
     screen = ops.skin_lbs(tv, ti, tw, mats)
     box = torch.stack([screen.amin((0, 1)), screen.amax((0, 1))]).cpu().numpy()
     cx, cy, size, span = animate.frame_window(box)
@@ -202,7 +243,10 @@ def main():
                 "assemble_host_ms": t_assemble,
                 "solve_ms": dict(t_solve, iterations=iters, recurrence_residual=float(res.max()), true_residual=true,
                                  tol=1e-10, nnz=int(A.nnz)),
-                "skinning_ms": t_skin, "render_ms": dict(t_render, size=int(size), span=float(span), ss=4,
+                "skinning_ms": t_skin,
+                "skinning_dqs_ms": dict(t_dqs, largest_distance_from_linear=float(apart.max()),
+                                        note="dual-quaternion blend of the same frames; host clock around one launch"),
+                "render_ms": dict(t_render, size=int(size), span=float(span), ss=4,
                                                          note="bin + raster + resolve + edges of the skinned frames"),
                 "animate_mesh_ms": dict(t_all, note="weights given; host arrays in, uploads included"),
                 "kernels": kernel_resources(), "device": torch.cuda.get_device_name(0)}
