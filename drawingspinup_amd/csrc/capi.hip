@@ -24,7 +24,7 @@ const char* dsu_strerror(int code) {
 
 int dsu_abi_version(void) { return 1; }
 
-int32_t dsu_onewave_grid_cap_value = 0;     // 0 = the resident count (geometry backward 512, texture backward 256)
+int32_t dsu_onewave_grid_cap_value = 0;     // CUs; 0 = the resident count (geometry backward 512, texture backward 256 workgroups)
 int32_t dsu_scatter_grid_cap_value = 0;     // 0 = the resident count (three 256-thread workgroups per CU: 768)
 int dsu_set_scatter_grid_cap(int32_t workgroups) {
   if (workgroups < 0 || workgroups > 4096) return DSU_EINVAL;
@@ -43,9 +43,9 @@ int dsu_set_nsr_side_stream_pooling(int32_t on) {
   dsu_nsr_side_pool_value = on;
   return DSU_OK;
 }
-int dsu_set_onewave_grid_cap(int32_t workgroups) {
-  if (workgroups < 0 || workgroups > 256) return DSU_EINVAL;
-  dsu_onewave_grid_cap_value = workgroups;
+int dsu_set_onewave_grid_cap(int32_t cus) {
+  if (cus < 0 || cus > 256) return DSU_EINVAL;
+  dsu_onewave_grid_cap_value = cus;
   return DSU_OK;
 }
 

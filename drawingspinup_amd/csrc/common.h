@@ -51,7 +51,7 @@ static inline int dsu_ab_int(const char*, int dflt) { return dflt; }
 static inline bool dsu_ab_is(const char*, const char*) { return false; }
 #endif
 
-// Workgroups of the two one-wave-per-SIMD kernels of the NSR step (dsu_set_onewave_grid_cap, capi.hip)
+// CUs given to the whole-SIMD kernels of the NSR step (dsu_set_onewave_grid_cap, capi.hip)
 extern "C" int32_t dsu_onewave_grid_cap_value;
 // Priority of the NSR driver's side stream (dsu_set_nsr_side_stream_priority, capi.hip; nsr_driver.hip has the story)
 #ifndef DSU_NSR_SIDE_PRIO_DEFAULT
@@ -60,9 +60,12 @@ extern "C" int32_t dsu_onewave_grid_cap_value;
 extern "C" int32_t dsu_nsr_side_priority_value;
 extern "C" int32_t dsu_nsr_side_pool_value;
 extern "C" int32_t dsu_scatter_grid_cap_value;
-static inline int dsu_onewave_blocks(int64_t n, int threads, int max_blocks) {
+// per_cu: workgroups of the kernel being sized that are resident on one CU; the cap counts CUs, so
+// a kernel resident at two workgroups per CU keeps both on each CU it is given.
+static inline int dsu_onewave_blocks(int64_t n, int threads, int max_blocks, int per_cu) {
   int cap = dsu_onewave_grid_cap_value;
-  if (cap < 1 || cap > max_blocks) cap = max_blocks;
+  if (cap < 1 || cap * per_cu > max_blocks) cap = max_blocks;
+  else cap *= per_cu;
   int64_t b = (n + threads - 1) / threads;
   if (b < 1) b = 1;
   return (int)(b > cap ? cap : b);

@@ -1796,8 +1796,11 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
   if (!workspace || workspace_bytes < need) return DSU_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const float eps2 = (float)((double)eps * (double)eps);
-  // (the workspace is sized for two workgroups per CU; dsu_set_onewave_grid_cap may launch fewer)
-  const int blocks = dsu_onewave_blocks(n, 256, BWD_MFMA_MAX_BLOCKS);
+  // (the workspace is sized for two workgroups per CU; dsu_set_onewave_grid_cap may launch fewer.
+  // The pipelined form with 4..6 active levels is resident at two workgroups per CU, the one with 7
+  // and the general kernel at one)
+  const bool two_per_cu = cfg->n_levels == 10 && enc_cache && active_levels >= 4 && active_levels <= 6;
+  const int blocks = dsu_onewave_blocks(n, 256, BWD_MFMA_MAX_BLOCKS, two_per_cu ? 2 : 1);
   const size_t shm1 = (size_t)K1_LDS_F * sizeof(float);
   const size_t shm2 = (size_t)SC_LDS_TOTAL * sizeof(float);
   float2* dinbuf = reinterpret_cast<float2*>((char*)workspace +

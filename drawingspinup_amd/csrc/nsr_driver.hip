@@ -744,11 +744,13 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
   a->out_next_n_rays = next_rays;
   if (a->prefetch_next) {
     // The next step's samples depend on the occupancy grid and the draws, not on the parameters.
-    // Their serial march (128 waves of ~100 registers for ~0.35 ms) cannot share a SIMD with the
-    // one-wave-per-SIMD kernels of a step (texture backward: 509 registers, MLP part of the
-    // geometry backward: 458) — started behind the geometry forward it delayed the texture
+    // Their march cannot share a SIMD with the whole-SIMD kernels of a step (texture backward:
+    // 509 registers, MLP part of the geometry backward) — as one ray per lane (128 waves of ~100
+    // registers for ~0.35 ms) and started behind the geometry forward it delayed the texture
     // backward's last workgroups by the march's remaining time (245 instead of 170 us, kernel
-    // trace).  It is therefore queued one step earlier, behind the MLP part of the backward the
+    // trace).  The march is one wave per ray now (8192 waves of 46 registers for ~0.115 ms,
+    // profiles/march_cooperative_ab.txt) and the ordering has not been re-measured with it: it
+    // is still queued one step earlier, behind the MLP part of the backward the
     // device is executing NOW (`gate`, recorded by the previous call): it then runs beside the
     // table-gradient scatter, the optimizer kernels and the next geometry forward, which all
     // leave registers free.  Set q was last read by step t-2, whose kernels precede `gate` in

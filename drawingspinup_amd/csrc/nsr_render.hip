@@ -100,41 +100,80 @@ __global__ void ray_aabb_kernel(const float* __restrict__ ro, const float* __res
   tmax_o[i] = far;
 }
 
-// advance_to_next_voxel (nerfacc): from the rejected lattice point tm, keep the sample lattice and
-// move to the first lattice point at or beyond the next voxel boundary (pure arithmetic).
-template <bool P2>
-__device__ __forceinline__ float skip_voxel(float tm, const float o[3], const float d[3],
-                                            const float inv[3], const Aabb& a, int res, float dt,
-                                            float far) {
-  const float p[3] = {o[0] + tm * d[0], o[1] + tm * d[1], o[2] + tm * d[2]};
-  float target = tm + dist_to_next_voxel<P2>(p, d, inv, a, res);
-  target = fminf(target, far);
-  float tt = tm;
-  do { tt += dt; } while (tt < target);
-  return tt;
-}
-
 // MODE 0: count only; 1: fill at offsets[i]; 2: single pass — fill a fixed-capacity scratch row
 // (i * cap) AND write the count, so the serial march runs once (compacted by ray_compact_kernel)
 //
-// One ray per lane, ~600 lattice points per ray, and the serial loop is ONE dependent occupancy
-// byte load (~250 ns measured, L2 hit) per lattice point or per skipped voxel: pure latency with
-// 32 waves on 256 CUs.  Both continuations of the recurrence are therefore computed ahead with
-// the same f32 operations the serial loop would execute (so the bits are the same):
-//   chain A: the next SPEC lattice points assuming every one is accepted,
-//   chain B: the next SB voxel skips assuming every landing point is rejected,
-// all SPEC+SB-1 occupancy bytes are fetched as independent loads, and the points are consumed in
-// order along whichever chain the first byte selects until the prediction fails.
-template <int MODE, bool HAS_OCC, bool P2, int SB>
-__global__ void ray_march_kernel(const float* __restrict__ ro, const float* __restrict__ rd,
-                                 const float* __restrict__ tmin, const float* __restrict__ tmax,
-                                 int64_t n, Aabb a, const uint8_t* __restrict__ occ, int res,
-                                 float step, const int32_t* __restrict__ offsets, int cap,
-                                 int32_t* __restrict__ num_steps,
-                                 int64_t* __restrict__ ray_indices, float* __restrict__ t_starts,
-                                 float* __restrict__ t_ends) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// A group of G lanes (G = 64: one wave) marches one ray.  The serial rule is one dependent
+// occupancy byte load per lattice point or per skipped voxel, ~600 lattice points per ray: with one
+// ray per lane that was pure latency (355 us per launch at 8192 rays, a few us of arithmetic;
+// 115 us in this form, bound by VALU issue: profiles/march_cooperative_ab.txt).
+// The points the rule can visit lie on additive chains that do not depend on the occupancy grid,
+// so the group evaluates G of them per round, one per lane, with G independent byte loads, and
+// then applies the rule to the whole window.  Every value is produced by the f32 operations the
+// serial loop would execute, in its order (lane k does its k chain additions one after the
+// other; a doubling scan would round differently), so the bits are the same.
+//   accept window, state (t0, t1, tm), tm not known to be rejected: lane b holds the b-th sample
+//     under "every point so far was accepted".  The first lane whose midpoint is past the far
+//     plane or unoccupied stops the run; the lanes below it emit their samples.
+//   reject window, c_0 = tm known to be rejected (or inside a skip whose target T is carried):
+//     lane k holds c_k = c_{k-1} + dt: nerfacc's advance_to_next_voxel moves from the rejected
+//     point tm to the first lattice point at or beyond the next voxel boundary (target =
+//     fminf(tm + dist_to_next_voxel(p(tm)), far); do tt += dt while (tt < target)), so
+//     consecutive skips walk this one chain from landing to landing.  The group hops from landing to landing (next landing of k: the first
+//     m > k with !(c_m < target_k), one ballot) until one is occupied or past the far plane.  A
+//     skip that leaves the window carries its target into the next one, starting at c_{G-1}.
+// The chain of a window: lane k of each group gets v_k = v_{k-1} + dt, v_0 = lane 0's input, by
+// G - 1 dependent additions that each read the lane below through DPP (every lane above 0 redoes
+// its addition each time and is final once the lane below it is; lane 0 has no source lane and
+// keeps its value).  One VALU instruction per chain step, where a loop with a lane-dependent trip
+// count costs three and the loop control (the marcher is bound by VALU issue: 8 waves per SIMD).
+// (G = 64; the timing variants loop.)  Written as assembly because the addition must stay the one DPP instruction; the wait states a
+// DPP operand needs after a VALU write of its register (2) or of EXEC (5) are therefore ours.
+template <int G>
+__device__ __forceinline__ float lane_chain(float v, float dt, int gl) {
+  if constexpr (G != 64) {             // the timing variants: plain loop, lane-dependent trip count
+    for (int k = 0; k < gl; ++k) v += dt;
+  } else {
+    asm volatile("s_nop 4\n\t.rept 63\n\ts_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t.endr"
+                 : "+v"(v) : "v"(dt));
+  }
+  return v;
+}
+
+// v of the lane below; `first` in lane 0 of the group
+template <int G>
+__device__ __forceinline__ float group_prev(float v, float first, int gl) {
+  if constexpr (G != 64) {
+    const float u = __shfl_up(v, 1, 64);
+    return gl == 0 ? first : u;
+  } else {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+        __builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xf,
+        0xf, false));
+  }
+}
+
+template <int G>
+__device__ __forceinline__ float group_bcast(float v, int src_lane) {
+  if (G == 64) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(
+                          __builtin_bit_cast(int, v), __builtin_amdgcn_readfirstlane(src_lane)));
+  return __shfl(v, src_lane, 64);
+}
+
+template <int MODE, bool HAS_OCC, bool P2, int G>
+__global__ __launch_bounds__(256) void ray_march_kernel(
+    const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ tmin,
+    const float* __restrict__ tmax, int64_t n, Aabb a, const uint8_t* __restrict__ occ, int res,
+    float step, const int32_t* __restrict__ offsets, int cap, int32_t* __restrict__ num_steps,
+    int64_t* __restrict__ ray_indices, float* __restrict__ t_starts, float* __restrict__ t_ends) {
+  static_assert(G == 16 || G == 32 || G == 64, "group: a power-of-two part of a wave");
+  const int lane = threadIdx.x & 63;
+  const int gl = lane & (G - 1);       // lane within the group
+  const int g0 = lane - gl;            // first lane of the group
+  const uint64_t gmask = (G == 64 ? ~0ull : (1ull << (G & 63)) - 1) << g0;
+  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
+  if (i >= n) return;                  // a whole group leaves together
   const float o[3] = {ro[i * 3], ro[i * 3 + 1], ro[i * 3 + 2]};
   const float d[3] = {rd[i * 3], rd[i * 3 + 1], rd[i * 3 + 2]};
   const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
@@ -143,98 +182,78 @@ __global__ void ray_march_kernel(const float* __restrict__ ro, const float* __re
   if (MODE == 1) base = offsets[i];
   if (MODE == 2) base = i * (int64_t)cap;
   const float dt = step;  // cone_angle == 0: calc_dt clamps to dt_min
+  // group-uniform state
   int j = 0;
   float t0 = near, t1 = t0 + dt, tm = (t0 + t1) * 0.5f;
-  constexpr int SPEC = 8;
-  while (tm < far) {
-    // ---- chain A: lattice points under "accepted"
-    float At0[SPEC], At1[SPEC], Atm[SPEC];
-    float a0 = t0, a1 = t1, am = tm;
-#pragma unroll
-    for (int b = 0; b < SPEC; ++b) {
-      At0[b] = a0; At1[b] = a1; Atm[b] = am;
-      a0 = a1;
-      a1 = a0 + dt;
-      am = (a0 + a1) * 0.5f;
-    }
-    bool Aocc[SPEC];
-    if (HAS_OCC) {
-      int Ai[SPEC];
-      bool Ain[SPEC];
-#pragma unroll
-      for (int b = 0; b < SPEC; ++b) {
-        const float p[3] = {o[0] + Atm[b] * d[0], o[1] + Atm[b] * d[1], o[2] + Atm[b] * d[2]};
-        Ai[b] = occ_cell<P2>(p, a, res, Ain[b]);
+  bool rejected = false, carried = false;
+  float carried_target = 0.0f;
+  for (;;) {
+    if (!HAS_OCC || !rejected) {
+      // ---- accept window: e_0 = t0, e_1 = t1, e_{k+1} = e_k + dt
+      const float e1 = lane_chain<G>(t1, dt, gl);          // e_{b+1}
+      const float e0 = group_prev<G>(e1, t0, gl);          // e_b
+      const float em = gl == 0 ? tm : (e0 + e1) * 0.5f;
+      const bool before_far = em < far;          // the serial loop's exit test
+      bool accept = before_far;
+      if (HAS_OCC) {
+        const float p[3] = {o[0] + em * d[0], o[1] + em * d[1], o[2] + em * d[2]};
+        bool in;
+        const int ci = occ_cell<P2>(p, a, res, in);
+        accept = before_far && in && occ[ci] != 0;
       }
-      uint32_t Av[SPEC];
-#pragma unroll
-      for (int b = 0; b < SPEC; ++b) Av[b] = occ[Ai[b]];
-      // ---- chain B: landing points of successive voxel skips under "rejected"
-      float Btm[SB + 1];
-      uint32_t Bv[SB];
-      bool Bin[SB];
-      Btm[0] = tm;
-      Bv[0] = 0;
-      Bin[0] = false;
-#pragma unroll
-      for (int k = 0; k < SB; ++k) {
-        Btm[k + 1] = skip_voxel<P2>(Btm[k], o, d, inv, a, res, dt, far);
-        if (k + 1 < SB) {
-          const float t = Btm[k + 1];
-          const float p[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
-          const int ci = occ_cell<P2>(p, a, res, Bin[k + 1]);
-          Bv[k + 1] = occ[ci];
-        }
+      const uint64_t past_far = __ballot(!before_far);
+      const uint64_t stops = __ballot(!accept) & gmask;
+      const int s = stops ? __ffsll((unsigned long long)stops) - 1 - g0 : G;   // accepted run
+      if (gl < s && (MODE == 1 || (MODE == 2 && j + gl < cap))) {
+        t_starts[base + j + gl] = e0;
+        t_ends[base + j + gl] = e1;
+        if (MODE == 1) ray_indices[base + j + gl] = i;
       }
-#pragma unroll
-      for (int b = 0; b < SPEC; ++b) Aocc[b] = Ain[b] && Av[b] != 0;
-      if (!Aocc[0]) {
-        // the current point is rejected: walk the skip chain while the landing points stay
-        // empty; stop on the first one that is occupied or past the far plane (it becomes the
-        // current point of the next round)
-        float nt = Btm[SB];
-        bool alive = true;
-#pragma unroll
-        for (int k = 1; k < SB; ++k) {
-          if (alive && (!(Btm[k] < far) || (Bin[k] && Bv[k] != 0))) {
-            nt = Btm[k];
-            alive = false;
-          }
-        }
-        tm = nt;
-        t0 = tm - dt * 0.5f;
-        t1 = tm + dt * 0.5f;
+      j += s;
+      if (s == G) {                              // all accepted: (e_G, e_{G+1}, their midpoint)
+        t0 = group_bcast<G>(e1, g0 + G - 1);
+        t1 = t0 + dt;
+        tm = (t0 + t1) * 0.5f;
         continue;
       }
+      if ((past_far >> (g0 + s)) & 1) break;     // stopped by the far plane: done
+      tm = group_bcast<G>(em, g0 + s);           // rejected: it starts a reject window
+      rejected = true;
+      carried = false;
     } else {
-#pragma unroll
-      for (int b = 0; b < SPEC; ++b) Aocc[b] = true;
-    }
-    bool alive = true;
-#pragma unroll
-    for (int b = 0; b < SPEC; ++b) {
-      if (alive) {
-        if (!(Atm[b] < far)) {          // the serial loop's exit test
-          t0 = At0[b]; t1 = At1[b]; tm = Atm[b];
-          alive = false;
-        } else if (Aocc[b]) {
-          if (MODE == 1 || (MODE == 2 && j < cap)) {
-            t_starts[base + j] = At0[b];
-            t_ends[base + j] = At1[b];
-            if (MODE == 1) ray_indices[base + j] = i;
-          }
-          ++j;
-        } else {
-          tm = skip_voxel<P2>(Atm[b], o, d, inv, a, res, dt, far);
+      // ---- reject window: c_0 = tm, c_k = c_{k-1} + dt
+      const float c = lane_chain<G>(tm, dt, gl);
+      const float p[3] = {o[0] + c * d[0], o[1] + c * d[1], o[2] + c * d[2]};
+      float target = c + dist_to_next_voxel<P2>(p, d, inv, a, res);
+      target = fminf(target, far);
+      if (gl == 0 && carried) target = carried_target;
+      bool in;
+      const int ci = occ_cell<P2>(p, a, res, in);
+      const bool lands = !(c < far) || (in && occ[ci] != 0);   // a landing here ends the skipping
+      const uint64_t landm = __ballot(lands);
+      int k = 0;
+      for (;;) {                                 // at most G - 1 hops: k grows with each
+        const float tk = group_bcast<G>(target, g0 + k);
+        const uint64_t above = gmask & ~((2ull << (g0 + k)) - 1);
+        const uint64_t m = __ballot(!(c < tk)) & above;
+        if (!m) {                                // the skip from k leaves the window
+          tm = group_bcast<G>(c, g0 + G - 1);
+          carried = true;
+          carried_target = tk;
+          break;
+        }
+        k = __ffsll((unsigned long long)m) - 1 - g0;
+        if ((landm >> (g0 + k)) & 1) {
+          tm = group_bcast<G>(c, g0 + k);
           t0 = tm - dt * 0.5f;
           t1 = tm + dt * 0.5f;
-          alive = false;
+          rejected = false;
+          break;
         }
       }
     }
-    if (alive) { t0 = a0; t1 = a1; tm = am; }   // all SPEC points accepted
   }
-  if (MODE != 1) num_steps[i] = j;
+  if (MODE != 1 && gl == 0) num_steps[i] = j;
 }
 
 // one wave per ray: scratch rows -> packed samples
@@ -648,40 +667,23 @@ Aabb make_aabb(const float* a6, int res = 1) {
 }  // namespace
 
 // march kernel variant: occupancy grid present or not, power-of-two box (exact reciprocal
-// multiplies instead of IEEE divisions), skip-chain length (DSU_MARCH_SB=4|8, default 4)
-static int march_sb() {
-  static int v = 0;
-  if (!v) v = dsu_ab_int("DSU_MARCH_SB", 4) == 8 ? 8 : 4;
-  return v;
-}
-// rays per workgroup (= lanes of the one wave that marches them): DSU_MARCH_THREADS=16|32|64.  A
-// wave executes the union of its rays' control paths round by round, so fewer rays per wave means
-// fewer rounds (and more, shorter waves).  16: with the march of every 16th step on the critical
-// path (the step behind an occupancy refresh cannot prefetch its samples) the NSR stage measured
-// 1.152 ms per step against 1.175 with 64 (three interleaved runs each, same box).
-static int march_threads() {
-  static int v = 0;
-  if (!v) {
-    const int t = dsu_ab_int("DSU_MARCH_THREADS", 16);
-    v = (t == 64 || t == 32) ? t : 16;
-  }
-  return v;
-}
-#define DSU_MARCH_ONE(M, O, P, S, nr, st, ...)                                              \
-  ray_march_kernel<M, O, P, S><<<dsu_blocks_for(nr, march_threads()), march_threads(), 0,   \
-                                 (hipStream_t)st>>>(__VA_ARGS__)
+// multiplies instead of IEEE divisions).  256-thread workgroups: four rays at one wave per ray.
+#ifndef DSU_MARCH_G
+#define DSU_MARCH_G 64   // lanes per ray; variant builds timed 16 and 32 (profiles/march_cooperative_ab.txt)
+#endif
+constexpr int MARCH_G = DSU_MARCH_G;
+#define DSU_MARCH_ONE(M, O, P, nr, st, ...)                                                 \
+  ray_march_kernel<M, O, P, MARCH_G><<<dsu_blocks_for(nr, 256 / MARCH_G), 256, 0,           \
+                                       (hipStream_t)st>>>(__VA_ARGS__)
 #define DSU_LAUNCH_MARCH(M, nr, st, box, occp, ...)                                   \
   do {                                                                                \
     const bool p2_ = (box).pow2 != 0;                                                 \
     if (!(occp)) {                                                                    \
-      if (p2_) DSU_MARCH_ONE(M, false, true, 4, nr, st, __VA_ARGS__);                 \
-      else DSU_MARCH_ONE(M, false, false, 4, nr, st, __VA_ARGS__);                    \
-    } else if (march_sb() == 8) {                                                     \
-      if (p2_) DSU_MARCH_ONE(M, true, true, 8, nr, st, __VA_ARGS__);                  \
-      else DSU_MARCH_ONE(M, true, false, 8, nr, st, __VA_ARGS__);                     \
+      if (p2_) DSU_MARCH_ONE(M, false, true, nr, st, __VA_ARGS__);                    \
+      else DSU_MARCH_ONE(M, false, false, nr, st, __VA_ARGS__);                       \
     } else {                                                                          \
-      if (p2_) DSU_MARCH_ONE(M, true, true, 4, nr, st, __VA_ARGS__);                  \
-      else DSU_MARCH_ONE(M, true, false, 4, nr, st, __VA_ARGS__);                     \
+      if (p2_) DSU_MARCH_ONE(M, true, true, nr, st, __VA_ARGS__);                     \
+      else DSU_MARCH_ONE(M, true, false, nr, st, __VA_ARGS__);                        \
     }                                                                                 \
   } while (0)
 

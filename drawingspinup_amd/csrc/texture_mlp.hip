@@ -1092,7 +1092,7 @@ int dsu_texture_bwd(const dsu_tex_mlp* mlp, const float* tex_in, const float* rg
   const int64_t need = dsu_texture_bwd_workspace_bytes(n);
   if (!workspace || workspace_bytes < need) return DSU_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS);
+  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
   const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
   static_assert(PART_N <= 4 * STAGE_F, "reduction buffer must fit the staging area");
   DSU_ENSURE_DYN_LDS(texture_bwd_kernel<false>, shm);
@@ -1119,7 +1119,7 @@ int dsu_texture_bwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const f
   const int64_t need = dsu_texture_bwd_workspace_bytes(n);
   if (!workspace || workspace_bytes < need) return DSU_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS);
+  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
   const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
   DSU_ENSURE_DYN_LDS(texture_bwd_kernel<true>, shm);
   texture_bwd_kernel<true><<<blocks, 256, shm, s>>>(*mlp, nullptr, ShadeIn{feature, grad},
@@ -1179,7 +1179,7 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
   const int64_t need = dsu_texture_bwd_workspace_bytes(n);
   if (!workspace || workspace_bytes < need) return DSU_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS);
+  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
   const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
   if (h1_mask) {
     DSU_ENSURE_DYN_LDS((texture_bwd_kernel<true, true>), shm);

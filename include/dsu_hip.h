@@ -35,12 +35,15 @@ const char* dsu_strerror(int code);
 int dsu_ab_switches(void);
 /* ABI version of this header; bumped on any signature change. */
 int dsu_abi_version(void);
-/* Workgroups of the two one-wave-per-SIMD kernels of the NSR step (the MLP part of the geometry
- * backward, the texture backward: 450-510 registers per lane, nothing else fits beside them on a
- * SIMD).  0 / 256 = one workgroup per CU (a single optimisation alone on the GPU); with several
- * drawings in flight on one GPU fewer workgroups leave CUs to the other drawings' kernels while such
- * a kernel runs (bench.py --inflight: 192).  Process-wide; workspaces stay sized for 256. */
-int dsu_set_onewave_grid_cap(int32_t workgroups);
+/* CUs given to the two whole-SIMD kernels of the NSR step (the MLP part of the geometry backward,
+ * the texture backward: their waves fill every SIMD of a CU they run on, nothing else fits beside
+ * them).  Each kernel launches cus x its resident workgroups per CU: one for the texture backward
+ * (450-510 registers per lane) and for the geometry backward at 7 active levels, two for the
+ * geometry backward at 4..6 active levels (<= 256 registers, two waves per SIMD).  0 = every CU (a
+ * single optimisation alone on the GPU); with several drawings in flight on one GPU fewer CUs
+ * leave the rest to the other drawings' kernels while such a kernel runs (bench.py --inflight: 192).
+ * Process-wide; workspaces stay sized for the resident count. */
+int dsu_set_onewave_grid_cap(int32_t cus);
 /* The same for the table-gradient scatter of the geometry backward (0 = its resident count: three
  * 256-thread workgroups of 45 KB LDS per CU). */
 int dsu_set_scatter_grid_cap(int32_t workgroups);
