@@ -154,6 +154,12 @@ _PROTOS = {
     "dsu_smooth_iterate": [P, c_i64, P, P, C.c_double, c_i32, P, P, P],
     "dsu_smooth_energy": [P, c_i64, P, P, P, P],
     "dsu_smooth_energy_partials": [],
+    "dsu_smooth_brick_side": [],
+    "dsu_smooth_bricks_flags": [P, c_i32, c_i32, c_i32, P, P],
+    "dsu_smooth_bricks_gather": [P, P, c_i32, c_i32, c_i32, P, P, c_i32, P, c_i32, P, P, P, P, P, P, P],
+    "dsu_smooth_bricks_iterate": [P, P, c_i32, P, P, P, c_i32, C.c_double, c_i32, c_i32, P, P, P],
+    "dsu_smooth_bricks_energy": [P, P, c_i32, P, P, P],
+    "dsu_smooth_bricks_scatter": [P, P, P, c_i32, c_i32, c_i32, c_i32, P, P],
     "dsu_set_onewave_grid_cap": [c_i32],
     "dsu_set_scatter_grid_cap": [c_i32],
     "dsu_set_nsr_side_stream_priority": [c_i32],

@@ -373,32 +373,50 @@ def signed_distance_band_tensor_program(binary, radius=5.0):
     return torch.where(b, d_in - 0.5, -(d_out - 0.5))
 
 
+# default bounds of the brick layout when the distinct distances are known up front: "coded" (one
+# byte per voxel into a table) or "stored" (the distance as a double); tools/smooth_probe.py measures both
+BRICK_BOUNDS = "coded"
+
+
 @torch.no_grad()
-def smooth_constrained(binary, max_iters=250, rel_tol=1e-6, band_radius=4.0, weight=0.5):
+def smooth_constrained(binary, max_iters=250, rel_tol=1e-6, band_radius=4.0, weight=0.5, layout=None):
     """mcubes.smooth for volumes of at most 512^3 voxels (see the module docstring).  Returns the
     float64 volume PyMCubes returns — the signed distance with the band replaced by the solution —
     except that distances beyond the band are capped at +-(band_radius + 1.5): they never reach the
     zero level set, and an exact far-field transform of 2 x 512^3 voxels would cost more than
     everything else in the export.
 
-    The unknowns are the band voxels only (a few million of the 134 M), compacted in x-major
-    order with six neighbour-slot arrays; F and F^T are gathers over them."""
+    The unknowns are the band voxels only (a few million of the 134 M).  layout: "bricks" (the
+    default on a device tensor: the band compacted in 8^3 bricks, csrc/mesh_smooth.hip) or "slots"
+    (compacted voxel by voxel in x-major order with six neighbour-slot arrays; F and F^T are
+    gathers over them: host tensors, and the comparison of the brick layout's tests)."""
     b = binary.bool()
-    dev = b.device
+    values = None
     if b.is_cuda and math.ceil(band_radius + 1.0) <= 8 and b.shape[2] <= 4096:
         dist, band = signed_distance_band_device(b, band_radius + 1.0, band_radius)
+        # every distance the transform can produce: the byte-coded bounds need no pass to find them
+        values = torch.from_numpy(np.unique(_band_tables(band_radius + 1.0, band_radius)[1]))
     else:
         dist = signed_distance_band(b, band_radius + 1.0)
         band = dist.abs() <= band_radius
+    return smooth_band(dist, band, max_iters, rel_tol, weight, layout, values)[0]
+
+
+def _slot_layout(dist, band):
+    """The band compacted voxel by voxel: (flat, nbr_slots, x, lower, upper), or None when the band
+    is empty.  flat: x-major linear index of the band voxels; nbr_slots: six (nv,) int32 tensors;
+    x: the band's distances; lower / upper: PyMCubes' bounds."""
     pos = torch.nonzero(band)
     nv = pos.shape[0]
     if nv == 0:
-        return dist
+        return None
+    shp = dist.shape
+    dev = dist.device
     # x-major linear index of the band voxels (the order nonzero / mask indexing walk them in)
-    flat = (pos[:, 0] * b.shape[1] + pos[:, 1]) * b.shape[2] + pos[:, 2]
-    slot = torch.full(b.shape, -1, dtype=torch.int32, device=dev)
+    flat = (pos[:, 0] * shp[1] + pos[:, 1]) * shp[2] + pos[:, 2]
+    slot = torch.full(shp, -1, dtype=torch.int32, device=dev)
     slot.view(-1)[flat] = torch.arange(nv, device=dev, dtype=torch.int32)
-    shape = torch.tensor(b.shape, device=dev)
+    shape = torch.tensor(shp, device=dev)
     nbr_slots = []                          # -x, +x, -y, +y, -z, +z : slot or -1
     for a in range(3):
         for sgn in (-1, 1):
@@ -416,28 +434,74 @@ def smooth_constrained(binary, max_iters=250, rel_tol=1e-6, band_radius=4.0, wei
     upper = torch.where(x < 0, x, torch.full_like(x, pinf))
     lower = torch.where(lower.abs() < 1, torch.zeros_like(x), lower)
     upper = torch.where(upper.abs() < 1, torch.zeros_like(x), upper)
+    return flat, nbr_slots, x, lower, upper
+
+
+def _bricks_supported(shape):
+    return len(shape) == 3 and min(shape) >= 1 and \
+        -(-shape[0] // 8) * -(-shape[1] // 8) * -(-shape[2] // 8) < 2 ** 22
+
+
+@torch.no_grad()
+def smooth_band(dist, band, max_iters=250, rel_tol=1e-6, weight=0.5, layout=None, values=None,
+                bounds=None, direct=False):
+    """The iteration of smooth_constrained on the voxels `band` (bool) of `dist` (f64, written in
+    place).  Returns (dist, iterations run).  values: the distinct distances of the band when the
+    caller knows them (ascending f64); bounds "coded" / "stored" and direct: the brick layout's
+    measured alternatives (ops.smooth_bricks_build, ops.smooth_bricks_iterate)."""
+    dev = dist.device
+    if layout is None:
+        layout = "bricks" if dist.is_cuda and _bricks_supported(dist.shape) else "slots"
+    if layout not in ("bricks", "slots"):
+        raise ValueError(f"layout {layout!r}: 'bricks' or 'slots'")
     check_each = 10
     cum_rel_tol = 1 - (1 - rel_tol) ** check_each
-    if b.is_cuda:
-        # the iteration itself: csrc/mesh_smooth.hip (two passes over the band per iteration)
+
+    def run(energy, iterate):
+        energy_now = float(energy())
+        done = 0
+        while done < max_iters:
+            step = min(check_each, max_iters - done)
+            iterate(step)
+            done += step
+            if step == check_each:
+                energy_before = energy_now
+                energy_now = float(energy())
+                if energy_before <= 0 or (energy_before - energy_now) / energy_before < cum_rel_tol:
+                    break
+        return done
+
+    if layout == "bricks":
+        from .. import ops
+        if not dist.is_cuda or not _bricks_supported(dist.shape):
+            raise ValueError("the brick layout needs a device volume of fewer than 2^22 bricks")
+        if bounds is None:
+            bounds = BRICK_BOUNDS if values is not None else "stored"
+        if bounds == "coded" and values is None:
+            values = torch.unique(dist[band])
+        bricks = ops.smooth_bricks_build(band, dist, values if bounds == "coded" else None)
+        if bricks is None:
+            return dist, 0
+        done = run(lambda: ops.smooth_bricks_energy(bricks),
+                   lambda step: ops.smooth_bricks_iterate(bricks, weight, step, direct))
+        ops.smooth_bricks_scatter(bricks, dist)     # (dist is the caller's own volume: written in place)
+        return dist, done
+    slots = _slot_layout(dist, band)
+    if slots is None:
+        return dist, 0
+    flat, nbr_slots, x, lower, upper = slots
+    nv = x.shape[0]
+    if dist.is_cuda:
+        # the iteration itself: csrc/mesh_smooth.hip (one pass over the band per iteration)
         from .. import ops
         nbr_t = torch.stack(nbr_slots).contiguous()
         lower, upper = lower.contiguous(), upper.contiguous()
         x = x.contiguous()
         ybuf = torch.empty(3 * nv, dtype=torch.float64, device=dev)
-        energy_now = float(ops.smooth_energy(nbr_t, x, ybuf))
-        done = 0
-        while done < max_iters:
-            step = min(check_each, max_iters - done)
-            ops.smooth_iterate(nbr_t, lower, upper, x, ybuf, weight, step)
-            done += step
-            if step == check_each:
-                energy_before = energy_now
-                energy_now = float(ops.smooth_energy(nbr_t, x, ybuf))
-                if energy_before <= 0 or (energy_before - energy_now) / energy_before < cum_rel_tol:
-                    break
+        done = run(lambda: ops.smooth_energy(nbr_t, x, ybuf),
+                   lambda step: ops.smooth_iterate(nbr_t, lower, upper, x, ybuf, weight, step))
         dist.view(-1)[flat] = x             # (dist is this call's own volume: written in place)
-        return dist
+        return dist, done
     # host tensors (CPU tests of the restatement): the same iteration as tensor programs
     nbr = [[nbr_slots[2 * a + k].clamp(min=0).long() for k in range(2)] for a in range(3)]
     has = [[(nbr_slots[2 * a + k] >= 0).to(torch.float64) for k in range(2)] for a in range(3)]
@@ -455,7 +519,9 @@ def smooth_constrained(binary, max_iters=250, rel_tol=1e-6, band_radius=4.0, wei
         diag += cdiag[a] ** 2 + has[a][0] + has[a][1]
     inv_d = 1.0 / diag
     energy_now = float((x * apply_q(x)).sum()) / 2
+    done = 0
     for i in range(max_iters):
+        done = i + 1
         x1 = -inv_d * (apply_q(x) - diag * x)               # -D^-1 R x
         x = weight * x1 + (1 - weight) * x
         x = torch.minimum(torch.maximum(x, lower), upper)
@@ -466,7 +532,7 @@ def smooth_constrained(binary, max_iters=250, rel_tol=1e-6, band_radius=4.0, wei
                 break
     out = dist.clone()
     out[band] = x
-    return out
+    return out, done
 
 
 # ------------------------------------------------------------------------------------------------

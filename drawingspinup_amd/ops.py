@@ -248,6 +248,90 @@ def smooth_energy(nbr, x, y):
     return part.sum() / 2
 
 
+class SmoothBricks:
+    """The band of one volume in the brick layout of csrc/mesh_smooth.hip (include/dsu_hip.h,
+    dsu_smooth_bricks_*): nb active bricks, x / y (nb, 512) f64, mask (nb, 8) i64 words, nbr6
+    (nb, 8) i32, bcoord (nb,) i32, and the bounds' initial distance as x0 (nb, 512) f64 or as code
+    (nb, 512) u8 into values (<= 255 ascending f64)."""
+    __slots__ = ("shape", "nb", "x", "y", "mask", "nbr6", "bcoord", "x0", "code", "values")
+
+
+def smooth_bricks_build(band, dist, values=None):
+    """band (X,Y,Z) bool/uint8, dist (X,Y,Z) f64 -> SmoothBricks, or None when the band is empty
+    (nothing but the occupancy pass is launched then).  values: ascending f64 candidates of the
+    band's distinct distances (<= 255) for the byte-coded bounds; None, or a band value outside
+    them, stores the distances as doubles instead."""
+    b = band.contiguous()
+    if b.dtype == torch.bool:
+        b = b.view(torch.uint8)
+    X, Y, Z = b.shape
+    dev = b.device
+    side = int(lib().dsu_smooth_brick_side())
+    nbricks = -(-X // side) * -(-Y // side) * -(-Z // side)
+    flags = torch.zeros(nbricks, dtype=torch.int32, device=dev)
+    check(lib().dsu_smooth_bricks_flags(ptr(b, torch.uint8), X, Y, Z, ptr(flags), stream()),
+          "dsu_smooth_bricks_flags")
+    bcoord = torch.nonzero(flags).view(-1).to(torch.int32)
+    nb = bcoord.shape[0]
+    if nb == 0:
+        return None
+    table = torch.full((nbricks,), -1, dtype=torch.int32, device=dev)
+    table[bcoord.long()] = torch.arange(nb, dtype=torch.int32, device=dev)
+    s = SmoothBricks()
+    s.shape, s.nb, s.bcoord = (X, Y, Z), nb, bcoord
+    s.x = torch.empty((nb, 512), dtype=torch.float64, device=dev)
+    s.y = torch.zeros((nb, 512), dtype=torch.float64, device=dev)
+    s.mask = torch.empty((nb, 8), dtype=torch.int64, device=dev)
+    s.nbr6 = torch.empty((nb, 8), dtype=torch.int32, device=dev)
+    s.x0 = s.code = s.values = None
+
+    def gather(x0, code, vals, miss):
+        check(lib().dsu_smooth_bricks_gather(
+            ptr(b, torch.uint8), ptr(dist, torch.float64), X, Y, Z, ptr(table), ptr(bcoord), nb,
+            ptr(vals, torch.float64), 0 if vals is None else vals.shape[0], ptr(s.x), ptr(x0),
+            ptr(code), ptr(s.mask), ptr(s.nbr6), ptr(miss), stream()), "dsu_smooth_bricks_gather")
+
+    if values is not None and 0 < values.shape[0] <= 255:
+        vals = values.to(device=dev, dtype=torch.float64).contiguous()
+        code = torch.empty((nb, 512), dtype=torch.uint8, device=dev)
+        miss = torch.zeros(1, dtype=torch.int32, device=dev)
+        gather(None, code, vals, miss)
+        if int(miss.item()) == 0:
+            s.code, s.values = code, vals
+            return s
+    s.x0 = torch.empty((nb, 512), dtype=torch.float64, device=dev)
+    gather(s.x0, None, None, None)
+    return s
+
+
+def smooth_bricks_iterate(s, weight, iters, direct=False):
+    """`iters` projected weighted-Jacobi iterations in place on s.x (one launch each)."""
+    check(lib().dsu_smooth_bricks_iterate(
+        ptr(s.nbr6, torch.int32), ptr(s.mask, torch.int64), s.nb, ptr(s.x0, torch.float64),
+        ptr(s.code, torch.uint8), ptr(s.values, torch.float64),
+        0 if s.values is None else s.values.shape[0], float(weight), int(iters), int(bool(direct)),
+        ptr(s.x, torch.float64), ptr(s.y, torch.float64), stream()), "dsu_smooth_bricks_iterate")
+
+
+def smooth_bricks_energy(s):
+    """x . Q x / 2 on the brick layout (device scalar, f64; fixed summation order)."""
+    part = torch.empty(s.nb, dtype=torch.float64, device=s.x.device)
+    check(lib().dsu_smooth_bricks_energy(ptr(s.nbr6, torch.int32), ptr(s.mask, torch.int64), s.nb,
+                                         ptr(s.x, torch.float64), ptr(part), stream()),
+          "dsu_smooth_bricks_energy")
+    return part.sum() / 2
+
+
+def smooth_bricks_scatter(s, dist):
+    """dist[band] = x, in place."""
+    X, Y, Z = s.shape
+    check(lib().dsu_smooth_bricks_scatter(ptr(s.x, torch.float64), ptr(s.mask, torch.int64),
+                                          ptr(s.bcoord, torch.int32), s.nb, X, Y, Z,
+                                          ptr(dist, torch.float64), stream()),
+          "dsu_smooth_bricks_scatter")
+    return dist
+
+
 def volume_band_distance(binary, R, value_table, band_table):
     """binary (X,Y,Z) bool/uint8 device volume -> (dist f64 (X,Y,Z), band bool (X,Y,Z)) through the
     caller's tables over d2 = min(squared distance to the nearest voxel of the other class, (R+1)^2):

@@ -991,6 +991,50 @@ int dsu_smooth_iterate(const int32_t* nbr, int64_t nv, const double* lower, cons
 int dsu_smooth_energy(const int32_t* nbr, int64_t nv, const double* x, double* y,
                       double* partials, void* stream);
 
+/* The same iteration (geometry.py:57-58) with the band compacted brick by brick instead of voxel by
+ * voxel: a brick is dsu_smooth_brick_side()^3 voxels (8^3) aligned to the volume grid and is active
+ * when it holds a band voxel; partial bricks at the far faces simply lack the voxels outside the
+ * volume.  Inside a brick a neighbour is an address, not a slot load.  Per active brick s (nb of them,
+ * in ascending order of the linear brick id (bx * nby + by) * nbz + bz, nb* = ceil(side / 8)):
+ *   x, y       (nb, 512) f64   the unknowns, z fastest, in two ping-pong copies (absent voxels: 0)
+ *   mask       (nb, 8)   u64   word lx, bit ly * 8 + lz: the voxel is a band voxel
+ *   nbr6       (nb, 8)   i32   slots of the -x,+x,-y,+y,-z,+z bricks or -1 (entries 6, 7 unused)
+ *   x0         (nb, 512) f64   the initial distance, from which the kernel derives PyMCubes' bounds
+ *                              (own-side bound = x0, 0 where |x0| < 1, unbounded on the other side)
+ *   code       (nb, 512) u8    or instead: index of x0 in values (nvalues <= 255 ascending doubles)
+ * A voxel is present when it is inside the volume, in an active brick and its mask bit is set;
+ * every other voxel is absent exactly as slot -1 is in dsu_smooth_iterate, and the per-voxel
+ * arithmetic is that function's, operand for operand: the results are equal bit for bit.
+ *   dsu_smooth_bricks_flags    flags[brick id] = 1 where band (X,Y,Z bytes) has a voxel (flags zeroed
+ *                              by the caller, who compacts them: table[brick id] = slot or -1,
+ *                              bcoord[slot] = brick id)
+ *   dsu_smooth_bricks_gather   band, dist -> x, mask, nbr6 and x0 and / or code (either may be NULL;
+ *                              miss[0] is set to 1 when a band value is not in values)
+ *   dsu_smooth_bricks_iterate  `iters` iterations in place on x (y: scratch of the same size), one
+ *                              launch each; code != NULL selects the byte-coded bounds; direct != 0
+ *                              reads neighbours straight from global memory instead of staging the
+ *                              brick and its six 2-deep face slabs in LDS (the measured comparison)
+ *   dsu_smooth_bricks_energy   partials[s] = sum over brick s of x . Q x, fixed order (the caller
+ *                              adds the nb partials in order and halves)
+ *   dsu_smooth_bricks_scatter  dist[v] = x where the mask is set, and nowhere else
+ * EUNSUP: a volume of 2^22 or more bricks. */
+int32_t dsu_smooth_brick_side(void);
+int dsu_smooth_bricks_flags(const uint8_t* band, int32_t X, int32_t Y, int32_t Z, int32_t* flags,
+                            void* stream);
+int dsu_smooth_bricks_gather(const uint8_t* band, const double* dist, int32_t X, int32_t Y, int32_t Z,
+                             const int32_t* table, const int32_t* bcoord, int32_t nb,
+                             const double* values, int32_t nvalues, double* x, double* x0,
+                             uint8_t* code, uint64_t* mask, int32_t* nbr6, int32_t* miss,
+                             void* stream);
+int dsu_smooth_bricks_iterate(const int32_t* nbr6, const uint64_t* mask, int32_t nb, const double* x0,
+                              const uint8_t* code, const double* values, int32_t nvalues,
+                              double weight, int32_t iters, int32_t direct, double* x, double* y,
+                              void* stream);
+int dsu_smooth_bricks_energy(const int32_t* nbr6, const uint64_t* mask, int32_t nb, const double* x,
+                             double* partials, void* stream);
+int dsu_smooth_bricks_scatter(const double* x, const uint64_t* mask, const int32_t* bcoord, int32_t nb,
+                              int32_t X, int32_t Y, int32_t Z, double* dist, void* stream);
+
 /* The signed distance transform mcubes.smooth starts from (PyMCubes: scipy's
  * distance_transform_edt on both classes, +-0.5 at the boundary voxels; geometry.py:57-58), in the
  * band that matters: exact wherever the other class is within R voxels (1 <= R <= 8).
