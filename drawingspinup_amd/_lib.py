@@ -195,6 +195,10 @@ _PROTOS = {
     "dsu_uv_dilate": [P, P, c_i32, P, P, P],
     "dsu_uv_project": [P, P, P, c_i64, c_i64, c_i32, P, P, c_f32, c_f32, c_f32, c_i32, P, P, P, P, P, P, c_i32,
                        C.c_double, P, P, P],
+    "dsu_uv_field_points": [P, P, P, c_i64, c_i64, c_i32, P, P, c_i64, c_i32, P, P, P],
+    "dsu_uv_field_resolve": [P, P, P, c_i64, c_i32, c_i32, P, P],
+    "dsu_uv_field_points_host": [P, P, P, c_i64, c_i64, c_i32, P, P, c_i64, c_i32, P, P],
+    "dsu_uv_field_resolve_host": [P, P, P, c_i64, c_i32, c_i32, P],
     "dsu_bone_visibility_workspace_bytes": [c_i32, c_i32, c_i32],
     "dsu_bone_visibility": [c_i32, P, P, P, c_i64, c_i64, c_i32, P, C.c_double, C.c_double, C.c_double,
                             C.c_double, c_i32, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P],

@@ -2,8 +2,9 @@
 #pragma once
 #include "common.h"
 
-// The three vertex indices of face m, or false when one of them is outside [0, V).
-__device__ __forceinline__ bool face_indices(const int32_t* __restrict__ faces, int64_t m, int64_t V,
+// The three vertex indices of face m, or false when one of them is outside [0, V).  (Host as well:
+// uv_field.h compiles its text for both.)
+__host__ __device__ __forceinline__ bool face_indices(const int32_t* __restrict__ faces, int64_t m, int64_t V,
                                              int& ia, int& ib, int& ic) {
   ia = faces[m * 3];
   ib = faces[m * 3 + 1];
@@ -46,7 +47,7 @@ __device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g)
 }
 
 // uv * size in float64 from the f32 uv
-__device__ __forceinline__ TriXY uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
+__host__ __device__ __forceinline__ TriXY uv_tri(const float* __restrict__ uvs, int ia, int ib, int ic, double S) {
   TriXY t;
   t.ax = (double)uvs[(int64_t)ia * 2] * S; t.ay = (double)uvs[(int64_t)ia * 2 + 1] * S;
   t.bx = (double)uvs[(int64_t)ib * 2] * S; t.by = (double)uvs[(int64_t)ib * 2 + 1] * S;
@@ -56,8 +57,8 @@ __device__ __forceinline__ TriXY uv_tri(const float* __restrict__ uvs, int ia, i
 
 // The atlas raster's edge functions.  Not edge_functions above: the operands are in the other order,
 // every value is the exact negation of that form, and the uv kernels accept this orientation only.
-__device__ __forceinline__ void uv_edges(const TriXY& t, double px, double py, double& w0, double& w1,
-                                         double& w2) {
+__host__ __device__ __forceinline__ void uv_edges(const TriXY& t, double px, double py, double& w0,
+                                                  double& w1, double& w2) {
   w0 = (t.cx - t.bx) * (py - t.by) - (t.cy - t.by) * (px - t.bx);
   w1 = (t.ax - t.cx) * (py - t.cy) - (t.ay - t.cy) * (px - t.cx);
   w2 = (t.bx - t.ax) * (py - t.ay) - (t.by - t.ay) * (px - t.ax);

@@ -19,11 +19,16 @@
 //   dsu_uv_dilate        one gutter round per launch, integer arithmetic
 //   dsu_uv_project       per-texel back-projection of the front / back drawings: one thread per
 //                        texel, the occluders from the z-parallel grid of mesh_post.hip
+//   dsu_uv_field_points  the field bake's sample points: one thread per (texel, sub-sample) of the
+//                        covered texels' list, the sub-sample fastest (uv_field.h has the text)
+//   dsu_uv_field_resolve the mean of a texel's evaluated samples into its three bytes: one thread
+//                        per listed texel
 // No floating-point atomics anywhere: two runs give the same bits.
 #include <cmath>
 #include "common.h"
 #include "bin_sort.h"
 #include "mesh_geom.h"
+#include "uv_field.h"
 
 namespace {
 
@@ -142,13 +147,6 @@ struct FaceTexelTiles {
   }
 };
 
-__device__ __forceinline__ uint8_t uv_quantise(double v) {
-  v = v * 255.0;
-  if (!(v == v)) return 0;                           // the reference's nan -> 0
-  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-  return (uint8_t)(int)v;                            // truncation, as astype(np.uint8)
-}
-
 __global__ __launch_bounds__(256) void uv_raster_kernel(
     const float* __restrict__ uvs, const int32_t* __restrict__ faces, const float* __restrict__ colours,
     const double* __restrict__ depth, int64_t V, int64_t M, int32_t S, int32_t G,
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(256) void uv_raster_kernel(
     const double b0 = w0 / area, b1 = w1 / area, b2 = w2 / area;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
-      q[ch] = uv_quantise((b0 * (double)colours[(int64_t)ia * 3 + ch] + b1 * (double)colours[(int64_t)ib * 3 + ch]) +
+      q[ch] = dsu_uvf::quantise((b0 * (double)colours[(int64_t)ia * 3 + ch] + b1 * (double)colours[(int64_t)ib * 3 + ch]) +
                           b2 * (double)colours[(int64_t)ic * 3 + ch]);
   }
   if (image) {
@@ -342,11 +340,64 @@ __global__ __launch_bounds__(256) void uv_project_kernel(
   source[at] = src;
 }
 
+// dsu_uv_field_points.  Neighbouring threads are the sub-samples of one texel, then the next listed
+// texel (ascending, so mostly the next column of one chart): a wave reads a handful of faces and
+// writes 64 consecutive points.  Nothing is shared, so no LDS and no barrier.
+__global__ __launch_bounds__(256) void uv_field_points_kernel(
+    const float* __restrict__ uvs, const int32_t* __restrict__ indices, const float* __restrict__ positions,
+    int64_t V, int64_t M, int32_t S, const int32_t* __restrict__ face_id, const int32_t* __restrict__ texels,
+    int64_t n_texels, int32_t s, float* __restrict__ points, uint8_t* __restrict__ valid) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int32_t ss = s * s;
+  if (i >= n_texels * ss) return;
+  const int64_t t = i / ss;
+  float p[3];
+  const bool ok = dsu_uvf::point(uvs, indices, positions, V, M, S, face_id, texels[t], s, (int32_t)(i - t * ss), p);
+  points[i * 3] = p[0];
+  points[i * 3 + 1] = p[1];
+  points[i * 3 + 2] = p[2];
+  valid[i] = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void uv_field_resolve_kernel(const float* __restrict__ colours,
+                                                               const uint8_t* __restrict__ valid,
+                                                               const int32_t* __restrict__ texels, int64_t n_texels,
+                                                               int32_t ss, int32_t S, uint8_t* __restrict__ image) {
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= n_texels) return;
+  dsu_uvf::resolve(colours, valid, t, ss, S, texels[t], image);
+}
+
 bool uv_size_ok(int32_t size) { return size >= 1 && size <= 8192; }
 
 int64_t uv_tiles(int32_t size) {
   const int64_t G = (size + UV_TILE - 1) / UV_TILE;
   return G * G;
+}
+
+// EINVAL / OK / "go on" (1) for the arguments the device and the host entries of the field bake share
+int uv_field_points_args(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                         int64_t n_faces, int32_t size, const int32_t* face_id, const int32_t* texels,
+                         int64_t n_texels, int32_t s, const float* points, const uint8_t* valid) {
+  if (!uv_size_ok(size) || s < 1 || s > dsu_uvf::MAX_S) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_texels < 0 || n_verts > (int64_t)1 << 30 || n_faces > (int64_t)1 << 30 ||
+      n_texels > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  if (!points || !valid) return DSU_EINVAL;
+  if (n_texels == 0) return DSU_OK;
+  if (!face_id || !texels) return DSU_EINVAL;
+  if (n_faces && (!uvs || !indices || !positions || n_verts == 0)) return DSU_EINVAL;
+  return 1;
+}
+
+int uv_field_resolve_args(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
+                          int32_t s, int32_t size, const uint8_t* image) {
+  if (!uv_size_ok(size) || s < 1 || s > dsu_uvf::MAX_S || n_texels < 0 || n_texels > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  if (!image) return DSU_EINVAL;
+  if (n_texels == 0) return DSU_OK;
+  if (!colours || !valid || !texels) return DSU_EINVAL;
+  return 1;
 }
 
 }  // namespace
@@ -456,6 +507,54 @@ int dsu_uv_project(const float* uvs, const int32_t* indices, const float* positi
                                                              mask_front, color_back, mask_back, res, z_tolerance,
                                                              image, source);
   DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_uv_field_points(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                        int64_t n_faces, int32_t size, const int32_t* face_id, const int32_t* texels,
+                        int64_t n_texels, int32_t s, float* points, uint8_t* valid, void* stream) {
+  const int rc = uv_field_points_args(uvs, indices, positions, n_verts, n_faces, size, face_id, texels, n_texels, s,
+                                      points, valid);
+  if (rc != 1) return rc;
+  uv_field_points_kernel<<<dsu_blocks_for(n_texels * s * s, 256), 256, 0, (hipStream_t)stream>>>(
+      uvs, indices, positions, n_verts, n_faces, size, face_id, texels, n_texels, s, points, valid);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_uv_field_resolve(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
+                         int32_t s, int32_t size, uint8_t* image, void* stream) {
+  const int rc = uv_field_resolve_args(colours, valid, texels, n_texels, s, size, image);
+  if (rc != 1) return rc;
+  uv_field_resolve_kernel<<<dsu_blocks_for(n_texels, 256), 256, 0, (hipStream_t)stream>>>(
+      colours, valid, texels, n_texels, s * s, size, image);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+// HOST: the same two texts (uv_field.h) on host arrays.
+int dsu_uv_field_points_host(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                             int64_t n_faces, int32_t size, const int32_t* face_id, const int32_t* texels,
+                             int64_t n_texels, int32_t s, float* points, uint8_t* valid) {
+  const int rc = uv_field_points_args(uvs, indices, positions, n_verts, n_faces, size, face_id, texels, n_texels, s,
+                                      points, valid);
+  if (rc != 1) return rc;
+  const int32_t ss = s * s;
+  for (int64_t i = 0; i < n_texels * ss; ++i) {
+    const int64_t t = i / ss;
+    valid[i] = dsu_uvf::point(uvs, indices, positions, n_verts, n_faces, size, face_id, texels[t], s,
+                              (int32_t)(i - t * ss), points + i * 3)
+                   ? 1
+                   : 0;
+  }
+  return DSU_OK;
+}
+
+int dsu_uv_field_resolve_host(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
+                              int32_t s, int32_t size, uint8_t* image) {
+  const int rc = uv_field_resolve_args(colours, valid, texels, n_texels, s, size, image);
+  if (rc != 1) return rc;
+  for (int64_t t = 0; t < n_texels; ++t) dsu_uvf::resolve(colours, valid, t, s * s, size, texels[t], image);
   return DSU_OK;
 }
 

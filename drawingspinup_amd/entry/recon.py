@@ -44,7 +44,7 @@ def parse(argv=None):
     ap.add_argument("--face_count", type=int, default=None)
     ap.add_argument("--resolution", type=int, default=None, help="model.geometry.isosurface.resolution")
     ap.add_argument("--thinning_type", default=None, choices=["double", "front", "back"])
-    ap.add_argument("--texture_source", default=None, choices=["vertex", "drawings"],
+    ap.add_argument("--texture_source", default=None, choices=["vertex", "drawings", "field"],
                     help="export.texture_source: what export.export_uv bakes into the atlas")
     for name in ("remeshing", "thinning", "smoothing", "shearing", "color_back_projection"):
         _bool_flag(ap, name)
@@ -69,11 +69,15 @@ def parse(argv=None):
     if args.resolution is not None:
         geo["isosurface"]["resolution"] = args.resolution
     source = ex.get("texture_source", "vertex")
-    if source not in ("vertex", "drawings"):
-        ap.error(f"export.texture_source must be 'vertex' or 'drawings', not {source!r}")
+    if source not in ("vertex", "drawings", "field"):
+        ap.error(f"export.texture_source must be 'vertex', 'drawings' or 'field', not {source!r}")
     if source == "drawings" and not (ex.get("export_uv", False) and ex["color_back_projection"]):
         # refused here, before hours of optimisation, not by save_obj after them
         ap.error("texture_source 'drawings' needs export.export_uv=true and export.color_back_projection on")
+    if source == "field" and not ex.get("export_uv", False):
+        ap.error("texture_source 'field' needs export.export_uv=true")
+    if not 1 <= int(ex.get("texture_samples", 2)) <= 8:
+        ap.error("export.texture_samples must be 1..8")
     return args, conf
 
 
@@ -130,14 +134,18 @@ def recon(uid, thinning, conf, dev):
             return torch.from_numpy(np.array(im.resize((2048, 2048), Image.LANCZOS))).to(dev)
         cbp = {"color_front": big("color", "front", "RGB"), "color_back": big("color", "back", "RGB"),
                "mask_front": big("mask", "front", "L")}
-    from ..nsr.mesh import save_obj
+    from ..nsr.mesh import field_colours, save_obj
     os.makedirs(out, exist_ok=True)
+    source = str(ex.get("texture_source", "vertex"))
     path = save_obj(os.path.join(out, name + ".obj"), mesh["verts"], mesh["faces"], mesh["vert_colors"],
                     ortho_scale=float(ex["ortho_scale"]), smoothing=bool(ex["smoothing"]),
                     shearing=bool(ex["shearing"]), color_back_projection=cbp,
                     thinning={"mask": fm, "type": ex["thinning_type"]} if thinning else None,
                     export_uv=bool(ex.get("export_uv", False)),
-                    texture_source=str(ex.get("texture_source", "vertex")))
+                    texture_source=source,
+                    # the field is the drawings' fallback too: what neither view sees comes from the network
+                    texture_field=field_colours(system.model) if source in ("field", "drawings") else None,
+                    texture_samples=int(ex.get("texture_samples", 2)))
     torch.save(system.model.state_dict(), os.path.join(out, f"it{system.global_step}.ckpt"))
     return path
 

@@ -740,6 +740,12 @@ def vertex_colors(model, verts, chunk=2097152):
     return torch.cat(out, 0) if out else torch.zeros((0, 3), device=verts.device)
 
 
+def field_colours(model):
+    """The texture field as a function of position, for nsr/uv.bake_field: (N,3) device points ->
+    (N,3) colours, evaluated as vertex_colors evaluates the vertices."""
+    return lambda p: vertex_colors(model, p)
+
+
 # ------------------------------------------------------------------------------------------------
 # save_mesh's host-side geometry steps that need no ray caster (mesh_utils.py:25-93)
 # ------------------------------------------------------------------------------------------------
@@ -967,18 +973,26 @@ def write_obj_textured(path, verts, faces, uvs, image, name):
 
 def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
              color_back_projection=None, thinning=None, export_uv=False, texture_size=1024,
-             texture_source="vertex"):
+             texture_source="vertex", texture_field=None, texture_samples=2):
     """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj, or with export_uv
     (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file.
     texture_source: "vertex" bakes the vertex colours (the reference's texture); "drawings" (an
     extension, needs export_uv and color_back_projection) projects the front / back drawings of
     color_back_projection into the atlas texel by texel, the vertex colours filling what neither
-    drawing sees (nsr/uv.bake_drawings)."""
-    if texture_source not in ("vertex", "drawings"):
-        raise ValueError("texture_source must be 'vertex' or 'drawings'")
+    drawing sees (nsr/uv.bake_drawings); "field" (an extension, needs export_uv and texture_field)
+    evaluates texture_field — a callable from (N,3) f32 points in the frame of `verts` to (N,3)
+    colours, field_colours(model) — at texture_samples^2 points per texel (nsr/uv.bake_field), the
+    vertex colours staying where nothing can be evaluated.  "drawings" with a texture_field uses the
+    field bake as its fallback; "vertex" ignores it."""
+    if texture_source not in ("vertex", "drawings", "field"):
+        raise ValueError("texture_source must be 'vertex', 'drawings' or 'field'")
     drawings = texture_source == "drawings"
     if drawings and not (export_uv and color_back_projection is not None):
         raise ValueError("texture_source='drawings' needs export_uv=True and the color_back_projection images")
+    if texture_source == "field" and not (export_uv and callable(texture_field)):
+        raise ValueError("texture_source='field' needs export_uv=True and a callable texture_field")
+    if texture_source != "vertex" and texture_field is not None and not callable(texture_field):
+        raise ValueError("texture_field must be callable")
     out, fz, c, *frame = post_process_mesh(verts, faces, colors, ortho_scale, smoothing, shearing,
                                            color_back_projection, thinning, return_projection_frame=drawings)
     if export_uv:
@@ -987,7 +1001,11 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
         from .uv import uv_mapping
         name = os.path.splitext(os.path.basename(path))[0]
         projection = dict(color_back_projection, positions=frame[0]) if drawings else None
+        field = None
+        if texture_source != "vertex" and texture_field is not None:
+            field = {"positions": verts.detach().float().cpu().numpy(), "eval_colours": texture_field,
+                     "samples": int(texture_samples)}
         m = uv_mapping(out, fz, c, name, size=int(texture_size),
-                       device=verts.device if verts.is_cuda else None, projection=projection)
+                       device=verts.device if verts.is_cuda else None, projection=projection, field=field)
         return write_obj_textured(path, m["verts"], m["faces"], m["uvs"], m["image"], name)
     return write_obj(path, out, fz, c)

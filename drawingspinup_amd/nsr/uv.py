@@ -6,6 +6,8 @@ rasteriser of the mesh's own triangles.
     bake_vertex_colours(uvs, indices, c) -> (size, size, 3) uint8, as compute_interpolation_map
     bake_drawings(uvs, indices, p, ...)  -> the same atlas with the input drawings projected into
                                             it texel by texel (an extension, see below)
+    bake_field(uvs, indices, p, eval)    -> the same atlas with the optimised texture field evaluated
+                                            texel by texel (an extension, see below)
     uv_mapping(v, faces, colours, name)  -> the textured mesh, as coloring_utils.uv_mapping
 
 Labels, charts, the atlas raster and the gutter fill run on the device (csrc/mesh_uv.hip, rules in
@@ -34,6 +36,15 @@ and keeps the vertex-colour bake where neither view sees it (dsu_uv_project in i
 has the rule in full).  What remains visible of the composition: a seam where projected and
 fallback texels meet, nearest-pixel sampling (no bilinear or area filter), and a fallback band along
 the silhouette as wide as the erosion of the masks (19 pixels of the 2048^2 drawings).
+
+Field.  bake_field asks the network the export has just optimised instead: every covered texel's
+surface point (samples x samples of them, a texel wide) goes back to the field's own frame through
+the atlas barycentrics and is evaluated by the caller's `eval_colours` (nsr/mesh.field_colours:
+the kernels vertex_colors runs); the mean of a texel's samples is its colour
+(dsu_uv_field_points / dsu_uv_field_resolve in include/dsu_hip.h).  The points lie on the
+triangles, not on the zero level set (no snapping), and a sub-sample that falls outside its face is
+evaluated on the face's plane.  With the drawings as well, the field takes the vertex bake's place
+as their fallback; the seam between the two stays.
 """
 import math
 
@@ -157,7 +168,7 @@ def layout(verts, faces, label, chart, size, gutter, scale=None):
 # ------------------------------------------------------------------ device parts
 class DeviceBackend:
     """The kernels behind the interface parametrize / bake_vertex_colours / bake_drawings use
-    (tests/uv_ref.py and tests/uv_project_ref.py have the float64 numpy one)."""
+    (tests/uv_ref.py, tests/uv_project_ref.py and tests/uv_field_ref.py have the float64 numpy one)."""
 
     def __init__(self, device=None):
         self.dev = torch.device(device if device is not None else "cuda")
@@ -198,6 +209,16 @@ class DeviceBackend:
         front, back = projection_masks(pos, ind, mf, res=cf.shape[0], ksize=int(erode))
         return ops.uv_project(t(uvs, np.float32), ind, pos, face_id, cf, front, cb, back, z_tolerance,
                               cells_per_axis=cells_per_axis)
+
+    def field_points(self, uvs, indices, positions, face_id, texels, samples):
+        from .. import ops
+        t = lambda a, dt: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.dev)
+        return ops.uv_field_points(t(uvs, np.float32), t(indices, np.int32), t(positions, np.float32), face_id,
+                                   texels, samples)
+
+    def field_resolve(self, colours, valid, texels, image):
+        from .. import ops
+        return ops.uv_field_resolve(colours, valid, texels, image)
 
     @staticmethod
     def to_numpy(a):
@@ -263,7 +284,7 @@ def bake_vertex_colours(uvs, indices, colours, size=1024, gutter=2, device=None,
 
 def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_back_u8, fallback_colours,
                   size=1024, gutter=2, z_tolerance=Z_TOLERANCE, erode=19, device=None, backend=None,
-                  return_maps=False):
+                  return_maps=False, fallback_image=None):
     """The atlas with the drawings projected into it: positions (V',3) are the atlas vertices in
     color_projection's frame (x right, y up, z front, inside [-0.5, 0.5]: after thinning and
     smoothing, before shear and ortho_scale), color_*_u8 (res,res,3) and mask_front_u8 (res,res) the
@@ -271,12 +292,17 @@ def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_
     mesh's silhouette, eroded with the `erode` ellipse, mirrored for the back view); a texel that
     neither view sees keeps the vertex-colour bake of fallback_colours (V',3); the gutter fill runs
     over the composition.  return_maps: also face_id (size,size) i32 and source (size,size) u8
-    (0 fallback, 1 front, 2 back)."""
+    (0 fallback, 1 front, 2 back).  fallback_image (size,size,3) u8 without gutter fill (bake_field's,
+    gutter=0) takes the place of the vertex-colour bake."""
     be = backend if backend is not None else DeviceBackend(device)
     uvs, indices = np.asarray(uvs, np.float32), np.asarray(indices, np.int64)
     img, fid, _ = be.bake(uvs, indices, np.asarray(fallback_colours, np.float32).reshape(-1, 3), int(size))
     proj, src = be.project(uvs, indices, np.asarray(_host(positions), np.float32).reshape(-1, 3), fid,
                            color_front_u8, mask_front_u8, color_back_u8, float(z_tolerance), int(erode))
+    if fallback_image is not None:
+        img = torch.as_tensor(_host(fallback_image)).to(src.device) if torch.is_tensor(src) else _host(fallback_image)
+        if tuple(img.shape) != tuple(proj.shape):
+            raise ValueError("fallback_image must be (size,size,3) uint8")
     where = torch.where if torch.is_tensor(src) else np.where
     out = where((src > 0)[..., None], proj, img)
     if gutter > 0:
@@ -285,23 +311,86 @@ def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_
     return (out, be.to_numpy(fid), be.to_numpy(src)) if return_maps else out
 
 
+def bake_field(uvs, indices, field_positions, eval_colours, fallback_colours=None, size=1024, gutter=2,
+               samples=2, chunk=1 << 21, device=None, backend=None, return_maps=False):
+    """The atlas with the texture field evaluated texel by texel: field_positions (V',3) are the
+    atlas vertices in the field's frame (the vertices the export received, in the atlas's vertex
+    order), eval_colours a callable taking (N,3) f32 points (on the device, with the device
+    backend) and returning (N,3) colours in [0,1].  The vertex bake of fallback_colours (V',3;
+    zeros when None) gives face_id and what stays where a texel has no valid sample; the covered
+    texels are then walked in pieces of at most chunk // samples^2 texels — points, eval_colours on
+    all points of the piece, the mean into the image — so that no more than `chunk` points exist at
+    a time; the gutter fill runs over the result.  samples: sub-samples per axis, 1..8.
+    return_maps: also face_id (size,size) i32 and evaluated (size,size) u8, 1 where at least one
+    sample was valid."""
+    be = backend if backend is not None else DeviceBackend(device)
+    s, S = int(samples), int(size)
+    if not 1 <= s <= 8:
+        raise ValueError("samples must be 1..8")
+    if not callable(eval_colours):
+        raise ValueError("eval_colours must be callable")
+    uvs, indices = np.asarray(uvs, np.float32), np.asarray(indices, np.int64)
+    pos = np.ascontiguousarray(np.asarray(_host(field_positions), np.float32).reshape(-1, 3))
+    if len(pos) != len(uvs):
+        raise ValueError("field_positions must hold one row per atlas vertex")
+    fallback = np.zeros((len(uvs), 3), np.float32) if fallback_colours is None else \
+        np.asarray(fallback_colours, np.float32).reshape(-1, 3)
+    img, fid, _ = be.bake(uvs, indices, fallback, S)
+    on_device = torch.is_tensor(fid)
+    if on_device:
+        texels = torch.nonzero(fid.reshape(-1) >= 0).reshape(-1).to(torch.int32)
+        evaluated = torch.zeros(S * S, dtype=torch.uint8, device=fid.device)
+        # uploaded once, not once per piece
+        put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(fid.device)
+        uvs_b, ind_b, pos_b = put(uvs, np.float32), put(indices, np.int32), put(pos, np.float32)
+    else:
+        texels = np.nonzero(np.asarray(fid).reshape(-1) >= 0)[0].astype(np.int32)
+        evaluated = np.zeros(S * S, np.uint8)
+        uvs_b, ind_b, pos_b = uvs, indices, pos
+    piece = max(1, int(chunk) // (s * s))
+    for at in range(0, len(texels), piece):
+        part = texels[at:at + piece]
+        points, valid = be.field_points(uvs_b, ind_b, pos_b, fid, part, s)
+        colours = eval_colours(points.reshape(-1, 3))
+        if tuple(colours.shape) != (len(part) * s * s, 3):
+            raise ValueError("eval_colours must return one (r, g, b) per point")
+        colours = colours.detach().float() if on_device else np.asarray(colours, np.float32)
+        img = be.field_resolve(colours.reshape(len(part), s * s, 3), valid, part, img)
+        hit = valid.reshape(len(part), s * s)
+        evaluated[part.long() if on_device else part] = hit.amax(1) if on_device else hit.max(1)
+    out = be.dilate(img, fid >= 0, int(gutter)) if gutter > 0 else img
+    out = be.to_numpy(out)
+    return (out, be.to_numpy(fid), be.to_numpy(evaluated.reshape(S, S))) if return_maps else out
+
+
 def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=None, backend=None,
-               projection=None):
+               projection=None, field=None):
     """coloring_utils.uv_mapping: parametrise, duplicate the vertices per chart, bake the colours.
     Returns the textured mesh as a dict (verts (V',3) f64, faces (M,3) i64, uvs (V',2) f32, image
     (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference.
     projection: dict(positions (V,3) in the order of v_np and in color_projection's frame,
     color_front, mask_front, color_back[, z_tolerance, erode]) bakes with bake_drawings, the vertex
-    colours being the fallback; None = the vertex colours alone."""
+    colours being the fallback; None = the vertex colours alone.
+    field: dict(positions (V,3) in the order of v_np and in the field's frame, eval_colours[,
+    samples, chunk]) bakes with bake_field, the vertex colours staying where no sample is valid; with
+    `projection` as well the drawings are composed over the field bake instead of the vertex bake."""
     v_np = np.asarray(v_np, np.float64).reshape(-1, 3)
     vmapping, indices, uvs = parametrize(v_np, faces, size, gutter, device=device, backend=backend)
     colours = np.asarray(vert_colors, np.float32)[vmapping]
-    if projection is None:
+    fallback_image = None
+    if field is not None:
+        fallback_image = bake_field(uvs, indices, _host(field["positions"]).reshape(-1, 3)[vmapping],
+                                    field["eval_colours"], colours, size, gutter if projection is None else 0,
+                                    samples=field.get("samples", 2), chunk=field.get("chunk", 1 << 21),
+                                    device=device, backend=backend)
+    if projection is None and field is not None:
+        image = fallback_image
+    elif projection is None:
         image = bake_vertex_colours(uvs, indices, colours, size, gutter, device=device, backend=backend)
     else:
         pr = projection
         image = bake_drawings(uvs, indices, _host(pr["positions"]).reshape(-1, 3)[vmapping], pr["color_front"],
                               pr["mask_front"], pr["color_back"], colours, size, gutter,
                               z_tolerance=pr.get("z_tolerance", Z_TOLERANCE), erode=pr.get("erode", 19),
-                              device=device, backend=backend)
+                              device=device, backend=backend, fallback_image=fallback_image)
     return {"verts": v_np[vmapping], "faces": indices, "uvs": uvs, "image": image, "name": save_name}

@@ -1812,6 +1812,49 @@ def uv_project(uvs, indices, positions, face_id, color_front, mask_front, color_
     return image, source
 
 
+def uv_field_points(uvs, indices, positions, face_id, texels, samples):
+    """dsu_uv_field_points (include/dsu_hip.h): the points at which the field bake evaluates the
+    texture field.  uvs (V',2) f32, indices (M,3), positions (V',3) f32 in the field's frame,
+    face_id (S,S) i32 from uv_bake, texels (T) i32 linear indices (ascending), all on the device;
+    samples: sub-samples per axis, 1..8.  -> points (T, samples^2, 3) f32, valid (T, samples^2) u8."""
+    uvs, positions = _f32c(uvs), _f32c(positions)
+    indices, texels = indices.to(torch.int32).contiguous(), texels.to(torch.int32).contiguous()
+    V, M, S, T, s, dev = uvs.shape[0], indices.shape[0], face_id.shape[0], texels.shape[0], int(samples), uvs.device
+    if uvs.shape != (V, 2) or positions.shape != (V, 3) or indices.shape != (M, 3) or face_id.shape != (S, S) or \
+            texels.dim() != 1:
+        raise ValueError("uvs (V',2), positions (V',3), indices (M,3), face_id (S,S) and texels (T) expected")
+    if not 1 <= s <= 8:
+        raise ValueError("samples must be 1..8")
+    points = torch.empty((T, s * s, 3), dtype=torch.float32, device=dev)
+    valid = torch.empty((T, s * s), dtype=torch.uint8, device=dev)
+    if T == 0:                                               # empty tensors have no address to hand over
+        return points, valid
+    check(lib().dsu_uv_field_points(ptr(uvs), ptr(indices), ptr(positions), V, M, S,
+                                    ptr(face_id.contiguous(), torch.int32), ptr(texels), T, s, ptr(points),
+                                    ptr(valid), stream()), "dsu_uv_field_points")
+    return points, valid
+
+
+def uv_field_resolve(colours, valid, texels, image):
+    """dsu_uv_field_resolve (include/dsu_hip.h): the mean of every listed texel's valid samples,
+    quantised as uv_bake does, written into image (S,S,3) u8 IN PLACE; a texel without a valid
+    sample keeps its bytes.  colours (T, samples^2, 3) f32, valid (T, samples^2) u8, texels (T) i32.
+    -> image."""
+    colours, texels = _f32c(colours), texels.to(torch.int32).contiguous()
+    T, S = texels.shape[0], image.shape[0]
+    if colours.dim() != 3 or colours.shape[0] != T or colours.shape[2] != 3 or valid.shape != colours.shape[:2] or \
+            image.shape != (S, S, 3) or image.dtype != torch.uint8:
+        raise ValueError("colours (T,n,3), valid (T,n), texels (T) and image (S,S,3) uint8 expected")
+    s = int(round(colours.shape[1] ** 0.5))
+    if s * s != colours.shape[1] or not 1 <= s <= 8:
+        raise ValueError("colours must hold samples^2 colours per texel, samples 1..8")
+    if T == 0:
+        return image
+    check(lib().dsu_uv_field_resolve(ptr(colours), ptr(valid.contiguous(), torch.uint8), ptr(texels), T, s, S,
+                                     ptr(image, torch.uint8), stream()), "dsu_uv_field_resolve")
+    return image
+
+
 # ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
 SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
 

@@ -1474,7 +1474,49 @@ int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float*
  * n_faces negative or above 2^30, image or source NULL; and, with n_faces > 0, n_verts == 0 or any
  * other pointer NULL.  n_faces == 0: DSU_OK, image and source zeroed, the other pointers unread.
  * The mesh must be wound outward in this frame (as marching cubes leaves it): the facing test reads
- * the winding, and a mesh wound inward projects nothing its views can see. */
+ * the winding, and a mesh wound inward projects nothing its views can see.
+ *
+ * f. dsu_uv_field_points: the sample points of the field bake (an extension: the reference bakes
+ * vertex colours, which hold no more detail than the vertices do; here the optimised texture field
+ * is evaluated per texel).  uvs, indices, size and face_id (size, size) i32 as dsu_uv_bake wrote
+ * them; positions (n_verts, 3) f32 are the atlas vertices IN THE FIELD'S FRAME (the world-frame
+ * vertices the export receives, before halving, axis swap, thinning, smoothing and shear, which
+ * move vertices but keep their order); texels (n_texels) i32: linear indices r size + c of the
+ * texels to sample, ascending (the caller lists nonzero(face_id >= 0)); s: sub-samples per axis,
+ * 1..8.  Outputs points (n_texels, s s, 3) f32 and valid (n_texels, s s) u8.  One thread per
+ * (texel, sub-sample), the sub-sample index fastest.  Everything in float64 from the f32 inputs, in
+ * this operand order.  Per texel (r, c) with m = face_id[r][c], sub-sample j = jy s + jx:
+ *   1. (x, y) = (c + o(jx), (size - 1 - r) + o(jy)),  o(i) = (2 i + 1 - s) / (2 s): an s x s grid
+ *      centred on the texel's own sample point and one texel wide.  For s = 1 it is that point,
+ *      the one dsu_uv_bake tests.
+ *   2. w0, w1, w2 and area exactly as in c. (vertex positions (double)u * size), b_i = w_i / area.
+ *      The b_i are NOT clamped: a sub-sample outside face m is evaluated on the affine extension of
+ *      m (no second raster, no dependence on neighbouring faces; the field is defined off the
+ *      surface too).
+ *   3. p = (b0 Pa + b1 Pb) + b2 Pc per coordinate, rounded once to f32.  For s = 1 the b_i and p
+ *      are those of e., steps 1-2.
+ *   4. valid = 1 when m is in [0, n_faces), its three indices are in [0, n_verts), area is finite
+ *      and > 0 and the three f32 coordinates of p are finite (a float64 p beyond the f32 range is
+ *      not); otherwise valid = 0 and the point is (0, 0, 0): the evaluator never sees a NaN.  A
+ *      texel index outside [0, size size) reads nothing and is invalid.
+ * DSU_EINVAL before any launch: size outside 1..8192, s outside 1..8, n_verts, n_faces or n_texels
+ * negative or above 2^30, points or valid NULL; and, with n_texels > 0, face_id or texels NULL, or
+ * with n_faces > 0 as well, n_verts == 0 or uvs, indices or positions NULL.  n_texels == 0: DSU_OK,
+ * nothing read or written.
+ *
+ * g. dsu_uv_field_resolve: colours (n_texels, s s, 3) f32 (the field evaluated at the points of
+ * f.), valid and texels as above -> image (size, size, 3) u8, written ONLY at the listed texels.
+ * Per texel and channel: sum = the (double)colour of the valid samples added in ascending j, n =
+ * their count.  n == 0: the texel is left untouched (the caller's fallback stays).  Otherwise the
+ * byte is dsu_uv_bake's quantisation of sum / n: times 255, clipped to [0, 255], truncated, NaN ->
+ * 0.  One thread per listed texel; a texel index outside [0, size size) writes nothing; the list
+ * must not name a texel twice.  No atomics: two runs give the same bits.
+ * DSU_EINVAL before any launch: size outside 1..8192, s outside 1..8, n_texels negative or above
+ * 2^30, image NULL; and, with n_texels > 0, colours, valid or texels NULL.  n_texels == 0: DSU_OK.
+ *
+ * dsu_uv_field_points_host / dsu_uv_field_resolve_host: HOST functions on HOST arrays — the same
+ * two texts (csrc/uv_field.h) compiled for the CPU, with the same argument checks, so that the
+ * rule can be held bit for bit without a device. */
 #define DSU_UV_COUNT 0
 #define DSU_UV_FILL 1
 #define DSU_UV_RASTER 2
@@ -1495,6 +1537,16 @@ int dsu_uv_project(const float* uvs, const int32_t* indices, const float* positi
                    float cell, int32_t g, const int32_t* offsets, const int32_t* items, const uint8_t* color_front,
                    const uint8_t* mask_front, const uint8_t* color_back, const uint8_t* mask_back, int32_t res,
                    double z_tolerance, uint8_t* image, uint8_t* source, void* stream);
+int dsu_uv_field_points(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                        int64_t n_faces, int32_t size, const int32_t* face_id, const int32_t* texels,
+                        int64_t n_texels, int32_t s, float* points, uint8_t* valid, void* stream);
+int dsu_uv_field_resolve(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
+                         int32_t s, int32_t size, uint8_t* image, void* stream);
+int dsu_uv_field_points_host(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                             int64_t n_faces, int32_t size, const int32_t* face_id, const int32_t* texels,
+                             int64_t n_texels, int32_t s, float* points, uint8_t* valid);
+int dsu_uv_field_resolve_host(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
+                              int32_t s, int32_t size, uint8_t* image);
 
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
