@@ -208,6 +208,13 @@ _PROTOS = {
     "dsu_skin_lbs": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P, P],
     "dsu_skin_dqs": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P, P],
     "dsu_skin_dqs_host": [P, P, P, P, c_i64, c_i32, c_i32, c_i32, P],
+    "dsu_corrective_smooth_workspace_bytes": [c_i64, c_i32],
+    "dsu_corrective_bind": [P, P, P, c_i64, P, P, c_i64, P, c_i64, c_i64, C.c_double, c_i32, P, c_i64, P, P, P],
+    "dsu_corrective_smooth": [P, P, P, P, c_i64, P, P, c_i64, P, c_i64, P, P, c_i64, c_i32, C.c_double, c_i32,
+                              P, c_i64, P, P],
+    "dsu_corrective_bind_host": [P, P, P, c_i64, P, P, c_i64, P, c_i64, c_i64, C.c_double, c_i32, P, c_i64, P, P],
+    "dsu_corrective_smooth_host": [P, P, P, P, c_i64, P, P, c_i64, P, c_i64, P, P, c_i64, c_i32, C.c_double,
+                                   c_i32, P, c_i64, P],
     "dsu_point_bin_count": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P],
     "dsu_point_bin_fill": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
     "dsu_knn8_blend": [P, c_i64, P, P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],

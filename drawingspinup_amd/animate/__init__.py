@@ -33,14 +33,19 @@ automatic joint placement (`fit_to_mesh` only scales and centres a skeleton); th
 that blender_animation.py:17-18 applies to two named clips is not restated.  FBX is not read.
 `animate_mesh(skinning="dual_quaternion")` blends unit dual quaternions instead of matrices (Blender's
 "Preserve Volume"; `dual_quaternions` makes the table), and `resample_clip` brings a clip to another
-frame rate (slerp of the local rotations).
+frame rate (slerp of the local rotations).  `animate_mesh(corrective_iterations=N)` smooths the
+skinned frames and puts the rest mesh's detail back (delta mush, Blender's Corrective Smooth;
+`smoothing_topology` builds the welded graph it walks): it repairs creases from bad weights, not the
+collapse of a twisted limb.
 """
 from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
                      read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
 from .skeleton import (Clip, Skeleton, dual_quaternions, fit_to_mesh, quaternion_rotations, read_bvh, resample_clip,
                        rest_clip, rotation_quaternions, skinning_matrices)
+from . import corrective
+from .corrective import smoothing_topology
 from .skin import animate_mesh, bone_heat_weights
 
 __all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "dual_quaternions", "fit_to_mesh",
            "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
-           "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate"]
+           "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate", "smoothing_topology"]

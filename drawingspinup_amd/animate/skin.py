@@ -13,6 +13,7 @@ import torch
 
 from .. import ops
 from ..nsr.thinning import _weld, cotmatrix
+from .corrective import check_parameters, smoothing_topology
 from .render import _texture_args, _vertex_colours, frame_window, position_colours
 from .skeleton import dual_quaternions, skinning_matrices
 
@@ -140,7 +141,8 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 
 @torch.no_grad()
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
-                 texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear"):
+                 texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear",
+                 corrective_iterations=0, corrective_factor=0.5):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
     weights)), skinning on the device, then the rasteriser of render_frames.  skinning: "linear"
     blends the joints' matrices (ops.skin_lbs, Blender's default), "dual_quaternion" their unit dual
@@ -148,11 +150,17 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     radius); the weights are the same for both.  The skinned vertices never leave the device; the
     window is frame_window's rule on their bounding box over all frames (Blender uses the object's
     bound_box).  texture, uvs, texture_filter, mip_coverage: as in render_frames (colours may be None
-    with a texture).
+    with a texture).  corrective_iterations N > 0 runs the corrective smoothing (delta mush,
+    ops.corrective_smooth: N smoothing steps of strength corrective_factor, then the rest mesh's
+    detail put back) on the skinned vertices of either blend: it repairs the creases that wrong or
+    abruptly changing weights leave at a joint; the topology and the bind are computed once per call
+    from the rest mesh, and window and `vertices` are taken from the corrected tensor.  0 (default)
+    is off.
 
     Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor."""
     if skinning not in SKINNING:
         raise ValueError(f"skinning {skinning!r}: one of {SKINNING}")
+    check_parameters(corrective_iterations, corrective_factor)
     dev = torch.device(device)
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
@@ -169,6 +177,10 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
         screen = ops.skin_lbs(rest, ti, tw, torch.from_numpy(mats).to(dev))
     else:
         screen = ops.skin_dqs(rest, ti, tw, torch.from_numpy(dual_quaternions(skinning_matrices(skeleton, clip))).to(dev))
+    if corrective_iterations:
+        topology = ops.corrective_topology(smoothing_topology(v, f), dev)
+        delta, valid = ops.corrective_bind(rest, topology, corrective_factor, corrective_iterations)
+        screen = ops.corrective_smooth(screen, topology, delta, valid, corrective_factor, corrective_iterations)
     box = torch.stack([screen.amin((0, 1)), screen.amax((0, 1))]).cpu().numpy()
     cx, cy, size, span = frame_window(box)
     pos = torch.from_numpy(position_colours(v).astype(np.float32)).to(dev)

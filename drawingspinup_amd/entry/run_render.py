@@ -25,6 +25,13 @@ their matrices (Blender's "Preserve Volume"; the default `linear` is Blender's d
 reference's), and `--fps N` resamples each clip to 1 / N s per frame after it is fitted to the mesh
 (default: the clip's own rate).  The cached weights serve both blends.  rest_pose and rest_rotate
 have no skeleton and ignore both.
+
+`--corrective_smooth N` runs N steps of corrective smoothing (delta mush, Blender's Corrective Smooth
+modifier; animate_mesh(corrective_iterations=N)) on the skinned vertices of every BVH action, with
+`--corrective_factor` (default 0.5, in [0, 1]) as the strength of a step: creases from wrong or
+abruptly changing weights are smoothed out and the rest mesh's detail is put back.  The bind is
+recomputed per run (one frame's worth of work); `skin_weights.npz` is neither read differently nor
+rewritten.  0 (default) is off; rest_pose and rest_rotate are rigid and are not touched.
 """
 import argparse
 import glob
@@ -92,8 +99,16 @@ def run(argv=None):
                     help="blend of the BVH actions: the joints' matrices, or their dual quaternions (preserve volume)")
     ap.add_argument("--fps", type=float, default=None,
                     help="resample each BVH clip to this many frames per second (default: the clip's own rate)")
+    ap.add_argument("--corrective_smooth", type=int, default=0, metavar="N",
+                    help="corrective smoothing (delta mush) of the BVH actions: N smoothing steps, 0..255 (0: off)")
+    ap.add_argument("--corrective_factor", type=float, default=0.5,
+                    help="strength of one corrective smoothing step, in [0, 1]")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    try:
+        animate.corrective.check_parameters(args.corrective_smooth, args.corrective_factor)
+    except ValueError as e:
+        ap.error(str(e))
     if args.fps is not None and not args.fps > 0:
         ap.error("--fps must be positive")
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
@@ -122,7 +137,9 @@ def run(argv=None):
             if args.fps is not None:
                 clip = animate.resample_clip(clip, 1.0 / args.fps)
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
-                                            ss=args.ss, device=args.device, skinning=args.skinning, **tex)
+                                            ss=args.ss, device=args.device, skinning=args.skinning,
+                                            corrective_iterations=args.corrective_smooth,
+                                            corrective_factor=args.corrective_factor, **tex)
         n = write_frames(out_dir, rendered)
         print((time.time() - start) / n, n)
     return out_dir, rendered

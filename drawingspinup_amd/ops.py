@@ -1972,3 +1972,78 @@ def skin_dqs(rest, influences, weights, dualquats):
     check(lib().dsu_skin_dqs(ptr(rest, torch.float32), ptr(influences, torch.int32), ptr(weights, torch.float32),
                              ptr(dualquats, torch.float64), V, K, F, J, ptr(out), stream()), "dsu_skin_dqs")
     return out
+
+
+CORRECTIVE_KEYS = ("rep", "faces", "nbr_rowptr", "nbr_cols", "cor_rowptr", "cor_faces")
+
+
+def corrective_topology(topology, device):
+    """The arrays of animate.corrective.smoothing_topology as contiguous int32 tensors on `device`
+    (a mapping that holds them already is returned as it is, so one upload serves bind and smooth)."""
+    import numpy as np
+    dev = torch.device(device)
+    out = {}
+    for k in CORRECTIVE_KEYS:
+        a = topology[k]
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a, np.int32))
+        out[k] = a.to(device=dev, dtype=torch.int32).contiguous()
+    V = out["rep"].numel()
+    if out["rep"].dim() != 1 or out["nbr_rowptr"].shape != (V + 1,) or out["cor_rowptr"].shape != (V + 1,) \
+            or out["faces"].dim() != 2 or out["faces"].shape[1] != 3 or out["nbr_cols"].dim() != 1 \
+            or out["cor_faces"].dim() != 1:
+        raise ValueError("topology: rep (V), faces (M,3), nbr_rowptr / cor_rowptr (V+1), nbr_cols, cor_faces expected")
+    return out
+
+
+def _corrective_args(t):
+    return (ptr(t["nbr_rowptr"], torch.int32), ptr(t["nbr_cols"], torch.int32), t["nbr_cols"].numel(),
+            ptr(t["cor_rowptr"], torch.int32), ptr(t["cor_faces"], torch.int32), t["cor_faces"].numel(),
+            ptr(t["faces"], torch.int32), t["faces"].shape[0])
+
+
+def _corrective_workspace(V, F, device):
+    nbytes = lib().dsu_corrective_smooth_workspace_bytes(V, F)
+    if nbytes < 0:
+        check(int(nbytes), "dsu_corrective_smooth_workspace_bytes")
+    return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device), nbytes
+
+
+def corrective_bind(rest, topology, factor, iterations):
+    """Bind of the corrective smoothing (dsu_corrective_bind): rest (V,3), topology as
+    animate.corrective.smoothing_topology gives it -> (delta (V,3) f64, valid (V,) uint8) on the
+    device: every representative's offset from its smoothed rest position in its local frame."""
+    rest = _f32c(rest)
+    if rest.dim() != 2 or rest.shape[1] != 3:
+        raise ValueError("rest (V,3) expected")
+    t = corrective_topology(topology, rest.device)
+    V = rest.shape[0]
+    if t["rep"].numel() != V:
+        raise ValueError("the topology is of another mesh")
+    delta = torch.zeros((V, 3), dtype=torch.float64, device=rest.device)
+    valid = torch.zeros((V,), dtype=torch.uint8, device=rest.device)
+    ws, nbytes = _corrective_workspace(V, 1, rest.device)
+    check(lib().dsu_corrective_bind(ptr(rest, torch.float32), *_corrective_args(t), V, float(factor), int(iterations),
+                                    ptr(ws), nbytes, ptr(delta), ptr(valid), stream()), "dsu_corrective_bind")
+    return delta, valid
+
+
+def corrective_smooth(skinned, topology, delta, valid, factor, iterations):
+    """Corrective smoothing of skinned frames (dsu_corrective_smooth): skinned (F,V,3), delta and
+    valid from corrective_bind with the same factor and iterations -> (F,V,3) f32 on the device.
+    `skinned` is not written."""
+    skinned = _f32c(skinned)
+    if skinned.dim() != 3 or skinned.shape[2] != 3:
+        raise ValueError("skinned (F,V,3) expected")
+    t = corrective_topology(topology, skinned.device)
+    F, V = skinned.shape[:2]
+    delta, valid = delta.to(torch.float64).contiguous(), valid.to(torch.uint8).contiguous()
+    if t["rep"].numel() != V or delta.shape != (V, 3) or valid.shape != (V,):
+        raise ValueError("topology, delta (V,3) and valid (V,) of the skinned mesh expected")
+    out = torch.empty((F, V, 3), dtype=torch.float32, device=skinned.device)
+    ws, nbytes = _corrective_workspace(V, F, skinned.device)
+    a = _corrective_args(t)
+    check(lib().dsu_corrective_smooth(ptr(skinned, torch.float32), ptr(t["rep"], torch.int32), *a,
+                                      ptr(delta, torch.float64), ptr(valid, torch.uint8), V, F, float(factor),
+                                      int(iterations), ptr(ws), nbytes, ptr(out), stream()), "dsu_corrective_smooth")
+    return out

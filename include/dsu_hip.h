@@ -1376,6 +1376,90 @@ int dsu_skin_dqs(const float* rest, const int32_t* influences, const float* weig
 int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float* weights,
                       const double* dualquats, int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints,
                       float* out);
+/* Corrective smoothing of skinned frames ("delta mush", Mancewicz et al., "Delta Mush: smoothing
+ * deformations while preserving detail", 2014; Blender's Corrective Smooth modifier).  Skinning moves
+ * every vertex by its own influences alone, so wrong or abruptly changing weights shear and crease
+ * the surface at a joint.  At bind time the rest mesh is smoothed and every vertex remembers, in a
+ * local surface frame, its offset from its smoothed position; per frame the skinned mesh is smoothed
+ * (which removes the creases) and the offsets are put back in that frame's local frames (which
+ * restores the detail).  Invariant under rigid motion; an extension of the reference, off by default;
+ * csrc/corrective_smooth.h holds the text, compiled for the kernels and for the host entries.
+ *
+ * Topology (device arrays, int32; drawingspinup_amd/animate/corrective.py builds it once per
+ * character on the WELDED mesh, so a seam-split export does not tear):
+ *   rep (n_verts)             the lowest index of each cluster of coincident vertices
+ *   faces (n_faces, 3)        the faces over representatives, degenerate ones dropped
+ *   nbr_rowptr (n_verts + 1), nbr_cols (n_nbr)    CSR: the row of a representative is the ascending,
+ *                             duplicate-free list of the other representatives it shares a face with;
+ *                             the row of a non-representative or of a vertex without a face is empty
+ *   cor_rowptr (n_verts + 1), cor_faces (n_cor)   CSR: the ascending indices into `faces` of the
+ *                             faces that contain the representative
+ * A row is rowptr[v] .. rowptr[v + 1] clamped to [0, n]; an entry outside its range (a neighbour or a
+ * face vertex outside [0, n_verts), a face outside [0, n_faces)) is left out of its row, as if it
+ * were not listed.
+ *
+ * Rule.  All arithmetic is float64 from the f32 inputs, sums of three terms are (a + b) + c, no
+ * products are fused.
+ *   Smoothing step, per (frame, vertex v) on an (n_frames, n_verts, 3) f32 buffer q: the neighbours'
+ *     q are added in row order to a sum that starts at 0; deg = the row's length; m = sum / deg;
+ *     out = (float)(q_v + factor (m - q_v)) per coordinate — one rounding to f32 per step, the
+ *     buffers between steps are f32.  deg = 0 copies the value.  `iterations` steps run, the first
+ *     from the input, the others between the two halves of the workspace; the input is never written.
+ *   Frame at a representative r from the fully smoothed buffer s:
+ *     N = sum over the corner row, in row order, from 0, of (b - a) x (c - a), with (a, b, c) the
+ *     face's vertices in stored order and (u x w)_x = u_y w_z - u_z w_y (cyclic);
+ *     n2 = (N_x N_x + N_y N_y) + N_z N_z; unless n2 > 0 and finite there is no frame; n = N / sqrt(n2)
+ *     component by component;  e = s[first neighbour] - s[r];  en = (e_x n_x + e_y n_y) + e_z n_z;
+ *     t = e - en n;  t2 = (t_x t_x + t_y t_y) + t_z t_z; unless t2 > 0 and finite there is no frame;
+ *     t = t / sqrt(t2);  b = n x t, not renormalised.  An empty neighbour row or an empty corner row:
+ *     no frame.
+ *   Bind (one frame, the rest mesh): d = rest[r] - s_rest[r];  delta[r] = (t.d, b.d, n.d), each dot
+ *     product (x + y) + z: (n_verts, 3) FLOAT64;  valid[r] = 1 if and only if a frame exists:
+ *     (n_verts) uint8.  Without a frame delta is 0.
+ *   Apply, per (frame, vertex v), r = rep[v]: if valid[r] and a frame exists at r in this frame,
+ *     out = (float)(s_r + ((t delta_0 + b delta_1) + n delta_2)) per coordinate; otherwise
+ *     out = in[frame, v] unchanged (also when r is outside [0, n_verts)).  All members of a welded
+ *     class receive the same position, computed from their representative's input.
+ * 0 <= factor <= 1, 1 <= iterations <= 255.  Deviations from Blender's modifier: uniform ("simple")
+ * neighbour weights only; one frame per vertex from the area-weighted normal and one edge (the
+ * paper's form, not Blender's per-corner accumulation); no boundary pinning and no vertex-group mask
+ * (an open boundary shrinks under the smoothing; the stored offsets put it back).  The rest pose is
+ * NOT returned byte for byte: R (R^T d) differs from d by about 2^-53 |d|, which shows in a
+ * coordinate far smaller than the offset; tests/test_corrective_host.py holds it to a bound.
+ * Kernels (csrc/mesh_corrective.hip): one thread per (frame, vertex), vertex fastest, 256 threads,
+ * the frame in blockIdx.y; no LDS, no atomics: two runs give the same bits.  dsu_corrective_smooth
+ * launches `iterations` smoothing steps and one apply (the apply reads the neighbours' final
+ * values, so it cannot be fused into the last step).
+ * workspace_bytes: two (n_frames, n_verts, 3) f32 buffers (dsu_corrective_bind: n_frames = 1).
+ * `out` may not be the input.  DSU_EINVAL before any launch: factor or iterations out of range,
+ * n_verts or n_faces negative or above 2^30, n_frames negative or above 65535, n_frames n_verts above
+ * 2^31, n_nbr or n_cor negative or above 2^31 - 1; and, with work to do, a null pointer (nbr_cols,
+ * cor_faces and faces may be null when their count is 0), out == skinned, or a short workspace.
+ * n_verts = 0 or n_frames = 0: DSU_OK, nothing read or written.
+ * dsu_corrective_bind_host / dsu_corrective_smooth_host: HOST functions on HOST arrays (workspace
+ * included), the same text evaluated on the CPU, the same argument checks. */
+int64_t dsu_corrective_smooth_workspace_bytes(int64_t n_verts, int32_t n_frames);
+int dsu_corrective_bind(const float* rest, const int32_t* nbr_rowptr, const int32_t* nbr_cols, int64_t n_nbr,
+                        const int32_t* cor_rowptr, const int32_t* cor_faces, int64_t n_cor, const int32_t* faces,
+                        int64_t n_faces, int64_t n_verts, double factor, int32_t iterations, void* workspace,
+                        int64_t workspace_bytes, double* delta, uint8_t* valid, void* stream);
+int dsu_corrective_smooth(const float* skinned, const int32_t* rep, const int32_t* nbr_rowptr,
+                          const int32_t* nbr_cols, int64_t n_nbr, const int32_t* cor_rowptr,
+                          const int32_t* cor_faces, int64_t n_cor, const int32_t* faces, int64_t n_faces,
+                          const double* delta, const uint8_t* valid, int64_t n_verts, int32_t n_frames,
+                          double factor, int32_t iterations, void* workspace, int64_t workspace_bytes, float* out,
+                          void* stream);
+int dsu_corrective_bind_host(const float* rest, const int32_t* nbr_rowptr, const int32_t* nbr_cols, int64_t n_nbr,
+                             const int32_t* cor_rowptr, const int32_t* cor_faces, int64_t n_cor,
+                             const int32_t* faces, int64_t n_faces, int64_t n_verts, double factor,
+                             int32_t iterations, void* workspace, int64_t workspace_bytes, double* delta,
+                             uint8_t* valid);
+int dsu_corrective_smooth_host(const float* skinned, const int32_t* rep, const int32_t* nbr_rowptr,
+                               const int32_t* nbr_cols, int64_t n_nbr, const int32_t* cor_rowptr,
+                               const int32_t* cor_faces, int64_t n_cor, const int32_t* faces, int64_t n_faces,
+                               const double* delta, const uint8_t* valid, int64_t n_verts, int32_t n_frames,
+                               double factor, int32_t iterations, void* workspace, int64_t workspace_bytes,
+                               float* out);
 
 /* ------------------------------------------------------------------------------------
  * UV export (the export_uv branch of save_mesh, mesh_utils.py:65-67; coloring_utils.py:140-167;
