@@ -139,8 +139,6 @@ _PROTOS = {
                                    c_f32, c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P, P,
                                    C.POINTER(PartialReduce), P],
     "dsu_texture_partial_map": [P],
-    "dsu_texture_bwd_shaded_partials": [C.POINTER(TexMlp), P, P, P, P, P, c_i64, c_i64, P, P, P, c_i64,
-                                        C.POINTER(PartialReduce), P],
     "dsu_texture_bwd_shaded_partials_m": [C.POINTER(TexMlp), P, P, P, P, P, c_i64, c_i64, P, P, P, P, c_i64,
                                           C.POINTER(PartialReduce), P],
     "dsu_texture_fwd_shaded_m": [C.POINTER(TexMlp), P, P, c_i64, P, P, P, P],
@@ -260,7 +258,6 @@ _PROTOS = {
     "dsu_texture_fwd": [C.POINTER(TexMlp), P, c_i64, P, P],
     "dsu_texture_bwd_workspace_bytes": [c_i64],
     "dsu_texture_bwd": [C.POINTER(TexMlp), P, P, P, c_i64, P, P, P, P, P, P, P, P, c_i64, P],
-    "dsu_texture_fwd_shaded": [C.POINTER(TexMlp), P, P, c_i64, P, P, P],
     "dsu_texture_bwd_shaded": [C.POINTER(TexMlp), P, P, P, P, P, c_i64, c_i64, P, P, P, P, P, P, P, P,
                                P, c_i64, P],
     "dsu_weights_from_alpha_fwd": [P, P, P, c_i64, P, P],

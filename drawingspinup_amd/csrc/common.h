@@ -16,7 +16,7 @@
 // the compiler, which does not look inside an asm statement — the texture forward read
 // accumulators early that way (caught by test_forward_matches_reference_forward_fixture).
 __device__ __forceinline__ float dsu_relu(float x) {
-#if defined(DSU_RELU_ONE_VMAX) && !defined(DSU_RELU_FMAXF)
+#ifdef DSU_RELU_ONE_VMAX
   float r;
   asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
   return r;
@@ -54,9 +54,6 @@ static inline bool dsu_ab_is(const char*, const char*) { return false; }
 // CUs given to the whole-SIMD kernels of the NSR step (dsu_set_onewave_grid_cap, capi.hip)
 extern "C" int32_t dsu_onewave_grid_cap_value;
 // Priority of the NSR driver's side stream (dsu_set_nsr_side_stream_priority, capi.hip; nsr_driver.hip has the story)
-#ifndef DSU_NSR_SIDE_PRIO_DEFAULT
-#define DSU_NSR_SIDE_PRIO_DEFAULT 1
-#endif
 extern "C" int32_t dsu_nsr_side_priority_value;
 extern "C" int32_t dsu_nsr_side_pool_value;
 extern "C" int32_t dsu_scatter_grid_cap_value;

@@ -125,13 +125,8 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(CArgs a) {
   const bool kfast = (a.C % BK) == 0;             // every UNet/VAE layer but conv_in (C = 8)
   int st_tap = 0, st_c = 0, st_chunk = -2;
 
-#ifdef DSU_CONV_PREFETCH1
-  f16x8 ra0[RA], rb0[RB];
-  uint32_t ok0 = 0;
-#else
   f16x8 ra0[RA], rb0[RB], ra1[RA], rb1[RB];
   uint32_t ok0 = 0, ok1 = 0;
-#endif
   // Every load is issued unconditionally (rows / taps outside the problem read element 0 and are
   // zeroed when the chunk is written to LDS): with a branch per load the compiler cannot count how
   // many loads follow a given one and waits for ALL of them (vmcnt(0)) in front of the first LDS
@@ -215,19 +210,6 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(CArgs a) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
     }
   };
-#ifdef DSU_CONV_PREFETCH1
-  // (A/B variant: the round-2 pipeline — one chunk ahead)
-  load_regs(ch0, ra0, rb0, ok0);
-  store_lds(ch0 & 1, ra0, rb0, ok0);
-  __syncthreads();
-  for (int ch = ch0; ch < nchunks; ++ch) {
-    const int buf = ch & 1;
-    if (ch + 1 < nchunks) load_regs(ch + 1, ra0, rb0, ok0);
-    compute(buf);
-    if (ch + 1 < nchunks) store_lds(buf ^ 1, ra0, rb0, ok0);
-    __syncthreads();
-  }
-#else
   // Two chunks ahead: the global loads of chunk k + 2 are issued before chunk k's MFMAs and written
   // to LDS behind chunk k + 1's.  One chunk is 16 MFMAs per wave (~0.5 k clocks); one chunk ahead,
   // every iteration ended on the tail of an L2 / HBM round trip (~1-2 k clocks).  Chunk k (counted
@@ -255,7 +237,6 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(CArgs a) {
     __syncthreads();
   }
   if (k < nk) compute(0);                            // odd count: the last chunk is already in buffer 0
-#endif
 
   // epilogue: lane -> pixel (wn*32*WJ + j*32 + l31); register quad r4 -> channels
   //   o = o0 + wm*32*WI + i*32 + 8*r4 + 4*hh + {0..3}
@@ -287,16 +268,6 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(CArgs a) {
     // 1.2 ms of 13) for its split-K layers.
     __shared__ int s_ticket;
     const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-#ifdef DSU_CONV_THREADFENCE
-    // (rounds 3-5, A/B variant: a device-scope fence by every thread on both sides)
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) s_ticket = atomicAdd(&a.counters[tile], 1);
-    __syncthreads();
-    if (s_ticket != a.split_k - 1) return;
-    __threadfence();
-    if (tid == 0) a.counters[tile] = 0;             // ready for the next launch on this stream
-#else
     // publish: every wave's slab stores have left the wave (vmcnt), ONE agent-scope release (the
     // write-back of this XCD's L2 is not per wave), then the relaxed ticket; the last arriver does
     // ONE agent-scope acquire for the workgroup.  A __threadfence() per thread on both sides is the
@@ -315,7 +286,6 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(CArgs a) {
       a.counters[tile] = 0;                         // ready for the next launch on this stream
     }
     __syncthreads();
-#endif
     const int hw = a.OH * a.OW;
     for (int idx = tid; idx < TN * (TM / 4); idx += 256) {
       const int64_t p = p0 + idx / (TM / 4);

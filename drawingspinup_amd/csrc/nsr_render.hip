@@ -103,7 +103,7 @@ __global__ void ray_aabb_kernel(const float* __restrict__ ro, const float* __res
 // MODE 0: count only; 1: fill at offsets[i]; 2: single pass — fill a fixed-capacity scratch row
 // (i * cap) AND write the count, so the serial march runs once (compacted by ray_compact_kernel)
 //
-// A group of G lanes (G = 64: one wave) marches one ray.  The serial rule is one dependent
+// A group of G = MARCH_G = 64 lanes, one wave, marches one ray.  The serial rule is one dependent
 // occupancy byte load per lattice point or per skipped voxel, ~600 lattice points per ray: with one
 // ray per lane that was pure latency (355 us per launch at 8192 rays, a few us of arithmetic;
 // 115 us in this form, bound by VALU issue: profiles/march_cooperative_ab.txt).
@@ -127,51 +127,40 @@ __global__ void ray_aabb_kernel(const float* __restrict__ ro, const float* __res
 // its addition each time and is final once the lane below it is; lane 0 has no source lane and
 // keeps its value).  One VALU instruction per chain step, where a loop with a lane-dependent trip
 // count costs three and the loop control (the marcher is bound by VALU issue: 8 waves per SIMD).
-// (G = 64; the timing variants loop.)  Written as assembly because the addition must stay the one DPP instruction; the wait states a
+// Written as assembly because the addition must stay the one DPP instruction; the wait states a
 // DPP operand needs after a VALU write of its register (2) or of EXEC (5) are therefore ours.
-template <int G>
-__device__ __forceinline__ float lane_chain(float v, float dt, int gl) {
-  if constexpr (G != 64) {             // the timing variants: plain loop, lane-dependent trip count
-    for (int k = 0; k < gl; ++k) v += dt;
-  } else {
-    asm volatile("s_nop 4\n\t.rept 63\n\ts_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t.endr"
-                 : "+v"(v) : "v"(dt));
-  }
+// (Groups of 16 and 32 lanes, which looped instead, were timed and lost: profiles/march_cooperative_ab.txt.)
+constexpr int MARCH_G = 64;
+__device__ __forceinline__ float lane_chain(float v, float dt) {
+  asm volatile("s_nop 4\n\t.rept 63\n\ts_nop 1\n\t"
+               "v_add_f32_dpp %0, %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t.endr"
+               : "+v"(v) : "v"(dt));
   return v;
 }
 
 // v of the lane below; `first` in lane 0 of the group
-template <int G>
-__device__ __forceinline__ float group_prev(float v, float first, int gl) {
-  if constexpr (G != 64) {
-    const float u = __shfl_up(v, 1, 64);
-    return gl == 0 ? first : u;
-  } else {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-        __builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xf,
-        0xf, false));
-  }
+__device__ __forceinline__ float group_prev(float v, float first) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+      __builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xf,
+      0xf, false));
 }
 
-template <int G>
 __device__ __forceinline__ float group_bcast(float v, int src_lane) {
-  if (G == 64) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(
-                          __builtin_bit_cast(int, v), __builtin_amdgcn_readfirstlane(src_lane)));
-  return __shfl(v, src_lane, 64);
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(
+      __builtin_bit_cast(int, v), __builtin_amdgcn_readfirstlane(src_lane)));
 }
 
-template <int MODE, bool HAS_OCC, bool P2, int G>
+template <int MODE, bool HAS_OCC, bool P2>
 __global__ __launch_bounds__(256) void ray_march_kernel(
     const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ tmin,
     const float* __restrict__ tmax, int64_t n, Aabb a, const uint8_t* __restrict__ occ, int res,
     float step, const int32_t* __restrict__ offsets, int cap, int32_t* __restrict__ num_steps,
     int64_t* __restrict__ ray_indices, float* __restrict__ t_starts, float* __restrict__ t_ends) {
-  static_assert(G == 16 || G == 32 || G == 64, "group: a power-of-two part of a wave");
+  constexpr int G = MARCH_G;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);       // lane within the group
   const int g0 = lane - gl;            // first lane of the group
-  const uint64_t gmask = (G == 64 ? ~0ull : (1ull << (G & 63)) - 1) << g0;
+  const uint64_t gmask = ~0ull << g0;
   const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
   if (i >= n) return;                  // a whole group leaves together
   const float o[3] = {ro[i * 3], ro[i * 3 + 1], ro[i * 3 + 2]};
@@ -190,8 +179,8 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
   for (;;) {
     if (!HAS_OCC || !rejected) {
       // ---- accept window: e_0 = t0, e_1 = t1, e_{k+1} = e_k + dt
-      const float e1 = lane_chain<G>(t1, dt, gl);          // e_{b+1}
-      const float e0 = group_prev<G>(e1, t0, gl);          // e_b
+      const float e1 = lane_chain(t1, dt);          // e_{b+1}
+      const float e0 = group_prev(e1, t0);          // e_b
       const float em = gl == 0 ? tm : (e0 + e1) * 0.5f;
       const bool before_far = em < far;          // the serial loop's exit test
       bool accept = before_far;
@@ -211,18 +200,18 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
       }
       j += s;
       if (s == G) {                              // all accepted: (e_G, e_{G+1}, their midpoint)
-        t0 = group_bcast<G>(e1, g0 + G - 1);
+        t0 = group_bcast(e1, g0 + G - 1);
         t1 = t0 + dt;
         tm = (t0 + t1) * 0.5f;
         continue;
       }
       if ((past_far >> (g0 + s)) & 1) break;     // stopped by the far plane: done
-      tm = group_bcast<G>(em, g0 + s);           // rejected: it starts a reject window
+      tm = group_bcast(em, g0 + s);           // rejected: it starts a reject window
       rejected = true;
       carried = false;
     } else {
       // ---- reject window: c_0 = tm, c_k = c_{k-1} + dt
-      const float c = lane_chain<G>(tm, dt, gl);
+      const float c = lane_chain(tm, dt);
       const float p[3] = {o[0] + c * d[0], o[1] + c * d[1], o[2] + c * d[2]};
       float target = c + dist_to_next_voxel<P2>(p, d, inv, a, res);
       target = fminf(target, far);
@@ -233,18 +222,18 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
       const uint64_t landm = __ballot(lands);
       int k = 0;
       for (;;) {                                 // at most G - 1 hops: k grows with each
-        const float tk = group_bcast<G>(target, g0 + k);
+        const float tk = group_bcast(target, g0 + k);
         const uint64_t above = gmask & ~((2ull << (g0 + k)) - 1);
         const uint64_t m = __ballot(!(c < tk)) & above;
         if (!m) {                                // the skip from k leaves the window
-          tm = group_bcast<G>(c, g0 + G - 1);
+          tm = group_bcast(c, g0 + G - 1);
           carried = true;
           carried_target = tk;
           break;
         }
         k = __ffsll((unsigned long long)m) - 1 - g0;
         if ((landm >> (g0 + k)) & 1) {
-          tm = group_bcast<G>(c, g0 + k);
+          tm = group_bcast(c, g0 + k);
           t0 = tm - dt * 0.5f;
           t1 = tm + dt * 0.5f;
           rejected = false;
@@ -668,13 +657,9 @@ Aabb make_aabb(const float* a6, int res = 1) {
 
 // march kernel variant: occupancy grid present or not, power-of-two box (exact reciprocal
 // multiplies instead of IEEE divisions).  256-thread workgroups: four rays at one wave per ray.
-#ifndef DSU_MARCH_G
-#define DSU_MARCH_G 64   // lanes per ray; variant builds timed 16 and 32 (profiles/march_cooperative_ab.txt)
-#endif
-constexpr int MARCH_G = DSU_MARCH_G;
 #define DSU_MARCH_ONE(M, O, P, nr, st, ...)                                                 \
-  ray_march_kernel<M, O, P, MARCH_G><<<dsu_blocks_for(nr, 256 / MARCH_G), 256, 0,           \
-                                       (hipStream_t)st>>>(__VA_ARGS__)
+  ray_march_kernel<M, O, P><<<dsu_blocks_for(nr, 256 / MARCH_G), 256, 0,                    \
+                              (hipStream_t)st>>>(__VA_ARGS__)
 #define DSU_LAUNCH_MARCH(M, nr, st, box, occp, ...)                                   \
   do {                                                                                \
     const bool p2_ = (box).pow2 != 0;                                                 \

@@ -1,5 +1,4 @@
-// Radiance ("texture") MLP of the NeuS model, forward and backward, on the f32 matrix pipe
-// (gfx950, v_mfma_f32_32x32x2_f32).
+// Radiance ("texture") MLP of the NeuS model, forward and backward, on the matrix pipes of gfx950.
 //
 // Replaces VolumeRadiance.forward (2_charactor_reconstructor/instant_nsr/models/texture.py:9-30)
 // = VanillaMLP 16 -> 64 -> 64 -> 3 with ReLU (models/network_utils.py:94-138, no weight norm for
@@ -11,22 +10,19 @@
 //   H^T[64 hidden x 32 samples] per sample half:  lane = sample, register quad = 4 hidden units,
 // and are fed straight back as the B operand of the next layer (the k-pair of one register is
 // (unit, unit+4) across the two lane halves; the weight operand is permuted to match, exactly as
-// in hashgrid_mfma.hip).  Only the parameter-gradient GEMMs (contraction over samples = lanes)
-// go through LDS, 32 samples at a time.  Exact f32 throughout.
+// in hashgrid_mfma.hip).
+//
+// Which pipe runs what:
+//   exact f32 (v_mfma_f32_32x32x2_f32): layers 0 and 1 of the forward kernel and of the backward's
+//     recompute, with their biases as one more k-pair.  Layer 2 (3 outputs), dPre1 = W2^T dz and the
+//     bias gradients gb1 / gb2 are plain VALU arithmetic.
+//   bf16 x 3 (v_mfma_f32_32x32x16_bf16, x = hi + mid, three products: 2^-16 relative): every GEMM
+//     of the backward proper.  dH0 = W1^T dPre1 and dIn = W0^T dPre0 take the accumulator of the
+//     previous phase as the B operand as it stands and read the weights from images in LDS; the
+//     parameter-gradient GEMMs gW2, gW1, gW0 (contraction over samples = lanes) go through
+//     transposed per-wave images in LDS, 32 samples at a time.  When the forward handed over the
+//     ReLU pattern of layer 1 (L1_MASK), the recompute of layer 1 runs this way too.
 #include "common.h"
-
-// -DDSU_TEX_PROF (variant build only): per-phase shader-clock totals of the backward kernel, summed
-// over the waves into dsu_tex_prof[] and read back with dsu_debug_tex_prof() (tools/texture_phase_clocks.py)
-#ifdef DSU_TEX_PROF
-__device__ unsigned long long dsu_tex_prof[16];
-#define TEX_PROF_DECL unsigned long long pt__[16] = {0}; unsigned long long pc__ = __builtin_readcyclecounter();
-#define TEX_PROF(i) { const unsigned long long n__ = __builtin_readcyclecounter(); pt__[i] += n__ - pc__; pc__ = n__; }
-#define TEX_PROF_END if ((threadIdx.x & 63) == 0) { for (int i__ = 0; i__ < 16; ++i__) atomicAdd(&dsu_tex_prof[i__], pt__[i__]); }
-#else
-#define TEX_PROF_DECL
-#define TEX_PROF(i)
-#define TEX_PROF_END
-#endif
 
 namespace {
 
@@ -35,7 +31,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // x = hi + mid + O(2^-16 |x|), hi and mid in bf16: operands of the "bf16 x 3" products
 // a b ~ a_hi b_hi + a_hi b_mid + a_mid b_hi on v_mfma_f32_32x32x16_bf16 (16x the f32 MFMA's rate),
-// used for the two backward GEMMs whose B operand is an accumulator as it stands (see the kernel)
+// used for the backward's GEMMs (see the file header)
 __device__ __forceinline__ void bf16_split8(const float* x, bf16x8& hi, bf16x8& mid) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -46,8 +42,14 @@ __device__ __forceinline__ void bf16_split8(const float* x, bf16x8& hi, bf16x8& 
 }
 
 constexpr int TIN = 16, THID = 64, TOUT = 3;
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-// LDS layout (floats)
+// LDS map of the backward kernel, in floats (the forward kernel has the weights only):
+//   [0, L_WEND)             5 576   weights and biases in f32 (load_weights)
+//   [L_WEND, L_IMG1)   4 x 5 920   per-wave staging: the transposed bf16 images X, Y, S
+//   [L_IMG1, L_IMG0)        4 096   W1 image of dH0
+//   [L_IMG0, L_IMGF)        2 048   W0 image of dIn
+//   [L_IMGF, BWD_LDS_F)     4 096   W1 image of the recompute of layer 1 (written by L1_MASK kernels)
+//   BWD_LDS_F = 39 496 floats = 154 KB of the CU's 160: one workgroup per CU.
+// The workgroup reduction at the end of the kernel reuses [0, 4 PART_STRIDE) for four partial images.
 constexpr int W1_ROW = 65;                       // padded row: conflict-free by row AND by column
 constexpr int W0_ROW = 17;
 constexpr int L_W1 = 0;
@@ -57,14 +59,8 @@ constexpr int L_B0 = L_W2P + 2 * TOUT * 32;      // 5440
 constexpr int L_B1 = L_B0 + THID;
 constexpr int L_B2 = L_B1 + THID;                // 5568
 constexpr int L_WEND = L_B2 + 8;                 // 5576
-// per-wave staging (backward)
-constexpr int SD_ROW = 68, SIN_ROW = 20, SDO_ROW = 4;
-#ifdef DSU_TEX_GEMM_F32
-// (variant build: the contraction-over-samples GEMMs in exact f32, rounds 2-5)
-constexpr int S_P = 0, S_H = 32 * SD_ROW, S_IN = 2 * 32 * SD_ROW, S_DO = S_IN + 32 * SIN_ROW;
-constexpr int STAGE_F = S_DO + 32 * SDO_ROW;     // 5120
-#else
-// Transposed bf16 images of the contraction-over-samples GEMMs (gW2, gW1, gW0 as bf16 x 3):
+// per-wave staging (backward): transposed bf16 images of the contraction-over-samples GEMMs
+// (gW2, gW1, gW0 as bf16 x 3):
 // [part hi | mid][row = unit (or output / input column)][TROW] bf16, element (row, s) = the value of
 // sample s of the 32-sample half.  TROW = 40 (80-byte rows): the 16-byte fragments of 16 lanes
 // (rows l31, l31 + 1, ...) fall on 16 different bank quads.  Two 64-row images (X, Y) and one
@@ -74,8 +70,6 @@ constexpr int TIMG_B = 2 * 64 * TROW;            // bf16 elements of a 64-row im
 constexpr int TSML_B = 2 * 20 * TROW;            // 20-row image
 constexpr int S_X = 0, S_Y = TIMG_B / 2, S_S = TIMG_B;          // float offsets
 constexpr int STAGE_F = TIMG_B + TSML_B / 2;     // 5120 + 800 = 5920 floats
-constexpr int S_P = 0, S_H = 0, S_IN = 0, S_DO = 0;              // (f32 staging areas: unused)
-#endif
 // bf16 images of the backward GEMMs' weight operands, one 16-byte fragment per lane and MFMA:
 //   W1 image [hi|mid][To][Tin][g][lane] : 8 values t -> w1[feat_of(Tin, 8 g + t, h)][32 To + l31]
 //   W0 image [hi|mid][T][g][lane]       : 8 values t -> w0[feat_of(T, 8 g + t, h)][l31] (0 for l31 >= 16)
@@ -85,14 +79,11 @@ constexpr int L_IMG0 = L_IMG1 + IMG1_F;
 //   W1 image of the backward's forward RECOMPUTE (L1_MASK kernels) [hi|mid][To][Tin][g][lane] :
 //   8 values t -> w1[32 To + l31][feat_of(Tin, 8 g + t, h)]
 constexpr int L_IMGF = L_IMG0 + IMG0_F;
-constexpr int BWD_LDS_F = L_IMGF + IMG1_F;       // 5576 + 4 x 5920 + 6144 + 4096 floats = 154 KB
+constexpr int BWD_LDS_F = L_IMGF + IMG1_F;       // 39 496 floats = 154 KB
 // per-workgroup partial vector
 constexpr int P_GW1 = 0, P_GW0 = 64 * 64, P_GW2 = P_GW0 + 64 * 32, P_GB1 = P_GW2 + 64 * 32,
               P_GB2 = P_GB1 + 64, PART_N = P_GB2 + 3, PART_STRIDE = 8320;
-#ifndef DSU_TEX_MAX_BLOCKS
-#define DSU_TEX_MAX_BLOCKS 256
-#endif
-constexpr int TEX_MAX_BLOCKS = DSU_TEX_MAX_BLOCKS;
+constexpr int TEX_MAX_BLOCKS = 256;
 
 __device__ __forceinline__ int feat_of(int T, int r, int h) {
   return 32 * T + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -332,10 +323,6 @@ __global__ __launch_bounds__(256) void texture_fwd_kernel(dsu_tex_mlp m,
   }
 }
 
-// SHADE (backward): the gradient of the input row is not stored as (n,16) but pulled back through
-// cat / normalize right here (what shade_prep_bwd_kernel did in a separate launch):
-//   d_feature[s] = d_x[0:13];  dn = d_x[13:16] + d_normal[s];  d_grad[s] = (dn - n (n.dn)) / |grad|
-#ifndef DSU_TEX_GEMM_F32
 // rows = hidden units: the lane's 32 values X[T][r] (unit 32 T + (r & 3) + 8 (r >> 2) + 4 h of the
 // sample in column l31) -> bf16 hi / mid at [unit][l31] of a transposed image
 __device__ __forceinline__ void stage_units_T(__bf16* img, const f32x16 (&X)[2], int l31, int h) {
@@ -391,8 +378,10 @@ __device__ __forceinline__ void gemm_samples_T(f32x16 (&acc0)[NJ], f32x16 (&acc1
     }
   }
 }
-#endif
 
+// SHADE (backward): the gradient of the input row is not stored as (n,16) but pulled back through
+// cat / normalize right here (what shade_prep_bwd_kernel did in a separate launch):
+//   d_feature[s] = d_x[0:13];  dn = d_x[13:16] + d_normal[s];  d_grad[s] = (dn - n (n.dn)) / |grad|
 struct ShadeOut {
   const float* d_normal;  // (n,3) from the compositing backward
   float* d_grad;          // (n,3)
@@ -407,18 +396,11 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
     float* __restrict__ d_x, float* __restrict__ partials,
     const uint32_t* __restrict__ h1_mask = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  TEX_PROF_DECL
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
   float* st = lds + L_WEND + wave * STAGE_F;
-  float* sP = st + S_P;
-  float* sH = st + S_H;
-  float* sIn = st + S_IN;
-  float* sDo = st + S_DO;
-#ifndef DSU_TEX_GEMM_F32
   __bf16* tX = reinterpret_cast<__bf16*>(st + S_X);
   __bf16* tY = reinterpret_cast<__bf16*>(st + S_Y);
   __bf16* tS = reinterpret_cast<__bf16*>(st + S_S);
-#endif
   load_weights(lds, m);
   __syncthreads();
   {   // bf16 hi / mid fragments of W1 and W0 in the order the backward MFMAs consume them
@@ -460,11 +442,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
       so.d_feature[n * 13 + t] = 0.0f;
   }
   f32x16 gw1[2][2], gw0[2], gw2[2];     // D[i = row unit][j]: W1[i][j], W0[i][k | bias], W2^T[i][o]
-#ifdef DSU_TEX_GEMM_F32
-  float gb1[2][16];
-#else
   float gb1row = 0.0f;                 // gb1[unit = lane]: row sums of the transposed dPre1 image (see gW1)
-#endif
   float gb2[TOUT] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int T = 0; T < 2; ++T)
@@ -472,9 +450,6 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
     for (int r = 0; r < 16; ++r) {
       gw1[T][0][r] = gw1[T][1][r] = 0.0f;
       gw0[T][r] = gw2[T][r] = 0.0f;
-#ifdef DSU_TEX_GEMM_F32
-      gb1[T][r] = 0.0f;
-#endif
     }
 
   const int64_t per = ((n + gridDim.x - 1) / gridDim.x + 31) / 32 * 32;   // see texture_fwd_kernel
@@ -486,7 +461,6 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
     const int64_t ii = valid ? i : r1 - 1;
     const int64_t wave_first = base + wave * 64;
     if (wave_first >= r1) continue;                    // wave-uniform, no workgroup barrier in the loop
-    TEX_PROF(9)   // (first block: kernel prologue; later: loop overhead)
     float in[TIN];
     if (SHADE) {
       float inv_len;
@@ -518,7 +492,6 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
 #pragma unroll 1
     for (int a = 0; a < 2; ++a) {
       if (wave_first + a * 32 >= r1) continue;
-      TEX_PROF(0)   // rows of the block / previous half's tail
       f32x16 H0[2], H1[2];
       forward_half<L1_MASK>(lds, in, a, l31, h, H0, H1);
       const uint32_t mk = a ? mk2[1] : mk2[0];
@@ -531,7 +504,6 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
           for (int r = 0; r < 16; ++r) H1[T][r] = ((mk >> (16 * T + r)) & 1u) ? H1[T][r] : 0.0f;
       }
       // dz of the samples of half a, in every lane of the pair
-      TEX_PROF(1)   // forward recompute
       float dza[TOUT];
 #pragma unroll
       for (int o = 0; o < TOUT; ++o) {
@@ -549,49 +521,8 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
           for (int o = 0; o < TOUT; ++o)
             v = fmaf(lds[L_W2P + (h * TOUT + o) * 32 + T * 16 + r], dza[o], v);
           D1[T][r] = (L1_MASK ? ((mk >> (16 * T + r)) & 1u) != 0u : H1[T][r] > 0.0f) ? v : 0.0f;
-#ifdef DSU_TEX_GEMM_F32
-          gb1[T][r] += D1[T][r];
-#endif
         }
-      TEX_PROF(2)   // dPre1
       // ---- gW2^T[unit][o] += sum_samples H1[sample][unit] * dz[sample][o]
-#ifdef DSU_TEX_GEMM_F32
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int T = 0; T < 2; ++T)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd)
-          *reinterpret_cast<float4*>(&sH[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
-              make_float4(H1[T][4 * qd], H1[T][4 * qd + 1], H1[T][4 * qd + 2], H1[T][4 * qd + 3]);
-      if (h == a)
-        *reinterpret_cast<float4*>(&sDo[l31 * SDO_ROW]) = make_float4(dz[0], dz[1], dz[2], 0.0f);
-      __builtin_amdgcn_wave_barrier();
-      {   // operands of the next four k-pairs in flight while the current eight MFMAs run
-        float q[2][12];
-        const int lo = l31 < SDO_ROW ? l31 : 0;
-        auto ld = [&](int tb, float* d) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int pr = 2 * (4 * tb + u) + h;
-            const float b = sDo[pr * SDO_ROW + lo];
-            d[3 * u + 0] = sH[pr * SD_ROW + l31];
-            d[3 * u + 1] = sH[pr * SD_ROW + 32 + l31];
-            d[3 * u + 2] = l31 < SDO_ROW ? b : 0.0f;
-          }
-        };
-        ld(0, q[0]);
-#pragma unroll
-        for (int tb = 0; tb < 4; ++tb) {
-          if (tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float* d = q[tb & 1] + 3 * u;
-            gw2[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], gw2[0], 0, 0, 0);
-            gw2[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], gw2[1], 0, 0, 0);
-          }
-        }
-      }
-#else
       // bf16 x 3 on v_mfma_f32_32x32x16_bf16 (K = 16 samples per MFMA): H1 and dz go to LDS
       // TRANSPOSED ([unit][sample], bf16 hi / mid, two-byte stores at compile-time offsets), so that
       // a lane's operand fragment — 8 consecutive samples of one row — is one 16-byte read.
@@ -612,48 +543,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
         f32x16 (&g1)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw2[1]);
         gemm_samples_T<1>(g0, g1, tX, 64 * TROW, tS, 20 * TROW, TOUT, l31, h);
       }
-#endif
       // ---- gW1[i][j] += sum_samples dPre1[sample][i] * H0[sample][j]
-      TEX_PROF(3)   // gW2
-#ifdef DSU_TEX_GEMM_F32
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int T = 0; T < 2; ++T)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          *reinterpret_cast<float4*>(&sP[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
-              make_float4(D1[T][4 * qd], D1[T][4 * qd + 1], D1[T][4 * qd + 2], D1[T][4 * qd + 3]);
-          *reinterpret_cast<float4*>(&sH[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
-              make_float4(H0[T][4 * qd], H0[T][4 * qd + 1], H0[T][4 * qd + 2], H0[T][4 * qd + 3]);
-        }
-      __builtin_amdgcn_wave_barrier();
-      {
-        float q[2][8];
-        auto ld = [&](int tb, float* d) {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int pr = 2 * (2 * tb + u) + h;
-            d[4 * u + 0] = sP[pr * SD_ROW + l31];
-            d[4 * u + 1] = sP[pr * SD_ROW + 32 + l31];
-            d[4 * u + 2] = sH[pr * SD_ROW + l31];
-            d[4 * u + 3] = sH[pr * SD_ROW + 32 + l31];
-          }
-        };
-        ld(0, q[0]);
-#pragma unroll
-        for (int tb = 0; tb < 8; ++tb) {
-          if (tb + 1 < 8) ld(tb + 1, q[(tb + 1) & 1]);
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const float* d = q[tb & 1] + 4 * u;
-            gw1[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], gw1[0][0], 0, 0, 0);
-            gw1[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[3], gw1[0][1], 0, 0, 0);
-            gw1[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], gw1[1][0], 0, 0, 0);
-            gw1[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[3], gw1[1][1], 0, 0, 0);
-          }
-        }
-      }
-#else
       __builtin_amdgcn_wave_barrier();           // (the gW2 reads of X are done: in-order LDS queue of the wave)
       stage_units_T(tY, D1, l31, h);
       stage_units_T(tX, H0, l31, h);
@@ -672,39 +562,12 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
         gb1row += srow;
       }
       gemm_samples_T<2>(gw1[0], gw1[1], tY, 64 * TROW, tX, 64 * TROW, 64, l31, h);   // 24 MFMAs instead of 64
-#endif
       // ---- dH0^T = W1^T . dPre1^T, then dPre0 = dH0 * relu'(H0)
-      TEX_PROF(4)   // gW1
       f32x16 D0[2];
 #pragma unroll
       for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int r = 0; r < 16; ++r) D0[T][r] = 0.0f;
-#ifdef DSU_TEX_F32
-      {   // weight operands one batch of four k-pairs ahead of their MFMAs (see forward_half)
-        float a[2][8];
-        auto load = [&](int s_, float* dst) {
-          const int T = s_ >> 2, rq = s_ & 3;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int k = feat_of(T, 4 * rq + j, h);
-            dst[2 * j + 0] = lds[L_W1 + k * W1_ROW + l31];
-            dst[2 * j + 1] = lds[L_W1 + k * W1_ROW + 32 + l31];
-          }
-        };
-        load(0, a[0]);
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-          if (s_ + 1 < 8) load(s_ + 1, a[(s_ + 1) & 1]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float b = D1[s_ >> 2][4 * (s_ & 3) + j];
-            D0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][2 * j + 0], b, D0[0], 0, 0, 0);
-            D0[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][2 * j + 1], b, D0[1], 0, 0, 0);
-          }
-        }
-      }
-#else
       {   // on the bf16 matrix pipe (bf16 x 3): registers 8 g + t of a lane's dPre1 accumulator hold
           // units feat_of(Tin, 8 g + t, h) of ITS sample — the B operand of one
           // v_mfma_f32_32x32x16_bf16 as they stand; the A fragment is W1 in the same order (image
@@ -733,55 +596,11 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
               D0[To] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh[Tin][g], D0[To], 0, 0, 0);
             }
       }
-#endif
 #pragma unroll
       for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int r = 0; r < 16; ++r) D0[T][r] = H0[T][r] > 0.0f ? D0[T][r] : 0.0f;
       // ---- gW0[i][k] += sum_samples dPre0[sample][i] * In[sample][k]  (k = 16: ones -> gb0)
-      TEX_PROF(5)   // dH0 + relu'
-#ifdef DSU_TEX_GEMM_F32
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int T = 0; T < 2; ++T)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd)
-          *reinterpret_cast<float4*>(&sP[l31 * SD_ROW + 32 * T + 8 * qd + 4 * h]) =
-              make_float4(D0[T][4 * qd], D0[T][4 * qd + 1], D0[T][4 * qd + 2], D0[T][4 * qd + 3]);
-      if (h == a) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<float4*>(&sIn[l31 * SIN_ROW + 4 * q]) =
-              make_float4(in[4 * q], in[4 * q + 1], in[4 * q + 2], in[4 * q + 3]);
-        sIn[l31 * SIN_ROW + 16] = 1.0f;
-      }
-      __builtin_amdgcn_wave_barrier();
-      {
-        float q[2][12];
-        const int li = l31 <= TIN ? l31 : 0;
-        auto ld = [&](int tb, float* d) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int pr = 2 * (4 * tb + u) + h;
-            const float b = sIn[pr * SIN_ROW + li];
-            d[3 * u + 0] = sP[pr * SD_ROW + l31];
-            d[3 * u + 1] = sP[pr * SD_ROW + 32 + l31];
-            d[3 * u + 2] = l31 <= TIN ? b : 0.0f;
-          }
-        };
-        ld(0, q[0]);
-#pragma unroll
-        for (int tb = 0; tb < 4; ++tb) {
-          if (tb + 1 < 4) ld(tb + 1, q[(tb + 1) & 1]);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float* d = q[tb & 1] + 3 * u;
-            gw0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[0], d[2], gw0[0], 0, 0, 0);
-            gw0[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[1], d[2], gw0[1], 0, 0, 0);
-          }
-        }
-      }
-#else
       __builtin_amdgcn_wave_barrier();
       stage_units_T(tY, D0, l31, h);
       if (h == a) {
@@ -800,59 +619,10 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
         f32x16 (&g1)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw0[1]);
         gemm_samples_T<1>(g0, g1, tY, 64 * TROW, tS, 20 * TROW, TIN + 1, l31, h);   // 12 MFMAs instead of 32
       }
-#endif
       // ---- dIn^T = W0^T . dPre0^T : row k = (r&3) + 8(r>>2) + 4h of the sample in column l31
-      TEX_PROF(6)   // gW0
       f32x16 din;
 #pragma unroll
       for (int r = 0; r < 16; ++r) din[r] = 0.0f;
-#ifdef DSU_TEX_F32
-      {   // same batching for the 32 weight operands of dIn
-        float a[2][8];
-        const int lc = l31 < TIN ? l31 : 0;
-        auto load = [&](int s_, float* dst) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int T = s_ >> 1, r = 8 * (s_ & 1) + j;
-            const float w = lds[L_W0 + feat_of(T, r, h) * W0_ROW + lc];
-            dst[j] = l31 < TIN ? w : 0.0f;
-          }
-        };
-        load(0, a[0]);
-#ifdef DSU_TEX_DIN_2ACC
-        // Staged variant (not measured yet): two alternating accumulators, so that the LDS reads of
-        // the next batch sit between MFMAs on DIFFERENT accumulators (MI355X_MICROARCH.md: an
-        // issue slot between two MFMAs on the same accumulator costs +43 cycles); summed at the end.
-        f32x16 din_b;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) din_b[r] = 0.0f;
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-          if (s_ + 1 < 4) load(s_ + 1, a[(s_ + 1) & 1]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (j & 1)
-              din_b = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][j], D0[s_ >> 1][8 * (s_ & 1) + j],
-                                                          din_b, 0, 0, 0);
-            else
-              din = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][j], D0[s_ >> 1][8 * (s_ & 1) + j],
-                                                        din, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) din[r] += din_b[r];
-#else
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-          if (s_ + 1 < 4) load(s_ + 1, a[(s_ + 1) & 1]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            din = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][j], D0[s_ >> 1][8 * (s_ & 1) + j],
-                                                      din, 0, 0, 0);
-        }
-#endif
-      }
-#else
       {   // bf16 x 3 as above: 2 x 2 x 3 = 12 MFMAs instead of 32
         const bf16x8* img0 = reinterpret_cast<const bf16x8*>(lds + L_IMG0);
 #pragma unroll
@@ -871,9 +641,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
             din = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, din, 0, 0, 0);
           }
       }
-#endif
       const int64_t si = wave_first + a * 32 + l31;              // the sample of column l31
-      TEX_PROF(7)   // dIn
       if (si < r1) {
         if (SHADE) {
           // lane h holds components 8q + 4h + {0..3}: h = 0 -> 0-3, 8-11; h = 1 -> 4-7, 12-15
@@ -906,36 +674,18 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
                 make_float4(din[4 * q], din[4 * q + 1], din[4 * q + 2], din[4 * q + 3]);
         }
       }
-      TEX_PROF(11)  // write-out of the half (sdf gradient / d_normal loads + stores)
     }
   }
 
   // ---- workgroup reduction of the parameter-gradient tiles -> one partial vector per workgroup.
-  // Plain stores into per-wave images, one barrier, element-wise sums by all threads.  The first form added all four waves' tiles into ONE image with LDS float
-  // atomics (160 per lane, every address hit by all four waves): 112 k of the kernel's 332 k clocks
-  // per wave (phase clocks, profiles/round6_texture_phase_clocks.txt).  The whole LDS is free here.
+  // Every wave stores its tiles into an image of its own, one barrier, then all 256 threads sum the
+  // four images element by element (fixed order) and write the partial vector.  The first form added
+  // all four waves' tiles into ONE image with LDS float atomics (160 per lane, every address hit by
+  // all four waves): 112 k of the kernel's 332 k clocks per wave (phase clocks,
+  // profiles/round6_texture_phase_clocks.txt).  The whole LDS is free here.
   __syncthreads();
-  TEX_PROF(8)   // last epilogue stores + wait for the other waves
-#if defined(DSU_TEX_ABL_RED) && DSU_TEX_ABL_RED == 1
-  // (timing ablation, variant build: no reduction at all — one value per lane keeps the accumulators alive)
-  partials[(size_t)blockIdx.x * PART_STRIDE + threadIdx.x] =
-      gw1[0][0][0] + gw1[0][1][1] + gw1[1][0][2] + gw1[1][1][3] + gw0[0][4] + gw0[1][5] + gw2[0][6] + gw2[1][7] + gb2[0];
-  return;
-#endif
-  static_assert(3 * PART_STRIDE <= BWD_LDS_F, "three partial images fit the kernel's LDS");
+  static_assert(4 * PART_STRIDE <= BWD_LDS_F, "four partial images fit the kernel's LDS");
   float gb2s[TOUT];
-#ifdef DSU_TEX_GEMM_F32
-  float gb1s[2][16];
-#pragma unroll
-  for (int T = 0; T < 2; ++T)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float s_ = gb1[T][r];                         // sum over the 32 sample columns of this half
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) s_ += __shfl_xor(s_, o);
-      gb1s[T][r] = s_;
-    }
-#endif
 #pragma unroll
   for (int o = 0; o < TOUT; ++o) {
     float s_ = gb2[o];
@@ -953,60 +703,18 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
         dst[P_GW1 + row * 64 + 32 + l31] = gw1[T][1][r];
         dst[P_GW0 + row * 32 + l31] = gw0[T][r];
         dst[P_GW2 + row * 32 + l31] = gw2[T][r];
-#ifdef DSU_TEX_GEMM_F32
-        if (l31 == 0) dst[P_GB1 + row] = gb1s[T][r];
-#endif
       }
-#ifndef DSU_TEX_GEMM_F32
     dst[P_GB1 + lane] = gb1row;
-#endif
     if (lane == 0) {
 #pragma unroll
       for (int o = 0; o < TOUT; ++o) dst[P_GB2 + o] = gb2s[o];
     }
   };
-  auto add_from = [&](const float* src) {
-#pragma unroll
-    for (int T = 0; T < 2; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = feat_of(T, r, h);
-        gw1[T][0][r] += src[P_GW1 + row * 64 + l31];
-        gw1[T][1][r] += src[P_GW1 + row * 64 + 32 + l31];
-        gw0[T][r] += src[P_GW0 + row * 32 + l31];
-        gw2[T][r] += src[P_GW2 + row * 32 + l31];
-#ifdef DSU_TEX_GEMM_F32
-        gb1s[T][r] += src[P_GB1 + row];
-#endif
-      }
-#ifndef DSU_TEX_GEMM_F32
-    gb1row += src[P_GB1 + lane];
-#endif
-#pragma unroll
-    for (int o = 0; o < TOUT; ++o) gb2s[o] += src[P_GB2 + o];
-  };
-  if constexpr (4 * PART_STRIDE <= BWD_LDS_F) {
-    // every wave's image, one barrier, then all 256 threads sum the four images element by element
-    // (fixed order) and write the partial vector
-    store_own(lds + wave * PART_STRIDE);
-    __syncthreads();
-    float* part = partials + (size_t)blockIdx.x * PART_STRIDE;
-    for (int v = threadIdx.x; v < PART_N; v += blockDim.x)
-      part[v] = (lds[v] + lds[PART_STRIDE + v]) + (lds[2 * PART_STRIDE + v] + lds[3 * PART_STRIDE + v]);
-  } else {
-    // (exact-f32 GEMM variant: three images fit) waves 2, 3 -> 0, 1; wave 1 -> 0; wave 0 writes
-    if (wave >= 2) store_own(lds + (wave - 2) * PART_STRIDE);
-    __syncthreads();
-    if (wave < 2) add_from(lds + wave * PART_STRIDE);
-    if (wave == 1) store_own(lds + 2 * PART_STRIDE);
-    __syncthreads();
-    if (wave == 0) {
-      add_from(lds + 2 * PART_STRIDE);
-      store_own(partials + (size_t)blockIdx.x * PART_STRIDE);
-    }
-  }
-  TEX_PROF(10)  // workgroup reduction
-  TEX_PROF_END
+  store_own(lds + wave * PART_STRIDE);
+  __syncthreads();
+  float* part = partials + (size_t)blockIdx.x * PART_STRIDE;
+  for (int v = threadIdx.x; v < PART_N; v += blockDim.x)
+    part[v] = (lds[v] + lds[PART_STRIDE + v]) + (lds[2 * PART_STRIDE + v] + lds[3 * PART_STRIDE + v]);
 }
 
 __global__ void texture_reduce_kernel(const float* __restrict__ partials, int nblocks,
@@ -1047,6 +755,29 @@ bool mlp_ok(const dsu_tex_mlp* m) {
   return m && m->w0 && m->b0 && m->w1 && m->b1 && m->w2 && m->b2;
 }
 
+// One launch of texture_bwd_kernel<SHADE, L1_MASK> for n > 0 validated samples: workspace check, one
+// workgroup per CU it is given, the whole dynamic LDS.  A template and not a run-time branch:
+// DSU_ENSURE_DYN_LDS keeps its high-water mark per expansion, i.e. per kernel instantiation.
+// The caller checks the launch; *blocks is the number of partial vectors left in the workspace.
+template <bool SHADE, bool L1_MASK>
+int launch_bwd(const dsu_tex_mlp* mlp, const float* x, ShadeIn sh, ShadeOut so, const float* rgb,
+               const float* d_rgb, int64_t n, float* d_x, const uint32_t* h1_mask, void* workspace,
+               int64_t workspace_bytes, hipStream_t s, int* blocks) {
+  if (!workspace || workspace_bytes < dsu_texture_bwd_workspace_bytes(n)) return DSU_EINVAL;
+  *blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
+  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
+  DSU_ENSURE_DYN_LDS((texture_bwd_kernel<SHADE, L1_MASK>), shm);
+  texture_bwd_kernel<SHADE, L1_MASK><<<*blocks, 256, shm, s>>>(*mlp, x, sh, so, rgb, d_rgb, n, d_x,
+                                                              (float*)workspace, h1_mask);
+  return DSU_OK;
+}
+
+void launch_reduce(const void* workspace, int blocks, float* g_w0, float* g_b0, float* g_w1,
+                   float* g_b1, float* g_w2, float* g_b2, hipStream_t s) {
+  texture_reduce_kernel<<<(PART_N + 63) / 64, 1024, 0, s>>>((const float*)workspace, blocks, g_w0,
+                                                           g_b0, g_w1, g_b1, g_w2, g_b2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1071,11 +802,6 @@ int dsu_texture_fwd_shaded_m(const dsu_tex_mlp* mlp, const float* feature, const
   return DSU_OK;
 }
 
-int dsu_texture_fwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                           int64_t n, float* normal, float* rgb, void* stream) {
-  return dsu_texture_fwd_shaded_m(mlp, feature, grad, n, normal, rgb, nullptr, stream);
-}
-
 int64_t dsu_texture_bwd_workspace_bytes(int64_t n) {
   if (n < 0) return DSU_EINVAL;
   return (int64_t)dsu_capped_blocks(n, 256, TEX_MAX_BLOCKS) * PART_STRIDE * sizeof(float);
@@ -1089,18 +815,12 @@ int dsu_texture_bwd(const dsu_tex_mlp* mlp, const float* tex_in, const float* rg
   if (!g_w0 || !g_b0 || !g_w1 || !g_b1 || !g_w2 || !g_b2) return DSU_EINVAL;
   if (n && (!tex_in || !rgb || !d_rgb || !d_tex_in)) return DSU_EINVAL;
   if (n == 0) return DSU_OK;
-  const int64_t need = dsu_texture_bwd_workspace_bytes(n);
-  if (!workspace || workspace_bytes < need) return DSU_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
-  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
-  static_assert(PART_N <= 4 * STAGE_F, "reduction buffer must fit the staging area");
-  DSU_ENSURE_DYN_LDS(texture_bwd_kernel<false>, shm);
-  texture_bwd_kernel<false><<<blocks, 256, shm, s>>>(*mlp, tex_in, ShadeIn{nullptr, nullptr},
-                                                    ShadeOut{nullptr, nullptr, nullptr, 0}, rgb, d_rgb,
-                                                    n, d_tex_in, (float*)workspace);
-  texture_reduce_kernel<<<(PART_N + 63) / 64, 1024, 0, s>>>((const float*)workspace, blocks, g_w0,
-                                                           g_b0, g_w1, g_b1, g_w2, g_b2);
+  int blocks;
+  const int rc = launch_bwd<false, false>(mlp, tex_in, ShadeIn{nullptr, nullptr},
+                                          ShadeOut{nullptr, nullptr, nullptr, 0}, rgb, d_rgb, n, d_tex_in,
+                                          nullptr, workspace, workspace_bytes, (hipStream_t)stream, &blocks);
+  if (rc != DSU_OK) return rc;
+  launch_reduce(workspace, blocks, g_w0, g_b0, g_w1, g_b1, g_w2, g_b2, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
@@ -1116,17 +836,13 @@ int dsu_texture_bwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const f
   if (tail_rows < 0 || (n && (!feature || !grad || !rgb || !d_rgb || !d_grad || !d_feature)))
     return DSU_EINVAL;
   if (n == 0) return DSU_EUNSUP;                    // the caller zeroes the tail itself
-  const int64_t need = dsu_texture_bwd_workspace_bytes(n);
-  if (!workspace || workspace_bytes < need) return DSU_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
-  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
-  DSU_ENSURE_DYN_LDS(texture_bwd_kernel<true>, shm);
-  texture_bwd_kernel<true><<<blocks, 256, shm, s>>>(*mlp, nullptr, ShadeIn{feature, grad},
-                                                   ShadeOut{d_normal, d_grad, d_feature, tail_rows}, rgb, d_rgb,
-                                                   n, nullptr, (float*)workspace);
-  texture_reduce_kernel<<<(PART_N + 63) / 64, 1024, 0, s>>>((const float*)workspace, blocks, g_w0,
-                                                           g_b0, g_w1, g_b1, g_w2, g_b2);
+  int blocks;
+  const int rc = launch_bwd<true, false>(mlp, nullptr, ShadeIn{feature, grad},
+                                         ShadeOut{d_normal, d_grad, d_feature, tail_rows}, rgb, d_rgb, n,
+                                         nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream,
+                                         &blocks);
+  if (rc != DSU_OK) return rc;
+  launch_reduce(workspace, blocks, g_w0, g_b0, g_w1, g_b1, g_w2, g_b2, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
@@ -1158,15 +874,6 @@ int32_t dsu_texture_partial_map(int32_t* map_host) {
   return PART_N;
 }
 
-int dsu_texture_bwd_shaded_partials(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                                    const float* rgb, const float* d_rgb, const float* d_normal,
-                                    int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
-                                    void* workspace, int64_t workspace_bytes,
-                                    dsu_partial_reduce* red, void* stream) {
-  return dsu_texture_bwd_shaded_partials_m(mlp, feature, grad, rgb, d_rgb, d_normal, n, tail_rows, d_grad,
-                                           d_feature, nullptr, workspace, workspace_bytes, red, stream);
-}
-
 int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
                                       const float* rgb, const float* d_rgb, const float* d_normal,
                                       int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
@@ -1176,22 +883,14 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
   if (tail_rows < 0 || (n && (!feature || !grad || !rgb || !d_rgb || !d_grad || !d_feature)))
     return DSU_EINVAL;
   if (n == 0) return DSU_EUNSUP;                    // the caller zeroes the tail itself
-  const int64_t need = dsu_texture_bwd_workspace_bytes(n);
-  if (!workspace || workspace_bytes < need) return DSU_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
-  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
-  if (h1_mask) {
-    DSU_ENSURE_DYN_LDS((texture_bwd_kernel<true, true>), shm);
-    texture_bwd_kernel<true, true><<<blocks, 256, shm, s>>>(*mlp, nullptr, ShadeIn{feature, grad},
-                                                           ShadeOut{d_normal, d_grad, d_feature, tail_rows}, rgb,
-                                                           d_rgb, n, nullptr, (float*)workspace, h1_mask);
-  } else {
-    DSU_ENSURE_DYN_LDS(texture_bwd_kernel<true>, shm);
-    texture_bwd_kernel<true><<<blocks, 256, shm, s>>>(*mlp, nullptr, ShadeIn{feature, grad},
-                                                     ShadeOut{d_normal, d_grad, d_feature, tail_rows}, rgb, d_rgb,
-                                                     n, nullptr, (float*)workspace);
-  }
+  const ShadeIn sh{feature, grad};
+  const ShadeOut so{d_normal, d_grad, d_feature, tail_rows};
+  int blocks;
+  const int rc = h1_mask ? launch_bwd<true, true>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, h1_mask,
+                                                  workspace, workspace_bytes, (hipStream_t)stream, &blocks)
+                         : launch_bwd<true, false>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, nullptr,
+                                                   workspace, workspace_bytes, (hipStream_t)stream, &blocks);
+  if (rc != DSU_OK) return rc;
   DSU_CHECK_LAUNCH();
   red->partials = (const float*)workspace;
   red->nblocks = blocks;
@@ -1199,17 +898,5 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
   red->n = PART_N;
   return DSU_OK;
 }
-
-#ifdef DSU_TEX_PROF
-int dsu_debug_tex_prof(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(dsu_tex_prof), 16 * sizeof(unsigned long long)) != hipSuccess)
-    return DSU_ELAUNCH;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(dsu_tex_prof), z, sizeof(z)) != hipSuccess) return DSU_ELAUNCH;
-  }
-  return DSU_OK;
-}
-#endif
 
 }  // extern "C"

@@ -594,14 +594,10 @@ def texture_fwd_shaded(params, feature, grad, with_mask=False):
     normal = torch.empty((n, 3), dtype=torch.float32, device=feature.device)
     rgb = torch.empty((n, 3), dtype=torch.float32, device=feature.device)
     m = _tex_struct(params)
-    if with_mask:
-        mask = torch.empty((n, 2), dtype=torch.int32, device=feature.device)
-        check(lib().dsu_texture_fwd_shaded_m(C.byref(m), ptr(feature), ptr(grad), n, ptr(normal), ptr(rgb),
-                                             ptr(mask), stream()), "dsu_texture_fwd_shaded_m")
-        return normal, rgb, mask
-    check(lib().dsu_texture_fwd_shaded(C.byref(m), ptr(feature), ptr(grad), n, ptr(normal), ptr(rgb),
-                                       stream()), "dsu_texture_fwd_shaded")
-    return normal, rgb
+    mask = torch.empty((n, 2), dtype=torch.int32, device=feature.device) if with_mask else None
+    check(lib().dsu_texture_fwd_shaded_m(C.byref(m), ptr(feature), ptr(grad), n, ptr(normal), ptr(rgb),
+                                         ptr(mask), stream()), "dsu_texture_fwd_shaded_m")
+    return (normal, rgb, mask) if with_mask else (normal, rgb)
 
 
 def texture_bwd_shaded(params, feature, grad, rgb, d_rgb, d_normal, tail_rows=0):

@@ -232,7 +232,7 @@ int dsu_sdf_fd_bwd_sorted_mid(const dsu_hashgrid_cfg* cfg, const void* table_f16
 
 /* dsu_sdf_fd_bwd_sorted_mid whose scatter launch also carries out `extra` (may be NULL), a deferred
  * partial sum of ANOTHER kernel that precedes this call on `stream` (the native NSR step passes the
- * texture backward's: dsu_texture_bwd_shaded_partials).  The backward's own partial sums always
+ * texture backward's: dsu_texture_bwd_shaded_partials_m).  The backward's own partial sums always
  * ride in that launch.  DSU_EUNSUP with `extra` on the fused / VALU variants. */
 int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f16,
                                const dsu_sdf_mlp* mlp, const float* pts_sorted, const int32_t* perm,
@@ -426,9 +426,11 @@ int dsu_texture_bwd(const dsu_tex_mlp* mlp, const float* tex_in, const float* rg
  * the compositing kernels), and the backward pulls the row's gradient back through cat / normalize
  * itself: d_feature (n + tail_rows, 13) (the tail rows zeroed), d_grad (n,3) =
  * (dn - n (n.dn)) / |sdf_grad| with dn = d_row[13:16] + d_normal (d_normal may be NULL).  Replaces
- * dsu_shade_prep_fwd + dsu_texture_fwd and dsu_texture_bwd + dsu_shade_prep_bwd. */
-int dsu_texture_fwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                           int64_t n, float* normal, float* rgb, void* stream);
+ * dsu_shade_prep_fwd + dsu_texture_fwd and dsu_texture_bwd + dsu_shade_prep_bwd.
+ * h1_mask (may be NULL): the forward also writes the ReLU pattern of hidden layer 1, (n, 2) uint32,
+ * word h of a sample = its hidden units 32 T + (r & 3) + 8 (r >> 2) + 4 h, bit 16 T + r. */
+int dsu_texture_fwd_shaded_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
+                             int64_t n, float* normal, float* rgb, uint32_t* h1_mask, void* stream);
 int dsu_texture_bwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
                            const float* rgb, const float* d_rgb, const float* d_normal, int64_t n,
                            int64_t tail_rows, float* d_grad, float* d_feature, float* g_w0,
@@ -440,20 +442,11 @@ int dsu_texture_bwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const f
  * caller sets red->map (device copy of dsu_texture_partial_map) and red->base (a contiguous
  * [w0 | b0 | w1 | b1 | w2 | b2] gradient block, accumulated +=) and hands the record to a launch that
  * carries it out (dsu_sdf_fd_bwd_sorted_fold).  dsu_texture_partial_map fills map_host (may be NULL)
- * and returns the number of entries. */
+ * and returns the number of entries.
+ * h1_mask (may be NULL): the pattern dsu_texture_fwd_shaded_m wrote.  The backward then recomputes
+ * layer 1 with three bf16 products per f32 product (2^-16 relative on the activations) while the
+ * masks stay the forward's, bit for bit.  NULL = exact f32 recompute, as in dsu_texture_bwd_shaded. */
 int32_t dsu_texture_partial_map(int32_t* map_host);
-int dsu_texture_bwd_shaded_partials(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                                    const float* rgb, const float* d_rgb, const float* d_normal,
-                                    int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
-                                    void* workspace, int64_t workspace_bytes,
-                                    dsu_partial_reduce* red, void* stream);
-/* The pair with the ReLU pattern of hidden layer 1 handed from the forward to the backward
- * (h1_mask: (n, 2) uint32, word h of a sample = its hidden units 32 T + (r & 3) + 8 (r >> 2) + 4 h,
- * bit 16 T + r): the backward then recomputes layer 1 with three bf16 products per f32 product
- * (2^-16 relative on the activations) while the masks stay the forward's, bit for bit.  NULL mask =
- * the calls above (exact f32 recompute). */
-int dsu_texture_fwd_shaded_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                             int64_t n, float* normal, float* rgb, uint32_t* h1_mask, void* stream);
 int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
                                       const float* rgb, const float* d_rgb, const float* d_normal,
                                       int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,

@@ -180,8 +180,9 @@ def test_fused_step_gradients_match_autograd_step(dev):
 
 @pytest.mark.parametrize("n", [1, 63, 64, 1000, 262144 + 37])
 def test_texture_mlp_kernels_match_torch(dev, n):
-    """sigmoid(VanillaMLP 16->64->64->3) forward and backward (f32 MFMA) vs torch f32
-    (tolerance: different f32 summation order only; reference texture.py:20-30)."""
+    """sigmoid(VanillaMLP 16->64->64->3) forward (f32 MFMA) and backward (recompute on the
+    f32 MFMA, gradient GEMMs as bf16 x 3: 2^-16 relative) vs torch f32 (tolerance: f32 summation order
+    forward, the bf16 x 3 bound backward; reference texture.py:20-30)."""
     g = torch.Generator().manual_seed(n)
     mk = lambda *s: (torch.randn(*s, generator=g)).to(dev)
     params = [mk(64, 16) * 0.3, mk(64) * 0.1, mk(64, 64) * 0.15, mk(64) * 0.1, mk(3, 64) * 0.2,
@@ -444,7 +445,7 @@ def test_packed_step_buffers_equal_the_plain_calls(dev):
 
 @pytest.mark.parametrize("n", [1, 63, 1000, 100003])
 def test_shaded_texture_kernels_equal_the_separate_launches(dev, n):
-    """dsu_texture_fwd_shaded / _bwd_shaded = shade_prep + texture MLP (+ their backward) in one
+    """dsu_texture_fwd_shaded_m / dsu_texture_bwd_shaded = shade_prep + texture MLP (+ their backward) in one
     launch each: the same arithmetic on the same values — per-sample results are bit-identical."""
     g = torch.Generator().manual_seed(n)
     mk = lambda *s: (torch.randn(*s, generator=g)).to(dev)
@@ -471,7 +472,7 @@ def test_shaded_texture_kernels_equal_the_separate_launches(dev, n):
 def test_deferred_partial_sums_in_the_scatter_launch_equal_the_separate_reductions(dev, n):
     """The native step's tail: the texture backward leaves its per-workgroup partial gradients and
     the geometry backward's scatter launch sums them (and its own) in its first workgroups
-    (dsu_texture_bwd_shaded_partials + dsu_sdf_fd_bwd_sorted_fold).  Same partials, same summation
+    (dsu_texture_bwd_shaded_partials_m + dsu_sdf_fd_bwd_sorted_fold).  Same partials, same summation
     order as the stand-alone reduction launches: the geometry gradients are bit-identical."""
     g = torch.Generator().manual_seed(n)
     mk = lambda *s: (torch.randn(*s, generator=g)).to(dev)
