@@ -119,22 +119,12 @@ _PROTOS = {
     "dsu_hashgrid_encode_bwd": [C.POINTER(HashGridCfg), P, P, c_i64, c_u32, P, P],
     "dsu_sdf_fwd": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, c_i64, c_f32, c_u32, c_u32,
                     P, P],
-    "dsu_sdf_fd_fwd": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, c_i64, c_f32, c_f32,
-                       c_u32, P, P, P, P, P],
-    "dsu_sdf_fd_bwd": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, c_i64, c_f32, c_f32,
-                       c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P],
     "dsu_sdf_fd_bwd_workspace_bytes": [C.POINTER(HashGridCfg), c_i64],
-    "dsu_sdf_fd_fwd_cached": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, c_i64, c_f32, c_f32,
-                              c_u32, P, P, P, P, P, P],
-    "dsu_sdf_fd_bwd_cached": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, c_i64, c_f32, c_f32,
-                              c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P, P],
     "dsu_sdf_fd_enc_cache_bytes": [c_i64, c_u32],
     "dsu_sdf_fd_fwd_sorted": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, P, c_i64, c_f32,
                               c_f32, c_u32, P, P, P, P, P, P],
     "dsu_sdf_fd_bwd_sorted": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, P, c_i64, c_f32,
                               c_f32, c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P, P],
-    "dsu_sdf_fd_bwd_sorted_mid": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, P, c_i64, c_f32,
-                                  c_f32, c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P, P, P],
     "dsu_sdf_fd_bwd_sorted_fold": [C.POINTER(HashGridCfg), P, C.POINTER(SdfMlp), P, P, c_i64, c_f32,
                                    c_f32, c_u32, P, P, P, P, P, P, P, P, P, P, c_i64, P, P,
                                    C.POINTER(PartialReduce), P],
@@ -216,7 +206,6 @@ _PROTOS = {
     "dsu_point_bin_count": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P],
     "dsu_point_bin_fill": [P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
     "dsu_knn8_blend": [P, c_i64, P, P, c_i64, c_f32, c_f32, c_f32, c_i32, P, P, P, P],
-    "dsu_ab_switches": [],
     "dsu_umbrella_implicit_solve": [P, P, c_i64, C.c_double, P, P, P, c_i32, P],
     "dsu_mesh_decimate_quadric": [P, c_i64, P, c_i64, c_i64, C.c_double, c_i32, P, P, P, P],
     "dsu_mesh_decimate_quadric_q": [P, c_i64, P, c_i64, c_i64, C.c_double, c_i32, P, P, P, P, P],
@@ -232,7 +221,6 @@ _PROTOS = {
     "dsu_nsr_driver_step": [c_vp, C.POINTER(NsrStepArgs), P],
     "dsu_nsr_driver_terms": [c_vp],
     "dsu_nsr_driver_adam_moments": [c_vp, c_i32],
-    "dsu_nsr_driver_sync": [c_vp],
     "dsu_nsr_driver_timing": [c_vp, c_i32],
     "dsu_nsr_driver_timing_read": [c_vp, c_i32, C.POINTER(c_i64), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)],
@@ -268,7 +256,6 @@ _PROTOS = {
                                P, P],
     "dsu_shade_prep_fwd": [P, P, c_i64, P, P, P],
     "dsu_shade_prep_bwd": [P, P, P, c_i64, P, P, P],
-    "dsu_shade_prep_bwd_tail": [P, P, P, c_i64, c_i64, P, P, P],
     "dsu_occgrid_ema": [P, P, P, c_i64, c_f32, P, P],
     "dsu_occgrid_binarize": [P, c_i64, c_f32, P, P],
     "dsu_ric_offsets": [c_i32, c_i32, P, P],
@@ -277,10 +264,6 @@ _PROTOS = {
     "dsu_mv_attention_fwd": [P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                              C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64),
                              C.POINTER(c_i64), c_f32, P],
-    "dsu_conv2d_nhwc_f16_fwd": [P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
-                                c_i32, P, P, P, P],
-    "dsu_conv2d_nhwc_f16_fwd_ws": [P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
-                                   c_i32, P, P, P, c_i32, P, c_i64, P],
     "dsu_conv2d_nhwc_f16_fwd_fx": [P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_i32, P, P, P, c_i32, P, c_i64, P, c_i64, P],
     "dsu_gemm_f16_fwd_fx": [P, P, P, c_i64, c_i32, c_i32, P, P, c_i32, c_i32, P, c_i64, P, c_i64, P],
@@ -288,7 +271,6 @@ _PROTOS = {
     "dsu_conv2d_nhwc_f16_workspace_bytes": [c_i32] * 9,
     "dsu_gemm_f16_split_k": [c_i64, c_i32, c_i32],
     "dsu_gemm_f16_workspace_bytes": [c_i64, c_i32, c_i32],
-    "dsu_gemm_f16_fwd": [P, P, P, c_i64, c_i32, c_i32, P, P, c_i32, c_i32, P, c_i64, P],
     "dsu_gemm_geglu_fwd": [P, P, P, c_i64, c_i32, c_i32, P, P],
     "dsu_groupnorm_nhwc_f16": [P, P, P, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, P, P, P],
     "dsu_layernorm_f16": [P, P, P, c_i64, c_i32, c_f32, P, P],

@@ -76,14 +76,4 @@ int dsu_ddim_cfg_step(const void* noise_pred, const void* latents, const void* v
                                      sqrt(rad > 0.0 ? rad : 0.0), std_dev, out, stream);
 }
 
-// 1 in a variant build with the A/B environment switches compiled in (-DDSU_AB_SWITCHES), 0 in the
-// product library
-int dsu_ab_switches(void) {
-#ifdef DSU_AB_SWITCHES
-  return 1;
-#else
-  return 0;
-#endif
-}
-
 }  // extern "C"

@@ -18,7 +18,7 @@
 // bias, per-(image, channel) vector add (ResnetBlock2D's time-embedding projection), residual.
 //
 // The same kernel is the GEMM of the UNet's linear layers (a 1x1 "convolution" over M rows):
-// dsu_gemm_f16_fwd (to_q / to_k / to_out, FeedForward output, proj_in / proj_out, the embedding
+// dsu_gemm_f16_fwd_fx (to_q / to_k / to_out, FeedForward output, proj_in / proj_out, the embedding
 // MLPs; mvdiffusion/models/transformer_mv2d.py:447-483, unet_mv2d_condition.py:313-319,374),
 // with two extra epilogues selected by the MODE template parameter:
 //   MODE 1  GEGLU (diffusers FeedForward's first layer): the 128 weight rows of a tile are 2 x 32
@@ -28,8 +28,6 @@
 //   transposed output (to_v): out[(image, channel, token)] so that the attention kernel reads V^T
 //           rows directly.
 #include "common.h"
-
-#include <stdlib.h>
 
 namespace {
 
@@ -438,9 +436,8 @@ __global__ __launch_bounds__(256) void conv_f16_reduce_kernel(CArgs a, int64_t n
 int conv_out_dim(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
 
 // 64 x 64 workgroup tiles when the 128 x 128 tiling would leave the chip under-filled
-// (DSU_CONV_SMALL_MAX_TILES: A/B switch, 0 = always 128 x 128)
 bool small_tiles(int64_t npix, int64_t O) {
-  static const int64_t max_big = dsu_ab_int("DSU_CONV_SMALL_MAX_TILES", 512);
+  constexpr int64_t max_big = 512;
   const int64_t big = ((npix + TN_BIG - 1) / TN_BIG) * ((O + TM_BIG - 1) / TM_BIG);
   return big < max_big;
 }
@@ -469,8 +466,7 @@ int32_t dsu_conv2d_nhwc_f16_split_k(int32_t B, int32_t H, int32_t W, int32_t C, 
   const int chunks = (k * k * C + BK - 1) / BK;
   const int64_t fill = tile == 64 ? 512 : 256;       // 64-tiles: four workgroups fit a CU
   if (tiles >= fill || chunks < 8) return 1;         // the output tiles already fill the chip
-  static const int64_t target_pct = dsu_ab_int("DSU_CONV_SPLIT_TARGET", 50);   // A/B: percent of fill
-  if (target_pct <= 0) return 1;
+  constexpr int64_t target_pct = 50;                 // percent of fill the split aims at
   // (measured on the UNet forward: 12.2 ms without split-K, 11.1 / 10.8 / 10.6 ms aiming at 2 x / 1 x /
   // 0.5 x fill — the f32 partials of a split cost a write and a read of the whole output each)
   int64_t s = (fill * target_pct / 100 + tiles - 1) / tiles;
@@ -487,17 +483,6 @@ int64_t dsu_conv2d_nhwc_f16_workspace_bytes(int32_t B, int32_t H, int32_t W, int
   const int OH = conv_out_dim(IH, k, stride, pad), OW = conv_out_dim(IW, k, stride, pad);
   if (OH <= 0 || OW <= 0) return DSU_EINVAL;
   return (int64_t)split_k * B * OH * OW * O * (int64_t)sizeof(float);
-}
-
-int dsu_conv2d_nhwc_f16_fwd_ws(const void* input, const void* weight_okc, const void* bias,
-                               int32_t B, int32_t H, int32_t W, int32_t C, int32_t O, int32_t k,
-                               int32_t stride, int32_t pad, int32_t upsample2x,
-                               const void* addvec, const void* residual, void* out,
-                               int32_t split_k, void* workspace, int64_t workspace_bytes,
-                               void* stream) {
-  return dsu_conv2d_nhwc_f16_fwd_fx(input, weight_okc, bias, B, H, W, C, O, k, stride, pad, upsample2x,
-                                    addvec, residual, out, split_k, workspace, workspace_bytes,
-                                    nullptr, 0, stream);
 }
 
 int dsu_conv2d_nhwc_f16_fwd_fx(const void* input, const void* weight_okc, const void* bias,
@@ -581,13 +566,6 @@ int64_t dsu_gemm_f16_workspace_bytes(int64_t M, int32_t N, int32_t split_k) {
 
 /* out (M, N) = x w^T (+ bias) (+ residual (M, N)).  tokens_per_image > 0: the output is written
  * TRANSPOSED per image, out[(m / tokens) * N * tokens + n * tokens + m % tokens]  (to_v -> V^T). */
-int dsu_gemm_f16_fwd(const void* x, const void* w, const void* bias, int64_t M, int32_t K, int32_t N,
-                     const void* residual, void* out, int32_t tokens_per_image, int32_t split_k,
-                     void* workspace, int64_t workspace_bytes, void* stream) {
-  return dsu_gemm_f16_fwd_fx(x, w, bias, M, K, N, residual, out, tokens_per_image, split_k, workspace,
-                             workspace_bytes, nullptr, 0, stream);
-}
-
 int dsu_gemm_f16_fwd_fx(const void* x, const void* w, const void* bias, int64_t M, int32_t K,
                         int32_t N, const void* residual, void* out, int32_t tokens_per_image,
                         int32_t split_k, void* workspace, int64_t workspace_bytes,
@@ -634,14 +612,6 @@ int dsu_gemm_geglu_fwd(const void* x, const void* w, const void* bias, int64_t M
   conv_f16_kernel<1, 2, 2><<<grid, 256, 0, (hipStream_t)stream>>>(a);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
-}
-
-int dsu_conv2d_nhwc_f16_fwd(const void* input, const void* weight_okc, const void* bias,
-                            int32_t B, int32_t H, int32_t W, int32_t C, int32_t O, int32_t k,
-                            int32_t stride, int32_t pad, int32_t upsample2x, const void* addvec,
-                            const void* residual, void* out, void* stream) {
-  return dsu_conv2d_nhwc_f16_fwd_ws(input, weight_okc, bias, B, H, W, C, O, k, stride, pad,
-                                    upsample2x, addvec, residual, out, 1, nullptr, 0, stream);
 }
 
 }  // extern "C"

@@ -872,20 +872,4 @@ int dsu_sdf_fd_fwd_sorted(const dsu_hashgrid_cfg* cfg, const void* table_f16, co
   return DSU_OK;
 }
 
-int dsu_sdf_fd_fwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
-                          float eps, uint32_t active_levels, float* sdf, float* grad,
-                          float* feature, float* laplace, void* enc_cache, void* stream) {
-  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               sdf, grad, feature, laplace, enc_cache, stream);
-}
-
-int dsu_sdf_fd_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, float* sdf, float* grad, float* feature,
-                   float* laplace, void* stream) {
-  return dsu_sdf_fd_fwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               sdf, grad, feature, laplace, nullptr, stream);
-}
-
 }  // extern "C"

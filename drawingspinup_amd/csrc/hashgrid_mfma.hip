@@ -1746,21 +1746,9 @@ int dsu_sdf_fd_bwd_sorted(const dsu_hashgrid_cfg* cfg, const void* table_f16, co
                    const float* d_feature, const float* d_laplace, float* grad_table,
                    float* g_w0, float* g_b0, float* g_w1, float* g_b1, void* workspace,
                    int64_t workspace_bytes, const void* enc_cache, void* stream) {
-  return dsu_sdf_fd_bwd_sorted_mid(cfg, table_f16, mlp, pts, perm, n, radius, eps, active_levels,
-                                   d_sdf, d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1,
-                                   g_b1, workspace, workspace_bytes, enc_cache, nullptr, stream);
-}
-
-int dsu_sdf_fd_bwd_sorted_mid(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                              const dsu_sdf_mlp* mlp, const float* pts, const int32_t* perm,
-                              int64_t n, float radius, float eps, uint32_t active_levels,
-                              const float* d_sdf, const float* d_grad, const float* d_feature,
-                              const float* d_laplace, float* grad_table, float* g_w0, float* g_b0,
-                              float* g_w1, float* g_b1, void* workspace, int64_t workspace_bytes,
-                              const void* enc_cache, void* mid_event, void* stream) {
   return dsu_sdf_fd_bwd_sorted_fold(cfg, table_f16, mlp, pts, perm, n, radius, eps, active_levels,
                                     d_sdf, d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1,
-                                    g_b1, workspace, workspace_bytes, enc_cache, mid_event, nullptr,
+                                    g_b1, workspace, workspace_bytes, enc_cache, nullptr, nullptr,
                                     stream);
 }
 
@@ -1847,29 +1835,6 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
   });
   DSU_CHECK_LAUNCH();
   return DSU_OK;
-}
-
-int dsu_sdf_fd_bwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
-                          float eps, uint32_t active_levels, const float* d_sdf,
-                          const float* d_grad, const float* d_feature, const float* d_laplace,
-                          float* grad_table, float* g_w0, float* g_b0, float* g_w1, float* g_b1,
-                          void* workspace, int64_t workspace_bytes, const void* enc_cache,
-                          void* stream) {
-  return dsu_sdf_fd_bwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               d_sdf, d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1,
-                               g_b1, workspace, workspace_bytes, enc_cache, stream);
-}
-
-int dsu_sdf_fd_bwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, const float* d_sdf, const float* d_grad,
-                   const float* d_feature, const float* d_laplace, float* grad_table,
-                   float* g_w0, float* g_b0, float* g_w1, float* g_b1, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
-  return dsu_sdf_fd_bwd_sorted(cfg, table_f16, mlp, pts, nullptr, n, radius, eps, active_levels,
-                               d_sdf, d_grad, d_feature, d_laplace, grad_table, g_w0, g_b0, g_w1,
-                               g_b1, workspace, workspace_bytes, nullptr, stream);
 }
 
 }  // extern "C"

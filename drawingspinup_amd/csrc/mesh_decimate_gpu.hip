@@ -32,8 +32,6 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <hipcub/hipcub.hpp>
 
@@ -649,9 +647,6 @@ int dsu_mesh_decimate_parallel(double* verts, int64_t n_verts, int32_t* faces, i
     DSU_HIP_TRY(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, s));
     DSU_HIP_TRY(hipStreamSynchronize(s));
     ++rounds;
-    if (dsu_ab_int("DSU_DECIMATE_DEBUG", 0))
-      fprintf(stderr, "[decimate] round %d nf %lld ne %lld ncand %lld applied %d rejected %d removed %d\n", rounds,
-              (long long)nf, (long long)ne, (long long)ncand, hc[0], hc[1], hc[2]);
     applied_total += hc[0];
     rejected_total += hc[1];
     if (hc[0] == 0) {

@@ -8,19 +8,18 @@
 //     (F_a v)(i) = cd_a(i) v(i) + v(n-_a(i)) + v(n+_a(i)),   cd_a = -2 + [no n-] + [no n+].
 // Energy |F v|^2, Q = sum_a F_a^T F_a.  One iteration (PyMCubes: weight 0.5, projection onto the
 // per-voxel bounds lower[i] <= x <= upper[i]: the initial distance on the voxel's own side, 0 for
-// the voxels next to the surface, +-inf on the other side) is two passes over the band:
-//     y_a = F_a x                                    (smooth_rows_kernel,   3 nv doubles out)
-//     x  <- clamp(w * (-(Q x - d x) / d) + (1 - w) x)  with Q x = sum_a F_a^T y_a, d = diag Q
-//                                                    (smooth_update_kernel)
-// and every tenth iteration the energy x . Q x / 2 as per-workgroup partial sums in a fixed order
-// (smooth_energy_kernel; the host adds the partials: the stopping test is deterministic).
-// The iteration itself runs as ONE kernel per step (smooth_fused_kernel): the three rows a voxel
-// needs per axis — its own and its two neighbours' — are recomputed from x with the very
-// expressions of smooth_rows_kernel (same operands, same order: bit-identical values), so y is
-// neither written nor read; x ping-pongs between the caller's x and the first nv doubles of y.
-// Unique memory per iteration: slots 24 nv + x 8 nv in + 8 nv out + bounds 16 nv = 56 nv bytes
-// against ~ (2 x 24 + 24 + 24 + 72 + 16 + 16) nv = 200 nv of the two-pass form; the band of a
-// 512^3 export is 2-5 M voxels, i.e. it lives in the Infinity Cache across iterations.
+// the voxels next to the surface, +-inf on the other side) is
+//     x  <- clamp(w * (-(Q x - d x) / d) + (1 - w) x)  with Q x = sum_a F_a^T (F_a x), d = diag Q
+// as ONE kernel per step (smooth_fused_kernel): the three rows y_a = F_a x a voxel needs per axis —
+// its own and its two neighbours' — are computed from x on the fly, so no row is written or read;
+// x ping-pongs between the caller's x and the first nv doubles of the scratch y.
+// Unique memory per iteration: slots 24 nv + x 8 nv in + 8 nv out + bounds 16 nv = 56 nv bytes (a
+// row pass and an update pass over stored rows, the form of rounds 2-4, moved ~200 nv); the band
+// of a 512^3 export is 2-5 M voxels, i.e. it lives in the Infinity Cache across iterations.
+// Every tenth iteration the energy x . Q x / 2: smooth_rows_kernel, the energy's row pass, stores
+// y_a = F_a x (3 nv doubles; the fused kernel's rows are the very expressions, same operands, same
+// order: bit-identical values), smooth_energy_kernel sums x . sum_a F_a^T y_a into per-workgroup
+// partials in a fixed order (the host adds the partials: the stopping test is deterministic).
 //
 // The export runs the iteration on the BRICK layout instead (dsu_smooth_bricks_*, second half of
 // this file): the band compacted in 8^3 bricks, so that a neighbour is an address and neighbouring
@@ -80,24 +79,6 @@ __device__ __forceinline__ void q_and_diag(const int32_t* __restrict__ nbr, int6
     const double* ya = y + (size_t)a * nv;
     q += cd * ya[i] + at_or_zero(ya, m) + at_or_zero(ya, p);
     d += cd * cd + hm + hp;
-  }
-}
-
-__global__ __launch_bounds__(256) void smooth_update_kernel(const int32_t* __restrict__ nbr,
-                                                            int64_t nv,
-                                                            const double* __restrict__ y,
-                                                            const double* __restrict__ lower,
-                                                            const double* __restrict__ upper,
-                                                            double weight, double* __restrict__ x) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    double q, d;
-    q_and_diag(nbr, nv, y, i, q, d);
-    const double xi = x[i];
-    const double x1 = -(1.0 / d) * (q - d * xi);                 // -D^-1 R x
-    double xn = weight * x1 + (1.0 - weight) * xi;
-    xn = fmin(fmax(xn, lower[i]), upper[i]);                     // np.maximum(x, lower); np.minimum(x, upper)
-    x[i] = xn;
   }
 }
 
@@ -535,14 +516,6 @@ int dsu_smooth_iterate(const int32_t* nbr, int64_t nv, const double* lower, cons
   if (nv == 0 || iters == 0) return DSU_OK;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = dsu_capped_blocks(nv, 256, 8192);
-  if (dsu_ab_is("DSU_SMOOTH", "two_pass")) {      // the form of rounds 2-4 (variant builds, A/B)
-    for (int it = 0; it < iters; ++it) {
-      smooth_rows_kernel<<<dim3(blocks), dim3(256), 0, s>>>(nbr, nv, x, y);
-      smooth_update_kernel<<<dim3(blocks), dim3(256), 0, s>>>(nbr, nv, y, lower, upper, weight, x);
-    }
-    DSU_CHECK_LAUNCH();
-    return DSU_OK;
-  }
   double* cur = x;
   double* nxt = y;                                  // first nv doubles of the scratch
   for (int it = 0; it < iters; ++it) {

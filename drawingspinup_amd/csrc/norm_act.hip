@@ -6,8 +6,6 @@
 // with 16-byte accesses and keeps statistics in f32.
 #include "common.h"
 
-#include <stdlib.h>
-
 namespace {
 
 typedef _Float16 f16;
@@ -369,14 +367,13 @@ int dsu_groupnorm_nhwc_f16(const void* x, const void* gamma, const void* beta, i
   hipStream_t s = (hipStream_t)stream;
   {
     // super-group form: groups of >= 8 channels whose super-group has <= 4 groups and fits the
-    // registers of one 1024-thread workgroup (DSU_GN_SUPER=0: A/B switch)
-    static const bool use_super = dsu_ab_int("DSU_GN_SUPER", 1) != 0;
+    // registers of one 1024-thread workgroup
     const int cpg = C / G;
     int SG = cpg;
     while (SG % 8 != 0) SG += cpg;
     // (measured per UNet shape, tools/gn_time.py: 19-47 us instead of 26-58 at 32x32, 15.6 instead of
     // 20.1 at 16x16x1280, a tie at 16x16x640, 2-3 us SLOWER on the 8x8 / 4x4 levels — few, fat workgroups)
-    if (use_super && HW >= 256 && cpg >= 8 && SG / cpg <= 4 && C % SG == 0 &&
+    if (HW >= 256 && cpg >= 8 && SG / cpg <= 4 && C % SG == 0 &&
         (int64_t)HW * (SG / 8) <= (int64_t)GS_KEEP * GS_THREADS && (int64_t)HW * C < ((int64_t)1 << 31)) {
       gn_super_kernel<<<B * (C / SG), GS_THREADS, 0, s>>>((const f16*)x, (const f16*)gamma,
                                                           (const f16*)beta, HW, C, cpg, SG, eps, silu,

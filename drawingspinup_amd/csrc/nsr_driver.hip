@@ -397,13 +397,7 @@ struct dsu_nsr_driver {
   hipStream_t side = nullptr;
   hipEvent_t ready[3] = {nullptr, nullptr, nullptr};   // side: set packed, stats copied to the host
   hipEvent_t gate = nullptr;                           // main: MLP part of the latest backward done
-  hipEvent_t fwd_done = nullptr;                       // main: this step's geometry forward done
-  bool fold = true;                 // DSU_NSR_FOLD (variant builds)
-  bool tex_masks = true;            // DSU_NSR_TEX_MASKS (variant builds)
-  bool side_high_priority = true;   // DSU_NSR_SIDE_PRIO
   int side_level = 1, side_device = 0;   // (what the side stream was made with: the pool's key)
-  int pack_gate = 0;                // DSU_NSR_PACK_GATE: 0 with the march, 1 behind this step's geometry
-                                    // forward (own event), 2 behind the MLP part of this step's backward
   int32_t* host_stats = nullptr;                       // pinned, 3 x int32[2]
   bool pf_valid[3] = {false, false, false};
   int64_t pf_step[3] = {-1, -1, -1};
@@ -551,11 +545,7 @@ int launch_small_update(dsu_nsr_driver* d, const dsu_nsr_step_args* a, int updat
   // ... and the hash table (active levels; level / decay bookkeeping is the caller's)
   dsu_table_adamw_args ta{};
   int table_blocks = 0;
-  if (update && a->table_p && !d->fold) {
-    DSU_TRY(dsu_table_adamw(a->table_p, a->table_grad, a->table_m, a->table_v,
-                            const_cast<void*>(a->table_img), a->table_n, a->table_lr, c.beta1, c.beta2,
-                            a->table_eps, a->table_wd, a->table_bc1, a->table_bc2_sqrt, s));
-  } else if (update && a->table_p) {
+  if (update && a->table_p) {
     if (a->table_n < 0 || (a->table_n & 3) || !a->table_grad || !a->table_m || !a->table_v ||
         !a->table_img || !(a->table_bc1 > 0.0f) || !(a->table_bc2_sqrt > 0.0f))
       return DSU_EINVAL;
@@ -624,14 +614,7 @@ int dsu_nsr_driver_create(const dsu_nsr_driver_cfg* cfg, dsu_nsr_driver** out) {
     }
   }
   int lo = 0, hi = 0;
-  const int side_prio = dsu_ab_int("DSU_NSR_SIDE_PRIO", dsu_nsr_side_priority_value);   // 1 high, 2 normal, 0 low
-  d->side_high_priority = side_prio == 1;
-  // 0 since round 4: with 16-ray marching waves and the shorter step the packing right behind the
-  // march measured 1.148 against 1.161 ms per step for "behind the geometry forward" (five
-  // interleaved pairs, same box) — and the main queue loses one event record per step
-  d->pack_gate = dsu_ab_int("DSU_NSR_PACK_GATE", 0);
-  d->fold = dsu_ab_int("DSU_NSR_FOLD", 1) != 0;
-  d->tex_masks = dsu_ab_int("DSU_NSR_TEX_MASKS", 1) != 0;   // (variant builds: 0 = exact f32 recompute, for A/B)
+  const int side_prio = dsu_nsr_side_priority_value;   // 1 high, 2 normal, 0 low
   d->side_level = side_prio;
   bool ok = hipGetDevice(&d->side_device) == hipSuccess;
   if (ok && dsu_nsr_side_pool_value) d->side = side_pool_take(d->side_device, side_prio);
@@ -642,7 +625,6 @@ int dsu_nsr_driver_create(const dsu_nsr_driver_cfg* cfg, dsu_nsr_driver** out) {
   for (int p = 0; p < 3; ++p)
     ok = ok && hipEventCreateWithFlags(&d->ready[p], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&d->gate, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&d->fwd_done, hipEventDisableTiming) == hipSuccess &&
        hipHostMalloc((void**)&d->host_stats, 6 * sizeof(int32_t), hipHostMallocDefault) == hipSuccess;
   if (!ok) {
     dsu_nsr_driver_destroy(d);
@@ -662,7 +644,6 @@ void dsu_nsr_driver_destroy(dsu_nsr_driver* d) {
   for (int p = 0; p < 3; ++p)
     if (d->ready[p]) (void)hipEventDestroy(d->ready[p]);
   if (d->gate) (void)hipEventDestroy(d->gate);
-  if (d->fwd_done) (void)hipEventDestroy(d->fwd_done);
   if (d->host_stats) (void)hipHostFree(d->host_stats);
   for (int f = 0; f < 2; ++f)
     for (hipEvent_t e : d->ev[f]) (void)hipEventDestroy(e);
@@ -768,11 +749,12 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
     d->pf_randomized[q] = a->randomized;
     d->pf_occ[q] = a->occ_binary;
     d->pf_occ_res[q] = a->occ_res;
-    if (d->pack_gate == 0) {
-      DSU_TRY(enqueue_pack(d, q, next_rays, na, false, d->side));
-      DSU_HIP(hipEventRecord(d->ready[q], d->side));
-      d->pf_valid[q] = true;                  // only once `ready[q]` is on the side stream
-    }
+    // The packing right behind the march since round 4: with 16-ray marching waves and the shorter
+    // step it measured 1.148 against 1.161 ms per step for "behind the geometry forward" (five
+    // interleaved pairs, same box) — and the main queue loses one event record per step
+    DSU_TRY(enqueue_pack(d, q, next_rays, na, false, d->side));
+    DSU_HIP(hipEventRecord(d->ready[q], d->side));
+    d->pf_valid[q] = true;                  // only once `ready[q]` is on the side stream
   }
 
   const float* pts = c.sort_bits ? f.sorted : f.points;
@@ -790,26 +772,10 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
                                 a->active_levels, L.a_sdf, L.a_grad, L.a_feat, nullptr, L.enc_cache, s));
   DSU_TRY(mark(d, 0, s));
   if (d->timing) { d->work[0] += alg_bytes; d->flops[0] += fwd_flops; }
-  if (a->prefetch_next && d->pack_gate == 1) {
-    // The packing / sorting launches of the next set (a dozen short, chip-wide kernels) slowed the
-    // gather-bound geometry forward by a quarter when they ran beside it (kernel trace: 221 vs
-    // 175 us); behind it they share the chip with the small shading / loss kernels instead.
-    const int q = (int)((a->step + 1) % 3);
-    dsu_nsr_step_args na = *a;
-    na.inj_index = na.inj_x = na.inj_y = nullptr;
-    na.inj_jitter = na.inj_pts_random = na.inj_perturb = nullptr;
-    na.inj_rays = nullptr;
-    DSU_HIP(hipEventRecord(d->fwd_done, s));
-    DSU_HIP(hipStreamWaitEvent(d->side, d->fwd_done, 0));
-    DSU_TRY(enqueue_pack(d, q, next_rays, na, false, d->side));
-    DSU_HIP(hipEventRecord(d->ready[q], d->side));
-    d->pf_valid[q] = true;
-  }
   if (n_s > 0) {
     dsu_tex_mlp tex{c.tex[0], c.tex[1], c.tex[2], c.tex[3], c.tex[4], c.tex[5]};
     // (with the ReLU pattern of hidden layer 1 for the backward: its recompute runs as bf16 x 3)
-    DSU_TRY(dsu_texture_fwd_shaded_m(&tex, L.a_feat, L.a_grad, n_s, L.normal, L.rgb,
-                                     d->tex_masks ? L.tex_mask : nullptr, s));
+    DSU_TRY(dsu_texture_fwd_shaded_m(&tex, L.a_feat, L.a_grad, n_s, L.normal, L.rgb, L.tex_mask, s));
     DSU_TRY(dsu_neus_composite_fwd(L.a_sdf, L.normal, L.rgb, f.rays_d, f.t_starts, f.t_ends,
                                    f.offsets, f.counts, a->n_rays, L.inv_s, a->cos_anneal_ratio,
                                    L.alpha, L.w, L.comp, s));
@@ -828,22 +794,13 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
                                    L.d_inv, s));
     dsu_tex_mlp tex{c.tex[0], c.tex[1], c.tex[2], c.tex[3], c.tex[4], c.tex[5]};
     // parameter gradients of the texture MLP: per-workgroup partials now, summed into g_tex by
-    // extra workgroups of the geometry backward's scatter launch (no launch of their own;
-    // DSU_NSR_FOLD=0 in variant builds: the separate reduction and table-AdamW launches, for A/B)
-    if (!d->fold) {
-      float* gt = L.g_tex;
-      DSU_TRY(dsu_texture_bwd_shaded(&tex, L.a_feat, L.a_grad, L.rgb, L.d_rgb, L.d_normal, n_s, 2 * n_r,
-                                     L.d_grad_all, L.d_feat_all, gt, gt + 1024, gt + 1088, gt + 5184,
-                                     gt + 5248, gt + 5440, L.tex_ws, L.tex_ws_bytes, s));
-    } else {
+    // extra workgroups of the geometry backward's scatter launch (no launch of their own)
     DSU_TRY(dsu_texture_bwd_shaded_partials_m(&tex, L.a_feat, L.a_grad, L.rgb, L.d_rgb, L.d_normal, n_s,
-                                              2 * n_r, L.d_grad_all, L.d_feat_all,
-                                              d->tex_masks ? L.tex_mask : nullptr, L.tex_ws,
+                                              2 * n_r, L.d_grad_all, L.d_feat_all, L.tex_mask, L.tex_ws,
                                               L.tex_ws_bytes, &tex_red, s));
     tex_red.map = L.tex_map;
     tex_red.base = L.g_tex;
     have_tex_red = true;
-    }
   } else {
     DSU_HIP(hipMemsetAsync(L.d_feat_all, 0, (size_t)(2 * n_r) * 13 * sizeof(float), s));
   }
@@ -859,17 +816,6 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
                                      L.enc_cache, d->gate, have_tex_red ? &tex_red : nullptr, s));
   DSU_TRY(mark(d, 1, s));
   if (d->timing) { d->work[1] += alg_bytes; d->flops[1] += bwd_flops; }
-  if (a->prefetch_next && d->pack_gate == 2) {
-    const int q = (int)((a->step + 1) % 3);
-    dsu_nsr_step_args na = *a;
-    na.inj_index = na.inj_x = na.inj_y = nullptr;
-    na.inj_jitter = na.inj_pts_random = na.inj_perturb = nullptr;
-    na.inj_rays = nullptr;
-    DSU_HIP(hipStreamWaitEvent(d->side, d->gate, 0));          // recorded inside the call above
-    DSU_TRY(enqueue_pack(d, q, next_rays, na, false, d->side));
-    DSU_HIP(hipEventRecord(d->ready[q], d->side));
-    d->pf_valid[q] = true;
-  }
   // ---- optimizer: the hash table and the small tensors in one launch
   DSU_TRY(launch_small_update(d, a, 1, s));
   d->last_step = a->step;
@@ -931,13 +877,6 @@ int dsu_nsr_driver_timing_read(dsu_nsr_driver* d, int32_t family, int64_t* launc
 int dsu_nsr_driver_timing_flops(dsu_nsr_driver* d, int32_t family, double* mlp_flops) {
   if (!d || family < 0 || family > 1 || !mlp_flops) return DSU_EINVAL;
   *mlp_flops = d->flops[family];
-  return DSU_OK;
-}
-
-int dsu_nsr_driver_sync(dsu_nsr_driver* d) {
-  if (!d) return DSU_EINVAL;
-  DSU_HIP(hipStreamSynchronize(d->side));
-  for (int k = 0; k < 3; ++k) d->pf_valid[k] = false;
   return DSU_OK;
 }
 

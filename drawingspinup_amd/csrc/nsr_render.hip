@@ -878,18 +878,10 @@ int dsu_shade_prep_fwd(const float* grad, const float* feature, int64_t n, float
 
 int dsu_shade_prep_bwd(const float* grad, const float* d_normal, const float* d_tex_in, int64_t n,
                        float* d_grad, float* d_feature, void* stream) {
-  return dsu_shade_prep_bwd_tail(grad, d_normal, d_tex_in, n, 0, d_grad, d_feature, stream);
-}
-
-int dsu_shade_prep_bwd_tail(const float* grad, const float* d_normal, const float* d_tex_in,
-                            int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
-                            void* stream) {
-  if (n < 0 || tail_rows < 0 || (n && (!grad || !d_tex_in || !d_grad)) ||
-      ((n || tail_rows) && !d_feature))
-    return DSU_EINVAL;
-  if (n + tail_rows == 0) return DSU_OK;
-  shade_prep_bwd_kernel<<<dsu_blocks_for(n + tail_rows, 256), 256, 0, (hipStream_t)stream>>>(
-      grad, d_normal, d_tex_in, n, tail_rows, d_grad, d_feature);
+  if (n < 0 || (n && (!grad || !d_tex_in || !d_grad || !d_feature))) return DSU_EINVAL;
+  if (n == 0) return DSU_OK;
+  shade_prep_bwd_kernel<<<dsu_blocks_for(n, 256), 256, 0, (hipStream_t)stream>>>(
+      grad, d_normal, d_tex_in, n, /*tail_rows*/ 0, d_grad, d_feature);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

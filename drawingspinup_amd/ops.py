@@ -144,7 +144,7 @@ def sdf_fd_fwd(cfg, table_f16, mlp, pts, radius, eps, active_levels, with_grad=T
                                       ptr(pts), ptr(perm, torch.int32), n, float(radius),
                                       float(eps), int(active_levels),
                                       ptr(sdf), ptr(grad), ptr(feat), ptr(lap), ptr(cache),
-                                      stream()), "dsu_sdf_fd_fwd")
+                                      stream()), "dsu_sdf_fd_fwd_sorted")
     if enc_cache:
         return sdf, grad, feat, lap, cache
     return sdf, grad, feat, lap
@@ -189,7 +189,8 @@ def sdf_fd_bwd(cfg, table_f16, mlp, pts, radius, eps, active_levels, d_sdf, d_gr
                                       float(eps), int(active_levels),
                                       ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), ptr(grad_table),
                                       ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(ws),
-                                      int(wbytes), ptr(enc_cache), stream()), "dsu_sdf_fd_bwd")
+                                      int(wbytes), ptr(enc_cache), stream()),
+          "dsu_sdf_fd_bwd_sorted")
     return grad_table, g
 
 
@@ -1203,7 +1204,7 @@ def conv2d_nhwc_f16(x_nhwc, w_okc, bias=None, k=3, stride=1, pad=1, upsample2x=F
                                            W, Cin, O, k, stride, pad, up, ptr(addvec, f16),
                                            ptr(residual, f16), ptr(out), int(split_k), ptr(ws),
                                            wbytes, ptr(cnt), _N_TILE_COUNTERS if cnt is not None else 0,
-                                           stream()), "dsu_conv2d_nhwc_f16_fwd")
+                                           stream()), "dsu_conv2d_nhwc_f16_fwd_fx")
     return out
 
 
@@ -1234,7 +1235,7 @@ def linear_f16(x, weight, bias=None, residual=None, transposed_tokens=0, split_k
                                     ptr(residual, f16), ptr(out), int(transposed_tokens), int(split_k),
                                     ptr(ws), wbytes, ptr(cnt),
                                     _N_TILE_COUNTERS if cnt is not None else 0, stream()),
-          "dsu_gemm_f16_fwd")
+          "dsu_gemm_f16_fwd_fx")
     return out
 
 

@@ -30,9 +30,6 @@ extern "C" {
 #define DSU_MAX_LEVELS 16
 
 const char* dsu_strerror(int code);
-/* 1 when the library was built with the A/B environment switches (variant builds for tools/), 0
- * for the product library: it reads no DSU_* environment variable. */
-int dsu_ab_switches(void);
 /* ABI version of this header; bumped on any signature change. */
 int dsu_abi_version(void);
 /* CUs given to the two whole-SIMD kernels of the NSR step (the MLP part of the geometry backward,
@@ -134,40 +131,18 @@ int dsu_sdf_fwd_lattice(const dsu_hashgrid_cfg* cfg, const void* table_f16, cons
 
 /* VolumeSDF.forward(points, with_grad, with_feature, with_laplace) with
  * grad_type=finite_difference (geometry.py:158-176): 7 network evaluations per point
- * (centre + 6 clamped +-eps offsets).  Outputs (any may be NULL except sdf):
- *   sdf (n), grad (n,3), feature (n,13), laplace (n). */
-int dsu_sdf_fd_fwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, float* sdf, float* grad, float* feature,
-                   float* laplace, void* stream);
-
-/* Backward of dsu_sdf_fd_fwd w.r.t. table and MLP parameters.  Upstream gradients
- * (NULL = zero): d_sdf (n), d_grad (n,3), d_feature (n,13), d_laplace (n).
- * Accumulates into grad_table (entries,2) f32 and g_w0 (64,23), g_b0 (64), g_w1 (13,64),
- * g_b1 (13) f32 — caller zeroes them.  `workspace` is caller-owned device scratch of at
- * least dsu_sdf_fd_bwd_workspace_bytes(cfg, n) bytes (contents undefined on return). */
-int dsu_sdf_fd_bwd(const dsu_hashgrid_cfg* cfg, const void* table_f16, const dsu_sdf_mlp* mlp,
-                   const float* pts, int64_t n, float radius, float eps,
-                   uint32_t active_levels, const float* d_sdf, const float* d_grad,
-                   const float* d_feature, const float* d_laplace, float* grad_table,
-                   float* g_w0, float* g_b0, float* g_w1, float* g_b1, void* workspace,
-                   int64_t workspace_bytes, void* stream);
-/* Same two calls with a feature cache between them: the forward pass stores the interpolated
- * f16 hash-grid features of all 7 evaluations ([eval][point][active level] half2,
+ * (centre + 6 clamped +-eps offsets), and its backward w.r.t. table and MLP parameters:
+ * dsu_sdf_fd_fwd_sorted / dsu_sdf_fd_bwd_sorted, declared below with the evaluation order they
+ * take.  Forward outputs (any may be NULL except sdf): sdf (n), grad (n,3), feature (n,13),
+ * laplace (n).  Upstream gradients of the backward (NULL = zero): d_sdf (n), d_grad (n,3),
+ * d_feature (n,13), d_laplace (n).  It accumulates into grad_table (entries,2) f32 and g_w0 (64,23),
+ * g_b0 (64), g_w1 (13,64), g_b1 (13) f32 — caller zeroes them.  `workspace` is caller-owned device
+ * scratch of at least dsu_sdf_fd_bwd_workspace_bytes(cfg, n) bytes (contents undefined on return).
+ * A feature cache may sit between the two calls: the forward pass stores the interpolated f16
+ * hash-grid features of all 7 evaluations ([eval][point][active level] half2,
  * dsu_sdf_fd_enc_cache_bytes(n, active_levels) bytes) and the backward pass reads them back
  * instead of repeating the 7 x active_levels x 8 table gathers per point.  Same results bit
- * for bit (the cached values ARE the forward's features); enc_cache NULL = the plain calls. */
-int dsu_sdf_fd_fwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
-                          float eps, uint32_t active_levels, float* sdf, float* grad,
-                          float* feature, float* laplace, void* enc_cache, void* stream);
-int dsu_sdf_fd_bwd_cached(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                          const dsu_sdf_mlp* mlp, const float* pts, int64_t n, float radius,
-                          float eps, uint32_t active_levels, const float* d_sdf,
-                          const float* d_grad, const float* d_feature, const float* d_laplace,
-                          float* grad_table, float* g_w0, float* g_b0, float* g_w1, float* g_b1,
-                          void* workspace, int64_t workspace_bytes, const void* enc_cache,
-                          void* stream);
+ * for bit (the cached values ARE the forward's features); enc_cache NULL = no cache. */
 int64_t dsu_sdf_fd_enc_cache_bytes(int64_t n, uint32_t active_levels);
 
 /* Spatially sorted evaluation order for one optimisation step.  VolumeSDF.forward is pointwise
@@ -178,7 +153,7 @@ int64_t dsu_sdf_fd_enc_cache_bytes(int64_t n, uint32_t active_levels);
  * bits 4..7): pts_sorted[i] = pts[perm[i]].  The *_sorted calls take the sorted points plus
  * perm and read / write every per-point array (sdf, grad, feature, laplace, d_*) in the
  * CALLER'S row order through it; the feature cache is kept in sorted order.  perm NULL = the
- * plain calls.  Same per-point arithmetic, bit for bit. */
+ * points as they are, in the caller's order.  Same per-point arithmetic, bit for bit. */
 int64_t dsu_spatial_sort_workspace_bytes(int64_t n, int32_t bits);
 int dsu_spatial_sort(const float* pts, int64_t n, float radius, int32_t bits, int32_t* perm,
                      float* pts_sorted, void* workspace, int64_t workspace_bytes, void* stream);
@@ -218,22 +193,14 @@ typedef struct dsu_partial_reduce {
   int32_t nblocks, stride, n;
 } dsu_partial_reduce;
 
-/* dsu_sdf_fd_bwd_sorted with a hipEvent_t (as void*, may be NULL) recorded on `stream` between the
- * two kernels of the backward: behind the MLP part, which occupies every SIMD with one
- * 458-register wave, and in front of the table-gradient scatter, which leaves room.  Work a caller
- * wants to overlap with the backward (the next step's ray march) waits for it. */
-int dsu_sdf_fd_bwd_sorted_mid(const dsu_hashgrid_cfg* cfg, const void* table_f16,
-                              const dsu_sdf_mlp* mlp, const float* pts_sorted, const int32_t* perm,
-                              int64_t n, float radius, float eps, uint32_t active_levels,
-                              const float* d_sdf, const float* d_grad, const float* d_feature,
-                              const float* d_laplace, float* grad_table, float* g_w0, float* g_b0,
-                              float* g_w1, float* g_b1, void* workspace, int64_t workspace_bytes,
-                              const void* enc_cache, void* mid_event, void* stream);
-
-/* dsu_sdf_fd_bwd_sorted_mid whose scatter launch also carries out `extra` (may be NULL), a deferred
- * partial sum of ANOTHER kernel that precedes this call on `stream` (the native NSR step passes the
- * texture backward's: dsu_texture_bwd_shaded_partials_m).  The backward's own partial sums always
- * ride in that launch.  DSU_EUNSUP with `extra` on the fused / VALU variants. */
+/* dsu_sdf_fd_bwd_sorted with two optional extras (dsu_sdf_fd_bwd_sorted passes NULL for both).
+ * `mid_event`: a hipEvent_t (as void*, may be NULL) recorded on `stream` between the two kernels of
+ * the backward: behind the MLP part, which fills every SIMD, and in front of the table-gradient
+ * scatter, which leaves room.  Work a caller wants to overlap with the backward (the next step's ray
+ * march) waits for it.  `extra` (may be NULL): a deferred partial sum of ANOTHER kernel that precedes
+ * this call on `stream` (the native NSR step passes the texture backward's:
+ * dsu_texture_bwd_shaded_partials_m), carried out by the scatter launch.  The backward's own partial
+ * sums always ride in that launch.  DSU_EUNSUP with `extra` and n == 0. */
 int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f16,
                                const dsu_sdf_mlp* mlp, const float* pts_sorted, const int32_t* perm,
                                int64_t n, float radius, float eps, uint32_t active_levels,
@@ -243,7 +210,7 @@ int dsu_sdf_fd_bwd_sorted_fold(const dsu_hashgrid_cfg* cfg, const void* table_f1
                                const void* enc_cache, void* mid_event,
                                const dsu_partial_reduce* extra, void* stream);
 
-/* Bytes of device scratch dsu_sdf_fd_bwd needs for n points (per-workgroup partial MLP
+/* Bytes of device scratch dsu_sdf_fd_bwd_sorted needs for n points (per-workgroup partial MLP
  * gradients, summed by a second kernel: deterministic, no same-address atomics).  <0 = error. */
 int64_t dsu_sdf_fd_bwd_workspace_bytes(const dsu_hashgrid_cfg* cfg, int64_t n);
 
@@ -397,11 +364,6 @@ int dsu_shade_prep_fwd(const float* grad, const float* feature, int64_t n, float
                        float* tex_in, void* stream);
 int dsu_shade_prep_bwd(const float* grad, const float* d_normal, const float* d_tex_in, int64_t n,
                        float* d_grad, float* d_feature, void* stream);
-/* The same, and rows [n, n + tail_rows) of d_feature set to zero: the regulariser points that
- * share the geometry launch with the n ray samples (neus.py:155-162) receive no feature gradient. */
-int dsu_shade_prep_bwd_tail(const float* grad, const float* d_normal, const float* d_tex_in,
-                            int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
-                            void* stream);
 
 /* VolumeRadiance (2_charactor_reconstructor/instant_nsr/models/texture.py:9-30): VanillaMLP
  * 16 -> 64 -> 64 -> 3, ReLU, no weight norm (models/network_utils.py:94-138), then sigmoid.
@@ -700,28 +662,18 @@ int dsu_mv_attention_fwd(const void* q, const void* k, const void* vt, void* out
  *   upsample2x != 0: the convolution reads the nearest-neighbour x2 upsampled input
  *   (Upsample2D = F.interpolate(scale 2, nearest) + conv) without materialising it.
  *   addvec (B,O) f16 or NULL: added per image and channel (time-embedding projection of
- *   ResnetBlock2D); residual (B,OH,OW,O) f16 or NULL: added last.  C % 8 == 0. */
-int dsu_conv2d_nhwc_f16_fwd(const void* input, const void* weight_okc, const void* bias,
-                            int32_t B, int32_t H, int32_t W, int32_t C, int32_t O, int32_t k,
-                            int32_t stride, int32_t pad, int32_t upsample2x, const void* addvec,
-                            const void* residual, void* out, void* stream);
-/* Same convolution with split-K: the k*k*C reduction is divided over `split_k` workgroups per
- * output tile (f32 partials in `workspace`, summed by a second kernel that also applies bias /
- * addvec / residual).  For the 8x8 and 4x4 levels of the UNet the output tiles alone occupy
- * 20-120 of the 256 CUs.  dsu_conv2d_nhwc_f16_split_k returns the factor the library would pick
- * (1 = plain kernel), dsu_conv2d_nhwc_f16_workspace_bytes the f32 scratch it needs. */
+ *   ResnetBlock2D); residual (B,OH,OW,O) f16 or NULL: added last.  C % 8 == 0.
+ * Split-K: the k*k*C reduction is divided over `split_k` workgroups per output tile (f32 partials
+ * in `workspace`, summed by a second kernel that also applies bias / addvec / residual).  For the
+ * 8x8 and 4x4 levels of the UNet the output tiles alone occupy 20-120 of the 256 CUs.
+ * dsu_conv2d_nhwc_f16_split_k returns the factor the library would pick (1 = plain kernel: no
+ * workspace needed), dsu_conv2d_nhwc_f16_workspace_bytes the f32 scratch it needs. */
 int32_t dsu_conv2d_nhwc_f16_split_k(int32_t B, int32_t H, int32_t W, int32_t C, int32_t O,
                                     int32_t k, int32_t stride, int32_t pad, int32_t upsample2x);
 int64_t dsu_conv2d_nhwc_f16_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t O, int32_t k,
                                             int32_t stride, int32_t pad, int32_t upsample2x,
                                             int32_t split_k);
-int dsu_conv2d_nhwc_f16_fwd_ws(const void* input, const void* weight_okc, const void* bias,
-                               int32_t B, int32_t H, int32_t W, int32_t C, int32_t O, int32_t k,
-                               int32_t stride, int32_t pad, int32_t upsample2x,
-                               const void* addvec, const void* residual, void* out,
-                               int32_t split_k, void* workspace, int64_t workspace_bytes,
-                               void* stream);
-/* Split-K with the reduction inside the kernel: `tile_counters` is a caller-owned, ZEROED int32
+/* The reduction can also run inside the kernel: `tile_counters` is a caller-owned, ZEROED int32
  * buffer of at least (output tiles) entries that stays allocated between calls; the last workgroup
  * of a tile to finish sums the split_k partial tiles (in z order) and runs the epilogue, then
  * resets the tile's counter — no separate reduce launch.  One buffer serves every launch issued
@@ -732,10 +684,6 @@ int dsu_conv2d_nhwc_f16_fwd_fx(const void* input, const void* weight_okc, const 
                                const void* addvec, const void* residual, void* out,
                                int32_t split_k, void* workspace, int64_t workspace_bytes,
                                int32_t* tile_counters, int64_t n_counters, void* stream);
-int dsu_gemm_f16_fwd_fx(const void* x, const void* w, const void* bias, int64_t M, int32_t K,
-                        int32_t N, const void* residual, void* out, int32_t tokens_per_image,
-                        int32_t split_k, void* workspace, int64_t workspace_bytes,
-                        int32_t* tile_counters, int64_t n_counters, void* stream);
 
 /* nn.Linear forward of the UNet's transformer blocks and embedding MLPs on the same MFMA kernel
  * (a 1x1 convolution over M rows): Attention.to_q / to_k / to_out, FeedForward.net.2,
@@ -746,13 +694,14 @@ int dsu_gemm_f16_fwd_fx(const void* x, const void* w, const void* bias, int64_t 
  *   tokens_per_image > 0 (M a multiple of it): out is written TRANSPOSED per image,
  *   out[(m / tokens) * N * tokens + n * tokens + m % tokens] — Attention.to_v, so that
  *   dsu_mv_attention_fwd reads V^T rows in place; no residual / split-K in that form.
- *   split_k / workspace as for dsu_conv2d_nhwc_f16_fwd_ws (dsu_gemm_f16_split_k = the library's
- *   choice, dsu_gemm_f16_workspace_bytes = f32 scratch). */
+ *   split_k / workspace / tile_counters as for dsu_conv2d_nhwc_f16_fwd_fx (dsu_gemm_f16_split_k =
+ *   the library's choice, dsu_gemm_f16_workspace_bytes = f32 scratch). */
 int32_t dsu_gemm_f16_split_k(int64_t M, int32_t K, int32_t N);
 int64_t dsu_gemm_f16_workspace_bytes(int64_t M, int32_t N, int32_t split_k);
-int dsu_gemm_f16_fwd(const void* x, const void* w, const void* bias, int64_t M, int32_t K, int32_t N,
-                     const void* residual, void* out, int32_t tokens_per_image, int32_t split_k,
-                     void* workspace, int64_t workspace_bytes, void* stream);
+int dsu_gemm_f16_fwd_fx(const void* x, const void* w, const void* bias, int64_t M, int32_t K,
+                        int32_t N, const void* residual, void* out, int32_t tokens_per_image,
+                        int32_t split_k, void* workspace, int64_t workspace_bytes,
+                        int32_t* tile_counters, int64_t n_counters, void* stream);
 /* diffusers FeedForward(activation_fn="geglu") first layer fused with its activation
  * (transformer_mv2d.py:483 -> GEGLU.forward): w (2N, K), bias (2N) or NULL;
  * out (M, N) = (x w[:N]^T + b[:N]) * gelu_erf(x w[N:]^T + b[N:]); both halves are rounded to f16
@@ -965,9 +914,6 @@ int dsu_nsr_driver_timing_flops(dsu_nsr_driver* d, int32_t family, double* mlp_f
  * ignored): the refresh of every 16th step without leaving the native path. */
 int dsu_nsr_driver_occ_refresh(dsu_nsr_driver* d, const dsu_occgrid_refresh_args* args,
                                void* main_stream);
-/* Wait for the side stream and drop a pending prefetch (before the caller changes the ray count,
- * the dataset or the occupancy grid behind the driver's back). */
-int dsu_nsr_driver_sync(dsu_nsr_driver* d);
 
 /* mcubes.smooth on the export's binary volume (MarchingCubeHelper.forward,
  * instant_nsr/models/geometry.py:57-58 -> PyMCubes' constrained smoothing): the weighted-Jacobi

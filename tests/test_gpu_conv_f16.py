@@ -101,7 +101,7 @@ def test_conv_f16_split_k_heuristic():
 
 
 # ---------------------------------------------------------------------------------------------
-# The UNet's linear layers on the same MFMA kernel (dsu_gemm_f16_fwd / dsu_gemm_geglu_fwd)
+# The UNet's linear layers on the same MFMA kernel (dsu_gemm_f16_fwd_fx / dsu_gemm_geglu_fwd)
 # ---------------------------------------------------------------------------------------------
 @gpu
 @pytest.mark.parametrize("M,K,N", [(12 * 1024, 320, 320), (12 * 256, 640, 640), (12 * 16, 1280, 1280),

@@ -26,6 +26,9 @@ def test_library_exports_every_declared_symbol():
     # and the ctypes prototype table covers the header (a new function cannot be forgotten)
     missing = [n for n in names if n not in _lib._PROTOS and n != "dsu_strerror"]
     assert not missing, missing
+    # ... and names nothing the header does not declare (a removed function cannot linger)
+    undeclared = [n for n in _lib._PROTOS if n not in names]
+    assert not undeclared, undeclared
     lib = _lib.lib()
     assert lib.dsu_abi_version() >= 1
     assert lib.dsu_strerror(-1).decode() == "invalid argument"
