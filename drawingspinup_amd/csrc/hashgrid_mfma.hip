@@ -25,6 +25,7 @@
 // (contraction over points = lanes) go through LDS, 32 points at a time.
 #include "hashgrid_dev.h"
 #include "partial_reduce.h"
+#include "tr_stage.h"
 
 #include <type_traits>
 
@@ -648,7 +649,7 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 //     of the centre's 13: their own body without the 13-wide output arrays, the feature-gradient
 //     rows and the gW1 GEMM; the centre evaluation keeps a body of its own.
 //   * ACT is a template parameter: layer 0 walks ACT + 2 k-pairs without a branch per level.
-//   * Two waves per SIMD (at most 256 registers per lane, 77 KB of LDS per workgroup: two workgroups
+//   * Two waves per SIMD (at most 256 registers per lane, 65 KB of LDS per workgroup: two workgroups
 //     per CU, or one beside another kernel's).  The weight fragments every wave reads are staged once
 //     per workgroup in LDS in the layout the MFMAs read (one 16-byte fragment per lane) and loaded per
 //     use; only the parameter-gradient accumulators live in registers for the whole launch.  The two
@@ -660,14 +661,16 @@ __global__ __launch_bounds__(256) void sdf_fd_bwd_mfma_kernel(
 // sdf_fd_bwd_mfma_kernel<NL, true>, tests/test_gpu_hashgrid.py).
 // The contractions over the points (gW0, and gW1 of the centre) and dIn, dPre of the centre and layer 0
 // of the recompute (ACT <= 6: its 2 KPA inputs fit one 16-deep MFMA) run as bf16 x 3 on
-// v_mfma_f32_32x32x16_bf16.  Operands of the contractions staged TRANSPOSED per wave:
-//   dPre^T (or H^T) [hi|mid][64 units][PT_ROW] bf16 — the hi / mid fragments the dIn product splits anyway —,
-//   In'^T [hi|mid][32 input columns][PT_ROW] (rows nobody writes stay zero for the launch); the centre's
-//   dOut^T borrows rows 0..12 of the In' image for its gW1 contraction and puts the zero rows back,
-// PT_ROW = 40 (80-byte rows: the 16-byte fragments of 16 lanes fall on 16 different bank quads).
-constexpr int PT_ROW = 40;
-constexpr int PT_IMGD = 2 * 64 * PT_ROW, PT_IMGI = 2 * 32 * PT_ROW;      // bf16 elements
-constexpr int PIPE_IMG_F = (PT_IMGD + PT_IMGI) / 2;                      // floats per wave (3840)
+// v_mfma_f32_32x32x16_bf16.  Operands of the contractions staged per wave as [point][column] images
+// (tr_stage.h: packed 8-byte stores of four units or columns, fragments read back transposed with
+// ds_read_b64_tr_b16; both conflict-free):
+//   dPre (or H) [hi|mid][32 points][64 units] bf16 — the hi / mid fragments the dIn product splits anyway —,
+//   In' [hi|mid][32 points][32 input columns] (columns nobody writes stay zero for the launch); the centre's
+//   dOut borrows the 13 columns no input uses for its gW1 contraction and puts the zeros back.
+typedef trs::Img<64> ImgD;
+typedef trs::Img<32> ImgI;
+constexpr int PT_IMGD_B = 2 * ImgD::PART_B, PT_IMGI_B = 2 * ImgI::PART_B;   // bytes: 8192, 4096
+constexpr int PIPE_IMG_F = (PT_IMGD_B + PT_IMGI_B) / 4;                     // floats per wave (3072)
 // shared weights (floats): layer 0 [T][hi|mid][lane] bf16x8 (<= 6 levels) or [T][k-pair][lane] f32 (7)
 // | W1^T [T][hi|mid][lane] bf16x8 | W0'^T [T][g][hi|mid][lane] bf16x8 | W1 row 0 [64]
 constexpr int PW_W0 = 0;
@@ -675,10 +678,13 @@ constexpr int PW_W1T = PW_W0 + 2 * 9 * 64;
 constexpr int PW_W0T = PW_W1T + 2 * 2 * 64 * 4;
 constexpr int PW_W1O0 = PW_W0T + 2 * 2 * 2 * 64 * 4;
 constexpr int PW_F = PW_W1O0 + 64;
-constexpr int PIPE_LDS_F = PW_F + 4 * PIPE_IMG_F;
+// (the workgroup reduction's four partial vectors are 256 bytes larger than weights + images)
+constexpr int PIPE_LDS_F = PW_F + 4 * PIPE_IMG_F > 4 * PART_STRIDE ? PW_F + 4 * PIPE_IMG_F : 4 * PART_STRIDE;
 static_assert(PIPE_LDS_F * sizeof(float) <= 80 * 1024, "two workgroups per CU");
 static_assert(4 * PART_STRIDE <= PIPE_LDS_F, "the workgroup reduction reuses the LDS");
 static_assert(PW_W1T % 4 == 0 && PW_W0T % 4 == 0 && PW_F % 4 == 0, "16-byte fragments");
+static_assert(PW_F * 4 % ImgD::ROW_B == 0 && PIPE_IMG_F * 4 % ImgD::ROW_B == 0 && PT_IMGD_B % ImgI::ROW_B == 0,
+              "image bases: multiples of the row (tr_stage.h)");
 
 // (7 levels, f32 layer 0: two waves per SIMD would spill ~28 registers; that instantiation stays at one)
 template <int NL, int ACT>
@@ -695,7 +701,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
   auto gw1_col = [](int o) { return o < 8 ? 2 * NL + 4 + o : 2 * ACT + (o - 8); };
   static_assert(2 * NL + 4 + 8 == 32 && 2 * ACT + NOUT - 8 <= 2 * NL, "gW1 columns free of inputs");
   constexpr bool L0BF = 2 * KPA <= 16;
-  __shared__ __attribute__((aligned(16))) float lds[PIPE_LDS_F];
+  __shared__ __attribute__((aligned(128))) float lds[PIPE_LDS_F];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   // weight reads go through `wo` (always 0), made opaque to the compiler at every point half: it would
@@ -775,9 +781,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
       }
     }
   }
-  __bf16* imgD = reinterpret_cast<__bf16*>(lds + PW_F + wave * PIPE_IMG_F);
-  __bf16* imgI = imgD + PT_IMGD;
-  for (int t = lane; t < PT_IMGI / 2; t += 64) reinterpret_cast<uint32_t*>(imgI)[t] = 0u;
+  // the wave's images (tr_stage.h), as LDS byte addresses: where the lane stores the row of the point
+  // in its column (slot bit 0 of the dPre image = the lane half's unit quad), and where it reads
+  {
+    uint32_t* imgI0 = reinterpret_cast<uint32_t*>(lds + PW_F + wave * PIPE_IMG_F) + PT_IMGD_B / 4;
+    for (int t = lane; t < PT_IMGI_B / 4; t += 64) imgI0[t] = 0u;
+  }
+  const uint32_t ldsD = __builtin_amdgcn_readfirstlane(trs::lds_addr(lds + PW_F + wave * PIPE_IMG_F));
+  const uint32_t ldsI = ldsD + PT_IMGD_B;
+  const uint32_t stD = ldsD + (ImgD::store_base(l31) ^ (8 * h));
+  // (the addresses used once or twice per point half are worked out where they are used, from a lane
+  // number the compiler cannot see through: kept for the whole launch they cost registers the kernel
+  // does not have at two waves per SIMD)
+  auto lane_again = [&]() {
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    return l;
+  };
   __syncthreads();
 
   // ONE accumulator tile pair for both contractions over the points: gw0[Ti][unit][column] holds gW0 in
@@ -867,16 +887,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
       }
     }
   };
-  // dPre x sigmoid of hidden tile T -> dIn MFMAs (bf16 x 3) and the hi / mid fragments -> dPre^T image
+  // dPre x sigmoid of hidden tile T -> dIn MFMAs (bf16 x 3) and the hi / mid fragments -> dPre image
   // (registers 8 g + t of tile T = units 32 T + (t & 3) + 8 (2 g + (t >> 2)) + 4 h of the point in
-  // column l31; two-byte stores at compile-time offsets)
+  // column l31: t = 0..3 and t = 4..7 are the slots 8 T + 4 g + h and 8 T + 4 g + 2 + h of its row)
   auto stage_dpre_T = [&](int T, int g, const bf16x8& bh, const bf16x8& bm) {
-    __bf16* base = imgD + 4 * h * PT_ROW + l31;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int u = 32 * T + (t & 3) + 8 * (2 * g + (t >> 2));
-      base[u * PT_ROW] = bh[t];
-      base[(64 + u) * PT_ROW] = bm[t];
+    for (int q = 0; q < 2; ++q) {
+      const int s = 8 * T + 4 * g + 2 * q;
+      trs::store_slot(stD, s, 0, q ? __builtin_shufflevector(bh, bh, 4, 5, 6, 7) : __builtin_shufflevector(bh, bh, 0, 1, 2, 3));
+      trs::store_slot(stD, s, ImgD::PART_B, q ? __builtin_shufflevector(bm, bm, 4, 5, 6, 7) : __builtin_shufflevector(bm, bm, 0, 1, 2, 3));
     }
   };
   auto din_tile = [&](int T, float (&dpre)[16], const f32x16& H, f32x16& din) {
@@ -894,30 +913,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
       stage_dpre_T(T, g, bh, bm);
     }
   };
-  // the lane's own inputs -> rows (input columns) of In'^T: features at their column, (x, y, z, 1) at 2 NL ..
-  auto stage_in_T = [&](const float (&in)[2 * KPA]) {
-    __bf16* base = imgI + l31;
+  // columns 4 s .. 4 s + 3 of the lane's own point -> its row of the In' image, hi and mid
+  auto put_cols = [&](uint32_t stI, int s, const float (&v)[4]) {
+    trs::bf16x4 hi, mid;
 #pragma unroll
-    for (int j = 0; j < 2 * KPA; ++j) {
-      const int row = j < 2 * ACT ? j : 2 * NL + (j - 2 * ACT);
-      const __bf16 hi = (__bf16)in[j];
-      base[row * PT_ROW] = hi;
-      base[(32 + row) * PT_ROW] = (__bf16)(in[j] - (float)hi);
+    for (int c = 0; c < 4; ++c) {
+      const __bf16 hh = (__bf16)v[c];
+      hi[c] = hh;
+      mid[c] = (__bf16)(v[c] - (float)hh);
+    }
+    trs::store_slot(stI, s, 0, hi);
+    trs::store_slot(stI, s, ImgI::PART_B, mid);
+  };
+  // input j of column `col` of the In' image (features at their column, (x, y, z, 1) at 2 NL ..), or -1
+  auto in_of_col = [](int col) {
+    return col < 2 * ACT ? col : (col >= 2 * NL && col < 2 * NL + 4 ? 2 * ACT + (col - 2 * NL) : -1);
+  };
+  // output o whose gW1 column is `col` (gw1_col), or -1
+  auto out_of_col = [](int col) {
+    return col >= 2 * NL + 4 ? col - (2 * NL + 4) : (col >= 2 * ACT && col < 2 * ACT + NOUT - 8 ? 8 + (col - 2 * ACT) : -1);
+  };
+  auto store_base_I = [&]() { return ldsI + ImgI::store_base(lane_again() & 31); };
+  // the lane's own inputs -> the slots of its row that hold an input column (the other columns of
+  // such a slot are gW1 columns: zero outside the centre's gW1 contraction)
+  auto stage_in_T = [&](const float (&in)[2 * KPA]) {
+    const uint32_t stI = store_base_I();
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      float v[4];
+      bool any = false;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = in_of_col(4 * s + c);
+        v[c] = j >= 0 ? in[j >= 0 ? j : 0] : 0.0f;
+        any = any || j >= 0;
+      }
+      if (any) put_cols(stI, s, v);
     }
   };
-  // acc[Ti][unit][column] += imgD^T . imgB over the 32 staged points (bf16 x 3)
-  auto gemm_T = [&](f32x16 (&acc)[2], const __bf16* imgB) {
-    auto frag = [&](const __bf16* img, int row, int ks) {
-      return *reinterpret_cast<const bf16x8*>(img + row * PT_ROW + 16 * ks + 8 * h);
-    };
+  // acc[Ti][unit][column] += dPre^T . In' over the 32 staged points (bf16 x 3): k index 8 h + j of
+  // k-step ks = point 16 ks + 8 h + j
+  auto gemm_T = [&](f32x16 (&acc)[2]) {
+    const int ln = lane_again();
+    const uint32_t rdD = ldsD + ImgD::read_base(ln), rdI = ldsI + ImgI::read_base(ln);
 #pragma unroll
-    for (int S = 0; S < 4; ++S) {
-      const int ks = S >> 1, Ti = S & 1;
-      const bf16x8 bh = frag(imgB, l31, ks), bm = frag(imgB + 32 * PT_ROW, l31, ks);
-      const bf16x8 ah = frag(imgD, 32 * Ti + l31, ks), am = frag(imgD + 64 * PT_ROW, 32 * Ti + l31, ks);
-      acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[Ti], 0, 0, 0);
-      acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[Ti], 0, 0, 0);
-      acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[Ti], 0, 0, 0);
+    for (int ks = 0; ks < 2; ++ks) {
+      const bf16x8 bh = trs::frag_tr<32>(rdI, ks, 0), bm = trs::frag_tr<32>(rdI, ks, 0, ImgI::PART_B);
+#pragma unroll
+      for (int Ti = 0; Ti < 2; ++Ti) {
+        const bf16x8 ah = trs::frag_tr<64>(rdD, ks, Ti), am = trs::frag_tr<64>(rdD, ks, Ti, ImgD::PART_B);
+        acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[Ti], 0, 0, 0);
+        acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[Ti], 0, 0, 0);
+        acc[Ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[Ti], 0, 0, 0);
+      }
     }
   };
 
@@ -1036,7 +1084,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
         // from the hidden activations (split here) and dOut^T (rows 0..12 of the In' image meanwhile)
         if (h == half) stage_in_T(in);
         __builtin_amdgcn_wave_barrier();
-        gemm_T(gw0, imgI);
+        gemm_T(gw0);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int T = 0; T < 2; ++T)
@@ -1049,34 +1097,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
             bf16_split8(hv, bh, bm);
             stage_dpre_T(T, g, bh, bm);
           }
-        if (h == half) {                       // In' rows -> 0, dOut^T into the gW1 rows
-          __bf16* base = imgI + l31;
-#pragma unroll
-          for (int j = 0; j < 2 * KPA; ++j) {
-            const int row = j < 2 * ACT ? j : 2 * NL + (j - 2 * ACT);
-            base[row * PT_ROW] = (__bf16)0.0f;
-            base[(32 + row) * PT_ROW] = (__bf16)0.0f;
-          }
+        if (h == half) {                       // In' columns -> 0, dOut into the gW1 columns
+          const uint32_t stI = store_base_I();
           const float dl_ = valid ? dl : 0.0f;
+          float dv[NOUT];
 #pragma unroll
           for (int o = 0; o < NOUT; ++o) {
             // dOut again from the upstream gradients (the same operations: not kept live through the GEMMs)
             float v = valid && d_feature ? d_feature[gi * NOUT + o] : 0.0f;
             if (o == 0 && valid) v += ds - 6.0f * dl_ / eps2;
-            const __bf16 hi = (__bf16)v;
-            base[gw1_col(o) * PT_ROW] = hi;
-            base[(32 + gw1_col(o)) * PT_ROW] = (__bf16)(v - (float)hi);
+            dv[o] = v;
+          }
+#pragma unroll
+          for (int s = 0; s < 8; ++s) {
+            float v[4];
+            bool any = false;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const int o = out_of_col(4 * s + c);
+              v[c] = o >= 0 ? dv[o >= 0 ? o : 0] : 0.0f;
+              any = any || o >= 0 || in_of_col(4 * s + c) >= 0;
+            }
+            if (any) put_cols(stI, s, v);
           }
         }
         __builtin_amdgcn_wave_barrier();
-        gemm_T(gw0, imgI);
+        gemm_T(gw0);
         __builtin_amdgcn_wave_barrier();
-        if (h == half) {                       // the gW1 rows back to zero
-          __bf16* base = imgI + l31;
+        if (h == half) {                       // the gW1 columns back to zero
+          const uint32_t stI = store_base_I();
+          const float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-          for (int o = 0; o < NOUT; ++o) {
-            base[gw1_col(o) * PT_ROW] = (__bf16)0.0f;
-            base[(32 + gw1_col(o)) * PT_ROW] = (__bf16)0.0f;
+          for (int s = 0; s < 8; ++s) {
+            bool any = false;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) any = any || out_of_col(4 * s + c) >= 0;
+            if (any) put_cols(stI, s, z);
           }
         }
         store_din(0, din, wave_first + half * 32 + l31, r1);
@@ -1171,7 +1227,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACT <= 6 ? 
         }
         if (h == half) stage_in_T(in);
         __builtin_amdgcn_wave_barrier();
-        gemm_T(gw0, imgI);
+        gemm_T(gw0);
         __builtin_amdgcn_wave_barrier();
         store_din(e, din, wave_first + half * 32 + l31, r1);
       }

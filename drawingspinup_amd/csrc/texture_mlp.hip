@@ -20,9 +20,12 @@
 //     of the backward proper.  dH0 = W1^T dPre1 and dIn = W0^T dPre0 take the accumulator of the
 //     previous phase as the B operand as it stands and read the weights from images in LDS; the
 //     parameter-gradient GEMMs gW2, gW1, gW0 (contraction over samples = lanes) go through
-//     transposed per-wave images in LDS, 32 samples at a time.  When the forward handed over the
+//     per-wave [sample][unit] images in LDS, 32 samples at a time: packed 8-byte stores of an
+//     accumulator's register quads, operand fragments through ds_read_b64_tr_b16, which transposes
+//     (tr_stage.h).  When the forward handed over the
 //     ReLU pattern of layer 1 (L1_MASK), the recompute of layer 1 runs this way too.
 #include "common.h"
+#include "tr_stage.h"
 
 namespace {
 
@@ -44,11 +47,12 @@ __device__ __forceinline__ void bf16_split8(const float* x, bf16x8& hi, bf16x8& 
 constexpr int TIN = 16, THID = 64, TOUT = 3;
 // LDS map of the backward kernel, in floats (the forward kernel has the weights only):
 //   [0, L_WEND)             5 576   weights and biases in f32 (load_weights)
-//   [L_WEND, L_IMG1)   4 x 5 920   per-wave staging: the transposed bf16 images X, Y, S
+//   [L_WEND, L_STAGE)          24   padding: the staging images start on a multiple of 128 bytes
+//   [L_STAGE, L_IMG1)  4 x 5 120   per-wave staging: the [sample][column] bf16 images X, Y, S
 //   [L_IMG1, L_IMG0)        4 096   W1 image of dH0
 //   [L_IMG0, L_IMGF)        2 048   W0 image of dIn
 //   [L_IMGF, BWD_LDS_F)     4 096   W1 image of the recompute of layer 1 (written by L1_MASK kernels)
-//   BWD_LDS_F = 39 496 floats = 154 KB of the CU's 160: one workgroup per CU.
+//   BWD_LDS_F = 36 320 floats = 142 KB of the CU's 160: one workgroup per CU.
 // The workgroup reduction at the end of the kernel reuses [0, 4 PART_STRIDE) for four partial images.
 constexpr int W1_ROW = 65;                       // padded row: conflict-free by row AND by column
 constexpr int W0_ROW = 17;
@@ -59,27 +63,29 @@ constexpr int L_B0 = L_W2P + 2 * TOUT * 32;      // 5440
 constexpr int L_B1 = L_B0 + THID;
 constexpr int L_B2 = L_B1 + THID;                // 5568
 constexpr int L_WEND = L_B2 + 8;                 // 5576
-// per-wave staging (backward): transposed bf16 images of the contraction-over-samples GEMMs
-// (gW2, gW1, gW0 as bf16 x 3):
-// [part hi | mid][row = unit (or output / input column)][TROW] bf16, element (row, s) = the value of
-// sample s of the 32-sample half.  TROW = 40 (80-byte rows): the 16-byte fragments of 16 lanes
-// (rows l31, l31 + 1, ...) fall on 16 different bank quads.  Two 64-row images (X, Y) and one
-// 20-row image (S: dz^T, then In^T) per wave.
-constexpr int TROW = 40;
-constexpr int TIMG_B = 2 * 64 * TROW;            // bf16 elements of a 64-row image (hi + mid) = 10 240 B
-constexpr int TSML_B = 2 * 20 * TROW;            // 20-row image
-constexpr int S_X = 0, S_Y = TIMG_B / 2, S_S = TIMG_B;          // float offsets
-constexpr int STAGE_F = TIMG_B + TSML_B / 2;     // 5120 + 800 = 5920 floats
+// per-wave staging (backward): bf16 images of the contraction-over-samples GEMMs (gW2, gW1, gW0 as
+// bf16 x 3), tr_stage.h:
+// [part hi | mid][sample of the 32-sample half][column = unit (or output / input column)] bf16.  A lane
+// stores the four units of an accumulator register quad of its sample packed (8 bytes); the operand
+// fragments — 8 consecutive samples of one column per lane — come back through the transposing read.
+// Stores and reads are conflict-free (computed in tr_stage.h).  Two 64-column images (X, Y) and one
+// 32-column image (S: dz in columns 0..2, then In in columns 0..15 and the ones column 16) per wave.
+typedef trs::Img<64> ImgU;
+typedef trs::Img<32> ImgS;
+constexpr int SB_X = 0, SB_Y = 2 * ImgU::PART_B, SB_S = 4 * ImgU::PART_B;     // byte offsets
+constexpr int STAGE_F = (4 * ImgU::PART_B + 2 * ImgS::PART_B) / 4;            // 5120 floats
+constexpr int L_STAGE = (L_WEND + 31) / 32 * 32;                              // 5600
+static_assert(STAGE_F * 4 % ImgU::ROW_B == 0 && SB_S % ImgS::ROW_B == 0, "image bases: multiples of the row");
 // bf16 images of the backward GEMMs' weight operands, one 16-byte fragment per lane and MFMA:
 //   W1 image [hi|mid][To][Tin][g][lane] : 8 values t -> w1[feat_of(Tin, 8 g + t, h)][32 To + l31]
 //   W0 image [hi|mid][T][g][lane]       : 8 values t -> w0[feat_of(T, 8 g + t, h)][l31] (0 for l31 >= 16)
 constexpr int IMG1_F = 2 * 8 * 64 * 4, IMG0_F = 2 * 4 * 64 * 4;       // floats (16 B = 4 floats per fragment)
-constexpr int L_IMG1 = L_WEND + 4 * STAGE_F;
+constexpr int L_IMG1 = L_STAGE + 4 * STAGE_F;
 constexpr int L_IMG0 = L_IMG1 + IMG1_F;
 //   W1 image of the backward's forward RECOMPUTE (L1_MASK kernels) [hi|mid][To][Tin][g][lane] :
 //   8 values t -> w1[32 To + l31][feat_of(Tin, 8 g + t, h)]
 constexpr int L_IMGF = L_IMG0 + IMG0_F;
-constexpr int BWD_LDS_F = L_IMGF + IMG1_F;       // 39 496 floats = 154 KB
+constexpr int BWD_LDS_F = L_IMGF + IMG1_F;       // 36 320 floats = 142 KB
 // per-workgroup partial vector
 constexpr int P_GW1 = 0, P_GW0 = 64 * 64, P_GW2 = P_GW0 + 64 * 32, P_GB1 = P_GW2 + 64 * 32,
               P_GB2 = P_GB1 + 64, PART_N = P_GB2 + 3, PART_STRIDE = 8320;
@@ -323,31 +329,46 @@ __global__ __launch_bounds__(256) void texture_fwd_kernel(dsu_tex_mlp m,
   }
 }
 
-// rows = hidden units: the lane's 32 values X[T][r] (unit 32 T + (r & 3) + 8 (r >> 2) + 4 h of the
-// sample in column l31) -> bf16 hi / mid at [unit][l31] of a transposed image
-__device__ __forceinline__ void stage_units_T(__bf16* img, const f32x16 (&X)[2], int l31, int h) {
-  __bf16* base = img + 4 * h * TROW + l31;
+// columns = hidden units: the lane's 32 values X[T][r] (unit 32 T + (r & 3) + 8 (r >> 2) + 4 h of the
+// sample in column l31) -> bf16 hi / mid in the sample's row of a 64-column image: registers
+// 4 g .. 4 g + 3 of tile T are slot 8 T + 2 g + h.  st = image address + (store_base(l31) ^ 8 h)
+__device__ __forceinline__ void stage_units_T(uint32_t st, const f32x16 (&X)[2]) {
 #pragma unroll
   for (int T = 0; T < 2; ++T)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int u = 32 * T + (r & 3) + 8 * (r >> 2);
-      const float x = X[T][r];
-      const __bf16 hi = (__bf16)x;
-      base[u * TROW] = hi;
-      base[(64 + u) * TROW] = (__bf16)(x - (float)hi);
+    for (int g = 0; g < 4; ++g) {
+      trs::bf16x4 hi, mid;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float x = X[T][4 * g + c];
+        const __bf16 hh = (__bf16)x;
+        hi[c] = hh;
+        mid[c] = (__bf16)(x - (float)hh);
+      }
+      trs::store_slot(st, 8 * T + 2 * g, 0, hi);
+      trs::store_slot(st, 8 * T + 2 * g, ImgU::PART_B, mid);
     }
 }
-// 16-byte fragment of a transposed image: 8 consecutive samples (k = 16 ks + 8 h ..) of row `row`
-__device__ __forceinline__ bf16x8 frag_T(const __bf16* img, int row, int ks, int h) {
-  return *reinterpret_cast<const bf16x8*>(img + row * TROW + 16 * ks + 8 * h);
+// four columns of the lane's own sample -> slot s of its row of the 32-column image, hi and mid
+__device__ __forceinline__ void stage_cols_S(uint32_t st, int s, float v0, float v1, float v2, float v3) {
+  const float v[4] = {v0, v1, v2, v3};
+  trs::bf16x4 hi, mid;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const __bf16 hh = (__bf16)v[c];
+    hi[c] = hh;
+    mid[c] = (__bf16)(v[c] - (float)hh);
+  }
+  trs::store_slot(st, s, 0, hi);
+  trs::store_slot(st, s, ImgS::PART_B, mid);
 }
-// acc[Ti][Tj] += A^T B over the 32 samples of the half, bf16 x 3: A / B images with 64 / (32 NJ) rows
-// (`rows_b` rows of B are real: lanes beyond them feed zeros)
+// acc[Ti][Tj] += A^T B over the 32 samples of the half, bf16 x 3: A / B images with 64 / (32 NJ) columns,
+// rdA / rdB = image address + read_base(lane): k index 8 h + j of k-step ks = sample 16 ks + 8 h + j.
+// (`cols_b` columns of B are real: lanes beyond them read like the others and feed zeros)
 template <int NJ>
-__device__ __forceinline__ void gemm_samples_T(f32x16 (&acc0)[NJ], f32x16 (&acc1)[NJ], const __bf16* A,
-                                               int a_mid, const __bf16* B, int b_mid, int rows_b,
-                                               int l31, int h) {
+__device__ __forceinline__ void gemm_samples_T(f32x16 (&acc0)[NJ], f32x16 (&acc1)[NJ], uint32_t rdA,
+                                               uint32_t rdB, int cols_b, int l31) {
+  constexpr int CB = 32 * NJ;
   bf16x8 z;
 #pragma unroll
   for (int e = 0; e < 8; ++e) z[e] = (__bf16)0.0f;
@@ -356,14 +377,13 @@ __device__ __forceinline__ void gemm_samples_T(f32x16 (&acc0)[NJ], f32x16 (&acc1
     bf16x8 ah[2], am[2], bh[NJ], bm[NJ];
 #pragma unroll
     for (int Ti = 0; Ti < 2; ++Ti) {
-      ah[Ti] = frag_T(A, 32 * Ti + l31, ks, h);
-      am[Ti] = frag_T(A + a_mid, 32 * Ti + l31, ks, h);
+      ah[Ti] = trs::frag_tr<64>(rdA, ks, Ti);
+      am[Ti] = trs::frag_tr<64>(rdA, ks, Ti, ImgU::PART_B);
     }
 #pragma unroll
     for (int Tj = 0; Tj < NJ; ++Tj) {
-      const int row = 32 * Tj + l31;
-      const bool real = row < rows_b;
-      const bf16x8 vh = frag_T(B, real ? row : 0, ks, h), vm = frag_T(B + b_mid, real ? row : 0, ks, h);
+      const bool real = 32 * Tj + l31 < cols_b;
+      const bf16x8 vh = trs::frag_tr<CB>(rdB, ks, Tj), vm = trs::frag_tr<CB>(rdB, ks, Tj, trs::Img<CB>::PART_B);
       bh[Tj] = real ? vh : z;
       bm[Tj] = real ? vm : z;
     }
@@ -395,12 +415,17 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
     const float* __restrict__ rgb, const float* __restrict__ d_rgb, int64_t n,
     float* __restrict__ d_x, float* __restrict__ partials,
     const uint32_t* __restrict__ h1_mask = nullptr) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+  extern __shared__ __attribute__((aligned(128))) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  float* st = lds + L_WEND + wave * STAGE_F;
-  __bf16* tX = reinterpret_cast<__bf16*>(st + S_X);
-  __bf16* tY = reinterpret_cast<__bf16*>(st + S_Y);
-  __bf16* tS = reinterpret_cast<__bf16*>(st + S_S);
+  // the wave's images X, Y, S (tr_stage.h) as LDS byte addresses: st* = where the lane stores the row
+  // of the sample in its column (X, Y: its lane half's unit quad), rd* = where it reads the fragments,
+  // colY = where it reads the column `lane` of Y
+  const uint32_t stg = trs::lds_addr(lds + L_STAGE + wave * STAGE_F);
+  const uint32_t stX = stg + SB_X + (ImgU::store_base(l31) ^ (8 * h)), stY = stX + (SB_Y - SB_X);
+  const uint32_t stS = stg + SB_S + ImgS::store_base(l31);
+  const uint32_t rdX = stg + SB_X + ImgU::read_base(lane), rdY = rdX + (SB_Y - SB_X);
+  const uint32_t rdS = stg + SB_S + ImgS::read_base(lane);
+  const uint32_t colY = stg + SB_Y + ImgU::col_base(lane);
   load_weights(lds, m);
   __syncthreads();
   {   // bf16 hi / mid fragments of W1 and W0 in the order the backward MFMAs consume them
@@ -523,45 +548,38 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
           D1[T][r] = (L1_MASK ? ((mk >> (16 * T + r)) & 1u) != 0u : H1[T][r] > 0.0f) ? v : 0.0f;
         }
       // ---- gW2^T[unit][o] += sum_samples H1[sample][unit] * dz[sample][o]
-      // bf16 x 3 on v_mfma_f32_32x32x16_bf16 (K = 16 samples per MFMA): H1 and dz go to LDS
-      // TRANSPOSED ([unit][sample], bf16 hi / mid, two-byte stores at compile-time offsets), so that
-      // a lane's operand fragment — 8 consecutive samples of one row — is one 16-byte read.
+      // bf16 x 3 on v_mfma_f32_32x32x16_bf16 (K = 16 samples per MFMA): H1 and dz go to LDS as
+      // [sample][unit] images (bf16 hi / mid, packed 8-byte stores), and a lane's operand fragment —
+      // 8 consecutive samples of one unit — comes back through two transposing reads.
       // 12 MFMAs of 32 clocks instead of 32 of 64.
       __builtin_amdgcn_wave_barrier();
-      stage_units_T(tX, H1, l31, h);
-      if (h == a) {
-#pragma unroll
-        for (int o = 0; o < TOUT; ++o) {
-          const __bf16 hi = (__bf16)dz[o];
-          tS[o * TROW + l31] = hi;
-          tS[(20 + o) * TROW + l31] = (__bf16)(dz[o] - (float)hi);
-        }
-      }
+      stage_units_T(stX, H1);
+      if (h == a) stage_cols_S(stS, 0, dz[0], dz[1], dz[2], 0.0f);
       __builtin_amdgcn_wave_barrier();
       {
         f32x16 (&g0)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw2[0]);
         f32x16 (&g1)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw2[1]);
-        gemm_samples_T<1>(g0, g1, tX, 64 * TROW, tS, 20 * TROW, TOUT, l31, h);
+        gemm_samples_T<1>(g0, g1, rdX, rdS, TOUT, l31);
       }
       // ---- gW1[i][j] += sum_samples dPre1[sample][i] * H0[sample][j]
       __builtin_amdgcn_wave_barrier();           // (the gW2 reads of X are done: in-order LDS queue of the wave)
-      stage_units_T(tY, D1, l31, h);
-      stage_units_T(tX, H0, l31, h);
+      stage_units_T(stY, D1);
+      stage_units_T(stX, H0);
       __builtin_amdgcn_wave_barrier();
-      {   // gb1[unit] += sum over the half's samples of dPre1: lane u adds up row u of the image it was
-          // just staged into (hi + mid: 2^-16 relative, like the products) — one accumulator per lane
-          // instead of 32 per-column partial sums
+      {   // gb1[unit] += sum over the half's samples of dPre1: lane u adds up column u of the image it was
+          // just staged into (hi + mid: 2^-16 relative, like the products), samples 0 .. 31 in order — one
+          // accumulator per lane instead of 32 per-column partial sums
         float srow = 0.0f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const bf16x8 vh = *reinterpret_cast<const bf16x8*>(tY + lane * TROW + 8 * q);
-          const bf16x8 vm = *reinterpret_cast<const bf16x8*>(tY + (64 + lane) * TROW + 8 * q);
+        for (int P0 = 0; P0 < 32; P0 += 4) {
+          const uint32_t a4 = (colY ^ (uint32_t)ImgU::col_xor(P0)) + P0 * ImgU::ROW_B;
+          const trs::bf16x4 vh = trs::read_tr(a4), vm = trs::read_tr(a4 + ImgU::PART_B);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) srow += (float)vh[e] + (float)vm[e];
+          for (int e = 0; e < 4; ++e) srow += (float)vh[e] + (float)vm[e];
         }
         gb1row += srow;
       }
-      gemm_samples_T<2>(gw1[0], gw1[1], tY, 64 * TROW, tX, 64 * TROW, 64, l31, h);   // 24 MFMAs instead of 64
+      gemm_samples_T<2>(gw1[0], gw1[1], rdY, rdX, 64, l31);   // 24 MFMAs instead of 64
       // ---- dH0^T = W1^T . dPre1^T, then dPre0 = dH0 * relu'(H0)
       f32x16 D0[2];
 #pragma unroll
@@ -602,22 +620,17 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
         for (int r = 0; r < 16; ++r) D0[T][r] = H0[T][r] > 0.0f ? D0[T][r] : 0.0f;
       // ---- gW0[i][k] += sum_samples dPre0[sample][i] * In[sample][k]  (k = 16: ones -> gb0)
       __builtin_amdgcn_wave_barrier();
-      stage_units_T(tY, D0, l31, h);
+      stage_units_T(stY, D0);
       if (h == a) {
 #pragma unroll
-        for (int k = 0; k < TIN; ++k) {
-          const __bf16 hi = (__bf16)in[k];
-          tS[k * TROW + l31] = hi;
-          tS[(20 + k) * TROW + l31] = (__bf16)(in[k] - (float)hi);
-        }
-        tS[TIN * TROW + l31] = (__bf16)1.0f;               // the ones column -> gb0
-        tS[(20 + TIN) * TROW + l31] = (__bf16)0.0f;
+        for (int s = 0; s < TIN / 4; ++s) stage_cols_S(stS, s, in[4 * s], in[4 * s + 1], in[4 * s + 2], in[4 * s + 3]);
+        stage_cols_S(stS, TIN / 4, 1.0f, 0.0f, 0.0f, 0.0f);  // the ones column -> gb0
       }
       __builtin_amdgcn_wave_barrier();
       {
         f32x16 (&g0)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw0[0]);
         f32x16 (&g1)[1] = *reinterpret_cast<f32x16 (*)[1]>(&gw0[1]);
-        gemm_samples_T<1>(g0, g1, tY, 64 * TROW, tS, 20 * TROW, TIN + 1, l31, h);   // 12 MFMAs instead of 32
+        gemm_samples_T<1>(g0, g1, rdY, rdS, TIN + 1, l31);   // 12 MFMAs instead of 32
       }
       // ---- dIn^T = W0^T . dPre0^T : row k = (r&3) + 8(r>>2) + 4h of the sample in column l31
       f32x16 din;
