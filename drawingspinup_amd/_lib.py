@@ -228,8 +228,6 @@ _PROTOS = {
     "dsu_spatial_sort": [P, c_i64, c_f32, c_i32, P, P, P, c_i64, P],
     "dsu_spatial_sort_workspace_bytes": [c_i64, c_i32],
     "dsu_ray_aabb": [P, P, c_i64, P, P, c_f32, P, P, P],
-    "dsu_ray_march_count": [P, P, P, P, c_i64, P, P, c_i32, c_f32, P, P],
-    "dsu_ray_march_fill": [P, P, P, P, c_i64, P, P, c_i32, c_f32, P, P, P, P, P],
     "dsu_ray_march_scratch": [P, P, P, P, c_i64, P, P, c_i32, c_f32, c_i32, P, P, P, P],
     "dsu_ray_compact": [P, P, c_i32, P, P, c_i64, P, P, P, P],
     "dsu_ray_compact_points": [P, P, c_i32, P, P, c_i64, P, P, P, P, P, P],

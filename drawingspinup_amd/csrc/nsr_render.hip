@@ -100,8 +100,8 @@ __global__ void ray_aabb_kernel(const float* __restrict__ ro, const float* __res
   tmax_o[i] = far;
 }
 
-// MODE 0: count only; 1: fill at offsets[i]; 2: single pass — fill a fixed-capacity scratch row
-// (i * cap) AND write the count, so the serial march runs once (compacted by ray_compact_kernel)
+// One pass: ray i fills its fixed-capacity scratch row (t_starts / t_ends at i * cap, the samples
+// past `cap` dropped) and writes its count; ray_compact_kernel packs the rows afterwards.
 //
 // A group of G = MARCH_G = 64 lanes, one wave, marches one ray.  The serial rule is one dependent
 // occupancy byte load per lattice point or per skipped voxel, ~600 lattice points per ray: with one
@@ -150,12 +150,12 @@ __device__ __forceinline__ float group_bcast(float v, int src_lane) {
       __builtin_bit_cast(int, v), __builtin_amdgcn_readfirstlane(src_lane)));
 }
 
-template <int MODE, bool HAS_OCC, bool P2>
+template <bool HAS_OCC, bool P2>
 __global__ __launch_bounds__(256) void ray_march_kernel(
     const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ tmin,
     const float* __restrict__ tmax, int64_t n, Aabb a, const uint8_t* __restrict__ occ, int res,
-    float step, const int32_t* __restrict__ offsets, int cap, int32_t* __restrict__ num_steps,
-    int64_t* __restrict__ ray_indices, float* __restrict__ t_starts, float* __restrict__ t_ends) {
+    float step, int cap, int32_t* __restrict__ num_steps, float* __restrict__ t_starts,
+    float* __restrict__ t_ends) {
   constexpr int G = MARCH_G;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);       // lane within the group
@@ -167,9 +167,7 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
   const float d[3] = {rd[i * 3], rd[i * 3 + 1], rd[i * 3 + 2]};
   const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
   const float near = tmin[i], far = tmax[i];
-  int64_t base = 0;
-  if (MODE == 1) base = offsets[i];
-  if (MODE == 2) base = i * (int64_t)cap;
+  const int64_t base = i * (int64_t)cap;
   const float dt = step;  // cone_angle == 0: calc_dt clamps to dt_min
   // group-uniform state
   int j = 0;
@@ -193,10 +191,9 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
       const uint64_t past_far = __ballot(!before_far);
       const uint64_t stops = __ballot(!accept) & gmask;
       const int s = stops ? __ffsll((unsigned long long)stops) - 1 - g0 : G;   // accepted run
-      if (gl < s && (MODE == 1 || (MODE == 2 && j + gl < cap))) {
+      if (gl < s && j + gl < cap) {
         t_starts[base + j + gl] = e0;
         t_ends[base + j + gl] = e1;
-        if (MODE == 1) ray_indices[base + j + gl] = i;
       }
       j += s;
       if (s == G) {                              // all accepted: (e_G, e_{G+1}, their midpoint)
@@ -242,7 +239,7 @@ __global__ __launch_bounds__(256) void ray_march_kernel(
       }
     }
   }
-  if (MODE != 1 && gl == 0) num_steps[i] = j;
+  if (gl == 0) num_steps[i] = j;
 }
 
 // one wave per ray: scratch rows -> packed samples
@@ -657,18 +654,18 @@ Aabb make_aabb(const float* a6, int res = 1) {
 
 // march kernel variant: occupancy grid present or not, power-of-two box (exact reciprocal
 // multiplies instead of IEEE divisions).  256-thread workgroups: four rays at one wave per ray.
-#define DSU_MARCH_ONE(M, O, P, nr, st, ...)                                                 \
-  ray_march_kernel<M, O, P><<<dsu_blocks_for(nr, 256 / MARCH_G), 256, 0,                    \
-                              (hipStream_t)st>>>(__VA_ARGS__)
-#define DSU_LAUNCH_MARCH(M, nr, st, box, occp, ...)                                   \
+#define DSU_MARCH_ONE(O, P, nr, st, ...)                                                    \
+  ray_march_kernel<O, P><<<dsu_blocks_for(nr, 256 / MARCH_G), 256, 0,                       \
+                           (hipStream_t)st>>>(__VA_ARGS__)
+#define DSU_LAUNCH_MARCH(nr, st, box, occp, ...)                                      \
   do {                                                                                \
     const bool p2_ = (box).pow2 != 0;                                                 \
     if (!(occp)) {                                                                    \
-      if (p2_) DSU_MARCH_ONE(M, false, true, nr, st, __VA_ARGS__);                    \
-      else DSU_MARCH_ONE(M, false, false, nr, st, __VA_ARGS__);                       \
+      if (p2_) DSU_MARCH_ONE(false, true, nr, st, __VA_ARGS__);                       \
+      else DSU_MARCH_ONE(false, false, nr, st, __VA_ARGS__);                          \
     } else {                                                                          \
-      if (p2_) DSU_MARCH_ONE(M, true, true, nr, st, __VA_ARGS__);                     \
-      else DSU_MARCH_ONE(M, true, false, nr, st, __VA_ARGS__);                        \
+      if (p2_) DSU_MARCH_ONE(true, true, nr, st, __VA_ARGS__);                        \
+      else DSU_MARCH_ONE(true, false, nr, st, __VA_ARGS__);                           \
     }                                                                                 \
   } while (0)
 
@@ -685,37 +682,6 @@ int dsu_ray_aabb(const float* rays_o, const float* rays_d, int64_t n_rays, const
   return DSU_OK;
 }
 
-int dsu_ray_march_count(const float* rays_o, const float* rays_d, const float* t_min,
-                        const float* t_max, int64_t n_rays, const float* aabb6,
-                        const uint8_t* occ_binary, int32_t res, float step,
-                        int32_t* num_steps, void* stream) {
-  if (n_rays < 0 || !aabb6 || !(step > 0.0f) || (occ_binary && res <= 0)) return DSU_EINVAL;
-  if (n_rays && (!rays_o || !rays_d || !t_min || !t_max || !num_steps)) return DSU_EINVAL;
-  if (n_rays == 0) return DSU_OK;
-  const Aabb box = make_aabb(aabb6, occ_binary ? res : 1);
-  DSU_LAUNCH_MARCH(0, n_rays, stream, box, occ_binary, rays_o, rays_d, t_min, t_max,
-                   n_rays, box,
-                   occ_binary, res, step, nullptr, 0, num_steps, nullptr, nullptr, nullptr);
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_ray_march_fill(const float* rays_o, const float* rays_d, const float* t_min,
-                       const float* t_max, int64_t n_rays, const float* aabb6,
-                       const uint8_t* occ_binary, int32_t res, float step,
-                       const int32_t* offsets, int64_t* ray_indices, float* t_starts,
-                       float* t_ends, void* stream) {
-  if (n_rays < 0 || !aabb6 || !(step > 0.0f) || (occ_binary && res <= 0)) return DSU_EINVAL;
-  if (n_rays && (!rays_o || !rays_d || !t_min || !t_max || !offsets)) return DSU_EINVAL;
-  if (n_rays == 0) return DSU_OK;
-  const Aabb box = make_aabb(aabb6, occ_binary ? res : 1);
-  DSU_LAUNCH_MARCH(1, n_rays, stream, box, occ_binary, rays_o, rays_d, t_min, t_max,
-                   n_rays, box,
-                   occ_binary, res, step, offsets, 0, nullptr, ray_indices, t_starts, t_ends);
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
 int dsu_ray_march_scratch(const float* rays_o, const float* rays_d, const float* t_min,
                           const float* t_max, int64_t n_rays, const float* aabb6,
                           const uint8_t* occ_binary, int32_t res, float step, int32_t capacity,
@@ -728,9 +694,8 @@ int dsu_ray_march_scratch(const float* rays_o, const float* rays_d, const float*
     return DSU_EINVAL;
   if (n_rays == 0) return DSU_OK;
   const Aabb box = make_aabb(aabb6, occ_binary ? res : 1);
-  DSU_LAUNCH_MARCH(2, n_rays, stream, box, occ_binary, rays_o, rays_d, t_min, t_max,
-                   n_rays, box,
-                   occ_binary, res, step, nullptr, capacity, num_steps, nullptr, scratch_t_starts, scratch_t_ends);
+  DSU_LAUNCH_MARCH(n_rays, stream, box, occ_binary, rays_o, rays_d, t_min, t_max, n_rays, box,
+                   occ_binary, res, step, capacity, num_steps, scratch_t_starts, scratch_t_ends);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

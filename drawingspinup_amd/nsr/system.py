@@ -31,8 +31,8 @@ VIEWS = ["front", "front_right", "right", "back", "left", "front_left"]
 # fused step (0 would keep the marcher's ray-major order).
 _SPATIAL_SORT_BITS = 6
 
-# capacity (samples) of the fixed-size buffers the prefetch path packs into: 2x the schedule's
-# target of 2^18 samples per step; a step that exceeds it is re-packed on the main stream
+# capacity (samples) of the fixed-size buffers the native driver packs into: 2x the schedule's
+# target of 2^18 samples per step; a step that exceeds it is retried with half the rays
 _PACK_CAPACITY = 1 << 19
 
 _AZIMUTH = {"front": 0.0, "front_right": 45.0, "right": 90.0, "back": 180.0, "left": 270.0,
@@ -183,63 +183,6 @@ class _LazyLoss:
         return float(self.detach())
 
     item = __float__
-
-
-class RayLossGraph:
-    """HIP-graph capture of OrthoNeuSSystem.ray_losses + d(loss)/d(comp) on fixed-capacity
-    buffers.  The ray count changes every step (dynamic ray sampling), so the tensors are padded
-    to `capacity` rows and the real rows are marked from a device-side count; replaying the graph
-    is ONE host call instead of ~200 small launches."""
-
-    KEYS = ("rgb", "normal", "mask", "cosines", "view_weights")
-
-    def __init__(self, system, capacity):
-        self.system, self.capacity = system, capacity
-        dev = system.device
-        z = lambda *shape: torch.zeros(*shape, device=dev)
-        self.comp = z(capacity, 8).requires_grad_(True)
-        self.bufs = {"rgb": z(capacity, 3), "normal": z(capacity, 3), "mask": z(capacity),
-                     "cosines": z(capacity), "view_weights": z(capacity)}
-        self.n_rays = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.graph = None
-        self.names = None
-
-    def _compute(self):
-        pad = torch.arange(self.capacity, device=self.comp.device) < self.n_rays
-        terms = self.system.ray_losses(self.comp, self.bufs, pad)
-        self.names = list(terms.keys())
-        total = sum(terms.values())
-        (g,) = torch.autograd.grad(total, self.comp)
-        return torch.stack([terms[k].detach() for k in self.names]), g
-
-    def _capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                self._compute()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out_terms, self.out_grad = self._compute()
-
-    @torch.no_grad()
-    def _load(self, comp, batch):
-        r = comp.shape[0]
-        assert r <= self.capacity
-        self.comp.data[:r].copy_(comp.detach())
-        for k in self.KEYS:
-            self.bufs[k][:r].copy_(batch[k])
-        self.n_rays.fill_(r)
-        return r
-
-    def run(self, comp, batch):
-        r = self._load(comp, batch)
-        if self.graph is None:
-            self._capture()
-        self.graph.replay()
-        terms = {k: self.out_terms[i] for i, k in enumerate(self.names)}
-        return terms, self.out_grad[:r]
 
 
 class TableAdamW:
@@ -564,8 +507,6 @@ class OrthoNeuSSystem:
         self._gamma = 0.1 ** (1.0 / decay_steps) if decay_steps > 0 else 1.0
         self.dataset = None
         self.last = {}
-        self.use_loss_graph = self.device.type == "cuda"
-        self._loss_graph = None
         # "fused": forward and backward of a step driven kernel by kernel (no autograd graph
         # except for the texture MLP and the tiny weight-norm / variance chains);
         # "autograd": the op-by-op step through torch.autograd (cross-check, same numbers)
@@ -574,13 +515,7 @@ class OrthoNeuSSystem:
         self.step_mode = "native"
         self.native_with_injected_draws = False     # tests: injected draws through the native driver
         self._native, self._python_steps = None, 0
-        self.use_prefetch = self.device.type == "cuda"
         self.fused_batch = True
-        self._side, self._prefetched = None, None
-        self.pack_on_side_stream = True
-        self._packed = {}
-        self._stats_pinned = [torch.empty(2, dtype=torch.int32).pin_memory() for _ in range(2)] \
-            if self.device.type == "cuda" and torch.cuda.is_available() else None
 
     # ----------------------------------------------------------------- data
     def preprocess_data(self, index=None, x=None, y=None):
@@ -616,10 +551,9 @@ class OrthoNeuSSystem:
                 "view_weights": view_weights}
 
     # ----------------------------------------------------------------- losses
-    def ray_losses(self, comp, batch, pad=None):
+    def ray_losses(self, comp, batch):
         """The three ray-level terms (neus_ortho.py:94-133) from the raw composite
-        comp (R,8) = [opacity, depth, rgb(3), sum w*normal(3)].  `pad` (R,) bool marks the real
-        rays when the tensors are padded to a fixed capacity (graph replay); None = all real."""
+        comp (R,8) = [opacity, depth, rgb(3), sum w*normal(3)]."""
         L = self.config.loss
         comp_rgb, opacity = comp[:, 2:5], comp[:, 0]
         comp_normal = F.normalize(comp[:, 5:8], p=2, dim=-1)
@@ -627,8 +561,6 @@ class OrthoNeuSSystem:
         cosines = torch.where(batch["cosines"] > -0.1, torch.zeros_like(batch["cosines"]),
                               batch["cosines"])                         # cosines[cosines > -0.1] = 0
         mask = (batch["mask"] > 0) & (cosines < -0.1)
-        real = torch.ones_like(mask) if pad is None else pad
-        mask = mask & real
         terms = {}
         # x[mask] of the reference evaluated without host round trips (ranking_loss_masked)
         err = F.mse_loss(comp_rgb, batch["rgb"], reduction="none")
@@ -640,14 +572,14 @@ class OrthoNeuSSystem:
         normal_errors = 1 - F.cosine_similarity(comp_normal, batch["normal"], dim=1)
         if L.geo_aware:
             e = torch.exp(cosines.abs())
-            normal_errors = normal_errors * e / (e * real).sum()
+            normal_errors = normal_errors * e / e.sum()
             ln = ranking_loss_masked(normal_errors, mask, L.normal_p_ratio, view_weights, "sum")
         else:
             ln = ranking_loss_masked(normal_errors, mask, L.normal_p_ratio, view_weights, "mean")
         terms["normal"] = ln * L.lambda_normal
         opac = torch.clamp(opacity, 1e-3, 1 - 1e-3)
-        lm = ranking_loss_masked(binary_cross_entropy(opac, batch["mask"].float()), real,
-                                 L.mask_p_ratio, view_weights)
+        lm = ranking_loss_masked(binary_cross_entropy(opac, batch["mask"].float()),
+                                 torch.ones_like(mask), L.mask_p_ratio, view_weights)
         terms["mask"] = lm * (L.lambda_mask if self.dataset.has_mask else 0.0)
         return terms
 
@@ -702,7 +634,7 @@ class OrthoNeuSSystem:
     def training_step(self, inject=None):
         fusable = self.model.fused_shading and self.train_num_rays <= ops.RAY_LOSS_MAX_RAYS
         native_ok = (self.step_mode == "native" and fusable and self.device.type == "cuda"
-                     and self.table_opt is not None and self.use_prefetch
+                     and self.table_opt is not None
                      and self.model.config.max_train_num_rays <= ops.RAY_LOSS_MAX_RAYS)
         # The two sequencings keep separate optimizer moments for the small tensors, so a system
         # stays on the one it started with: native when its first step draws its own rays,
@@ -819,95 +751,6 @@ class OrthoNeuSSystem:
                      "n_rays": n_rays, **terms}
         return self.last
 
-    # ------------------------------------------------------------- ray batch + march (prefetchable)
-    def _march_begin(self, inject=None):
-        """preprocess_data + ray/box intersection + single-pass march + offsets scan on the
-        CURRENT stream; nothing waits for the device."""
-        m = self.model
-        inject = inject or {}
-        # tests may hand over a whole ray batch (rays, rgb, normal, mask, cosines, view_weights)
-        batch = inject.get("batch") or \
-            self.preprocess_data(inject.get("index"), inject.get("x"), inject.get("y"))
-        rays = batch["rays"]
-        rays_o, rays_d = rays[:, 0:3].contiguous(), rays[:, 3:6].contiguous()
-        jitter = inject.get("jitter")
-        if jitter is None and m.randomized:
-            jitter = torch.rand(rays.shape[0], device=rays.device)
-        with torch.no_grad():
-            tmin, tmax = ops.ray_aabb(rays_o, rays_d, m._aabb_host,
-                                      jitter if m.randomized else None, m.render_step_size)
-            occ, res = None, 0
-            if m.config.grid_prune:
-                occ, res = m.occupancy_grid.binary_u8(), m.occupancy_grid.res
-            h = ops.ray_march_begin(rays_o, rays_d, tmin, tmax, m._aabb_host, occ, res,
-                                    m.render_step_size)
-        # the 2048 random points of the sparsity / smoothness terms and their perturbation
-        # (neus.py:155-162) are independent of the parameters as well
-        pts_random, perturb = inject.get("pts_random"), inject.get("perturb")
-        if pts_random is None:
-            pts_random = torch.rand([1024 * 2, 3], device=rays.device) * 2 - 1
-        if perturb is None:
-            perturb = torch.randn_like(pts_random)
-        return {"batch": batch, "handle": h, "keep": (tmin, tmax, jitter, rays),
-                "pts_random": pts_random, "perturb": perturb}
-
-    def _launch_prefetch(self, done=None):
-        """The next step's ray batch and march depend on the occupancy grid and the RNG, not on
-        the parameters this step is about to update: run them on a side stream, concurrently with
-        this step's geometry / backward kernels (32 marching waves next to a 4-wave-per-CU
-        backward), and hand the sample count to the host through pinned memory.  Skipped when
-        the next step refreshes the occupancy grid (every 16th step) — that must see the updated
-        parameters first."""
-        if not self.use_prefetch:
-            return
-        nxt = self.global_step + 1
-        if self.model.config.grid_prune and nxt % 16 == 0:
-            return
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            # high priority: its 32 marching waves must not queue behind the main stream's
-            # chip-filling kernels, or the next step blocks on the sample count
-            self._side = torch.cuda.Stream(priority=-1)
-        if done is None:
-            done = torch.cuda.Event()
-            done.record(main)
-        self._side.wait_event(done)            # compaction of THIS step (and a grid refresh) done
-        with torch.cuda.stream(self._side):
-            prep = self._march_begin()
-            if self.pack_on_side_stream:
-                # compaction + random tail + Morton sort of the next step's points, off the main
-                # stream (8 launches, ~55 us per step)
-                n_r = prep["pts_random"].shape[0]
-                key = nxt & 1
-                bufs = self._packed.get(key)
-                if bufs is None or bufs.tail_rows != 2 * n_r:
-                    bufs = self._packed[key] = ops.PackedStepBuffers(
-                        _PACK_CAPACITY, 2 * n_r, _SPATIAL_SORT_BITS, self.device)
-                ops.ray_pack_prefetched(prep["handle"], bufs, prep["pts_random"], prep["perturb"],
-                                        self.model.geometry.radius)
-                prep["packed"] = bufs
-            host = self._stats_pinned[nxt & 1]
-            host.copy_(prep["handle"].stats, non_blocking=True)
-            prep["stats_host"] = host
-            prep["ready"] = torch.cuda.Event()
-            prep["ready"].record(self._side)
-        prep["step"] = nxt
-        # No tensor.record_stream(main) here.  These tensors come from the side stream's pool and
-        # are read by main-stream kernels of the NEXT step; their blocks return to that pool when
-        # the step drops them and can only be re-used by a later prefetch, which the side stream
-        # starts after waiting for an event recorded on main behind that step's kernels (`done`
-        # above), so the re-use is already ordered.  record_stream would make the allocator put
-        # one hipEventRecord per tensor (16) into the MAIN queue between AdamW and the next step's
-        # compaction: ~80 us of command-processor work per step (hip-runtime trace).
-        self._prefetched = prep
-
-    def _take_prefetch(self):
-        prep, self._prefetched = self._prefetched, None
-        if prep is not None and (prep["step"] != self.global_step
-                                 or prep["handle"].n != self.train_num_rays):
-            return None
-        return prep
-
     def training_step_fused(self, inject=None):
         """Same step as training_step_autograd (neus_ortho.py:84-160 + the model forward
         neus.py:115-196), with the backward pass sequenced by hand over the fused kernels:
@@ -922,42 +765,40 @@ class OrthoNeuSSystem:
         m.update_step(0, self.global_step)
         if self.table_opt is not None:
             self.table_opt.activate(int(geo.active_levels))
-        prep = self._take_prefetch() if not inject else None
-        if prep is None:
-            prep = self._march_begin(inject)
-            total, cmax = prep["handle"].stats.tolist()              # the step's one host sync
-        else:
-            # The host waits for the event, so everything the side stream did before it is
-            # complete: no device-side wait is needed on the main stream (a cross-queue barrier
-            # packet cost ~80 us of main-stream idle time per step even when already signalled).
-            prep["ready"].synchronize()                              # stats are in pinned memory
-            total, cmax = prep["stats_host"].tolist()
-        batch, rays_d, h = prep["batch"], prep["handle"].rays_d, prep["handle"]
+        # tests may hand over a whole ray batch (rays, rgb, normal, mask, cosines, view_weights)
+        batch = inject.get("batch") or \
+            self.preprocess_data(inject.get("index"), inject.get("x"), inject.get("y"))
+        rays = batch["rays"]
+        rays_o, rays_d = rays[:, 0:3].contiguous(), rays[:, 3:6].contiguous()
         dev = rays_d.device
         n_rays = rays_d.shape[0]
-        pts_random, perturb = prep["pts_random"], prep["perturb"]
+        jitter = inject.get("jitter")
+        if jitter is None and m.randomized:
+            jitter = torch.rand(n_rays, device=dev)
+        with torch.no_grad():
+            tmin, tmax = ops.ray_aabb(rays_o, rays_d, m._aabb_host,
+                                      jitter if m.randomized else None, m.render_step_size)
+            occ, res = None, 0
+            if m.config.grid_prune:
+                occ, res = m.occupancy_grid.binary_u8(), m.occupancy_grid.res
+            h = ops.ray_march_begin(rays_o, rays_d, tmin, tmax, m._aabb_host, occ, res,
+                                    m.render_step_size)
+        # the 2048 random points of the sparsity / smoothness terms and their perturbation
+        # (neus.py:155-162)
+        pts_random, perturb = inject.get("pts_random"), inject.get("perturb")
+        if pts_random is None:
+            pts_random = torch.rand([1024 * 2, 3], device=dev) * 2 - 1
+        if perturb is None:
+            perturb = torch.randn_like(pts_random)
         n_r = pts_random.shape[0]
-        packed = prep.get("packed")
-        perm, presorted = None, False
-        off, cnt, n_s = h.offsets, h.counts, total
+        n_s, cmax = h.stats.tolist()                                 # the step's one host sync
+        off, cnt = h.offsets, h.counts
         RayPacking.total = n_s
-        if packed is not None and cmax <= h.cap and total <= packed.capacity:
-            # the side stream already packed the samples, appended the random points and sorted
-            # everything (fixed-capacity buffers; the total was on the device only)
-            n_pk = n_s + 2 * n_r
-            ts, te = packed.t_starts[:n_s], packed.t_ends[:n_s]
-            if packed.bits:
-                allp, perm, presorted = packed.sorted[:n_pk], packed.perm[:n_pk], True
-            else:
-                allp = packed.points[:n_pk]
-        else:
-            with torch.no_grad():
-                allp, ts, te = ops.ray_march_finish(h, total, cmax, tail_rows=2 * n_r)
-                allp[n_s:n_s + n_r] = pts_random
-                torch.add(pts_random, perturb, alpha=1e-2, out=allp[n_s + n_r:])
-        # the march scratch rows may be overwritten by the next prefetch once this has run
-        done_event = torch.cuda.Event()
-        done_event.record(torch.cuda.current_stream())
+        with torch.no_grad():
+            allp, ts, te = ops.ray_march_finish(h, n_s, cmax, tail_rows=2 * n_r)
+            allp[n_s:n_s + n_r] = pts_random
+            torch.add(pts_random, perturb, alpha=1e-2, out=allp[n_s + n_r:])
+        perm = None
         if m.config.dynamic_ray_sampling and n_s > 0:
             tr = int(self.train_num_rays * (self.train_num_samples / n_s))
             self.train_num_rays = min(int(self.train_num_rays * 0.9 + tr * 0.1),
@@ -984,18 +825,11 @@ class OrthoNeuSSystem:
             # the geometry network is evaluated in Morton order of the sample positions (the
             # ray-major order of random pixels scatters a wave's table accesses over the whole
             # volume); its per-point results come back in ray order through `perm`
-            if _SPATIAL_SORT_BITS and not presorted:
+            if _SPATIAL_SORT_BITS:
                 allp, perm = ops.spatial_sort(allp, geo.radius, _SPATIAL_SORT_BITS)
             a_sdf, a_grad, a_feat, _, enc_cache = ops.sdf_fd_fwd(
                 enc.cfg, table, mlp, allp, geo.radius, eps, active, True, True, False,
                 enc_cache=True, perm=perm)
-            if not inject:
-                # issued once the geometry forward (0.3 ms of device work) is in the queue: the
-                # host's ~0.15 ms of launches for the next batch then cost the device nothing, and
-                # the march has the rest of this step to finish, so the next step never blocks
-                # on it (a cProfile of the loop showed 0.43 ms per step in Event.synchronize when
-                # the prefetch was issued behind the geometry backward)
-                self._launch_prefetch(done_event)
             normal, tex_in = ops.shade_prep_fwd(a_grad[:n_s], a_feat[:n_s])
         tex_fused = m.texture.fused_ok
         if tex_fused:
@@ -1090,20 +924,9 @@ class OrthoNeuSSystem:
                                       self.model.config.max_train_num_rays)
         self._set_lr()
         self.zero_grad()
-        if self.use_loss_graph and "comp_raw" in out:
-            # ray-level losses + their gradient w.r.t. the composite: one captured HIP graph
-            # (fixed max_train_num_rays capacity, real rays marked by a device-side count)
-            if self._loss_graph is None:
-                self._loss_graph = RayLossGraph(self, self.model.config.max_train_num_rays)
-            rterms, d_comp = self._loss_graph.run(out["comp_raw"], batch)
-            sterms = self.sample_losses(out)
-            torch.autograd.backward([sum(sterms.values()), out["comp_raw"]], [None, d_comp])
-            terms = {**rterms, **sterms}
-            loss = sum(terms.values())
-        else:
-            terms = self.losses(out, batch)
-            loss = sum(terms.values())
-            loss.backward()
+        terms = self.losses(out, batch)
+        loss = sum(terms.values())
+        loss.backward()
         self._step_small()
         enc = self.model.geometry.hashgrid
         if self.table_opt is not None:

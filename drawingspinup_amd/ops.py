@@ -376,40 +376,26 @@ def ray_aabb(rays_o, rays_d, aabb6, jitter=None, step=0.0):
     return t_min, t_max
 
 
-def ray_march(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
-    """Two-pass marching.  Returns ray_indices (int64), t_starts, t_ends (n,), and the per-ray
-    (offsets, counts) int32 packing the compositing kernels consume."""
-    rays_o, rays_d = _f32c(rays_o), _f32c(rays_d)
-    n = rays_o.shape[0]
-    dev = rays_o.device
-    a = (C.c_float * 6)(*[float(v) for v in aabb6])
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    occp = ptr(occ_binary, torch.uint8) if occ_binary is not None else None
-    check(lib().dsu_ray_march_count(ptr(rays_o), ptr(rays_d), ptr(t_min), ptr(t_max), n, a, occp,
-                                    int(res), float(step), ptr(counts), stream()),
-          "dsu_ray_march_count")
-    csum = torch.cumsum(counts, 0, dtype=torch.int32)
-    offsets = (csum - counts).contiguous()
-    total = int(csum[-1].item()) if n > 0 else 0
-    ray_indices = torch.empty(total, dtype=torch.int64, device=dev)
-    t_starts = torch.empty(total, dtype=torch.float32, device=dev)
-    t_ends = torch.empty(total, dtype=torch.float32, device=dev)
-    if total > 0:
-        check(lib().dsu_ray_march_fill(ptr(rays_o), ptr(rays_d), ptr(t_min), ptr(t_max), n, a,
-                                       occp, int(res), float(step), ptr(offsets),
-                                       ptr(ray_indices), ptr(t_starts), ptr(t_ends), stream()),
-              "dsu_ray_march_fill")
-    return ray_indices, t_starts, t_ends, offsets, counts
-
-
 # lazily built, process-wide; keyed by stream: drawings in flight on one GPU run on their own streams
 _MARCH_SCRATCH = {}
 
 
-def ray_march_single_pass(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
-    """Same outputs as ray_march with ONE serial march (fixed-capacity scratch rows + compaction).
-    The capacity covers the longest possible chord of the box; rays are re-marched with the
-    two-pass path in the (never observed) case that a count exceeds it."""
+class MarchHandle:
+    """State between ray_march_begin (march + offsets scan, all asynchronous) and the packing
+    (needs the host-side total to size the packed outputs)."""
+    __slots__ = ("rays_o", "rays_d", "counts", "offsets", "stats", "scratch", "cap", "n")
+
+    def check_capacity(self, cmax):
+        """The rows hold cap = int(diag / step) + 8 samples, diag the box diagonal.  A ray has at
+        most (far - near) / step + 2 samples and far - near <= diag (both ends lie in the box), so
+        this cannot trip; the marcher drops what a longer ray would write past its row."""
+        if cmax > self.cap:
+            raise DsuError(f"a ray produced {cmax} samples, above the scratch capacity {self.cap}")
+
+
+def ray_march_begin(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
+    """Launch the march into the scratch rows and the offsets scan.  Nothing here waits for the
+    device; the caller reads `handle.stats` (int32[2] = total, max count)."""
     import math
     rays_o, rays_d = _f32c(rays_o), _f32c(rays_d)
     n = rays_o.shape[0]
@@ -418,51 +404,6 @@ def ray_march_single_pass(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, 
     diag = math.sqrt(sum((aabb6[3 + d] - aabb6[d]) ** 2 for d in range(3)))
     cap = int(diag / step) + 8
     key = (str(dev), cap, stream().value)          # scratch rows belong to ONE stream's launches
-    sc = _MARCH_SCRATCH.get(key)
-    if sc is None or sc[0].shape[0] < n * cap:
-        rows = max(n, 8192)
-        sc = (torch.empty(rows * cap, dtype=torch.float32, device=dev),
-              torch.empty(rows * cap, dtype=torch.float32, device=dev))
-        _MARCH_SCRATCH[key] = sc
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    occp = ptr(occ_binary, torch.uint8) if occ_binary is not None else None
-    check(lib().dsu_ray_march_scratch(ptr(rays_o), ptr(rays_d), ptr(t_min), ptr(t_max), n, a, occp,
-                                      int(res), float(step), cap, ptr(counts), ptr(sc[0]),
-                                      ptr(sc[1]), stream()), "dsu_ray_march_scratch")
-    csum = torch.cumsum(counts, 0, dtype=torch.int32)
-    offsets = (csum - counts).contiguous()
-    stats = torch.stack([csum[-1], counts.max()]).tolist() if n > 0 else [0, 0]   # one host sync
-    total, cmax = int(stats[0]), int(stats[1])
-    if cmax > cap:
-        return ray_march(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step)
-    ray_indices = torch.empty(total, dtype=torch.int64, device=dev)
-    t_starts = torch.empty(total, dtype=torch.float32, device=dev)
-    t_ends = torch.empty(total, dtype=torch.float32, device=dev)
-    if total > 0:
-        check(lib().dsu_ray_compact(ptr(sc[0]), ptr(sc[1]), cap, ptr(offsets), ptr(counts), n,
-                                    ptr(ray_indices), ptr(t_starts), ptr(t_ends), stream()),
-              "dsu_ray_compact")
-    return ray_indices, t_starts, t_ends, offsets, counts
-
-
-class MarchHandle:
-    """State between ray_march_begin (march + offsets scan, all asynchronous) and
-    ray_march_finish (needs the host-side total to size the packed outputs)."""
-    __slots__ = ("rays_o", "rays_d", "counts", "offsets", "stats", "scratch", "cap", "n")
-
-
-def ray_march_begin(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
-    """Launch the single-pass march into the scratch rows and the offsets scan.  Nothing here
-    waits for the device; `handle.stats` (int32[2] = total, max count) is read by the caller
-    (directly, or through an asynchronous copy when the march is prefetched on a side stream)."""
-    import math
-    rays_o, rays_d = _f32c(rays_o), _f32c(rays_d)
-    n = rays_o.shape[0]
-    dev = rays_o.device
-    a = (C.c_float * 6)(*[float(v) for v in aabb6])
-    diag = math.sqrt(sum((aabb6[3 + d] - aabb6[d]) ** 2 for d in range(3)))
-    cap = int(diag / step) + 8
-    key = (str(dev), cap, stream().value)
     sc = _MARCH_SCRATCH.get(key)
     if sc is None or sc[0].shape[0] < n * cap:
         rows = max(n, 8192)
@@ -483,10 +424,26 @@ def ray_march_begin(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
     return h
 
 
+def ray_march(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
+    """nerfacc's ray_marching.  Returns ray_indices (int64), t_starts, t_ends (n,), and the per-ray
+    (offsets, counts) int32 packing the compositing kernels consume."""
+    h = ray_march_begin(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step)
+    total, cmax = h.stats.tolist()                                # one host sync
+    h.check_capacity(cmax)
+    dev = h.rays_o.device
+    ray_indices = torch.empty(total, dtype=torch.int64, device=dev)
+    t_starts = torch.empty(total, dtype=torch.float32, device=dev)
+    t_ends = torch.empty(total, dtype=torch.float32, device=dev)
+    if total > 0:
+        check(lib().dsu_ray_compact(ptr(h.scratch[0]), ptr(h.scratch[1]), h.cap, ptr(h.offsets),
+                                    ptr(h.counts), h.n, ptr(ray_indices), ptr(t_starts),
+                                    ptr(t_ends), stream()), "dsu_ray_compact")
+    return ray_indices, t_starts, t_ends, h.offsets, h.counts
+
+
 def ray_march_finish(h, total, cmax, tail_rows=0):
     """Pack the scratch rows: returns (points (total + tail_rows, 3), t_starts, t_ends)."""
-    if cmax > h.cap:
-        raise DsuError(f"a ray produced {cmax} samples, above the scratch capacity {h.cap}")
+    h.check_capacity(cmax)
     dev = h.rays_o.device
     points = torch.empty(total + tail_rows, 3, dtype=torch.float32, device=dev)
     t_starts = torch.empty(total, dtype=torch.float32, device=dev)
@@ -497,44 +454,6 @@ def ray_march_finish(h, total, cmax, tail_rows=0):
                                            ptr(h.rays_d), ptr(t_starts), ptr(t_ends), ptr(points),
                                            stream()), "dsu_ray_compact_points")
     return points, t_starts, t_ends
-
-
-class PackedStepBuffers:
-    """Fixed-capacity outputs of the prefetch path (one set per step parity): packed sample
-    positions + tail rows, t_starts / t_ends, their Morton-sorted copy + permutation, sort scratch."""
-
-    def __init__(self, capacity, tail_rows, bits, device):
-        self.capacity, self.tail_rows, self.bits = int(capacity), int(tail_rows), int(bits)
-        rows = self.capacity + self.tail_rows
-        f32 = dict(dtype=torch.float32, device=device)
-        self.points = torch.empty(rows, 3, **f32)
-        self.t_starts = torch.empty(self.capacity, **f32)
-        self.t_ends = torch.empty(self.capacity, **f32)
-        self.sorted = torch.empty(rows, 3, **f32) if bits else None
-        self.perm = torch.empty(rows, dtype=torch.int32, device=device) if bits else None
-        self.ws_bytes = int(lib().dsu_spatial_sort_workspace_bytes(rows, self.bits)) if bits else 0
-        self.ws = torch.empty(max(self.ws_bytes, 4) // 4, dtype=torch.int32, device=device)
-
-
-def ray_pack_prefetched(h, bufs, pts_random, perturb, radius, alpha=1e-2):
-    """On the CURRENT (side) stream, without knowing the sample total on the host: compaction of
-    the march scratch into bufs.points / t_starts / t_ends, the random + perturbed points behind
-    the samples, and the Morton sort of all of them (count read from h.stats on the device)."""
-    n_r = pts_random.shape[0]
-    assert 2 * n_r == bufs.tail_rows
-    check(lib().dsu_ray_compact_points_cap(ptr(h.scratch[0]), ptr(h.scratch[1]), h.cap,
-                                           ptr(h.offsets), ptr(h.counts), h.n, ptr(h.rays_o),
-                                           ptr(h.rays_d), ptr(bufs.t_starts), ptr(bufs.t_ends),
-                                           ptr(bufs.points), bufs.capacity, stream()),
-          "dsu_ray_compact_points_cap")
-    check(lib().dsu_points_tail(ptr(bufs.points), bufs.capacity + bufs.tail_rows, ptr(h.stats),
-                                ptr(_f32c(pts_random)), ptr(_f32c(perturb)), n_r, float(alpha),
-                                stream()), "dsu_points_tail")
-    if bufs.bits:
-        check(lib().dsu_spatial_sort_dev(ptr(bufs.points), bufs.capacity + bufs.tail_rows,
-                                         ptr(h.stats), bufs.tail_rows, float(radius), bufs.bits,
-                                         ptr(bufs.perm), ptr(bufs.sorted), ptr(bufs.ws),
-                                         bufs.ws_bytes, stream()), "dsu_spatial_sort_dev")
 
 
 def ray_march_points(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step, tail_rows=0):

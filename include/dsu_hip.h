@@ -224,26 +224,12 @@ int64_t dsu_sdf_fd_bwd_workspace_bytes(const dsu_hashgrid_cfg* cfg, int64_t n);
 int dsu_ray_aabb(const float* rays_o, const float* rays_d, int64_t n_rays, const float* aabb6,
                  const float* jitter, float step, float* t_min, float* t_max, void* stream);
 
-/* Pass 1 of ray_marching: count samples per ray through the binary occupancy grid
- * (res^3 uint8, index x*res*res + y*res + z).  num_steps: (n_rays) int32. */
-int dsu_ray_march_count(const float* rays_o, const float* rays_d, const float* t_min,
-                        const float* t_max, int64_t n_rays, const float* aabb6,
-                        const uint8_t* occ_binary, int32_t res, float step,
-                        int32_t* num_steps, void* stream);
-
-/* Pass 2: fill.  offsets: (n_rays) int32 exclusive prefix sum of num_steps.
- * ray_indices: (n_samples) int64; t_starts/t_ends: (n_samples) f32. */
-int dsu_ray_march_fill(const float* rays_o, const float* rays_d, const float* t_min,
-                       const float* t_max, int64_t n_rays, const float* aabb6,
-                       const uint8_t* occ_binary, int32_t res, float step,
-                       const int32_t* offsets, int64_t* ray_indices, float* t_starts,
-                       float* t_ends, void* stream);
-
-/* Single-pass variant of the two calls above: the serial march runs ONCE, writing each ray's
- * samples into a fixed-capacity scratch row (ray r at scratch[r*capacity ...]) together with
- * its count; dsu_ray_compact then packs the rows at the exclusive prefix sum of the counts.
- * Identical results (same stepping loop); a ray with more than `capacity` samples is
- * reported through num_steps (caller checks max(num_steps) <= capacity). */
+/* ray_marching through the binary occupancy grid (res^3 uint8, index x*res*res + y*res + z; NULL:
+ * no grid), in one pass: each ray's samples go into a fixed-capacity scratch row (ray r at
+ * scratch[r*capacity ...]) and its count into num_steps (n_rays) int32; dsu_ray_compact* then
+ * pack the rows at the exclusive prefix sum of the counts (dsu_ray_offsets).  A ray with more
+ * than `capacity` samples keeps the first `capacity` and is reported through num_steps (the
+ * caller checks max(num_steps) <= capacity). */
 int dsu_ray_march_scratch(const float* rays_o, const float* rays_d, const float* t_min,
                           const float* t_max, int64_t n_rays, const float* aabb6,
                           const uint8_t* occ_binary, int32_t res, float step, int32_t capacity,

@@ -9,8 +9,8 @@ fixture (tests/golden/nsr_step_reference.npz, made with plain stand-ins instead 
 
 /root/reference exists only in the build container, which has no GPU, and the product's kernels
 exist only on the GPU: so here the five C-ABI wrappers the shims reach on this path
-(drawingspinup_amd.ops: hashgrid_encode_fwd, ray_aabb, ray_march_single_pass,
-weights_from_alpha_fwd, accumulate_fwd) are replaced by the CPU oracle — TEST INFRASTRUCTURE, in
+(drawingspinup_amd.ops: hashgrid_encode_fwd, ray_aabb, ray_march, weights_from_alpha_fwd,
+accumulate_fwd) are replaced by the CPU oracle — TEST INFRASTRUCTURE, in
 this process only.  What this pins is the seam itself: constructor signatures, keyword sets,
 argument layouts / dtypes, return structures and the parameter layout the reference's code
 relies on.  The kernels behind the same wrappers are checked against the same fixture on the GPU
@@ -52,7 +52,7 @@ def main():
         tmin, tmax = nr.ray_aabb_intersect(rays_o.numpy(), rays_d.numpy(), np.asarray(aabb6, np.float32))
         return torch.from_numpy(tmin), torch.from_numpy(tmax)
 
-    def ray_march_single_pass(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
+    def ray_march(rays_o, rays_d, t_min, t_max, aabb6, occ_binary, res, step):
         occ = None if occ_binary is None else occ_binary.numpy().astype(bool)
         ri, ts, te, cnt = nr.ray_marching(rays_o.numpy(), rays_d.numpy(), t_min.numpy(), t_max.numpy(),
                                           np.asarray(aabb6, np.float32), occ, res, step)
@@ -70,7 +70,7 @@ def main():
         return torch.from_numpy(out.astype(np.float32))
 
     for name, fn in dict(hashgrid_encode_fwd=hashgrid_encode_fwd, ray_aabb=ray_aabb,
-                         ray_march_single_pass=ray_march_single_pass,
+                         ray_march=ray_march,
                          weights_from_alpha_fwd=weights_from_alpha_fwd,
                          accumulate_fwd=accumulate_fwd).items():
         setattr(ops, name, fn)

@@ -1,8 +1,8 @@
 """The one-wave-per-ray marcher against the serial rule of oracle/nerfacc_ref.py, bit for bit.
 
-Every case goes through ops.ray_march (count + fill at offsets) and through the scratch-row entry
-(dsu_ray_march_scratch) and must give the oracle's counts, ray indices and the bits of
-t_starts / t_ends.  The oracle is a Python loop, so the grids are res 16..32, the step is
+Every case goes through ops.ray_march (the shipped path: scratch rows, offsets scan, compaction)
+and through the scratch-row entry itself (dsu_ray_march_scratch) and must give the oracle's counts,
+ray indices and the bits of t_starts / t_ends.  The oracle is a Python loop, so the grids are res 16..32, the step is
 2*1.732/256 and a case holds a few hundred rays; each oracle result is computed once.
 """
 import ctypes as C

@@ -79,26 +79,3 @@ def test_short_training_converges_on_sphere(dev):
     sd = sysm.model.geometry.forward_level(pts)
     torch.testing.assert_close(coarse[0, 0, 5], sd[0], rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(coarse[3, 0, 0], sd[1], rtol=1e-4, atol=1e-5)
-
-
-def test_loss_graph_replay_matches_eager(dev):
-    """Captured (padded, device-counted) ray losses + gradient == the eager evaluation."""
-    from drawingspinup_amd.nsr.system import RayLossGraph
-    ds = OrthoData.synthetic_sphere(256, device=dev)
-    sysm = OrthoNeuSSystem(device=dev, seed=5)
-    sysm.dataset = ds
-    g = torch.Generator().manual_seed(0)
-    graph = RayLossGraph(sysm, 1024)
-    for r in (300, 1000, 37):                       # replays with changing ray counts
-        comp = (torch.rand(r, 8, generator=g) * 0.8 + 0.1).to(dev).requires_grad_(True)
-        batch = {"rgb": torch.rand(r, 3, generator=g).to(dev),
-                 "normal": torch.nn.functional.normalize(torch.randn(r, 3, generator=g), dim=-1).to(dev),
-                 "mask": (torch.rand(r, generator=g) > 0.3).float().to(dev),
-                 "cosines": (-torch.rand(r, generator=g)).to(dev),
-                 "view_weights": torch.ones(r, device=dev)}
-        terms_g, d_comp = graph.run(comp, batch)
-        terms_e = sysm.ray_losses(comp, batch)
-        (g_e,) = torch.autograd.grad(sum(terms_e.values()), comp)
-        for k in terms_e:
-            torch.testing.assert_close(terms_g[k], terms_e[k].detach(), rtol=1e-5, atol=1e-7)
-        torch.testing.assert_close(d_comp, g_e, rtol=1e-4, atol=1e-7)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from drawingspinup_amd import ops
+from drawingspinup_amd._lib import check, lib, ptr, stream
 from drawingspinup_amd.nsr.system import (DEFAULT_SYSTEM_CONFIG, Cfg, OrthoData, OrthoNeuSSystem)
 
 pytestmark = pytest.mark.gpu
@@ -124,8 +125,7 @@ def test_sample_losses_kernel_matches_torch_path(dev, n_s, n_r, smooth):
 
 
 def test_march_points_matches_packed_march(dev):
-    """ray_march_points = ray_march_single_pass + the reference's position arithmetic, bit for
-    bit, with the offsets scan kernel instead of cumsum."""
+    """ray_march_points = ray_march + the reference's position arithmetic, bit for bit."""
     g = torch.Generator().manual_seed(2)
     n = 3000
     o = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.3
@@ -137,7 +137,7 @@ def test_march_points_matches_packed_march(dev):
     aabb = [-1.0, -1.0, -1.0, 1.0, 1.0, 1.0]
     step = 1.732 * 2 / 512
     tmin, tmax = ops.ray_aabb(o, d, aabb, None, step)
-    ri, ts, te, off, cnt = ops.ray_march_single_pass(o, d, tmin, tmax, aabb, occ, res, step)
+    ri, ts, te, off, cnt = ops.ray_march(o, d, tmin, tmax, aabb, occ, res, step)
     pts, ts2, te2, off2, cnt2, total = ops.ray_march_points(o, d, tmin, tmax, aabb, occ, res, step,
                                                             tail_rows=5)
     assert total == ri.shape[0] > 1000 and pts.shape == (total + 5, 3)
@@ -380,32 +380,42 @@ def test_small_adamw_matches_torch_adamw(dev):
             torch.testing.assert_close(p.detach(), r.detach(), rtol=3e-6, atol=3e-8)
 
 
-def test_side_stream_packing_matches_main_stream_packing(dev):
-    """The prefetch path packs / appends the random points / sorts the next step's samples on the
-    side stream into fixed-capacity buffers (sample total still on the device); the optimisation
-    must follow the same trajectory as with the main-stream packing (same RNG draws; only the
-    order inside a Morton bin, i.e. float summation order, may differ)."""
-    def run(pack):
-        ds = OrthoData.synthetic_sphere(256, device=dev)
-        sysm = OrthoNeuSSystem(device=dev, seed=11)
-        sysm.dataset = ds
-        sysm.step_mode = "fused"                             # the Python-sequenced step is under test
-        sysm.pack_on_side_stream = pack
-        out = []
-        for _ in range(40):
-            r = sysm.training_step()
-            out.append((float(r["loss"]), int(r["n_samples"]), int(r["n_rays"])))
-        used = sum(1 for k in sysm._packed) if pack else 0
-        return out, used
-    a, used_a = run(True)
-    b, used_b = run(False)
-    assert used_a == 2 and used_b == 0                       # both parities of the packed buffers in use
-    # INT: same rays, same sample counts (up to the first occupancy refresh at step 16, which
-    # thresholds float densities)
-    assert [x[1:] for x in a[:15]] == [x[1:] for x in b[:15]]
-    la, lb = np.array([x[0] for x in a]), np.array([x[0] for x in b])
-    np.testing.assert_allclose(la[:15], lb[:15], rtol=2e-3)
-    assert la[-1] < la[0] and lb[-1] < lb[0]
+class PackedStepBuffers:
+    """Fixed-capacity outputs of the packing the native driver runs on its side stream: packed sample
+    positions + tail rows, t_starts / t_ends, their Morton-sorted copy + permutation, sort scratch."""
+
+    def __init__(self, capacity, tail_rows, bits, device):
+        self.capacity, self.tail_rows, self.bits = int(capacity), int(tail_rows), int(bits)
+        rows = self.capacity + self.tail_rows
+        f32 = dict(dtype=torch.float32, device=device)
+        self.points = torch.empty(rows, 3, **f32)
+        self.t_starts = torch.empty(self.capacity, **f32)
+        self.t_ends = torch.empty(self.capacity, **f32)
+        self.sorted = torch.empty(rows, 3, **f32) if bits else None
+        self.perm = torch.empty(rows, dtype=torch.int32, device=device) if bits else None
+        self.ws_bytes = int(lib().dsu_spatial_sort_workspace_bytes(rows, self.bits)) if bits else 0
+        self.ws = torch.empty(max(self.ws_bytes, 4) // 4, dtype=torch.int32, device=device)
+
+
+def ray_pack_prefetched(h, bufs, pts_random, perturb, radius, alpha=1e-2):
+    """Without knowing the sample total on the host: compaction of the march scratch into
+    bufs.points / t_starts / t_ends, the random + perturbed points behind the samples, and the
+    Morton sort of all of them (count read from h.stats on the device)."""
+    n_r = pts_random.shape[0]
+    assert 2 * n_r == bufs.tail_rows
+    check(lib().dsu_ray_compact_points_cap(ptr(h.scratch[0]), ptr(h.scratch[1]), h.cap,
+                                           ptr(h.offsets), ptr(h.counts), h.n, ptr(h.rays_o),
+                                           ptr(h.rays_d), ptr(bufs.t_starts), ptr(bufs.t_ends),
+                                           ptr(bufs.points), bufs.capacity, stream()),
+          "dsu_ray_compact_points_cap")
+    check(lib().dsu_points_tail(ptr(bufs.points), bufs.capacity + bufs.tail_rows, ptr(h.stats),
+                                ptr(pts_random.contiguous()), ptr(perturb.contiguous()), n_r,
+                                float(alpha), stream()), "dsu_points_tail")
+    if bufs.bits:
+        check(lib().dsu_spatial_sort_dev(ptr(bufs.points), bufs.capacity + bufs.tail_rows,
+                                         ptr(h.stats), bufs.tail_rows, float(radius), bufs.bits,
+                                         ptr(bufs.perm), ptr(bufs.sorted), ptr(bufs.ws),
+                                         bufs.ws_bytes, stream()), "dsu_spatial_sort_dev")
 
 
 def test_packed_step_buffers_equal_the_plain_calls(dev):
@@ -427,9 +437,9 @@ def test_packed_step_buffers_equal_the_plain_calls(dev):
     pts[total:total + 64] = pr
     torch.add(pr, pe, alpha=1e-2, out=pts[total + 64:])
     for cap in (total + 1000, total, total - 37):             # roomy, exact, too small (rows dropped)
-        bufs = ops.PackedStepBuffers(cap, 128, 6, dev)
+        bufs = PackedStepBuffers(cap, 128, 6, dev)
         bufs.points.fill_(7.0)
-        ops.ray_pack_prefetched(h, bufs, pr, pe, 1.0)
+        ray_pack_prefetched(h, bufs, pr, pe, 1.0)
         m = min(total, cap)
         assert torch.equal(bufs.t_starts[:m], ts[:m]) and torch.equal(bufs.t_ends[:m], te[:m])
         assert torch.equal(bufs.points[:m], pts[:m])
