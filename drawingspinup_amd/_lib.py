@@ -187,6 +187,10 @@ _PROTOS = {
     "dsu_uv_field_resolve": [P, P, P, c_i64, c_i32, c_i32, P, P],
     "dsu_uv_field_points_host": [P, P, P, c_i64, c_i64, c_i32, P, P, c_i64, c_i32, P, P],
     "dsu_uv_field_resolve_host": [P, P, P, c_i64, c_i32, c_i32, P],
+    "dsu_uv_seam_gather": [P, P, P, c_i64, c_i64, c_i64, c_i32, P, P, P, P, P, P, P],
+    "dsu_uv_seam_apply": [P, P, P, c_i64, c_i64, c_i64, c_i32, P, P, P, P, P, P, P],
+    "dsu_uv_seam_gather_host": [P, P, P, c_i64, c_i64, c_i64, c_i32, P, P, P, P, P, P],
+    "dsu_uv_seam_apply_host": [P, P, P, c_i64, c_i64, c_i64, c_i32, P, P, P, P, P, P],
     "dsu_bone_visibility_workspace_bytes": [c_i32, c_i32, c_i32],
     "dsu_bone_visibility": [c_i32, P, P, P, c_i64, c_i64, c_i32, P, C.c_double, C.c_double, C.c_double,
                             C.c_double, c_i32, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P],

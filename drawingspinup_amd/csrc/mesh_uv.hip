@@ -23,12 +23,17 @@
 //                        covered texels' list, the sub-sample fastest (uv_field.h has the text)
 //   dsu_uv_field_resolve the mean of a texel's evaluated samples into its three bytes: one thread
 //                        per listed texel
-// No floating-point atomics anywhere: two runs give the same bits.
+//   dsu_uv_seam_gather   seam levelling: one thread per texel, the projected texels' colour
+//                        differences into per-group 64-bit integer sums (uv_seam.h has the text)
+//   dsu_uv_seam_apply    the composed image: drawing texels copied, fallback texels plus the
+//                        interpolated offset; one thread per texel
+// No floating-point atomics anywhere (the seam gather's are integer adds): two runs give the same bits.
 #include <cmath>
 #include "common.h"
 #include "bin_sort.h"
 #include "mesh_geom.h"
 #include "uv_field.h"
+#include "uv_seam.h"
 
 namespace {
 
@@ -368,6 +373,85 @@ __global__ __launch_bounds__(256) void uv_field_resolve_kernel(const float* __re
   dsu_uvf::resolve(colours, valid, t, ss, S, texels[t], image);
 }
 
+// dsu_uv_seam_gather.  Tiles as in uv_project_kernel: a tile's texels are neighbours in one chart,
+// so its up to 768 contributions go to the few groups of a handful of faces.  They are summed in LDS
+// first, in an open-addressing table keyed by group (SEAM_SLOTS >= 3 x 256 keys, so linear probing
+// always ends at the key or at a free slot; 36 KB, four workgroups per CU), and every used slot then
+// adds its four sums to global memory once.  All sums are 64-bit integers and the adds relaxed
+// atomics whose result nobody reads: the totals do not depend on any order.  A tile without a
+// projected texel (two thirds of a 1024^2 atlas) leaves before touching the table.
+constexpr int SEAM_BITS = 10;
+constexpr int SEAM_SLOTS = 1 << SEAM_BITS;
+static_assert(SEAM_SLOTS >= 3 * UV_TILE * UV_TILE, "the table must hold a key per corner of the tile's texels");
+
+struct SeamTableAdd {
+  int32_t* key;                    // SEAM_SLOTS, -1 = free
+  unsigned long long* sum;         // SEAM_SLOTS x 4: den, num[0..2]
+  __device__ __forceinline__ void operator()(int g, int64_t q, const int64_t n[3]) const {
+    unsigned h = ((unsigned)g * 2654435761u) >> (32 - SEAM_BITS);
+    for (int probe = 0; probe < SEAM_SLOTS; ++probe) {
+      const int32_t k = atomicCAS(&key[h], -1, g);
+      if (k == -1 || k == g) break;
+      h = (h + 1) & (SEAM_SLOTS - 1);
+    }
+    atomicAdd(&sum[h * 4], (unsigned long long)q);                         // two's complement throughout
+    atomicAdd(&sum[h * 4 + 1], (unsigned long long)n[0]);
+    atomicAdd(&sum[h * 4 + 2], (unsigned long long)n[1]);
+    atomicAdd(&sum[h * 4 + 3], (unsigned long long)n[2]);
+  }
+};
+
+// the texel (linear index r S + c) of this thread in tile blockIdx.x of `tiles` per axis; -1 beyond the image
+__device__ __forceinline__ int64_t uv_tile_texel(int32_t S, int32_t tiles) {
+  const int tid = threadIdx.x;
+  const int bin = blockIdx.x;
+  const int ty = bin / tiles, tx = bin - ty * tiles;
+  const int x = tx * UV_TILE + (tid & (UV_TILE - 1)), y = ty * UV_TILE + tid / UV_TILE;
+  if (x >= S || y >= S) return -1;
+  return (int64_t)(S - 1 - y) * S + x;
+}
+
+__global__ __launch_bounds__(256) void uv_seam_gather_kernel(dsu_uvs::Atlas a, int32_t tiles,
+                                                             const int32_t* __restrict__ face_id,
+                                                             const uint8_t* __restrict__ source,
+                                                             const uint8_t* __restrict__ proj,
+                                                             const uint8_t* __restrict__ fallback,
+                                                             int64_t* __restrict__ num, int64_t* __restrict__ den) {
+  __shared__ int32_t key[SEAM_SLOTS];
+  __shared__ unsigned long long sum[SEAM_SLOTS * 4];
+  const int tid = threadIdx.x;
+  const int64_t at = uv_tile_texel(a.S, tiles);                    // -1 beyond the image: still at every barrier
+  if (!__syncthreads_or(at >= 0 && source[at] != 0)) return;   // the whole workgroup leaves, or none of it
+  for (int i = tid; i < SEAM_SLOTS; i += 256) {
+    key[i] = -1;
+    sum[i * 4] = sum[i * 4 + 1] = sum[i * 4 + 2] = sum[i * 4 + 3] = 0;
+  }
+  __syncthreads();
+  if (at >= 0) dsu_uvs::gather(a, face_id, source, proj, fallback, at, SeamTableAdd{key, sum});
+  __syncthreads();
+  for (int i = tid; i < SEAM_SLOTS; i += 256) {
+    const int32_t g = key[i];
+    if (g < 0) continue;
+    atomicAdd(reinterpret_cast<unsigned long long*>(den + g), sum[i * 4]);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      if (sum[i * 4 + 1 + ch])
+        atomicAdd(reinterpret_cast<unsigned long long*>(num + (int64_t)g * 3 + ch), sum[i * 4 + 1 + ch]);
+  }
+}
+
+// dsu_uv_seam_apply.  Every texel writes its own three bytes; nothing is shared.
+__global__ __launch_bounds__(256) void uv_seam_apply_kernel(dsu_uvs::Atlas a, int32_t tiles,
+                                                            const int32_t* __restrict__ face_id,
+                                                            const uint8_t* __restrict__ source,
+                                                            const uint8_t* __restrict__ proj,
+                                                            const uint8_t* __restrict__ fallback,
+                                                            const double* __restrict__ d, uint8_t* __restrict__ image) {
+  const int64_t at = uv_tile_texel(a.S, tiles);
+  if (at < 0) return;
+  dsu_uvs::apply(a, face_id, source, proj, fallback, d, at, image);
+}
+
 bool uv_size_ok(int32_t size) { return size >= 1 && size <= 8192; }
 
 int64_t uv_tiles(int32_t size) {
@@ -397,6 +481,38 @@ int uv_field_resolve_args(const float* colours, const uint8_t* valid, const int3
   if (!image) return DSU_EINVAL;
   if (n_texels == 0) return DSU_OK;
   if (!colours || !valid || !texels) return DSU_EINVAL;
+  return 1;
+}
+
+// EINVAL / OK / "go on" (1) for the arguments the device and the host entries of the seam steps share
+bool uv_seam_counts_ok(int64_t n_verts, int64_t n_faces, int64_t n_groups, int32_t size) {
+  const int64_t cap = (int64_t)1 << 30;
+  return uv_size_ok(size) && n_verts >= 0 && n_faces >= 0 && n_groups >= 0 && n_verts <= cap && n_faces <= cap &&
+         n_groups <= cap;
+}
+
+int uv_seam_gather_args(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                        int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                        const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const int64_t* num,
+                        const int64_t* den) {
+  if (!uv_seam_counts_ok(n_verts, n_faces, n_groups, size)) return DSU_EINVAL;
+  if (!num || !den) return DSU_EINVAL;
+  if (n_groups == 0 || n_faces == 0) return DSU_OK;
+  if (!uvs || !indices || !group || n_verts == 0 || !face_id || !source || !proj || !fallback) return DSU_EINVAL;
+  return 1;
+}
+
+// the atlas of apply: without faces or groups no face is sound and its arrays are not read
+int uv_seam_apply_args(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                       int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                       const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
+                       const uint8_t* image, dsu_uvs::Atlas& a) {
+  if (!uv_seam_counts_ok(n_verts, n_faces, n_groups, size)) return DSU_EINVAL;
+  if (!image) return DSU_EINVAL;
+  if (!face_id || !source || !proj || !fallback) return DSU_EINVAL;
+  const bool atlas = n_faces > 0 && n_groups > 0;
+  if (atlas && (!uvs || !indices || !group || !d || n_verts == 0)) return DSU_EINVAL;
+  a = dsu_uvs::Atlas{uvs, indices, group, n_verts, atlas ? n_faces : 0, atlas ? n_groups : 0, size};
   return 1;
 }
 
@@ -555,6 +671,65 @@ int dsu_uv_field_resolve_host(const float* colours, const uint8_t* valid, const 
   const int rc = uv_field_resolve_args(colours, valid, texels, n_texels, s, size, image);
   if (rc != 1) return rc;
   for (int64_t t = 0; t < n_texels; ++t) dsu_uvf::resolve(colours, valid, t, s * s, size, texels[t], image);
+  return DSU_OK;
+}
+
+int dsu_uv_seam_gather(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                       int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                       const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, int64_t* num,
+                       int64_t* den, void* stream) {
+  const int rc = uv_seam_gather_args(uvs, indices, group, n_verts, n_faces, n_groups, size, face_id, source, proj,
+                                     fallback, num, den);
+  if (rc != 1) return rc;
+  const int32_t G = (size + UV_TILE - 1) / UV_TILE;
+  uv_seam_gather_kernel<<<(unsigned)uv_tiles(size), 256, 0, (hipStream_t)stream>>>(
+      dsu_uvs::Atlas{uvs, indices, group, n_verts, n_faces, n_groups, size}, G, face_id, source, proj, fallback, num,
+      den);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_uv_seam_apply(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                      int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                      const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
+                      uint8_t* image, void* stream) {
+  dsu_uvs::Atlas a;
+  const int rc = uv_seam_apply_args(uvs, indices, group, n_verts, n_faces, n_groups, size, face_id, source, proj,
+                                    fallback, d, image, a);
+  if (rc != 1) return rc;
+  const int32_t G = (size + UV_TILE - 1) / UV_TILE;
+  uv_seam_apply_kernel<<<(unsigned)uv_tiles(size), 256, 0, (hipStream_t)stream>>>(a, G, face_id, source, proj,
+                                                                                 fallback, d, image);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+// HOST: the same two texts (uv_seam.h) on host arrays, texel after texel and a plain +=.
+int dsu_uv_seam_gather_host(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                            int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                            const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, int64_t* num,
+                            int64_t* den) {
+  const int rc = uv_seam_gather_args(uvs, indices, group, n_verts, n_faces, n_groups, size, face_id, source, proj,
+                                     fallback, num, den);
+  if (rc != 1) return rc;
+  const dsu_uvs::Atlas a{uvs, indices, group, n_verts, n_faces, n_groups, size};
+  for (int64_t at = 0; at < (int64_t)size * size; ++at)
+    dsu_uvs::gather(a, face_id, source, proj, fallback, at, [=](int g, int64_t q, const int64_t n[3]) {
+      den[g] += q;
+      for (int ch = 0; ch < 3; ++ch) num[(int64_t)g * 3 + ch] += n[ch];
+    });
+  return DSU_OK;
+}
+
+int dsu_uv_seam_apply_host(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                           int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                           const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
+                           uint8_t* image) {
+  dsu_uvs::Atlas a;
+  const int rc = uv_seam_apply_args(uvs, indices, group, n_verts, n_faces, n_groups, size, face_id, source, proj,
+                                    fallback, d, image, a);
+  if (rc != 1) return rc;
+  for (int64_t at = 0; at < (int64_t)size * size; ++at) dsu_uvs::apply(a, face_id, source, proj, fallback, d, at, image);
   return DSU_OK;
 }
 

@@ -46,6 +46,8 @@ def parse(argv=None):
     ap.add_argument("--thinning_type", default=None, choices=["double", "front", "back"])
     ap.add_argument("--texture_source", default=None, choices=["vertex", "drawings", "field"],
                     help="export.texture_source: what export.export_uv bakes into the atlas")
+    ap.add_argument("--texture_seam", default=None, choices=["none", "level"],
+                    help="export.texture_seam: level the fallback texels to the drawings (texture_source drawings)")
     for name in ("remeshing", "thinning", "smoothing", "shearing", "color_back_projection"):
         _bool_flag(ap, name)
     ap.add_argument("overrides", nargs="*", help="OmegaConf-style dotlist, e.g. trainer.max_steps=100")
@@ -59,7 +61,7 @@ def parse(argv=None):
                            ("thinning", ex, "thinning"), ("smoothing", ex, "smoothing"),
                            ("shearing", ex, "shearing"), ("thinning_type", ex, "thinning_type"),
                            ("color_back_projection", ex, "color_back_projection"),
-                           ("texture_source", ex, "texture_source")):
+                           ("texture_source", ex, "texture_source"), ("texture_seam", ex, "texture_seam")):
         if getattr(args, key) is not None:
             dst[name] = getattr(args, key)
     if args.max_steps is not None:
@@ -78,6 +80,11 @@ def parse(argv=None):
         ap.error("texture_source 'field' needs export.export_uv=true")
     if not 1 <= int(ex.get("texture_samples", 2)) <= 8:
         ap.error("export.texture_samples must be 1..8")
+    seam = ex.get("texture_seam", "none")
+    if seam not in ("none", "level"):
+        ap.error(f"export.texture_seam must be 'none' or 'level', not {seam!r}")
+    if seam == "level" and source != "drawings":
+        ap.error("texture_seam 'level' needs texture_source 'drawings'")
     return args, conf
 
 
@@ -145,7 +152,8 @@ def recon(uid, thinning, conf, dev):
                     texture_source=source,
                     # the field is the drawings' fallback too: what neither view sees comes from the network
                     texture_field=field_colours(system.model) if source in ("field", "drawings") else None,
-                    texture_samples=int(ex.get("texture_samples", 2)))
+                    texture_samples=int(ex.get("texture_samples", 2)),
+                    texture_seam=str(ex.get("texture_seam", "none")))
     torch.save(system.model.state_dict(), os.path.join(out, f"it{system.global_step}.ckpt"))
     return path
 

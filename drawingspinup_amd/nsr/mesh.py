@@ -973,7 +973,7 @@ def write_obj_textured(path, verts, faces, uvs, image, name):
 
 def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
              color_back_projection=None, thinning=None, export_uv=False, texture_size=1024,
-             texture_source="vertex", texture_field=None, texture_samples=2):
+             texture_source="vertex", texture_field=None, texture_samples=2, texture_seam="none"):
     """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj, or with export_uv
     (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file.
     texture_source: "vertex" bakes the vertex colours (the reference's texture); "drawings" (an
@@ -983,10 +983,17 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
     evaluates texture_field — a callable from (N,3) f32 points in the frame of `verts` to (N,3)
     colours, field_colours(model) — at texture_samples^2 points per texel (nsr/uv.bake_field), the
     vertex colours staying where nothing can be evaluated.  "drawings" with a texture_field uses the
-    field bake as its fallback; "vertex" ignores it."""
+    field bake as its fallback; "vertex" ignores it.
+    texture_seam: "level" (needs texture_source="drawings") levels the fallback texels to the
+    drawings where the two meet (nsr/uv.bake_drawings, seam="level"); "none" composes them as they
+    are."""
     if texture_source not in ("vertex", "drawings", "field"):
         raise ValueError("texture_source must be 'vertex', 'drawings' or 'field'")
+    if texture_seam not in ("none", "level"):
+        raise ValueError("texture_seam must be 'none' or 'level'")
     drawings = texture_source == "drawings"
+    if texture_seam == "level" and not drawings:
+        raise ValueError("texture_seam='level' needs texture_source='drawings'")
     if drawings and not (export_uv and color_back_projection is not None):
         raise ValueError("texture_source='drawings' needs export_uv=True and the color_back_projection images")
     if texture_source == "field" and not (export_uv and callable(texture_field)):
@@ -1000,7 +1007,7 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
             raise ValueError("export_uv needs vertex colours")
         from .uv import uv_mapping
         name = os.path.splitext(os.path.basename(path))[0]
-        projection = dict(color_back_projection, positions=frame[0]) if drawings else None
+        projection = dict(color_back_projection, positions=frame[0], seam=texture_seam) if drawings else None
         field = None
         if texture_source != "vertex" and texture_field is not None:
             field = {"positions": verts.detach().float().cpu().numpy(), "eval_colours": texture_field,

@@ -34,8 +34,9 @@ per texel, which pixel of the front or back drawing the texel's surface point se
 nsr/mesh_post.color_projection asks per vertex (same frame, same masks, same nearest-pixel read) —
 and keeps the vertex-colour bake where neither view sees it (dsu_uv_project in include/dsu_hip.h
 has the rule in full).  What remains visible of the composition: a seam where projected and
-fallback texels meet, nearest-pixel sampling (no bilinear or area filter), and a fallback band along
-the silhouette as wide as the erosion of the masks (19 pixels of the 2048^2 drawings).
+fallback texels meet (unless it is levelled, below), nearest-pixel sampling (no bilinear or area
+filter), and a fallback band along the silhouette as wide as the erosion of the masks (19 pixels of
+the 2048^2 drawings).
 
 Field.  bake_field asks the network the export has just optimised instead: every covered texel's
 surface point (samples x samples of them, a texel wide) goes back to the field's own frame through
@@ -44,7 +45,18 @@ the kernels vertex_colors runs); the mean of a texel's samples is its colour
 (dsu_uv_field_points / dsu_uv_field_resolve in include/dsu_hip.h).  The points lie on the
 triangles, not on the zero level set (no snapping), and a sub-sample that falls outside its face is
 evaluated on the face's plane.  With the drawings as well, the field takes the vertex bake's place
-as their fallback; the seam between the two stays.
+as their fallback; the seam between the two stays unless it is levelled.
+
+Seam.  bake_drawings(seam="level") (projection["seam"], save_obj's texture_seam; off by default)
+levels the fallback to the drawings (Lempitsky & Ivanov 2007): the drawing texels keep their bytes,
+the fallback texels get a smooth colour offset.  dsu_uv_seam_gather sums drawing - fallback of the
+projected texels per welded vertex group (seam_groups: the chart copies of a vertex are one
+unknown, so the offset is continuous across chart borders); seam_offsets makes a group with a whole
+texel's weight known and extends the known offsets harmonically over the welded mesh's edges
+(uniform weights: an M-matrix, so no offset leaves the range of the known ones; solved by
+dsu_spd_cg_block); dsu_uv_seam_apply adds the offset interpolated within each face and rounds.  What
+stays of the seam: the high-frequency mismatch (sharp ink beside a smooth field), which an offset
+that is smooth over the mesh does not touch.
 """
 import math
 
@@ -67,6 +79,11 @@ FILL_TARGET = 0.6       # first scale: the charts' projected area over the atlas
 # between 1e-5, 1e-4 and 1e-3, so that mesh does not tell the candidates apart; a marching-cubes
 # mesh with thin folds has not been swept.
 Z_TOLERANCE = 1e-4
+# Seam levelling: a group's offset is known when the projected texels around it weigh at least one
+# whole texel (the gather's fixed point: a barycentric of 1 is 2^20); slivers do not pin an offset.
+SEAM_MIN_WEIGHT = 1 << 20
+SEAM_TOL = 1e-10
+SEAM_MAX_ITERS = 20000
 
 
 # ------------------------------------------------------------------ host parts
@@ -168,7 +185,8 @@ def layout(verts, faces, label, chart, size, gutter, scale=None):
 # ------------------------------------------------------------------ device parts
 class DeviceBackend:
     """The kernels behind the interface parametrize / bake_vertex_colours / bake_drawings use
-    (tests/uv_ref.py, tests/uv_project_ref.py and tests/uv_field_ref.py have the float64 numpy one)."""
+    (tests/uv_ref.py, tests/uv_project_ref.py, tests/uv_field_ref.py and tests/uv_seam_ref.py have the
+    float64 numpy one)."""
 
     def __init__(self, device=None):
         self.dev = torch.device(device if device is not None else "cuda")
@@ -219,6 +237,34 @@ class DeviceBackend:
     def field_resolve(self, colours, valid, texels, image):
         from .. import ops
         return ops.uv_field_resolve(colours, valid, texels, image)
+
+    def _seam_atlas(self, uvs, indices, group):
+        t = lambda a, dt: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.dev)
+        return t(uvs, np.float32), t(indices, np.int32), t(group, np.int32)
+
+    def seam_gather(self, uvs, indices, group, n_groups, face_id, source, proj, fallback):
+        from .. import ops
+        return ops.uv_seam_gather(*self._seam_atlas(uvs, indices, group), face_id, source, proj, fallback, n_groups)
+
+    def seam_solve(self, A, rhs):
+        """A (n,n) scipy csr with sorted indices, symmetric positive definite, rhs (n,3) -> x (n,3)
+        f64 (numpy) by dsu_spd_cg_block; .seam_iterations holds the iteration count."""
+        from .. import ops
+        x, iters, res = ops.spd_cg_block(torch.from_numpy(A.indptr.astype(np.int32)).to(self.dev),
+                                         torch.from_numpy(A.indices.astype(np.int32)).to(self.dev),
+                                         torch.from_numpy(A.data.astype(np.float64)).to(self.dev),
+                                         torch.from_numpy(np.ascontiguousarray(rhs, np.float64)).to(self.dev),
+                                         tol=SEAM_TOL, max_iters=SEAM_MAX_ITERS)
+        if iters >= SEAM_MAX_ITERS and not (res <= SEAM_TOL).all():
+            raise RuntimeError(f"seam solve did not converge in {SEAM_MAX_ITERS} iterations "
+                               f"(residual {res.max():.3e})")
+        self.seam_iterations = iters
+        return x.cpu().numpy()
+
+    def seam_apply(self, uvs, indices, group, face_id, source, proj, fallback, d):
+        from .. import ops
+        return ops.uv_seam_apply(*self._seam_atlas(uvs, indices, group), face_id, source, proj, fallback,
+                                 torch.from_numpy(np.ascontiguousarray(d, np.float64)).to(self.dev))
 
     @staticmethod
     def to_numpy(a):
@@ -282,9 +328,64 @@ def bake_vertex_colours(uvs, indices, colours, size=1024, gutter=2, device=None,
     return (out, be.to_numpy(fid)) if return_maps else out
 
 
+def seam_groups(verts, faces, vmapping):
+    """The unknowns of seam levelling: verts (V,3) and faces (M,3) of the mesh before the charts,
+    vmapping (V') as parametrize returns it.  -> group (V') int32, the welded class of every atlas
+    vertex (nsr/thinning._weld's representative of vmapping[k], compacted to [0, G)): the chart
+    copies of one vertex and coincident vertices are one unknown; group_faces (F,3) int64, the faces
+    over the groups without those whose three groups are not distinct (the graph's triangles)."""
+    from .thinning import _weld
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    vmapping = np.asarray(vmapping, np.int64).reshape(-1)
+    rep, _ = _weld(np.asarray(verts, np.float64).reshape(-1, 3), faces)
+    reps, group = np.unique(rep[vmapping], return_inverse=True)
+    g = np.searchsorted(reps, rep[faces]) if len(faces) else np.zeros((0, 3), np.int64)
+    distinct = (g[:, 0] != g[:, 1]) & (g[:, 1] != g[:, 2]) & (g[:, 0] != g[:, 2])
+    return group.reshape(-1).astype(np.int32), g[distinct].astype(np.int64)
+
+
+def seam_offsets(num, den, group_faces, backend):
+    """The host step of seam levelling (include/dsu_hip.h, between h. and i.): num (G,3) and den (G)
+    int64 from seam_gather -> d (G,3) f64, known (G) bool.  A group with den >= SEAM_MIN_WEIGHT is
+    known, d = num / den.  The others solve the uniform Laplacian over the edges of group_faces,
+    deg(u) d_u - sum of unknown neighbours = sum of known neighbours, through backend.seam_solve
+    (three columns at once); a connected set of unknowns without a known neighbour keeps 0."""
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    num = np.asarray(_host(num), np.int64).reshape(-1, 3)
+    den = np.asarray(_host(den), np.int64).reshape(-1)
+    G = len(den)
+    known = den >= SEAM_MIN_WEIGHT
+    d = np.zeros((G, 3), np.float64)
+    d[known] = num[known].astype(np.float64) / den[known].astype(np.float64)[:, None]
+    gf = np.asarray(group_faces, np.int64).reshape(-1, 3)
+    if G == 0 or not len(gf) or known.all() or not known.any():
+        return d, known
+    e = np.concatenate([gf[:, [0, 1]], gf[:, [1, 2]], gf[:, [2, 0]]], 0)
+    e = np.unique(np.sort(e, 1), axis=0)                               # every undirected edge once
+    A = sp.csr_matrix((np.ones(2 * len(e)), (np.concatenate([e[:, 0], e[:, 1]]), np.concatenate([e[:, 1], e[:, 0]]))),
+                      shape=(G, G))
+    deg = np.asarray(A.sum(1)).reshape(-1)
+    unknown = np.flatnonzero(~known)
+    Auu, Auk = A[unknown][:, unknown], A[unknown][:, np.flatnonzero(known)]
+    _, comp = connected_components(Auu, directed=False)
+    touches = np.asarray(Auk.sum(1)).reshape(-1) > 0
+    fed = np.zeros(comp.max() + 1, bool)
+    fed[comp[touches]] = True
+    keep = np.flatnonzero(fed[comp])                                   # rows of `unknown` that are solved
+    if not len(keep):
+        return d, known
+    L = (sp.diags(deg[unknown[keep]]) - Auu[keep][:, keep]).tocsr()
+    L.sum_duplicates()
+    L.sort_indices()
+    rhs = Auk[keep] @ d[known]
+    d[unknown[keep]] = np.asarray(backend.seam_solve(L, np.ascontiguousarray(rhs, np.float64)), np.float64)
+    return d, known
+
+
 def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_back_u8, fallback_colours,
                   size=1024, gutter=2, z_tolerance=Z_TOLERANCE, erode=19, device=None, backend=None,
-                  return_maps=False, fallback_image=None):
+                  return_maps=False, fallback_image=None, seam="none", groups=None, group_faces=None):
     """The atlas with the drawings projected into it: positions (V',3) are the atlas vertices in
     color_projection's frame (x right, y up, z front, inside [-0.5, 0.5]: after thinning and
     smoothing, before shear and ortho_scale), color_*_u8 (res,res,3) and mask_front_u8 (res,res) the
@@ -293,7 +394,15 @@ def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_
     neither view sees keeps the vertex-colour bake of fallback_colours (V',3); the gutter fill runs
     over the composition.  return_maps: also face_id (size,size) i32 and source (size,size) u8
     (0 fallback, 1 front, 2 back).  fallback_image (size,size,3) u8 without gutter fill (bake_field's,
-    gutter=0) takes the place of the vertex-colour bake."""
+    gutter=0) takes the place of the vertex-colour bake.
+    seam: "none" composes with a hard where(source > 0, drawing, fallback); "level" leaves the
+    drawing texels alone and adds to the fallback texels a smooth offset that meets the drawing at
+    the border (dsu_uv_seam_gather, seam_offsets, dsu_uv_seam_apply); it needs groups (V') and
+    group_faces (F,3) from seam_groups."""
+    if seam not in ("none", "level"):
+        raise ValueError("seam must be 'none' or 'level'")
+    if seam == "level" and (groups is None or group_faces is None):
+        raise ValueError("seam='level' needs groups and group_faces (seam_groups)")
     be = backend if backend is not None else DeviceBackend(device)
     uvs, indices = np.asarray(uvs, np.float32), np.asarray(indices, np.int64)
     img, fid, _ = be.bake(uvs, indices, np.asarray(fallback_colours, np.float32).reshape(-1, 3), int(size))
@@ -303,8 +412,17 @@ def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_
         img = torch.as_tensor(_host(fallback_image)).to(src.device) if torch.is_tensor(src) else _host(fallback_image)
         if tuple(img.shape) != tuple(proj.shape):
             raise ValueError("fallback_image must be (size,size,3) uint8")
-    where = torch.where if torch.is_tensor(src) else np.where
-    out = where((src > 0)[..., None], proj, img)
+    if seam == "level":
+        groups = np.ascontiguousarray(groups, np.int32).reshape(-1)
+        if len(groups) != len(uvs):
+            raise ValueError("groups must hold one class per atlas vertex")
+        n_groups = int(groups.max()) + 1 if len(groups) else 0
+        num, den = be.seam_gather(uvs, indices, groups, n_groups, fid, src, proj, img)
+        d, _ = seam_offsets(be.to_numpy(num), be.to_numpy(den), group_faces, be)
+        out = be.seam_apply(uvs, indices, groups, fid, src, proj, img, d)
+    else:
+        where = torch.where if torch.is_tensor(src) else np.where
+        out = where((src > 0)[..., None], proj, img)
     if gutter > 0:
         out = be.dilate(out, fid >= 0, int(gutter))
     out = be.to_numpy(out)
@@ -369,8 +487,9 @@ def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=
     Returns the textured mesh as a dict (verts (V',3) f64, faces (M,3) i64, uvs (V',2) f32, image
     (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference.
     projection: dict(positions (V,3) in the order of v_np and in color_projection's frame,
-    color_front, mask_front, color_back[, z_tolerance, erode]) bakes with bake_drawings, the vertex
-    colours being the fallback; None = the vertex colours alone.
+    color_front, mask_front, color_back[, z_tolerance, erode, seam]) bakes with bake_drawings, the
+    vertex colours being the fallback (seam "level": the fallback texels levelled to the drawings,
+    the groups built from v_np, faces and vmapping); None = the vertex colours alone.
     field: dict(positions (V,3) in the order of v_np and in the field's frame, eval_colours[,
     samples, chunk]) bakes with bake_field, the vertex colours staying where no sample is valid; with
     `projection` as well the drawings are composed over the field bake instead of the vertex bake."""
@@ -389,8 +508,11 @@ def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=
         image = bake_vertex_colours(uvs, indices, colours, size, gutter, device=device, backend=backend)
     else:
         pr = projection
+        seam = pr.get("seam", "none")
+        groups, group_faces = seam_groups(v_np, faces, vmapping) if seam == "level" else (None, None)
         image = bake_drawings(uvs, indices, _host(pr["positions"]).reshape(-1, 3)[vmapping], pr["color_front"],
                               pr["mask_front"], pr["color_back"], colours, size, gutter,
                               z_tolerance=pr.get("z_tolerance", Z_TOLERANCE), erode=pr.get("erode", 19),
-                              device=device, backend=backend, fallback_image=fallback_image)
+                              device=device, backend=backend, fallback_image=fallback_image, seam=seam,
+                              groups=groups, group_faces=group_faces)
     return {"verts": v_np[vmapping], "faces": indices, "uvs": uvs, "image": image, "name": save_name}

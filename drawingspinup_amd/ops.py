@@ -1771,6 +1771,61 @@ def uv_field_resolve(colours, valid, texels, image):
     return image
 
 
+def _uv_seam_args(uvs, indices, group, face_id, source, proj, fallback):
+    uvs = _f32c(uvs)
+    indices, group = indices.to(torch.int32).contiguous(), group.to(torch.int32).contiguous()
+    V, M, S = uvs.shape[0], indices.shape[0], face_id.shape[0]
+    if uvs.shape != (V, 2) or indices.shape != (M, 3) or group.shape != (V,) or face_id.shape != (S, S):
+        raise ValueError("uvs (V',2), indices (M,3), group (V') and face_id (S,S) expected")
+    if face_id.dtype != torch.int32 or source.dtype != torch.uint8 or source.shape != (S, S):
+        raise ValueError("face_id (S,S) int32 and source (S,S) uint8 expected")
+    for img in (proj, fallback):
+        if tuple(img.shape) != (S, S, 3) or img.dtype != torch.uint8:
+            raise ValueError("proj and fallback must be (S,S,3) uint8")
+    return (uvs, indices, group, face_id.contiguous(), source.contiguous(), proj.contiguous(),
+            fallback.contiguous()), (V, M, S)
+
+
+def uv_seam_gather(uvs, indices, group, face_id, source, proj, fallback, n_groups):
+    """dsu_uv_seam_gather (include/dsu_hip.h, UV export h.): the projected texels' differences
+    proj - fallback summed per welded vertex group in 64-bit fixed point.  uvs (V',2) f32, indices
+    (M,3), group (V') i32 in [0, n_groups), face_id (S,S) i32 from uv_bake, source (S,S) u8 and proj
+    (S,S,3) u8 from uv_project, fallback (S,S,3) u8 without gutter fill, all on the device.
+    -> num (n_groups,3) i64, den (n_groups) i64."""
+    (uvs, indices, group, face_id, source, proj, fallback), (V, M, S) = \
+        _uv_seam_args(uvs, indices, group, face_id, source, proj, fallback)
+    G = int(n_groups)
+    if G < 0:
+        raise ValueError("n_groups must not be negative")
+    num = torch.zeros((G, 3), dtype=torch.int64, device=uvs.device)
+    den = torch.zeros(G, dtype=torch.int64, device=uvs.device)
+    if G == 0 or M == 0:                                     # empty tensors have no address to hand over
+        return num, den
+    check(lib().dsu_uv_seam_gather(ptr(uvs), ptr(indices), ptr(group), V, M, G, S, ptr(face_id), ptr(source),
+                                   ptr(proj), ptr(fallback), ptr(num), ptr(den), stream()), "dsu_uv_seam_gather")
+    return num, den
+
+
+def uv_seam_apply(uvs, indices, group, face_id, source, proj, fallback, d):
+    """dsu_uv_seam_apply (include/dsu_hip.h, UV export i.): the composed atlas — proj where source is
+    set, elsewhere fallback plus the offsets d (G,3) f64 of the face's three groups interpolated with
+    the texel's barycentrics, rounded to nearest and clipped.  Arguments as uv_seam_gather.
+    -> image (S,S,3) u8."""
+    (uvs, indices, group, face_id, source, proj, fallback), (V, M, S) = \
+        _uv_seam_args(uvs, indices, group, face_id, source, proj, fallback)
+    d = d.to(torch.float64).contiguous()
+    if d.dim() != 2 or d.shape[1] != 3:
+        raise ValueError("d must be (G,3)")
+    G = d.shape[0]
+    image = torch.empty((S, S, 3), dtype=torch.uint8, device=uvs.device)
+    atlas = M > 0 and G > 0
+    check(lib().dsu_uv_seam_apply(ptr(uvs) if atlas else None, ptr(indices) if atlas else None,
+                                  ptr(group) if atlas else None, V, M, G, S, ptr(face_id), ptr(source), ptr(proj),
+                                  ptr(fallback), ptr(d) if atlas else None, ptr(image), stream()),
+          "dsu_uv_seam_apply")
+    return image
+
+
 # ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
 SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
 

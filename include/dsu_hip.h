@@ -1525,7 +1525,61 @@ int dsu_corrective_smooth_host(const float* skinned, const int32_t* rep, const i
  *
  * dsu_uv_field_points_host / dsu_uv_field_resolve_host: HOST functions on HOST arrays — the same
  * two texts (csrc/uv_field.h) compiled for the CPU, with the same argument checks, so that the
- * rule can be held bit for bit without a device. */
+ * rule can be held bit for bit without a device.
+ *
+ * h. / i. Seam levelling (an extension; Lempitsky & Ivanov 2007): where the drawings of e. are
+ * composed over a fallback bake (the vertex bake of c. or the field bake of g.), the two disagree in
+ * tone and a step runs along every border between them.  The drawing texels are left alone; the
+ * fallback texels get a colour offset that equals drawing - fallback at the border and is the
+ * harmonic extension of that over the MESH elsewhere (not over the texture: the border crosses the
+ * charts).  Inputs of both steps: the atlas (uvs, indices, size) and face_id (size, size) i32 as
+ * dsu_uv_bake wrote it; source (size, size) u8 and proj (size, size, 3) u8 as dsu_uv_project wrote
+ * them; fallback (size, size, 3) u8, the vertex or field bake BEFORE the gutter fill; group
+ * (n_verts) i32, the welded class of every atlas vertex in [0, n_groups) — the chart copies of one
+ * mesh vertex, and the coincident vertices marching cubes leaves behind, are one unknown
+ * (nsr/uv.seam_groups).  A face m is SOUND at a texel (row r, column c) when m is in [0, n_faces),
+ * its three indices are in [0, n_verts), the three groups g_0, g_1, g_2 of its corners are in
+ * [0, n_groups), and, with w0, w1, w2 and area at (x, y) = (c, size - 1 - r) exactly as in e. step
+ * 1, area is finite and > 0; then b_i = w_i / area.
+ *
+ * h. dsu_uv_seam_gather.  One thread per texel, one workgroup per 16x16 tile.  A texel with
+ * source == 0, or whose face m = face_id[r][c] is not sound, adds nothing.  Otherwise, per corner i:
+ *     q_i = (int64) floor(b_i 2^20 + 0.5), clipped to [0, 2^20]  (a NaN counts as 0);
+ * and for each corner with q_i > 0
+ *     den[g_i] += q_i,    num[g_i][ch] += q_i ((int) proj[ch] - (int) fallback[ch])   ch = 0, 1, 2
+ * as 64-bit INTEGER atomic adds into the caller-zeroed den (n_groups) i64 and num (n_groups, 3) i64
+ * (the kernel first sums a tile's contributions per group in LDS, also in 64-bit integers, and adds
+ * each group's four sums once).  Integer sums do not depend on the order of arrival or on how they
+ * are grouped: two runs give the same bits.  |num| is at most size^2 2^20 255 < 2^54 for
+ * size <= 8192.
+ * DSU_EINVAL before any launch: size outside 1..8192, n_verts, n_faces or n_groups negative or
+ * above 2^30, num or den NULL.  Then n_groups == 0 or n_faces == 0: DSU_OK, nothing read or
+ * written.  Then DSU_EINVAL for n_verts == 0 or any input pointer NULL.
+ *
+ * The host (nsr/uv.seam_offsets) turns the sums into one offset d (n_groups, 3) f64 per group: a
+ * group with den >= 2^20 (one whole texel's weight) is KNOWN and has d = num / den; the others are
+ * the unknowns of the uniform graph Laplacian over the welded mesh's edges, deg(u) d_u - sum of the
+ * unknown neighbours' d = sum of the known neighbours' d, solved for the three channels at once
+ * with dsu_spd_cg_block; an unknown in a component without a known group has d = 0.  Uniform
+ * weights keep the matrix an M-matrix: no offset leaves the range of the known ones.
+ *
+ * i. dsu_uv_seam_apply.  One thread per texel, tiles as above; every texel of image (size, size, 3)
+ * u8 is written.  In this order:
+ *   face_id < 0:       0, 0, 0;
+ *   source != 0:       the bytes of proj;
+ *   the face is sound: per channel  e = (b0 d[g_0][ch] + b1 d[g_1][ch]) + b2 d[g_2][ch],
+ *                      v = (double) fallback[ch] + e;  the byte is floor(v + 0.5) clipped to
+ *                      [0, 255], or the fallback byte when v is not finite;
+ *   otherwise:         the bytes of fallback.
+ * No atomics.  The gutter fill (d.) runs over the result.
+ * DSU_EINVAL before any launch: size outside 1..8192, n_verts, n_faces or n_groups negative or
+ * above 2^30, image, face_id, source, proj or fallback NULL; and, with n_faces > 0 and
+ * n_groups > 0, n_verts == 0 or uvs, indices, group or d NULL.  With n_faces == 0 or n_groups == 0
+ * no face is sound and uvs, indices, group and d are not read.
+ *
+ * dsu_uv_seam_gather_host / dsu_uv_seam_apply_host: HOST functions on HOST arrays — the same two
+ * texts (csrc/uv_seam.h) compiled for the CPU (a plain loop over the texels and a plain +=), with
+ * the same argument checks. */
 #define DSU_UV_COUNT 0
 #define DSU_UV_FILL 1
 #define DSU_UV_RASTER 2
@@ -1556,6 +1610,22 @@ int dsu_uv_field_points_host(const float* uvs, const int32_t* indices, const flo
                              int64_t n_texels, int32_t s, float* points, uint8_t* valid);
 int dsu_uv_field_resolve_host(const float* colours, const uint8_t* valid, const int32_t* texels, int64_t n_texels,
                               int32_t s, int32_t size, uint8_t* image);
+int dsu_uv_seam_gather(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                       int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                       const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, int64_t* num,
+                       int64_t* den, void* stream);
+int dsu_uv_seam_apply(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                      int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                      const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
+                      uint8_t* image, void* stream);
+int dsu_uv_seam_gather_host(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                            int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                            const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, int64_t* num,
+                            int64_t* den);
+int dsu_uv_seam_apply_host(const float* uvs, const int32_t* indices, const int32_t* group, int64_t n_verts,
+                           int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
+                           const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
+                           uint8_t* image);
 
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
