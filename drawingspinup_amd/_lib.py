@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (A/B measurements); unset = the in-tree library.
 LIB_PATH = os.environ.get("DSU_HIP_LIB") or os.path.join(_HERE, "libdsu_hip.so")
 MAX_LEVELS = 16
+ABI_VERSION = 2                                       # dsu_abi_version() of the header _PROTOS restates
 
 c_i32, c_i64, c_u32, c_f32, c_vp = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_void_p
 
@@ -51,6 +52,10 @@ class OccRefreshArgs(C.Structure):                    # dsu_occgrid_refresh_args
                 ("inj_count", c_i32), ("inj_cells", c_vp), ("inj_rand", c_vp), ("thre_out", c_vp),
                 ("workspace", c_vp), ("workspace_bytes", c_i64), ("cells_out", c_vp),
                 ("rand_out", c_vp)]
+
+
+class RenderTexture(C.Structure):                     # dsu_render_texture
+    _fields_ = [("uv", c_vp), ("texels", c_vp), ("tex_size", c_i32), ("filter", c_i32)]
 
 
 class NormCfg(C.Structure):
@@ -163,17 +168,12 @@ _PROTOS = {
     "dsu_raster_mask": [P, c_i64, c_f32, c_i32, P, P],
     "dsu_erode_ellipse_u8": [P, c_i32, c_i32, c_i32, P, P],
     "dsu_mesh_render_ortho_workspace_bytes": [c_i32, c_i32],
-    "dsu_mesh_render_ortho": [c_i32, P, P, P, P, c_i32, c_i64, c_i64, C.c_double, C.c_double,
-                              C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
-    "dsu_mesh_render_ortho_textured": [P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i64, c_i64, C.c_double,
-                                       C.c_double, C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P,
-                                       P, P, P, P],
+    "dsu_mesh_render_ortho": [c_i32, P, P, P, P, C.POINTER(RenderTexture), c_i32, c_i64, c_i64, C.c_double,
+                              C.c_double, C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
     "dsu_mip_levels": [c_i32],
     "dsu_mip_pyramid_texels": [c_i32],
     "dsu_mip_workspace_bytes": [c_i32],
     "dsu_mip_pyramid_build": [P, P, c_i32, c_i32, P, P, c_i64, P],
-    "dsu_mesh_render_ortho_mip": [P, P, P, P, P, P, c_i32, c_i32, c_i64, c_i64, C.c_double, C.c_double,
-                                  C.c_double, c_i32, c_i32, P, c_i64, P, c_i64, P, P, P, P, P, P, P],
     "dsu_mip_sample_host": [P, c_i32, P, P, P, c_i64, P],
     "dsu_pos_edge_u8": [P, c_i32, c_i32, c_i32, P, P],
     "dsu_uv_face_labels": [P, P, c_i64, c_i64, P, P, P, P],
@@ -333,6 +333,9 @@ def lib():
         h = C.CDLL(LIB_PATH)
         h.dsu_strerror.restype = C.c_char_p
         h.dsu_strerror.argtypes = [C.c_int]
+        if h.dsu_abi_version() != ABI_VERSION:         # before the table: a stale library may lack its names
+            raise DsuError(f"{LIB_PATH} has ABI version {h.dsu_abi_version()}, this package binds version "
+                           f"{ABI_VERSION}: rebuild it (`python -m drawingspinup_amd.build`).")
         for name, args in _PROTOS.items():
             fn = getattr(h, name)  # AttributeError here = header/library mismatch
             fn.restype = _RESTYPES.get(name, C.c_int64 if name.endswith("_bytes") else C.c_int)

@@ -1,5 +1,5 @@
 // The mip pyramid of the UV atlas behind the trilinear filter of the frame rasteriser
-// (dsu_mesh_render_ortho_mip, mesh_render.hip).  The rule is stated in full in include/dsu_hip.h
+// (DSU_TEX_TRILINEAR of dsu_mesh_render_ortho, mesh_render.hip).  The rule is stated in full in include/dsu_hip.h
 // ("Mip-mapped frames"); tests/frame_render_mip_ref.py restates it by brute force.
 //
 //   level 0      the atlas, byte for byte

@@ -21,13 +21,13 @@
 // workgroup then resolves: no global atomics on the frame, no visibility buffer in HBM.
 // LDS: 32 KB of keys + 1 KB of lattice coordinates at ss = 4.
 //
-// Textured frames (dsu_mesh_render_ortho_textured): the same visibility, and in the resolve the three
+// Textured frames (`tex` with filter NEAREST or BILINEAR): the same visibility, and in the resolve the three
 // colour channels of a sample come from the UV atlas — the face's uvs interpolated with the sample's
 // edge functions, then a nearest or bilinear read of the RGBA8 texture under the bake's convention
 // (image row r, column c holds uv T = (c, T - 1 - r)).  The texels are read through L2: neighbouring
 // samples share them.  The position pass is untouched.
 //
-// Mip-mapped frames (dsu_mesh_render_ortho_mip): the atlas is the pyramid of mesh_mip.hip and a sample
+// Mip-mapped frames (`tex` with filter TRILINEAR): the atlas is the pyramid of mesh_mip.hip and a sample
 // blends the bilinear reads of two neighbouring levels (mip_sample.h).  The view is orthographic and
 // uv is affine on a face, so the level is constant per (frame, face): it is computed where the
 // face's attributes are loaded.  The two levels of a face lie near each other in the buffer.
@@ -133,7 +133,8 @@ struct RenderTexture {
   int32_t T;
 };
 
-constexpr int TEX_NONE = -1, TEX_NEAREST = 0, TEX_BILINEAR = 1, TEX_TRILINEAR = 2;
+constexpr int TEX_NONE = -1, TEX_NEAREST = DSU_TEX_NEAREST, TEX_BILINEAR = DSU_TEX_BILINEAR,
+              TEX_TRILINEAR = DSU_TEX_TRILINEAR;
 
 __device__ __forceinline__ float texel_channel(uint32_t p, int ch) { return (float)((p >> (8 * ch)) & 255u); }
 
@@ -400,6 +401,44 @@ int64_t bins_of(int32_t F, int32_t S) {
   return (int64_t)F * G * G;
 }
 
+bool texture_ok(const dsu_render_texture& t) {
+  return t.uv && t.texels && (uintptr_t)t.texels % 4 == 0 &&   // a texel is one 32-bit load
+         t.tex_size >= 1 && t.tex_size <= dsu_mip::MAX_T && t.filter >= TEX_NEAREST && t.filter <= TEX_TRILINEAR;
+}
+
+// The arguments of the RASTER launch, and the kernel of a (SS, colour source) pair.
+struct RasterCall {
+  unsigned bins;
+  hipStream_t st;
+  const float* screen;
+  const int32_t* faces;
+  const float* colour;
+  const float* pos;
+  int64_t V, M;
+  RenderView view;
+  const int32_t* offsets;
+  const int32_t* items;
+  int64_t n_items;
+  RenderTexture tex;
+  RenderOut out;
+
+  template <int SS, int TEX>
+  void go() const {
+    if constexpr (TEX == TEX_NONE)
+      mesh_raster_resolve_kernel<SS><<<bins, 256, 0, st>>>(screen, faces, colour, pos, V, M, view, offsets,
+                                                           items, n_items, out);
+    else
+      mesh_raster_resolve_textured_kernel<SS, TEX><<<bins, 256, 0, st>>>(screen, faces, pos, V, M, view, offsets,
+                                                                         items, n_items, tex, out);
+  }
+  template <int TEX>
+  void launch(int ss) const {
+    if (ss == 1) go<1, TEX>();
+    else if (ss == 2) go<2, TEX>();
+    else go<4, TEX>();
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -410,11 +449,11 @@ int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size) {
 }
 
 int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
-                          const float* colour, const float* pos, int32_t n_frames, int64_t n_verts,
-                          int64_t n_faces, double cx, double cy, double span, int32_t size, int32_t ss,
-                          void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
-                          uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
-                          float* frames, float* pixels, void* stream) {
+                          const float* colour, const float* pos, const dsu_render_texture* tex,
+                          int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
+                          double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
+                          int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
+                          int32_t* face_id, float* depth, float* frames, float* pixels, void* stream) {
   if (stage < DSU_RENDER_COUNT || stage > DSU_RENDER_RASTER) return DSU_EINVAL;
   if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
   if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
@@ -424,95 +463,24 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
   if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
   if (n_faces && (!screen || !faces || n_verts == 0)) return DSU_EINVAL;
   if (stage != DSU_RENDER_COUNT && n_items && !items) return DSU_EINVAL;
-  if (stage == DSU_RENDER_RASTER && n_faces && (!colour || !pos)) return DSU_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
   if (stage != DSU_RENDER_RASTER)
     return dsu_bin::run_stage(stage, FrameTriangleTiles{screen, faces, n_verts, n_faces, view},
                               (int64_t)n_frames * n_faces, workspace, nb, items, n_items, st);
-  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
-  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
-#define DSU_RASTER(SS_)                                                                         \
-  mesh_raster_resolve_kernel<SS_><<<(unsigned)nb, 256, 0, st>>>(screen, faces, colour, pos, n_verts, \
-                                                                n_faces, view, offsets, items,   \
-                                                                n_faces ? n_items : 0, out)
-  if (ss == 1) DSU_RASTER(1);
-  else if (ss == 2) DSU_RASTER(2);
-  else DSU_RASTER(4);
-#undef DSU_RASTER
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, const float* colour,
-                                   const float* pos, const float* uv, const uint8_t* texture,
-                                   int32_t tex_size, int32_t filter, int32_t n_frames, int64_t n_verts,
-                                   int64_t n_faces, double cx, double cy, double span, int32_t size,
-                                   int32_t ss, void* workspace, int64_t workspace_bytes, int32_t* items,
-                                   int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id,
-                                   float* depth, float* frames, float* pixels, void* stream) {
-  (void)colour;                                          // the atlas replaces the vertex colours
-  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
-  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
-      n_verts > (int64_t)1 << 30)
-    return DSU_EINVAL;
-  if (!uv || !texture || tex_size < 1 || tex_size > 8192 || (filter != 0 && filter != 1)) return DSU_EINVAL;
-  if ((uintptr_t)texture % 4) return DSU_EINVAL;         // a texel is one 32-bit load
-  const int64_t nb = bins_of(n_frames, size);
-  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
-  if (n_faces && (!screen || !faces || !pos || n_verts == 0)) return DSU_EINVAL;
-  if (n_items && !items) return DSU_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
-  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
-  const RenderTexture tex{uv, reinterpret_cast<const uint32_t*>(texture), tex_size};
-  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
-#define DSU_RASTER(SS_, F_)                                                                     \
-  mesh_raster_resolve_textured_kernel<SS_, F_><<<(unsigned)nb, 256, 0, st>>>(                    \
-      screen, faces, pos, n_verts, n_faces, view, offsets, items, n_faces ? n_items : 0, tex, out)
-  if (filter == TEX_NEAREST) {
-    if (ss == 1) DSU_RASTER(1, TEX_NEAREST);
-    else if (ss == 2) DSU_RASTER(2, TEX_NEAREST);
-    else DSU_RASTER(4, TEX_NEAREST);
-  } else {
-    if (ss == 1) DSU_RASTER(1, TEX_BILINEAR);
-    else if (ss == 2) DSU_RASTER(2, TEX_BILINEAR);
-    else DSU_RASTER(4, TEX_BILINEAR);
+  if (n_faces && !pos) return DSU_EINVAL;
+  if (tex ? !texture_ok(*tex) : (n_faces && !colour)) return DSU_EINVAL;
+  const RasterCall call{(unsigned)nb, st, screen, faces, colour, pos, n_verts, n_faces, view,
+                        dsu_bin::split(workspace, nb).offsets, items, n_faces ? n_items : 0,
+                        tex ? RenderTexture{tex->uv, reinterpret_cast<const uint32_t*>(tex->texels), tex->tex_size}
+                            : RenderTexture{nullptr, nullptr, 0},
+                        RenderOut{color_u8, pos_u8, face_id, depth, frames, pixels}};
+  switch (tex ? tex->filter : TEX_NONE) {   // source first, then ss: the order the kernels have in the code object
+    case TEX_NONE: call.launch<TEX_NONE>(ss); break;
+    case TEX_NEAREST: call.launch<TEX_NEAREST>(ss); break;
+    case TEX_BILINEAR: call.launch<TEX_BILINEAR>(ss); break;
+    case TEX_TRILINEAR: call.launch<TEX_TRILINEAR>(ss); break;
   }
-#undef DSU_RASTER
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_mesh_render_ortho_mip(const float* screen, const int32_t* faces, const float* colour,
-                              const float* pos, const float* uv, const uint8_t* pyramid, int32_t tex_size,
-                              int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
-                              double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
-                              int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
-                              int32_t* face_id, float* depth, float* frames, float* pixels, void* stream) {
-  (void)colour;                                          // the atlas replaces the vertex colours
-  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
-  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
-      n_verts > (int64_t)1 << 30)
-    return DSU_EINVAL;
-  if (!uv || !pyramid || tex_size < 1 || tex_size > dsu_mip::MAX_T) return DSU_EINVAL;
-  if ((uintptr_t)pyramid % 4) return DSU_EINVAL;         // a texel is one 32-bit load
-  const int64_t nb = bins_of(n_frames, size);
-  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
-  if (n_faces && (!screen || !faces || !pos || n_verts == 0)) return DSU_EINVAL;
-  if (n_items && !items) return DSU_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
-  const int32_t* offsets = dsu_bin::split(workspace, nb).offsets;
-  const RenderTexture tex{uv, reinterpret_cast<const uint32_t*>(pyramid), tex_size};
-  const RenderOut out{color_u8, pos_u8, face_id, depth, frames, pixels};
-#define DSU_RASTER(SS_)                                                                         \
-  mesh_raster_resolve_textured_kernel<SS_, TEX_TRILINEAR><<<(unsigned)nb, 256, 0, st>>>(         \
-      screen, faces, pos, n_verts, n_faces, view, offsets, items, n_faces ? n_items : 0, tex, out)
-  if (ss == 1) DSU_RASTER(1);
-  else if (ss == 2) DSU_RASTER(2);
-  else DSU_RASTER(4);
-#undef DSU_RASTER
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

@@ -1417,6 +1417,8 @@ class _BinnedPlan:
 
 # ------------------------------------------------------------------ frame rendering (csrc/mesh_render.hip)
 RENDER_COUNT, RENDER_FILL, RENDER_RASTER = 0, 1, 2
+MIP_TRILINEAR = "trilinear"
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1, MIP_TRILINEAR: 2}    # DSU_TEX_*
 
 
 class MeshRenderPlan(_BinnedPlan):
@@ -1434,9 +1436,10 @@ class MeshRenderPlan(_BinnedPlan):
         self._alloc(lib().dsu_mesh_render_ortho_workspace_bytes(self.F, self.size),
                     "dsu_mesh_render_ortho_workspace_bytes", self.screen.device)
 
-    def _stage(self, stage, colour=None, pos=None, outs=(None,) * 6):
+    def _stage(self, stage, colour=None, pos=None, tex=None, outs=(None,) * 6):
         check(lib().dsu_mesh_render_ortho(
             stage, ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), ptr(colour), ptr(pos),
+            None if tex is None else C.byref(tex),
             self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss,
             *self._bin_args(), *[ptr(o) for o in outs], stream()), "dsu_mesh_render_ortho")
 
@@ -1447,9 +1450,9 @@ class MeshRenderPlan(_BinnedPlan):
         (F,S,S,8) f32.
 
         With uv (V,2) f32 and texture (T,T,3) or (T,T,4) uint8 (both or neither) the colour of every
-        sample comes from the texture (dsu_mesh_render_ortho_textured; filter "bilinear" or
+        sample comes from the texture (the `tex` of dsu_mesh_render_ortho; filter "bilinear" or
         "nearest") and `colour` may be None; without them this is the vertex-colour call.
-        filter "trilinear" reads the texture's mip pyramid (dsu_mesh_render_ortho_mip): `pyramid`, a
+        filter "trilinear" reads the texture's mip pyramid: `pyramid`, a
         MipPyramid of this texture from mip_pyramid(), or None to build it here with every texel
         covered and the default gutter."""
         if self.items is None:
@@ -1466,47 +1469,36 @@ class MeshRenderPlan(_BinnedPlan):
         pos = _f32c(pos)
         if pos.shape != (self.V, 3):
             raise ValueError("colour and pos must be (V,3)")
+        tex = None
         if texture is None:
             colour = _f32c(colour)
             if colour.shape != (self.V, 3):
                 raise ValueError("colour and pos must be (V,3)")
-            out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
-            self._stage(RENDER_RASTER, colour, pos, [out.get(k) for k in shapes])
-            return out
-        if filter not in TEXTURE_FILTERS:
-            raise ValueError(f"filter must be one of {sorted(TEXTURE_FILTERS)}")
-        uv, rgba = _f32c(uv), texture_rgba(texture)
-        if uv.shape != (self.V, 2):
-            raise ValueError("uv must be (V,2)")
+        else:
+            if filter not in TEXTURE_FILTERS:
+                raise ValueError(f"filter must be one of {sorted(TEXTURE_FILTERS)}")
+            uv, texels = _f32c(uv), texture_rgba(texture)
+            if uv.shape != (self.V, 2):
+                raise ValueError("uv must be (V,2)")
+            T = texels.shape[0]
+            if filter == MIP_TRILINEAR:
+                if pyramid is None:
+                    pyramid = mip_pyramid(texels)
+                if not isinstance(pyramid, MipPyramid) or pyramid.T != T or pyramid.buffer.device != dev:
+                    raise ValueError("pyramid must be the MipPyramid of this texture, on the mesh's device")
+                texels = pyramid.buffer
+            elif pyramid is not None:
+                raise ValueError("a pyramid goes with filter 'trilinear'")
+            colour = None                             # not read
+            tex = _lib.RenderTexture(ptr(uv), ptr(texels, torch.uint8), T, TEXTURE_FILTERS[filter])
         out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
-        if filter == MIP_TRILINEAR:
-            if pyramid is None:
-                pyramid = mip_pyramid(rgba)
-            if not isinstance(pyramid, MipPyramid) or pyramid.T != rgba.shape[0] or pyramid.buffer.device != dev:
-                raise ValueError("pyramid must be the MipPyramid of this texture, on the mesh's device")
-            check(lib().dsu_mesh_render_ortho_mip(
-                ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), None, ptr(pos), ptr(uv),
-                ptr(pyramid.buffer, torch.uint8), pyramid.T, self.F, self.V, self.M,
-                self.cx, self.cy, self.span, self.size, self.ss, *self._bin_args(),
-                *[ptr(out.get(k)) for k in shapes], stream()), "dsu_mesh_render_ortho_mip")
-            return out
-        if pyramid is not None:
-            raise ValueError("a pyramid goes with filter 'trilinear'")
-        check(lib().dsu_mesh_render_ortho_textured(
-            ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), None, ptr(pos), ptr(uv),
-            ptr(rgba, torch.uint8), rgba.shape[0], TEXTURE_FILTERS[filter], self.F, self.V, self.M,
-            self.cx, self.cy, self.span, self.size, self.ss, *self._bin_args(),
-            *[ptr(out.get(k)) for k in shapes], stream()), "dsu_mesh_render_ortho_textured")
+        self._stage(RENDER_RASTER, colour, pos, tex, [out.get(k) for k in shapes])
         return out
-
-
-MIP_TRILINEAR = "trilinear"
-TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1, MIP_TRILINEAR: 2}
 
 
 def texture_rgba(texture):
     """(T,T,3) or (T,T,4) uint8 on the device -> the contiguous (T,T,4) RGBA8 texture of
-    dsu_mesh_render_ortho_textured (an opaque alpha is added to three channels; four are kept)."""
+    dsu_render_texture (an opaque alpha is added to three channels; four are kept)."""
     if not torch.is_tensor(texture) or texture.dtype != torch.uint8 or texture.dim() != 3 or \
             texture.shape[0] != texture.shape[1] or texture.shape[2] not in (3, 4) or texture.shape[0] < 1:
         raise ValueError("texture (T,T,3) or (T,T,4) uint8 expected")
@@ -1562,8 +1554,8 @@ def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
                       pyramid=None):
     """Orthographic render of F frames of one mesh with two attribute sets (include/dsu_hip.h,
     dsu_mesh_render_ortho): bin, then rasterise and resolve.  The colours are the vertex colours,
-    or with uv and texture the texture's (dsu_mesh_render_ortho_textured; filter "trilinear":
-    dsu_mesh_render_ortho_mip on `pyramid`, built from the texture when None)."""
+    or with uv and texture the texture's (filter "trilinear": its mip `pyramid`, built from the
+    texture when None)."""
     return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want, uv, texture,
                                                                               filter, pyramid)
 

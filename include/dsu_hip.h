@@ -30,7 +30,8 @@ extern "C" {
 #define DSU_MAX_LEVELS 16
 
 const char* dsu_strerror(int code);
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header, 2 now; bumped by any change to an exported signature or to the layout
+ * of a struct declared here.  A caller that binds by hand (ctypes) compares it before the first call. */
 int dsu_abi_version(void);
 /* CUs given to the two whole-SIMD kernels of the NSR step (the MLP part of the geometry backward,
  * the texture backward: their waves fill every SIMD of a CU they run on, nothing else fits beside
@@ -1035,7 +1036,11 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
  * Inputs: screen (n_frames, n_verts, 3) f32 per-frame vertices (x right, y up, z towards the
  * viewer); faces (n_faces, 3) i32; colour, pos (n_verts, 3) f32, clamped to [0, 1]; the window
  * centre (cx, cy) and world width span; output side `size` (a multiple of 4, at most 2048);
- * ss in {1, 2, 4} sub-samples per pixel side.
+ * ss in {1, 2, 4} sub-samples per pixel side.  tex: NULL = the colours are the vertex colours, and
+ * colour is required at DSU_RENDER_RASTER; otherwise the colours come from the atlas or the pyramid
+ * that *tex names ("Textured frames" and "Mip-mapped frames" below), and colour is not read and may
+ * be NULL.  tex is read and validated at DSU_RENDER_RASTER only: COUNT and FILL ignore it, as they
+ * ignore colour and pos.
  *
  * Rule.  Fine lattice N = size * ss: sample (R, C) sits at x = cx + ((C + 0.5) / N - 0.5) * span,
  * y = cy - ((R + 0.5) / N - 0.5) * span, in float64 in this order (it depends on N only).  With the
@@ -1063,27 +1068,16 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
  *                      its last entry is n_items, the length of `items` (int32, caller-owned)
  *   DSU_RENDER_FILL    triangle ids into items
  *   DSU_RENDER_RASTER  one workgroup per bin: visibility in LDS, resolve, all outputs
- * bins = n_frames * ceil(size / 16)^2; workspace_bytes = (3 bins + 1) * 4. */
-#define DSU_RENDER_COUNT 0
-#define DSU_RENDER_FILL 1
-#define DSU_RENDER_RASTER 2
-int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size);
-int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
-                          const float* colour, const float* pos, int32_t n_frames, int64_t n_verts,
-                          int64_t n_faces, double cx, double cy, double span, int32_t size, int32_t ss,
-                          void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
-                          uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
-                          float* frames, float* pixels, void* stream);
-/* Textured frames: the RASTER stage of dsu_mesh_render_ortho with the colour of every sample taken
- * from a UV atlas instead of the vertex colours (the reference's Blender reads the OBJ's map_Kd).
- * Binning is dsu_mesh_render_ortho's COUNT and FILL on the same arguments and the same workspace.
+ * bins = n_frames * ceil(size / 16)^2; workspace_bytes = (3 bins + 1) * 4.
  *
- * Additional inputs: uv (n_verts, 2) f32; texture (tex_size, tex_size, 4) uint8 RGBA, 4-byte
- * aligned (a texel is one 32-bit load; the fourth byte is not read); 1 <= tex_size <= 8192;
- * filter 0 = nearest, 1 = bilinear.  colour is not read and may be NULL.
+ * Textured frames (tex with DSU_TEX_NEAREST or DSU_TEX_BILINEAR): the colour of every sample is taken
+ * from a UV atlas instead of the vertex colours (the reference's Blender reads the OBJ's map_Kd).
+ * uv (n_verts, 2) f32; texels (tex_size, tex_size, 4) uint8 RGBA, 4-byte aligned (a texel is one
+ * 32-bit load; the fourth byte is not read); 1 <= tex_size <= 8192.  DSU_EINVAL before any launch:
+ * uv or texels NULL, texels misaligned, tex_size out of range, filter not one of DSU_TEX_*.
  *
  * Rule.  Visibility, depth, alpha, the position pass, frames, the layout of pixels and everything
- * downstream of pos_u8 are dsu_mesh_render_ortho's: the texture enters through the three colour
+ * downstream of pos_u8 are as without tex: the texture enters through the three colour
  * channels and in no other way.  For a covered sample whose winner is face (a, b, c), with w0, w1,
  * w2 and area as above and the vertex uvs widened from f32 to float64:
  *     u = (w0 ua + w1 ub + w2 uc) / area,  v likewise,  tx = u T,  ty = v T  (T = tex_size);
@@ -1099,15 +1093,29 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
  * The per-sample value goes where the interpolated vertex colour goes: accumulated in float64 over
  * the pixel's covered samples in row-major order, divided by their count, uint8 = floor(v 255 + 0.5).
  * These two filters read level 0 only: a texture much finer than the sample lattice aliases under
- * them.  dsu_mesh_render_ortho_mip below is the filtered read; there is no area or anisotropic
- * sampling. */
-int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, const float* colour,
-                                   const float* pos, const float* uv, const uint8_t* texture,
-                                   int32_t tex_size, int32_t filter, int32_t n_frames, int64_t n_verts,
-                                   int64_t n_faces, double cx, double cy, double span, int32_t size,
-                                   int32_t ss, void* workspace, int64_t workspace_bytes, int32_t* items,
-                                   int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id,
-                                   float* depth, float* frames, float* pixels, void* stream);
+ * them.  DSU_TEX_TRILINEAR ("Mip-mapped frames" below) is the filtered read; there is no area or
+ * anisotropic sampling.  The library cannot tell a level-0 image from a pyramid: texels that hold
+ * only the former, passed with DSU_TEX_TRILINEAR, are read past their end. */
+#define DSU_RENDER_COUNT 0
+#define DSU_RENDER_FILL 1
+#define DSU_RENDER_RASTER 2
+#define DSU_TEX_NEAREST   0
+#define DSU_TEX_BILINEAR  1
+#define DSU_TEX_TRILINEAR 2
+typedef struct dsu_render_texture {
+  const float*   uv;        /* (n_verts, 2) f32 */
+  const uint8_t* texels;    /* NEAREST / BILINEAR: (T, T, 4) RGBA8.  TRILINEAR: the pyramid buffer of
+                               dsu_mip_pyramid_build for a level 0 of side T.  4-byte aligned. */
+  int32_t tex_size;         /* T, 1 .. 8192 */
+  int32_t filter;           /* DSU_TEX_* */
+} dsu_render_texture;
+int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size);
+int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
+                          const float* colour, const float* pos, const dsu_render_texture* tex,
+                          int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
+                          double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
+                          int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
+                          int32_t* face_id, float* depth, float* frames, float* pixels, void* stream);
 /* Mip-mapped frames: the pyramid of the atlas (csrc/mesh_mip.hip) and the trilinear read of it in
  * the resolve (csrc/mesh_render.hip; the arithmetic of both sides is csrc/mip_sample.h).
  *
@@ -1132,9 +1140,9 @@ int dsu_mesh_render_ortho_textured(const float* screen, const int32_t* faces, co
  * (workspace may be NULL) for T = 1.  DSU_EINVAL before any launch: T or gutter out of range,
  * texture or pyramid NULL or not 4-byte aligned, workspace NULL, short or misaligned.
  *
- * b. dsu_mesh_render_ortho_mip: dsu_mesh_render_ortho_textured with the pyramid buffer in place of
- * `texture` and no `filter`.  Visibility, depth, alpha, the position pass, frames and pixels are
- * untouched; tx, ty of a sample are formed as there.
+ * b. dsu_mesh_render_ortho, tex with DSU_TEX_TRILINEAR: texels is the pyramid buffer of a, tex_size
+ * the side of its level 0.  Visibility, depth, alpha, the position pass, frames and pixels are
+ * untouched; tx, ty of a sample are formed as in "Textured frames".
  *   Level of detail.  The view is orthographic and uv is affine on a face, so the texel footprint
  *   of one sub-sample is constant per (frame, face).  Float64 from the f32 screen vertices a, b, c
  *   and the f32 uvs, in this operand order, no products fused:
@@ -1167,12 +1175,6 @@ int64_t dsu_mip_pyramid_texels(int32_t tex_size);
 int64_t dsu_mip_workspace_bytes(int32_t tex_size);
 int dsu_mip_pyramid_build(const uint8_t* texture, const uint8_t* covered, int32_t tex_size, int32_t gutter,
                           uint8_t* pyramid, void* workspace, int64_t workspace_bytes, void* stream);
-int dsu_mesh_render_ortho_mip(const float* screen, const int32_t* faces, const float* colour,
-                              const float* pos, const float* uv, const uint8_t* pyramid, int32_t tex_size,
-                              int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
-                              double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
-                              int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
-                              int32_t* face_id, float* depth, float* frames, float* pixels, void* stream);
 int dsu_mip_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tx, const double* ty,
                         const double* rho, int64_t n, float* rgb_out);
 /* pos2edge (run_render.py:31-57) and the inversion of run_render.py:120 on RGBA8 position images

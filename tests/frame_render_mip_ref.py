@@ -1,5 +1,5 @@
 """Float64 / integer restatement of the mip-mapped frame-rendering rule (include/dsu_hip.h,
-"Mip-mapped frames": dsu_mip_pyramid_build, dsu_mesh_render_ortho_mip) in numpy.  Test
+"Mip-mapped frames": dsu_mip_pyramid_build, DSU_TEX_TRILINEAR) in numpy.  Test
 infrastructure only.
 
 Pyramid: T_0 = T, T_k = ceil(T_{k-1} / 2), L levels down to size 1.  Level 0 is the input.  Texel

@@ -1,5 +1,5 @@
 """Float64 restatement of the textured frame-rendering rule (include/dsu_hip.h,
-dsu_mesh_render_ortho_textured) in numpy.  Test infrastructure only.
+"Textured frames": dsu_mesh_render_ortho with a tex) in numpy.  Test infrastructure only.
 
 Visibility is frame_render_ref.render_frame's, unchanged.  For a covered sample whose winner is face
 (a, b, c): u = (w0 ua + w1 ub + w2 uc) / area, v likewise (uvs f32 widened to float64), tx = u T,

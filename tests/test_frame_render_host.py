@@ -217,6 +217,48 @@ def test_raster_kernel_has_no_scratch_and_two_workgroups_of_lds_per_cu():
 
 
 # ------------------------------------------------------------------ argument checks
+def render_entry_refusals(flt):
+    """Every refusal of dsu_mesh_render_ortho for one colour source: flt None = tex NULL (vertex colours),
+    else the DSU_TEX_* of a tex.  No call here may get as far as a launch with faces: the pointers are
+    host memory.  Shared with the textured and the mip host tests."""
+    from drawingspinup_amd import _lib
+    lib = _lib.lib()
+    P = ctypes.c_void_p
+    buf = np.zeros(4096, np.int32)                          # host memory standing in: nothing may touch it
+    ws, fake = P(buf.ctypes.data), P(buf.ctypes.data)
+
+    def call(stage=0, screen=fake, faces=fake, colour=fake if flt is None else None, pos=fake, uv=fake,
+             texels=fake, T=8, flt=flt, F=1, V=3, M=1, span=1.35, S=16, ss=4, workspace=ws, wbytes=4096 * 4,
+             items=fake, n_items=1):
+        tex = None if flt is None else ctypes.byref(_lib.RenderTexture(uv, texels, T, flt))
+        return lib.dsu_mesh_render_ortho(stage, screen, faces, colour, pos, tex, F, V, M, 0.0, 0.0, span, S, ss,
+                                         workspace, wbytes, items, n_items, None, None, None, None,
+                                         None, None, None)
+
+    for stage in (0, 2):
+        assert call(stage, ss=3) == -1
+        assert call(stage, S=18) == -1 and call(stage, S=0) == -1 and call(stage, S=2052) == -1
+        assert call(stage, workspace=None) == -1 and call(stage, wbytes=8) == -1
+        assert call(stage, screen=None) == -1 and call(stage, faces=None) == -1
+        assert call(stage, span=0.0) == -1 and call(stage, span=float("nan")) == -1
+        assert call(stage, F=0) == -1 and call(stage, M=-1) == -1
+    assert call(stage=1, items=None) == -1 and call(stage=3) == -1 and call(stage=-1) == -1
+    assert call(stage=2, pos=None) == -1 and call(stage=2, items=None) == -1
+    if flt is None:
+        assert call(stage=2, colour=None) == -1
+    else:                                                   # every call here has colour=None: it is not asked for
+        assert call(stage=2, uv=None) == -1 and call(stage=2, texels=None) == -1
+        assert call(stage=2, T=0) == -1 and call(stage=2, T=8193) == -1 and call(stage=2, T=-4) == -1
+        assert call(stage=2, flt=3) == -1 and call(stage=2, flt=-1) == -1
+        assert call(stage=2, texels=P(buf.ctypes.data + 2)) == -1       # a texel is one aligned 32-bit word
+        # COUNT and FILL do not look at tex: with no faces (nothing is launched) a tex that RASTER refuses
+        # field by field gets as far as tex = NULL does, past the argument checks
+        for stage in (0, 1):
+            plain = call(stage, M=0, flt=None, colour=fake)
+            assert plain != -1 and call(stage, M=0, uv=None, texels=P(buf.ctypes.data + 2), T=-4, flt=99) == plain
+    assert not buf.any()
+
+
 def test_render_entry_points_validate_before_launching():
     from drawingspinup_amd import _lib
     lib = _lib.lib()
@@ -225,25 +267,8 @@ def test_render_entry_points_validate_before_launching():
     assert lib.dsu_mesh_render_ortho_workspace_bytes(1, 510) == -1
     assert lib.dsu_mesh_render_ortho_workspace_bytes(1, 2052) == -1
     assert lib.dsu_mesh_render_ortho_workspace_bytes(0, 512) == -1
-    P = ctypes.c_void_p
-    buf = np.zeros(4096, np.int32)                          # host memory standing in: nothing may touch it
-    ws, fake = P(buf.ctypes.data), P(buf.ctypes.data)
-
-    def call(stage=0, screen=fake, faces=fake, colour=fake, pos=fake, F=1, V=3, M=1, span=1.35, S=16, ss=4,
-             workspace=ws, wbytes=4096 * 4, items=fake, n_items=1):
-        return lib.dsu_mesh_render_ortho(stage, screen, faces, colour, pos, F, V, M, 0.0, 0.0, span, S, ss,
-                                         workspace, wbytes, items, n_items, None, None, None, None,
-                                         None, None, None)
-
-    assert call(ss=3) == -1
-    assert call(S=18) == -1 and call(S=0) == -1 and call(S=2052) == -1
-    assert call(workspace=None) == -1 and call(wbytes=8) == -1
-    assert call(screen=None) == -1 and call(faces=None) == -1
-    assert call(stage=2, colour=None) == -1 and call(stage=2, pos=None) == -1
-    assert call(stage=1, items=None) == -1 and call(stage=3) == -1 and call(stage=-1) == -1
-    assert call(span=0.0) == -1 and call(span=float("nan")) == -1
-    assert call(F=0) == -1 and call(M=-1) == -1
-    assert not buf.any()
+    render_entry_refusals(None)
+    fake = ctypes.c_void_p(np.zeros(64, np.int32).ctypes.data)
     assert lib.dsu_pos_edge_u8(None, 1, 8, 8, fake, None) == -1
     assert lib.dsu_pos_edge_u8(fake, 1, 8, 8, None, None) == -1
     assert lib.dsu_pos_edge_u8(fake, 0, 8, 8, fake, None) == -1

@@ -204,27 +204,10 @@ def test_pyramid_build_validates_before_launching():
 
 
 def test_mip_entry_point_validates_before_launching():
+    from test_frame_render_host import render_entry_refusals
+    render_entry_refusals(2)                                # DSU_TEX_TRILINEAR
     lib = _lib()
-    buf = np.zeros(4096, np.int32)
-    ws, fake = P(buf.ctypes.data), P(buf.ctypes.data)
-
-    def call(screen=fake, faces=fake, pos=fake, uv=fake, pyramid=fake, T=8, F=1, V=3, M=1, span=1.35, S=16, ss=4,
-             workspace=ws, wbytes=4096 * 4, items=fake, n_items=1):
-        return lib.dsu_mesh_render_ortho_mip(screen, faces, None, pos, uv, pyramid, T, F, V, M, 0.0, 0.0, span, S,
-                                             ss, workspace, wbytes, items, n_items, None, None, None, None, None,
-                                             None, None)
-
-    assert call(uv=None) == -1 and call(pyramid=None) == -1
-    assert call(T=0) == -1 and call(T=8193) == -1
-    assert call(pyramid=P(buf.ctypes.data + 2)) == -1
-    assert call(ss=3) == -1 and call(S=18) == -1 and call(workspace=None) == -1 and call(wbytes=8) == -1
-    assert call(screen=None) == -1 and call(faces=None) == -1 and call(pos=None) == -1 and call(items=None) == -1
-    assert call(span=0.0) == -1 and call(F=0) == -1 and call(M=-1) == -1
-    assert not buf.any()
-    # the two-filter entry keeps refusing the new value
-    assert lib.dsu_mesh_render_ortho_textured(fake, fake, None, fake, fake, fake, 8, 2, 1, 3, 1, 0.0, 0.0, 1.35, 16,
-                                              4, ws, 4096 * 4, fake, 1, None, None, None, None, None, None,
-                                              None) == -1
+    fake = P(np.zeros(16, np.int32).ctypes.data)
     assert lib.dsu_mip_sample_host(None, 8, None, None, None, 0, None) == -1
     assert lib.dsu_mip_sample_host(fake, 8, None, None, None, 1, None) == -1
     assert lib.dsu_mip_sample_host(fake, 8, None, None, None, 0, None) == 0

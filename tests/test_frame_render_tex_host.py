@@ -1,8 +1,7 @@
 """CPU: the host side of the textured frames — the textured OBJ reader, the float64 restatement of
-the sampling rule (tests/frame_render_tex_ref.py) on hand-computed answers, the argument checks of
-dsu_mesh_render_ortho_textured (no launch happens here: there is no GPU) and run_render's refusal
-of an untextured OBJ."""
-import ctypes
+the sampling rule (tests/frame_render_tex_ref.py) on hand-computed answers, the argument checks of the
+entry point with a tex (listed in test_frame_render_host.render_entry_refusals) and run_render's
+refusal of an untextured OBJ."""
 import os
 
 import numpy as np
@@ -149,28 +148,9 @@ def test_restatement_renders_the_texture_and_keeps_everything_else():
 
 # ------------------------------------------------------------------ argument checks
 def test_textured_entry_point_validates_before_launching():
-    from drawingspinup_amd import _lib
-    lib = _lib.lib()
-    P = ctypes.c_void_p
-    buf = np.zeros(4096, np.int32)                          # host memory standing in: nothing may touch it
-    ws, fake = P(buf.ctypes.data), P(buf.ctypes.data)
-
-    def call(screen=fake, faces=fake, colour=None, pos=fake, uv=fake, texture=fake, T=8, flt=1, F=1, V=3, M=1,
-             span=1.35, S=16, ss=4, workspace=ws, wbytes=4096 * 4, items=fake, n_items=1):
-        return lib.dsu_mesh_render_ortho_textured(screen, faces, colour, pos, uv, texture, T, flt, F, V, M, 0.0,
-                                                  0.0, span, S, ss, workspace, wbytes, items, n_items, None,
-                                                  None, None, None, None, None, None)
-
-    assert call(uv=None) == -1 and call(texture=None) == -1
-    assert call(T=0) == -1 and call(T=8193) == -1 and call(T=-4) == -1
-    assert call(flt=2) == -1 and call(flt=-1) == -1
-    assert call(texture=P(buf.ctypes.data + 2)) == -1       # a texel is one aligned 32-bit word
-    assert call(ss=3) == -1 and call(S=18) == -1 and call(S=2052) == -1
-    assert call(workspace=None) == -1 and call(wbytes=8) == -1
-    assert call(screen=None) == -1 and call(faces=None) == -1 and call(pos=None) == -1
-    assert call(items=None) == -1
-    assert call(span=0.0) == -1 and call(span=float("nan")) == -1 and call(F=0) == -1 and call(M=-1) == -1
-    assert not buf.any()
+    from test_frame_render_host import render_entry_refusals
+    for flt in (0, 1):                                      # DSU_TEX_NEAREST, DSU_TEX_BILINEAR
+        render_entry_refusals(flt)
 
 
 def test_textured_render_needs_the_device_and_both_arguments():

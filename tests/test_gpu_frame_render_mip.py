@@ -1,6 +1,6 @@
 """GPU: mip-mapped frames — the atlas pyramid (csrc/mesh_mip.hip, dsu_mip_pyramid_build) and the
 trilinear read of it in the resolve of the frame rasteriser (csrc/mesh_render.hip,
-dsu_mesh_render_ortho_mip) against known answers and the restatement of the rule
+DSU_TEX_TRILINEAR) against known answers and the restatement of the rule
 (tests/frame_render_mip_ref.py), and the way through animate and run_render."""
 import functools
 import os

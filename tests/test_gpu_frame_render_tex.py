@@ -1,5 +1,5 @@
 """GPU: textured frames — the UV atlas sampled inside the resolve of the frame rasteriser
-(csrc/mesh_render.hip, dsu_mesh_render_ortho_textured) against known answers and the float64
+(csrc/mesh_render.hip, dsu_mesh_render_ortho with a tex) against known answers and the float64
 restatement of its rule (tests/frame_render_tex_ref.py), its self-consistency at production size
 and the way through animate and run_render."""
 import functools

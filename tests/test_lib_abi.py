@@ -30,8 +30,20 @@ def test_library_exports_every_declared_symbol():
     undeclared = [n for n in _lib._PROTOS if n not in names]
     assert not undeclared, undeclared
     lib = _lib.lib()
-    assert lib.dsu_abi_version() >= 1
+    assert lib.dsu_abi_version() == _lib.ABI_VERSION
     assert lib.dsu_strerror(-1).decode() == "invalid argument"
+
+
+def test_loader_refuses_a_library_of_another_abi_version(monkeypatch):
+    """A stale libdsu_hip.so under a newer prototype table would take arguments in the wrong places."""
+    from drawingspinup_amd import _lib
+    _lib.lib()
+    monkeypatch.setattr(_lib, "_lib", None)                 # the cached handle; both restored afterwards
+    monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
+    built, bound = _lib.ABI_VERSION - 1, _lib.ABI_VERSION
+    with pytest.raises(_lib.DsuError, match=rf"version {built}\b.*version {bound}\b.*rebuild") as e:
+        _lib.lib()
+    assert _lib.LIB_PATH in str(e.value) and _lib._lib is None
 
 
 def test_host_only_entry_point_matches_oracle():
@@ -108,7 +120,7 @@ def test_variant_library_override(tmp_path):
     from drawingspinup_amd import _lib
     alt = tmp_path / "libdsu_hip_alt.so"
     shutil.copy(_lib.LIB_PATH, alt)
-    code = ("from drawingspinup_amd import _lib; assert _lib.lib().dsu_abi_version() >= 1; "
+    code = ("from drawingspinup_amd import _lib; assert _lib.lib().dsu_abi_version() == _lib.ABI_VERSION; "
             "print(_lib.LIB_PATH)")
     env = dict(os.environ, DSU_HIP_LIB=str(alt), PYTHONPATH=ROOT)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)

@@ -118,7 +118,7 @@ def main():
             "pos_u8": torch.empty(F, S, S, 4, dtype=torch.uint8, device=dev),
             "frames": torch.empty(F, 6, S, S, device=dev)}
     order = ("color_u8", "pos_u8", "face_id", "depth", "frames", "pixels")
-    t_raster = timed(lambda: plan._stage(ops.RENDER_RASTER, colour, pos, [outs.get(k) for k in order]), a.runs)
+    t_raster = timed(lambda: plan._stage(ops.RENDER_RASTER, colour, pos, outs=[outs.get(k) for k in order]), a.runs)
     t_edge = timed(lambda: ops.pos_edge_u8(outs["pos_u8"]), a.runs)
     t_all = timed(lambda: animate.render_frames(v, f, col, xyz, ss=a.ss, device=dev, window=(cx, cy, size, span)),
                   max(3, a.runs // 4))
