@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (A/B measurements); unset = the in-tree library.
 LIB_PATH = os.environ.get("DSU_HIP_LIB") or os.path.join(_HERE, "libdsu_hip.so")
 MAX_LEVELS = 16
-ABI_VERSION = 2                                       # dsu_abi_version() of the header _PROTOS restates
+ABI_VERSION = 3                                       # dsu_abi_version() of the header _PROTOS restates
 
 c_i32, c_i64, c_u32, c_f32, c_vp = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_void_p
 
@@ -136,6 +136,9 @@ _PROTOS = {
     "dsu_texture_partial_map": [P],
     "dsu_texture_bwd_shaded_partials_m": [C.POINTER(TexMlp), P, P, P, P, P, c_i64, c_i64, P, P, P, P, c_i64,
                                           C.POINTER(PartialReduce), P],
+    "dsu_texture_bwd_shaded_partials_live": [C.POINTER(TexMlp), P, P, P, P, P, c_i64, c_i64, P, P, P, P, P,
+                                             c_i64, C.POINTER(PartialReduce), P],
+    "dsu_texture_live_partition": [P, c_i64, c_i32, c_i32, P],
     "dsu_texture_fwd_shaded_m": [C.POINTER(TexMlp), P, P, c_i64, P, P, P, P],
     "dsu_occgrid_refresh_workspace_bytes": [c_i32],
     "dsu_occgrid_refresh": [C.POINTER(OccRefreshArgs), P],
@@ -225,6 +228,7 @@ _PROTOS = {
     "dsu_nsr_driver_step": [c_vp, C.POINTER(NsrStepArgs), P],
     "dsu_nsr_driver_terms": [c_vp],
     "dsu_nsr_driver_adam_moments": [c_vp, c_i32],
+    "dsu_nsr_driver_live_halves": [c_vp, c_i64],
     "dsu_nsr_driver_timing": [c_vp, c_i32],
     "dsu_nsr_driver_timing_read": [c_vp, c_i32, C.POINTER(c_i64), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)],
@@ -256,6 +260,8 @@ _PROTOS = {
     "dsu_neus_composite_fwd": [P, P, P, P, P, P, P, P, c_i64, P, c_f32, P, P, P, P],
     "dsu_neus_composite_bwd": [P, P, P, P, P, P, P, P, c_i64, P, c_f32, P, P, P, P, P, P, P,
                                P, P],
+    "dsu_neus_composite_bwd_live": [P, P, P, P, P, P, P, P, c_i64, P, c_f32, P, P, P, P, P, P, P,
+                                    P, P, P],
     "dsu_shade_prep_fwd": [P, P, c_i64, P, P, P],
     "dsu_shade_prep_bwd": [P, P, P, c_i64, P, P, P],
     "dsu_occgrid_ema": [P, P, P, c_i64, c_f32, P, P],
@@ -312,7 +318,7 @@ _PROTOS = {
 
 # return types that are neither an error code nor a byte count
 _RESTYPES = {"dsu_nsr_driver_destroy": None, "dsu_nsr_driver_terms": c_vp,
-             "dsu_nsr_driver_adam_moments": c_vp,
+             "dsu_nsr_driver_adam_moments": c_vp, "dsu_nsr_driver_live_halves": c_vp,
              "dsu_conv_x3_packed_elems": C.c_int64, "dsu_mip_pyramid_texels": C.c_int64}
 
 _lib = None

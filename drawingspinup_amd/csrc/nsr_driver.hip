@@ -110,6 +110,8 @@ struct SmallArgs {
   // outputs for the next step
   float *w0_eff, *w1_eff, *inv_s;
   float* zero_terms;   // the three sample-loss accumulators of the NEXT step
+  uint32_t* zero_live; // the NEXT step's liveness bitmap of the texture backward (live_words words)
+  int32_t live_words;
   const float* terms;  // this step's eight loss terms ...
   float* terms_out;    // ... and where the caller wants a copy of them (may be null)
   float lr_geo, lr_tex, lr_var, beta1, beta2, eps, wd, bc1, bc2_sqrt;
@@ -238,6 +240,7 @@ __global__ __launch_bounds__(1024) void small_update_kernel(SmallArgs a, dsu_tab
       a.d_inv[0] = 0.0f;
     }
     if (t < 3) a.zero_terms[t] = 0.0f;
+    for (int i = t; i < a.live_words; i += 1024) a.zero_live[i] = 0u;
     if (t >= 8 && t < 16 && a.terms_out) a.terms_out[t - 8] = a.terms[t - 8];
     __syncthreads();                                   // every read of s_gain / g_tex is done
     if (t < 64) s_gain[t] = new_gain;
@@ -299,6 +302,11 @@ struct Layout {
   void *tex_ws, *sdf_ws;
   int32_t* tex_map;                   // dsu_texture_partial_map, uploaded at creation
   uint32_t* tex_mask;                 // (cap_points, 2): layer 1's ReLU pattern, texture forward -> backward
+  // one bit per 32-sample half of the ray samples: some d_rgb of the half is not zero (compositing
+  // backward -> texture backward).  Two sets, by step & 1, like `terms`: the optimizer kernel of step
+  // t zeroes the set of step t + 1
+  uint32_t* live_halves[2];
+  int32_t live_words;
   float *g_geo, *g_tex, *d_inv;      // contiguous: zeroed as one block
   float *w0_eff, *w1_eff, *inv_s, *adam_m, *adam_v;
   int64_t tex_ws_bytes, sdf_ws_bytes, sort_ws_bytes, enc_cache_bytes, total;
@@ -346,6 +354,9 @@ int carve(const dsu_nsr_driver_cfg& c, char* base, Layout& L) {
   L.sdf_ws = k.take<char>(L.sdf_ws_bytes > 4 ? L.sdf_ws_bytes : 4);
   L.tex_map = k.take<int32_t>(dsu_texture_partial_map(nullptr));
   L.tex_mask = k.take<uint32_t>(N * 2);
+  L.live_words = (int32_t)((N + 1023) / 1024);
+  L.live_halves[0] = k.take<uint32_t>(2 * (int64_t)L.live_words);
+  L.live_halves[1] = L.live_halves[0] ? L.live_halves[0] + L.live_words : nullptr;
   L.g_geo = k.take<float>(N_GEO + N_TEX + 1);
   L.g_tex = L.g_geo ? L.g_geo + N_GEO : nullptr;
   L.d_inv = L.g_geo ? L.g_geo + N_GEO + N_TEX : nullptr;
@@ -532,6 +543,8 @@ int launch_small_update(dsu_nsr_driver* d, const dsu_nsr_step_args* a, int updat
   sa.w0_eff = d->L.w0_eff; sa.w1_eff = d->L.w1_eff; sa.inv_s = d->L.inv_s;
   sa.zero_terms = d->L.terms + 8 * (int)((a->step + 1) & 1) + 4;
   sa.terms = d->L.terms + 8 * (int)(a->step & 1);
+  sa.zero_live = d->L.live_halves[(a->step + 1) & 1];
+  sa.live_words = update ? d->L.live_words : 0;
   sa.terms_out = update ? a->terms_out : nullptr;
   sa.beta1 = c.beta1; sa.beta2 = c.beta2; sa.eps = c.adam_eps; sa.wd = c.weight_decay;
   sa.update = update;
@@ -652,6 +665,10 @@ void dsu_nsr_driver_destroy(dsu_nsr_driver* d) {
 
 const float* dsu_nsr_driver_terms(const dsu_nsr_driver* d) { return d ? d->L.terms : nullptr; }
 
+const uint32_t* dsu_nsr_driver_live_halves(const dsu_nsr_driver* d, int64_t step) {
+  return d ? d->L.live_halves[step & 1] : nullptr;
+}
+
 const float* dsu_nsr_driver_adam_moments(const dsu_nsr_driver* d, int32_t second) {
   return d ? (second ? d->L.adam_v : d->L.adam_m) : nullptr;
 }
@@ -676,11 +693,14 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
       if (!ok) for (int k = 0; k < 3; ++k) d->pf_valid[k] = false;
     }
   } guard{d};
-  if (d->initialised && a->step != d->last_step + 1)
-    // the previous step pre-zeroed the accumulators of `last_step + 1`, not of this step (the
-    // caller moved global_step: resume, tests): zero this step's set here
+  if (d->initialised && a->step != d->last_step + 1) {
+    // the previous step pre-zeroed the accumulators and the liveness bitmap of `last_step + 1`, not
+    // of this step (the caller moved global_step: resume, tests): zero this step's sets here
     DSU_HIP(hipMemsetAsync(terms + 4, 0, 3 * sizeof(float), s));
+    DSU_HIP(hipMemsetAsync(L.live_halves[a->step & 1], 0, (size_t)L.live_words * sizeof(uint32_t), s));
+  }
   if (!d->initialised) {
+    DSU_HIP(hipMemsetAsync(L.live_halves[0], 0, 2 * (size_t)L.live_words * sizeof(uint32_t), s));
     // zeroed accumulators and optimizer moments
     DSU_HIP(hipMemsetAsync(L.g_geo, 0, (N_GEO + N_TEX + 1) * sizeof(float), s));
     DSU_HIP(hipMemsetAsync(L.adam_m, 0, N_SMALL * sizeof(float), s));
@@ -788,16 +808,18 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* a, void* main_stre
   dsu_partial_reduce tex_red{};
   bool have_tex_red = false;
   if (n_s > 0) {
-    DSU_TRY(dsu_neus_composite_bwd(L.a_sdf, L.normal, L.rgb, f.rays_d, f.t_starts, f.t_ends,
-                                   f.offsets, f.counts, a->n_rays, L.inv_s, a->cos_anneal_ratio,
-                                   L.alpha, L.w, L.d_comp, nullptr, L.d_sdf_all, L.d_normal, L.d_rgb,
-                                   L.d_inv, s));
+    uint32_t* live = L.live_halves[a->step & 1];
+    DSU_TRY(dsu_neus_composite_bwd_live(L.a_sdf, L.normal, L.rgb, f.rays_d, f.t_starts, f.t_ends,
+                                        f.offsets, f.counts, a->n_rays, L.inv_s, a->cos_anneal_ratio,
+                                        L.alpha, L.w, L.d_comp, nullptr, L.d_sdf_all, L.d_normal, L.d_rgb,
+                                        L.d_inv, live, s));
     dsu_tex_mlp tex{c.tex[0], c.tex[1], c.tex[2], c.tex[3], c.tex[4], c.tex[5]};
     // parameter gradients of the texture MLP: per-workgroup partials now, summed into g_tex by
     // extra workgroups of the geometry backward's scatter launch (no launch of their own)
-    DSU_TRY(dsu_texture_bwd_shaded_partials_m(&tex, L.a_feat, L.a_grad, L.rgb, L.d_rgb, L.d_normal, n_s,
-                                              2 * n_r, L.d_grad_all, L.d_feat_all, L.tex_mask, L.tex_ws,
-                                              L.tex_ws_bytes, &tex_red, s));
+    // (dead halves skipped, live ones balanced over the workgroups: the bitmap the compositing backward just filled)
+    DSU_TRY(dsu_texture_bwd_shaded_partials_live(&tex, L.a_feat, L.a_grad, L.rgb, L.d_rgb, L.d_normal, n_s,
+                                                 2 * n_r, L.d_grad_all, L.d_feat_all, L.tex_mask, live,
+                                                 L.tex_ws, L.tex_ws_bytes, &tex_red, s));
     tex_red.map = L.tex_map;
     tex_red.base = L.g_tex;
     have_tex_red = true;

@@ -497,6 +497,10 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
 }
 
 // d_comp (R,8) -> d_sdf (N), d_normal (N,3), d_rgb (N,3); d_inv_s accumulated (1 float)
+// live_halves (may be null): one bit per 32-sample half of [0, N), set where a sample's d_rgb is not
+// all zero — behind the front surface the transmittance underflows to 0.0f and w, hence d_rgb, is
+// exactly zero to the end of the ray; the texture backward skips halves whose bit is clear.  The
+// caller hands the words over zeroed; a half can span two rays, hence the (order-independent) OR.
 __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float* __restrict__ sdf, const float* __restrict__ normal,
     const float* __restrict__ rgb, const float* __restrict__ rays_d,
@@ -506,7 +510,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float* __restrict__ w_s,
     const float* __restrict__ d_comp, const float* __restrict__ d_w_extra,
     float* __restrict__ d_sdf, float* __restrict__ d_normal, float* __restrict__ d_rgb,
-    float* __restrict__ d_inv_s) {
+    float* __restrict__ d_inv_s, uint32_t* __restrict__ live_halves) {
   const float inv_raw = *inv_s_p;
   const float inv_s = fminf(fmaxf(inv_raw, 1e-6f), 1e6f);
   const bool inv_pass = inv_raw >= 1e-6f && inv_raw <= 1e6f;   // clip passes the gradient inside
@@ -558,6 +562,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
       const float before = done + (pin - gww);              // sum_{k<j}
       T *= __shfl(incl, 63);
       done += __shfl(pin, 63);
+      bool lit = false;                                     // this lane's sample has a colour gradient
       if (v) {
         const float accum = total - before;                 // sum_{k>=j} gw_k w_k
         const float galpha = (gw * Tj - accum) / fmaxf(1.0f - al, 1e-10f);
@@ -585,7 +590,19 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         d_normal[i * 3] = dn[0] + w * dc[5];
         d_normal[i * 3 + 1] = dn[1] + w * dc[6];
         d_normal[i * 3 + 2] = dn[2] + w * dc[7];
-        d_rgb[i * 3] = w * dc[2]; d_rgb[i * 3 + 1] = w * dc[3]; d_rgb[i * 3 + 2] = w * dc[4];
+        const float c0 = w * dc[2], c1 = w * dc[3], c2 = w * dc[4];
+        d_rgb[i * 3] = c0; d_rgb[i * 3 + 1] = c1; d_rgb[i * 3 + 2] = c2;
+        lit = c0 != 0.0f || c1 != 0.0f || c2 != 0.0f;
+      }
+      if (live_halves) {                                    // (wave-uniform; the ballot is outside `if (v)`)
+        // the 64 samples of this iteration touch up to three halves: the first lane of each half's
+        // part looks at the lanes of that part and sets the half's bit if one of them is lit
+        const uint64_t m = __ballot(lit);
+        if (v && (lane == 0 || (i & 31) == 0)) {
+          const int span = 32 - (int)(i & 31);
+          const uint64_t part = span >= 64 - lane ? ~0ull << lane : ((1ull << span) - 1ull) << lane;
+          if (m & part) atomicOr(&live_halves[i >> 10], 1u << ((i >> 5) & 31));
+        }
       }
     }
   }
@@ -826,7 +843,26 @@ int dsu_neus_composite_bwd(const float* sdf, const float* normal, const float* r
   if (n_rays == 0) return DSU_OK;
   composite_bwd_kernel<<<(unsigned)((n_rays + 3) / 4), 256, 0, (hipStream_t)stream>>>(
       sdf, normal, rgb, rays_d, t_starts, t_ends, offsets, counts, n_rays, inv_s,
-      cos_anneal_ratio, alpha, weights, d_comp, d_weights, d_sdf, d_normal, d_rgb, d_inv_s);
+      cos_anneal_ratio, alpha, weights, d_comp, d_weights, d_sdf, d_normal, d_rgb, d_inv_s, nullptr);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+int dsu_neus_composite_bwd_live(const float* sdf, const float* normal, const float* rgb,
+                                const float* rays_d, const float* t_starts, const float* t_ends,
+                                const int32_t* offsets, const int32_t* counts, int64_t n_rays,
+                                const float* inv_s, float cos_anneal_ratio, const float* alpha,
+                                const float* weights, const float* d_comp, const float* d_weights,
+                                float* d_sdf, float* d_normal, float* d_rgb, float* d_inv_s,
+                                uint32_t* live_halves, void* stream) {
+  if (n_rays < 0 || !inv_s || !live_halves ||
+      (n_rays && (!rays_d || !offsets || !counts || !d_comp || !d_inv_s)))
+    return DSU_EINVAL;
+  if (n_rays == 0) return DSU_OK;
+  composite_bwd_kernel<<<(unsigned)((n_rays + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+      sdf, normal, rgb, rays_d, t_starts, t_ends, offsets, counts, n_rays, inv_s,
+      cos_anneal_ratio, alpha, weights, d_comp, d_weights, d_sdf, d_normal, d_rgb, d_inv_s,
+      live_halves);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

@@ -24,8 +24,10 @@
 //     accumulator's register quads, operand fragments through ds_read_b64_tr_b16, which transposes
 //     (tr_stage.h).  When the forward handed over the
 //     ReLU pattern of layer 1 (L1_MASK), the recompute of layer 1 runs this way too.
+#include <vector>
 #include "common.h"
 #include "tr_stage.h"
+#include "tex_partition.h"
 
 namespace {
 
@@ -52,7 +54,7 @@ constexpr int TIN = 16, THID = 64, TOUT = 3;
 //   [L_IMG1, L_IMG0)        4 096   W1 image of dH0
 //   [L_IMG0, L_IMGF)        2 048   W0 image of dIn
 //   [L_IMGF, BWD_LDS_F)     4 096   W1 image of the recompute of layer 1 (written by L1_MASK kernels)
-//   BWD_LDS_F = 36 320 floats = 142 KB of the CU's 160: one workgroup per CU.
+//   BWD_LDS_F = 36 320 floats = 142 KB of the CU's 160: one workgroup per CU.  (+ 16 KB behind it: L_SCAN)
 // The workgroup reduction at the end of the kernel reuses [0, 4 PART_STRIDE) for four partial images.
 constexpr int W1_ROW = 65;                       // padded row: conflict-free by row AND by column
 constexpr int W0_ROW = 17;
@@ -86,6 +88,11 @@ constexpr int L_IMG0 = L_IMG1 + IMG1_F;
 //   8 values t -> w1[32 To + l31][feat_of(Tin, 8 g + t, h)]
 constexpr int L_IMGF = L_IMG0 + IMG0_F;
 constexpr int BWD_LDS_F = L_IMGF + IMG1_F;       // 36 320 floats = 142 KB
+//   [L_SCAN, BWD_LDS_ALL_F)  the liveness bitmap of the halves and its scan (tex_partition.h): 16 KB more,
+//   158 KB in all.  Not part of what the final reduction reuses.
+constexpr int L_SCAN = BWD_LDS_F;
+constexpr int BWD_LDS_ALL_F = L_SCAN + 2 * texpart::MAX_WORDS + 8;
+static_assert(BWD_LDS_ALL_F * 4 <= 160 * 1024, "the backward kernel's LDS fits the CU");
 // per-workgroup partial vector
 constexpr int P_GW1 = 0, P_GW0 = 64 * 64, P_GW2 = P_GW0 + 64 * 32, P_GB1 = P_GW2 + 64 * 32,
               P_GB2 = P_GB1 + 64, PART_N = P_GB2 + 3, PART_STRIDE = 8320;
@@ -409,14 +416,100 @@ struct ShadeOut {
   int64_t tail;           // not ray samples: the regulariser points of the same geometry launch)
 };
 
+// a value every lane of the wave holds alike, moved to scalar registers (loop bounds read from LDS)
+__device__ __forceinline__ int64_t dsu_uniform64(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// d_grad of sample si from the gradient (d0, d1, d2) of its normal, d_normal added: normalize's backward
+__device__ __forceinline__ void shade_grad_out(const ShadeIn& sh, const ShadeOut& so, int64_t si,
+                                               float d0, float d1, float d2) {
+  const float g0 = sh.grad[si * 3], g1 = sh.grad[si * 3 + 1], g2 = sh.grad[si * 3 + 2];
+  const float len = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
+  const float inv = 1.0f / fmaxf(len, 1e-12f);
+  const float n0 = g0 * inv, n1 = g1 * inv, n2 = g2 * inv;
+  if (so.d_normal) {
+    d0 += so.d_normal[si * 3]; d1 += so.d_normal[si * 3 + 1]; d2 += so.d_normal[si * 3 + 2];
+  }
+  const float dot = n0 * d0 + n1 * d1 + n2 * d2;
+  const bool ok = len > 1e-12f;
+  so.d_grad[si * 3] = ok ? (d0 - n0 * dot) * inv : d0 * inv;
+  so.d_grad[si * 3 + 1] = ok ? (d1 - n1 * dot) * inv : d1 * inv;
+  so.d_grad[si * 3 + 2] = ok ? (d2 - n2 * dot) * inv : d2 * inv;
+}
+
+// the rows of a sample in a dead half: what the live path writes for dIn = 0
+template <bool SHADE>
+__device__ __forceinline__ void dead_sample_out(const ShadeIn& sh, const ShadeOut& so, float* __restrict__ d_x,
+                                                int64_t i) {
+  if (SHADE) {
+#pragma unroll
+    for (int k = 0; k < 13; ++k) so.d_feature[i * 13 + k] = 0.0f;
+    shade_grad_out(sh, so, i, 0.0f, 0.0f, 0.0f);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<float4*>(d_x + i * TIN + 4 * q) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+}
+
+// One bit per 32-sample half: some d_rgb of the half is not zero.  What the compositing backward of the
+// NSR step fills on its way (nsr_render.hip); the stand-alone entry points launch this in front of the
+// backward kernel.  One 1024-thread workgroup = one word: no atomics on memory, nothing to clear.
+__global__ __launch_bounds__(1024) void texture_live_kernel(const float* __restrict__ d_rgb, int64_t n,
+                                                            uint32_t* __restrict__ live_halves) {
+  __shared__ uint32_t word;
+  if (threadIdx.x == 0) word = 0u;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+  const bool lit = i < n && (d_rgb[i * 3] != 0.0f || d_rgb[i * 3 + 1] != 0.0f || d_rgb[i * 3 + 2] != 0.0f);
+  const uint64_t m = __ballot(lit);
+  if ((threadIdx.x & 63) == 0) {
+    const uint32_t two = ((uint32_t)m != 0u ? 1u : 0u) | ((uint32_t)(m >> 32) != 0u ? 2u : 0u);
+    if (two) atomicOr(&word, two << (2 * (threadIdx.x >> 6)));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) live_halves[blockIdx.x] = word;
+}
+
+// DEAD HALVES.  A 32-sample half whose d_rgb rows are all zero (samples behind the front surface: the
+// f32 transmittance has underflowed, w = 0 and d_rgb = w dc = 0 exactly) has dz = 0, hence dPre1, dH0,
+// dPre0, dIn and its share of every parameter gradient exactly zero: it is not recomputed, staged or
+// multiplied — its d_feature rows are written as zeros and its d_grad from d_normal alone, by a sweep of
+// the whole grid over the dead halves in front of the waves' walks.  Work is handed out by the live halves
+// (tex_partition.h, live_halves = one bit per half): a workgroup, and each of its waves, takes a
+// contiguous run of halves with an equal share of the live ones.  The BIT decides what is dead: a set
+// bit on a half of zeros only costs its time (the live path computes the same zeros), a clear bit on a
+// half with a colour gradient would lose it — both producers set the bit of every such half.  Rays the
+// colour loss gives no gradient (dc = 0) are dead from end to end, as are the samples behind the surface:
+// three halves of four in the bench's fits (profiles/texture_dead_halves_share.txt).  Without a bitmap (n beyond
+// texpart::MAX_WORDS x 1024 samples, which the LDS scan does not hold) the runs are the static ones:
+// equal numbers of halves per workgroup and wave, and a wave finds its dead halves by a ballot over the
+// d_rgb it has just loaded and writes their rows itself.
 template <bool SHADE, bool L1_MASK = false>
 __global__ __launch_bounds__(256) void texture_bwd_kernel(
     dsu_tex_mlp m, const float* __restrict__ x, ShadeIn sh, ShadeOut so,
     const float* __restrict__ rgb, const float* __restrict__ d_rgb, int64_t n,
     float* __restrict__ d_x, float* __restrict__ partials,
-    const uint32_t* __restrict__ h1_mask = nullptr) {
+    const uint32_t* __restrict__ h1_mask, const uint32_t* __restrict__ live_halves) {
   extern __shared__ __attribute__((aligned(128))) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
+  // The kernel is written for one wave per SIMD and is to HAVE the SIMD (nsr_driver.hip: the ray marcher of
+  // the side stream beside it delays its last workgroups).  The compiler needs 464 registers here, which would
+  // leave the 48 a marching wave takes; the kernel before needed 474, an allocation of 480, which does not.
+  // Naming accumulation register 223 keeps the allocation at 480 whatever the compiler needs (the effect of
+  // 464 on the step has not been measured).
+  asm volatile("" ::: "a223");
+  // ---- dead halves: the bitmap and its scan (live halves before every word) in an LDS area of their own
+  const int64_t halves = (n + 31) / 32;
+  const bool scanned = live_halves != nullptr && halves <= 32 * (int64_t)texpart::MAX_WORDS;   // (per launch)
+  uint32_t* sbits = reinterpret_cast<uint32_t*>(lds + L_SCAN);
+  uint32_t* spre = sbits + texpart::MAX_WORDS;
+  const int words = scanned ? (int)((halves + 31) / 32) : 0;
+  for (int w = threadIdx.x; w < words; w += blockDim.x)
+    sbits[w] = texpart::clip_word(live_halves[w], w, (int)halves);
   // the wave's images X, Y, S (tr_stage.h) as LDS byte addresses: st* = where the lane stores the row
   // of the sample in its column (X, Y: its lane half's unit quad), rd* = where it reads the fragments,
   // colY = where it reads the column `lane` of Y
@@ -428,6 +521,25 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
   const uint32_t colY = stg + SB_Y + ImgU::col_base(lane);
   load_weights(lds, m);
   __syncthreads();
+  if (scanned && wave == 0) {     // a chunk of words per lane, scan over the lanes; the other waves start on the images
+    const int chunk = (words + 63) / 64, w0 = lane * chunk;
+    int sum = 0;
+    for (int k = 0; k < chunk; ++k)
+      if (w0 + k < words) sum += __popc(sbits[w0 + k]);
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    int before = incl - sum;
+    for (int k = 0; k < chunk; ++k)
+      if (w0 + k < words) {
+        spre[w0 + k] = (uint32_t)before;
+        before += __popc(sbits[w0 + k]);
+      }
+    if (lane == 63) spre[words] = (uint32_t)incl;
+  }
   {   // bf16 hi / mid fragments of W1 and W0 in the order the backward MFMAs consume them
     bf16x8* img1 = reinterpret_cast<bf16x8*>(lds + L_IMG1);
     bf16x8* img0 = reinterpret_cast<bf16x8*>(lds + L_IMG0);
@@ -477,15 +589,55 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
       gw0[T][r] = gw2[T][r] = 0.0f;
     }
 
-  const int64_t per = ((n + gridDim.x - 1) / gridDim.x + 31) / 32 * 32;   // see texture_fwd_kernel
-  const int64_t r0 = blockIdx.x * per;
-  const int64_t r1 = r0 + per < n ? r0 + per : n;
-  for (int64_t base = r0; base < r1; base += blockDim.x) {
-    const int64_t i = base + threadIdx.x;
+  // ---- the dead halves' rows, by all threads of the grid side by side: independent iterations, where the
+  // walk below is one chain of memory latencies per 64 samples for a single wave per SIMD — as part of that
+  // walk the longest stretch of dead rays (tens of halves) set the kernel's time: 104 instead of 70 us
+  if (scanned) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t hf = t >> 5;
+      if (!((sbits[hf >> 5] >> (hf & 31)) & 1u)) dead_sample_out<SHADE>(sh, so, d_x, t);
+    }
+  }
+  // ---- the wave's run of halves [wh0, wh1)
+  int64_t wh0, wh1;
+  if (scanned) {
+    const texpart::Scan sc{sbits, spre, words, (int)halves};
+    const texpart::Run wg = texpart::split(sc, texpart::whole(sc), (int)gridDim.x, (int)blockIdx.x);
+    const texpart::Run wr = texpart::split(sc, wg, 4, wave);
+    wh0 = wr.h0; wh1 = wr.h1;
+  } else {
+    const int64_t per = (halves + gridDim.x - 1) / gridDim.x;
+    const int64_t b0 = blockIdx.x * per < halves ? blockIdx.x * per : halves;
+    const int64_t len = (b0 + per < halves ? b0 + per : halves) - b0;
+    wh0 = b0 + wave * len / 4; wh1 = b0 + (wave + 1) * len / 4;
+  }
+  // the wave's samples [32 wh0, r1), 64 per iteration (wave-uniform bounds, no workgroup barrier in the loop)
+  const int64_t r0 = 32 * dsu_uniform64(wh0);
+  const int64_t r1 = 32 * dsu_uniform64(wh1) < n ? 32 * dsu_uniform64(wh1) : n;
+  for (int64_t wave_first = r0; wave_first < r1; wave_first += 64) {
+    const int64_t i = wave_first + lane;
     const bool valid = i < r1;
     const int64_t ii = valid ? i : r1 - 1;
-    const int64_t wave_first = base + wave * 64;
-    if (wave_first >= r1) continue;                    // wave-uniform, no workgroup barrier in the loop
+    // which of the two halves carry a colour gradient at all: the bitmap says so before anything is loaded
+    // (their rows are written by the sweep above); without a bitmap, a ballot over the d_rgb just loaded
+    bool live0 = true, live1 = true;
+    if (scanned) {
+      const int64_t hf = wave_first >> 5;
+      const uint32_t b0 = sbits[hf >> 5] >> (hf & 31), b1 = hf + 1 < halves ? sbits[(hf + 1) >> 5] >> ((hf + 1) & 31) : 0u;
+      live0 = (__builtin_amdgcn_readfirstlane(b0) & 1u) != 0u;
+      live1 = (__builtin_amdgcn_readfirstlane(b1) & 1u) != 0u;
+      if (!live0 && !live1) continue;
+    }
+    float dr[TOUT];
+#pragma unroll
+    for (int o = 0; o < TOUT; ++o) dr[o] = d_rgb[ii * TOUT + o];
+    if (!scanned) {
+      const uint64_t lit = __ballot(valid && (dr[0] != 0.0f || dr[1] != 0.0f || dr[2] != 0.0f));
+      live0 = (uint32_t)lit != 0u;
+      live1 = (uint32_t)(lit >> 32) != 0u;
+      if (valid && !(h ? live1 : live0)) dead_sample_out<SHADE>(sh, so, d_x, i);
+      if (lit == 0ull) continue;
+    }
     float in[TIN];
     if (SHADE) {
       float inv_len;
@@ -502,7 +654,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
 #pragma unroll
     for (int o = 0; o < TOUT; ++o) {
       const float s = rgb[ii * TOUT + o];
-      dz[o] = valid ? d_rgb[ii * TOUT + o] * s * (1.0f - s) : 0.0f;
+      dz[o] = valid ? dr[o] * s * (1.0f - s) : 0.0f;
       gb2[o] += dz[o];
     }
     uint32_t mk2[2] = {0u, 0u};         // layer 1's ReLU pattern of the samples in column l31 of both halves
@@ -516,7 +668,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
     }
 #pragma unroll 1
     for (int a = 0; a < 2; ++a) {
-      if (wave_first + a * 32 >= r1) continue;
+      if (wave_first + a * 32 >= r1 || !(a ? live1 : live0)) continue;
       f32x16 H0[2], H1[2];
       forward_half<L1_MASK>(lds, in, a, l31, h, H0, H1);
       const uint32_t mk = a ? mk2[1] : mk2[0];
@@ -665,21 +817,7 @@ __global__ __launch_bounds__(256) void texture_bwd_kernel(
               const int comp = 8 * q + 4 * h + e;
               if (comp < 13) so.d_feature[si * 13 + comp] = din[4 * q + e];
             }
-          if (h == 1) {
-            const float g0 = sh.grad[si * 3], g1 = sh.grad[si * 3 + 1], g2 = sh.grad[si * 3 + 2];
-            const float len = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
-            const float inv = 1.0f / fmaxf(len, 1e-12f);
-            const float n0 = g0 * inv, n1 = g1 * inv, n2 = g2 * inv;
-            float d0 = din[5], d1 = din[6], d2 = din[7];          // components 13, 14, 15
-            if (so.d_normal) {
-              d0 += so.d_normal[si * 3]; d1 += so.d_normal[si * 3 + 1]; d2 += so.d_normal[si * 3 + 2];
-            }
-            const float dot = n0 * d0 + n1 * d1 + n2 * d2;
-            const bool ok = len > 1e-12f;
-            so.d_grad[si * 3] = ok ? (d0 - n0 * dot) * inv : d0 * inv;
-            so.d_grad[si * 3 + 1] = ok ? (d1 - n1 * dot) * inv : d1 * inv;
-            so.d_grad[si * 3 + 2] = ok ? (d2 - n2 * dot) * inv : d2 * inv;
-          }
+          if (h == 1) shade_grad_out(sh, so, si, din[5], din[6], din[7]);   // components 13, 14, 15
         } else {
 #pragma unroll
           for (int q = 0; q < 2; ++q)
@@ -764,6 +902,9 @@ __global__ void texture_reduce_kernel(const float* __restrict__ partials, int nb
   }
 }
 
+// words of the liveness bitmap of n samples: 32 halves of 32 samples each
+int64_t live_words(int64_t n) { return (n + 1023) / 1024; }
+
 bool mlp_ok(const dsu_tex_mlp* m) {
   return m && m->w0 && m->b0 && m->w1 && m->b1 && m->w2 && m->b2;
 }
@@ -772,16 +913,27 @@ bool mlp_ok(const dsu_tex_mlp* m) {
 // workgroup per CU it is given, the whole dynamic LDS.  A template and not a run-time branch:
 // DSU_ENSURE_DYN_LDS keeps its high-water mark per expansion, i.e. per kernel instantiation.
 // The caller checks the launch; *blocks is the number of partial vectors left in the workspace.
+// live: the liveness bitmap of the halves (see DEAD HALVES above); null = found here from d_rgb, into
+// the words behind the partial vectors of the workspace.
 template <bool SHADE, bool L1_MASK>
 int launch_bwd(const dsu_tex_mlp* mlp, const float* x, ShadeIn sh, ShadeOut so, const float* rgb,
-               const float* d_rgb, int64_t n, float* d_x, const uint32_t* h1_mask, void* workspace,
-               int64_t workspace_bytes, hipStream_t s, int* blocks) {
+               const float* d_rgb, int64_t n, float* d_x, const uint32_t* h1_mask, const uint32_t* live,
+               void* workspace, int64_t workspace_bytes, hipStream_t s, int* blocks) {
   if (!workspace || workspace_bytes < dsu_texture_bwd_workspace_bytes(n)) return DSU_EINVAL;
   *blocks = dsu_onewave_blocks(n, 256, TEX_MAX_BLOCKS, 1);
-  const size_t shm = (size_t)BWD_LDS_F * sizeof(float);
+  const int64_t words = live_words(n);
+  if (words > texpart::MAX_WORDS) {
+    live = nullptr;                                  // the kernel's static ranges
+  } else if (!live) {
+    uint32_t* own = reinterpret_cast<uint32_t*>((float*)workspace +
+                                                (size_t)dsu_capped_blocks(n, 256, TEX_MAX_BLOCKS) * PART_STRIDE);
+    texture_live_kernel<<<(unsigned)words, 1024, 0, s>>>(d_rgb, n, own);
+    live = own;
+  }
+  const size_t shm = (size_t)BWD_LDS_ALL_F * sizeof(float);
   DSU_ENSURE_DYN_LDS((texture_bwd_kernel<SHADE, L1_MASK>), shm);
   texture_bwd_kernel<SHADE, L1_MASK><<<*blocks, 256, shm, s>>>(*mlp, x, sh, so, rgb, d_rgb, n, d_x,
-                                                              (float*)workspace, h1_mask);
+                                                              (float*)workspace, h1_mask, live);
   return DSU_OK;
 }
 
@@ -817,7 +969,9 @@ int dsu_texture_fwd_shaded_m(const dsu_tex_mlp* mlp, const float* feature, const
 
 int64_t dsu_texture_bwd_workspace_bytes(int64_t n) {
   if (n < 0) return DSU_EINVAL;
-  return (int64_t)dsu_capped_blocks(n, 256, TEX_MAX_BLOCKS) * PART_STRIDE * sizeof(float);
+  // the partial vectors, then the liveness bitmap the stand-alone entry points build (launch_bwd)
+  const int64_t words = live_words(n) <= texpart::MAX_WORDS ? live_words(n) : 0;
+  return ((int64_t)dsu_capped_blocks(n, 256, TEX_MAX_BLOCKS) * PART_STRIDE + words) * (int64_t)sizeof(float);
 }
 
 int dsu_texture_bwd(const dsu_tex_mlp* mlp, const float* tex_in, const float* rgb,
@@ -831,7 +985,8 @@ int dsu_texture_bwd(const dsu_tex_mlp* mlp, const float* tex_in, const float* rg
   int blocks;
   const int rc = launch_bwd<false, false>(mlp, tex_in, ShadeIn{nullptr, nullptr},
                                           ShadeOut{nullptr, nullptr, nullptr, 0}, rgb, d_rgb, n, d_tex_in,
-                                          nullptr, workspace, workspace_bytes, (hipStream_t)stream, &blocks);
+                                          nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream,
+                                          &blocks);
   if (rc != DSU_OK) return rc;
   launch_reduce(workspace, blocks, g_w0, g_b0, g_w1, g_b1, g_w2, g_b2, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
@@ -852,8 +1007,8 @@ int dsu_texture_bwd_shaded(const dsu_tex_mlp* mlp, const float* feature, const f
   int blocks;
   const int rc = launch_bwd<true, false>(mlp, nullptr, ShadeIn{feature, grad},
                                          ShadeOut{d_normal, d_grad, d_feature, tail_rows}, rgb, d_rgb, n,
-                                         nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream,
-                                         &blocks);
+                                         nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                                         (hipStream_t)stream, &blocks);
   if (rc != DSU_OK) return rc;
   launch_reduce(workspace, blocks, g_w0, g_b0, g_w1, g_b1, g_w2, g_b2, (hipStream_t)stream);
   DSU_CHECK_LAUNCH();
@@ -887,11 +1042,11 @@ int32_t dsu_texture_partial_map(int32_t* map_host) {
   return PART_N;
 }
 
-int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
-                                      const float* rgb, const float* d_rgb, const float* d_normal,
-                                      int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
-                                      const uint32_t* h1_mask, void* workspace, int64_t workspace_bytes,
-                                      dsu_partial_reduce* red, void* stream) {
+static int shaded_partials(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
+                           const float* rgb, const float* d_rgb, const float* d_normal,
+                           int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
+                           const uint32_t* h1_mask, const uint32_t* live, void* workspace,
+                           int64_t workspace_bytes, dsu_partial_reduce* red, void* stream) {
   if (!mlp_ok(mlp) || n < 0 || !red) return DSU_EINVAL;
   if (tail_rows < 0 || (n && (!feature || !grad || !rgb || !d_rgb || !d_grad || !d_feature)))
     return DSU_EINVAL;
@@ -899,9 +1054,9 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
   const ShadeIn sh{feature, grad};
   const ShadeOut so{d_normal, d_grad, d_feature, tail_rows};
   int blocks;
-  const int rc = h1_mask ? launch_bwd<true, true>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, h1_mask,
+  const int rc = h1_mask ? launch_bwd<true, true>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, h1_mask, live,
                                                   workspace, workspace_bytes, (hipStream_t)stream, &blocks)
-                         : launch_bwd<true, false>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, nullptr,
+                         : launch_bwd<true, false>(mlp, nullptr, sh, so, rgb, d_rgb, n, nullptr, nullptr, live,
                                                    workspace, workspace_bytes, (hipStream_t)stream, &blocks);
   if (rc != DSU_OK) return rc;
   DSU_CHECK_LAUNCH();
@@ -909,6 +1064,50 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
   red->nblocks = blocks;
   red->stride = PART_STRIDE;
   red->n = PART_N;
+  return DSU_OK;
+}
+
+int dsu_texture_bwd_shaded_partials_live(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
+                                         const float* rgb, const float* d_rgb, const float* d_normal,
+                                         int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
+                                         const uint32_t* h1_mask, const uint32_t* live_halves,
+                                         void* workspace, int64_t workspace_bytes,
+                                         dsu_partial_reduce* red, void* stream) {
+  if (!live_halves) return DSU_EINVAL;
+  return shaded_partials(mlp, feature, grad, rgb, d_rgb, d_normal, n, tail_rows, d_grad, d_feature, h1_mask,
+                         live_halves, workspace, workspace_bytes, red, stream);
+}
+
+int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
+                                      const float* rgb, const float* d_rgb, const float* d_normal,
+                                      int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
+                                      const uint32_t* h1_mask, void* workspace, int64_t workspace_bytes,
+                                      dsu_partial_reduce* red, void* stream) {
+  return shaded_partials(mlp, feature, grad, rgb, d_rgb, d_normal, n, tail_rows, d_grad, d_feature, h1_mask,
+                         nullptr, workspace, workspace_bytes, red, stream);
+}
+
+int dsu_texture_live_partition(const uint32_t* live_halves, int64_t n_halves, int32_t parts,
+                               int32_t waves, int32_t* runs) {
+  if (!live_halves || !runs || n_halves < 1 || parts < 1 || waves < 1) return DSU_EINVAL;
+  const int64_t words = (n_halves + 31) / 32;
+  if (words > texpart::MAX_WORDS) return DSU_EUNSUP;
+  std::vector<uint32_t> bits((size_t)words), pre((size_t)words + 1);
+  pre[0] = 0;
+  for (int64_t w = 0; w < words; ++w) {
+    bits[w] = texpart::clip_word(live_halves[w], (int)w, (int)n_halves);
+    pre[w + 1] = pre[w] + (uint32_t)texpart::popc(bits[w]);
+  }
+  const texpart::Scan sc{bits.data(), pre.data(), (int)words, (int)n_halves};
+  const texpart::Run all = texpart::whole(sc);
+  for (int b = 0; b < parts; ++b) {
+    const texpart::Run wg = texpart::split(sc, all, parts, b);
+    for (int w = 0; w < waves; ++w) {
+      const texpart::Run r = texpart::split(sc, wg, waves, w);
+      runs[2 * (b * waves + w)] = r.h0;
+      runs[2 * (b * waves + w) + 1] = r.h1;
+    }
+  }
   return DSU_OK;
 }
 

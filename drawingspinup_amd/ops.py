@@ -1294,6 +1294,41 @@ def neus_composite_bwd(sdf, normal, rgb, rays_d, t_starts, t_ends, offsets, coun
     return d_sdf, d_normal, d_rgb, d_inv
 
 
+def neus_composite_bwd_live(sdf, normal, rgb, rays_d, t_starts, t_ends, offsets, counts, inv_s, car,
+                            alpha, weights, d_comp):
+    """neus_composite_bwd as the NSR step runs it: also returns the liveness bitmap of the texture
+    backward (int32 words, one bit per 32-sample half: some d_rgb of the half is not zero)."""
+    n, n_rays = sdf.shape[0], rays_d.shape[0]
+    dev = sdf.device
+    d_sdf = torch.empty(n, dtype=torch.float32, device=dev)
+    d_normal = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    d_rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    d_inv = torch.zeros(1, dtype=torch.float32, device=dev)
+    live = torch.zeros((n + 1023) // 1024, dtype=torch.int32, device=dev)
+    check(lib().dsu_neus_composite_bwd_live(ptr(_f32c(sdf)), ptr(_f32c(normal)), ptr(_f32c(rgb)),
+                                            ptr(_f32c(rays_d)), ptr(_f32c(t_starts)), ptr(_f32c(t_ends)),
+                                            ptr(offsets, torch.int32), ptr(counts, torch.int32), n_rays,
+                                            ptr(inv_s, torch.float32), float(car), ptr(alpha),
+                                            ptr(weights), ptr(_f32c(d_comp)), None, ptr(d_sdf),
+                                            ptr(d_normal), ptr(d_rgb), ptr(d_inv), ptr(live, torch.int32),
+                                            stream()),
+          "dsu_neus_composite_bwd_live")
+    return d_sdf, d_normal, d_rgb, d_inv, live
+
+
+def texture_live_partition(live_words, n_halves, parts, waves=4):
+    """Host only: the runs of 32-sample halves the texture backward gives `parts` workgroups of `waves`
+    waves for a liveness bitmap (numpy uint32 words): int32 array (parts, waves, 2) of [first, end)."""
+    import numpy as np
+    words = np.ascontiguousarray(live_words, dtype=np.uint32)
+    assert words.size * 32 >= n_halves
+    runs = np.empty((parts, waves, 2), dtype=np.int32)
+    check(lib().dsu_texture_live_partition(words.ctypes.data_as(C.c_void_p), int(n_halves), int(parts),
+                                           int(waves), runs.ctypes.data_as(C.c_void_p)),
+          "dsu_texture_live_partition")
+    return runs
+
+
 # ------------------------------------------------------------------ export: mesh post-processing
 class ZGrid:
     """Uniform xy grid over a triangle soup (tris (F,3,3) f32 on the device) for z-parallel ray

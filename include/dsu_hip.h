@@ -345,6 +345,16 @@ int dsu_neus_composite_bwd(const float* sdf, const float* normal, const float* r
                            const float* weights, const float* d_comp, const float* d_weights,
                            float* d_sdf, float* d_normal, float* d_rgb, float* d_inv_s,
                            void* stream);
+/* The same, and the liveness bitmap of the texture backward on the way: bit (i >> 5) & 31 of word
+ * i >> 10 of live_halves is set where some d_rgb of sample i is not zero (behind the front surface
+ * the weights are exactly 0.0f).  (n + 1023) / 1024 words, zeroed by the caller. */
+int dsu_neus_composite_bwd_live(const float* sdf, const float* normal, const float* rgb,
+                                const float* rays_d, const float* t_starts, const float* t_ends,
+                                const int32_t* offsets, const int32_t* counts, int64_t n_rays,
+                                const float* inv_s, float cos_anneal_ratio, const float* alpha,
+                                const float* weights, const float* d_comp, const float* d_weights,
+                                float* d_sdf, float* d_normal, float* d_rgb, float* d_inv_s,
+                                uint32_t* live_halves, void* stream);
 /* normal = F.normalize(sdf_grad) and the texture-MLP input cat(feature, normal) (neus.py:143,
  * texture.py:22) in one pass; and its backward. */
 int dsu_shade_prep_fwd(const float* grad, const float* feature, int64_t n, float* normal,
@@ -401,6 +411,26 @@ int dsu_texture_bwd_shaded_partials_m(const dsu_tex_mlp* mlp, const float* featu
                                       int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
                                       const uint32_t* h1_mask, void* workspace, int64_t workspace_bytes,
                                       dsu_partial_reduce* red, void* stream);
+/* Dead halves.  A 32-sample half of [0, n) whose d_rgb rows are all zero contributes exact zeros to
+ * d_feature, to the MLP's part of d_grad and to every parameter gradient: the backward kernels skip
+ * its recompute and products, write d_feature = 0 and d_grad from d_normal alone, and hand every
+ * workgroup (and every wave of it) a contiguous run of halves with an equal share of the LIVE ones
+ * (csrc/tex_partition.h).  The entry points above find the live halves from d_rgb themselves (one small
+ * launch; the bitmap sits behind the partial vectors in `workspace`); this one takes the bitmap
+ * dsu_neus_composite_bwd_live filled.  The bit decides: a set bit on a dead half only costs its time, a
+ * clear bit on a half with a non-zero d_rgb loses that half's gradients.  Beyond 2 097 152 samples the
+ * bitmap is not read (static ranges, dead halves found from d_rgb). */
+int dsu_texture_bwd_shaded_partials_live(const dsu_tex_mlp* mlp, const float* feature, const float* grad,
+                                         const float* rgb, const float* d_rgb, const float* d_normal,
+                                         int64_t n, int64_t tail_rows, float* d_grad, float* d_feature,
+                                         const uint32_t* h1_mask, const uint32_t* live_halves,
+                                         void* workspace, int64_t workspace_bytes,
+                                         dsu_partial_reduce* red, void* stream);
+/* Host only: the runs of halves the backward kernel gives its workgroups and waves for a bitmap of
+ * n_halves bits (host memory) and a grid of `parts` workgroups of `waves` waves.  runs: parts x waves
+ * pairs (first half, one past the last), in order. */
+int dsu_texture_live_partition(const uint32_t* live_halves, int64_t n_halves, int32_t parts,
+                               int32_t waves, int32_t* runs);
 
 /* OrthoNeuSSystem.preprocess_data (systems/neus_ortho.py:26-82) for n sampled (view, y, x)
  * triples (int64, drawn by the caller): c2w gather, get_ortho_rays (models/ray_utils.py:36-58),
@@ -877,6 +907,10 @@ int dsu_nsr_driver_step(dsu_nsr_driver* d, dsu_nsr_step_args* args, void* main_s
  * loss terms: rgb_mse, rgb_l1, normal, mask, eikonal, sparsity, normal_smooth (each already
  * multiplied by its lambda).  A set is reused (zeroed) at the end of the following step. */
 const float* dsu_nsr_driver_terms(const dsu_nsr_driver* d);
+/* Device pointer to the liveness bitmap of step `step`'s texture backward (one bit per 32-sample half of
+ * its out_n_samples ray samples, see dsu_neus_composite_bwd_live): valid from that step's return until
+ * the end of the following step. */
+const uint32_t* dsu_nsr_driver_live_halves(const dsu_nsr_driver* d, int64_t step);
 /* Device pointer to the first (second = 0) or second (1) AdamW moments of the 13 small tensors,
  * 7 902 floats in the order lin0.weight_v (64x23), lin0.weight_g (64), lin0.bias (64),
  * lin1.weight_v (13x64), lin1.weight_g (13), lin1.bias (13), the texture MLP's w0 b0 w1 b1 w2 b2,
