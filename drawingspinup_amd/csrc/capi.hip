@@ -22,7 +22,7 @@ const char* dsu_strerror(int code) {
   }
 }
 
-int dsu_abi_version(void) { return 3; }
+int dsu_abi_version(void) { return DSU_ABI_VERSION; }
 
 int32_t dsu_onewave_grid_cap_value = 0;     // CUs; 0 = the resident count (geometry backward 512, texture backward 256 workgroups)
 int32_t dsu_scatter_grid_cap_value = 0;     // 0 = the resident count (three 256-thread workgroups per CU: 768)

@@ -606,7 +606,7 @@ def ortho_ray_batch(index, x, y, c2w, origins, directions, images, normals, mask
     return out
 
 
-RAY_LOSS_MAX_RAYS = 8192      # DSU_RAY_LOSS_MAX_RAYS (include/dsu_hip.h)
+RAY_LOSS_MAX_RAYS = _lib.DEFINES["DSU_RAY_LOSS_MAX_RAYS"]
 
 
 def ray_losses(comp, rgb, normal, mask, cosines, view_weights, cfg):
@@ -1413,7 +1413,9 @@ def knn8_blend(query_xy, known_xy, known_rgb):
 class _BinnedPlan:
     """The binning half of a staged entry point (csrc/bin_sort.h): stage 0 counts the items per bin
     into the workspace, the prefix sum is taken here (torch), stage 1 fills the ids in.  A subclass
-    calls _alloc() from its constructor and states its entry point's argument list in _stage()."""
+    names its entry point's two stage constants (COUNT, FILL), calls _alloc() from its constructor and
+    states its entry point's argument list in _stage()."""
+    COUNT = FILL = None
 
     def _alloc(self, nbytes, name, device):
         if nbytes < 0:
@@ -1432,7 +1434,7 @@ class _BinnedPlan:
         raise NotImplementedError
 
     def count(self):
-        self._stage(0)                              # = RENDER_COUNT = UV_COUNT = SKIN_COUNT
+        self._stage(self.COUNT)
 
     def scan(self):
         nb = self.bins
@@ -1442,7 +1444,7 @@ class _BinnedPlan:
 
     def fill(self, total):
         self.items = torch.empty(max(total, 1), dtype=torch.int32, device=self.workspace.device)[:total]
-        self._stage(1)                              # = RENDER_FILL = UV_FILL = SKIN_FILL
+        self._stage(self.FILL)
 
     def bin(self):
         self.count()
@@ -1451,15 +1453,16 @@ class _BinnedPlan:
 
 
 # ------------------------------------------------------------------ frame rendering (csrc/mesh_render.hip)
-RENDER_COUNT, RENDER_FILL, RENDER_RASTER = 0, 1, 2
+RENDER_COUNT, RENDER_FILL, RENDER_RASTER = (_lib.DEFINES["DSU_RENDER_" + k] for k in ("COUNT", "FILL", "RASTER"))
 MIP_TRILINEAR = "trilinear"
-TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1, MIP_TRILINEAR: 2}    # DSU_TEX_*
+TEXTURE_FILTERS = {k: _lib.DEFINES["DSU_TEX_" + k.upper()] for k in ("nearest", "bilinear", MIP_TRILINEAR)}
 
 
 class MeshRenderPlan(_BinnedPlan):
     """The binning half of dsu_mesh_render_ortho for one (screen, faces, window): (frame, triangle)
     pairs counted per 16x16-pixel tile, the prefix sum (torch), the triangle ids filled in.
     screen (F,V,3) f32, faces (M,3) i32 on the device; size a multiple of 4 (<= 2048), ss 1 | 2 | 4."""
+    COUNT, FILL = RENDER_COUNT, RENDER_FILL
 
     def __init__(self, screen, faces, cx, cy, span, size, ss):
         self.screen, self.faces = _f32c(screen), faces.to(torch.int32).contiguous()
@@ -1608,7 +1611,7 @@ def pos_edge_u8(pos_rgba):
 
 
 # ------------------------------------------------------------------ uv export (csrc/mesh_uv.hip)
-UV_COUNT, UV_FILL, UV_RASTER = 0, 1, 2
+UV_COUNT, UV_FILL, UV_RASTER = (_lib.DEFINES["DSU_UV_" + k] for k in ("COUNT", "FILL", "RASTER"))
 
 
 def uv_face_labels(verts, faces):
@@ -1668,6 +1671,7 @@ def uv_components(adjacency, label, check_every=4, max_rounds=1 << 20):
 class UvBakePlan(_BinnedPlan):
     """The binning half of dsu_uv_bake for one (uvs, indices, size): faces counted per 16x16-texel
     tile, the prefix sum (torch), the ids filled in.  uvs (V,2) f32, indices (M,3) on the device."""
+    COUNT, FILL = UV_COUNT, UV_FILL
 
     def __init__(self, uvs, indices, size):
         self.uvs, self.indices = _f32c(uvs), indices.to(torch.int32).contiguous()
@@ -1854,7 +1858,7 @@ def uv_seam_apply(uvs, indices, group, face_id, source, proj, fallback, d):
 
 
 # ------------------------------------------------------------------ rigging (csrc/mesh_skin.hip)
-SKIN_COUNT, SKIN_FILL, SKIN_RUN = 0, 1, 2
+SKIN_COUNT, SKIN_FILL, SKIN_RUN = (_lib.DEFINES["DSU_SKIN_" + k] for k in ("COUNT", "FILL", "RUN"))
 
 
 class BoneVisibilityPlan(_BinnedPlan):
@@ -1862,6 +1866,7 @@ class BoneVisibilityPlan(_BinnedPlan):
     uniform 3-D grid over the mesh and the bones, the prefix sum (torch), the ids filled in; and the
     vertex order (by cell) that keeps a workgroup's segments together.
     verts (V,3) f32, faces (M,3) i32, bones (B,2,3) f32 on the device."""
+    COUNT, FILL = SKIN_COUNT, SKIN_FILL
 
     def __init__(self, verts, faces, bones, cells_per_axis=None):
         import math

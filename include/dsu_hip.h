@@ -30,8 +30,10 @@ extern "C" {
 #define DSU_MAX_LEVELS 16
 
 const char* dsu_strerror(int code);
-/* ABI version of this header, 2 now; bumped by any change to an exported signature or to the layout
- * of a struct declared here.  A caller that binds by hand (ctypes) compares it before the first call. */
+/* ABI version of this header: DSU_ABI_VERSION, bumped by any change to an exported signature or to the
+ * layout of a struct declared here.  dsu_abi_version() returns the value the library was compiled with;
+ * a caller that binds from this header (drawingspinup_amd/_lib.py) compares the two before the first call. */
+#define DSU_ABI_VERSION 3
 int dsu_abi_version(void);
 /* CUs given to the two whole-SIMD kernels of the NSR step (the MLP part of the geometry backward,
  * the texture backward: their waves fill every SIMD of a CU they run on, nothing else fits beside

@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/dsu_hip.h declares (no
-compute calls: there is no GPU here), and the product path fails loudly without a device."""
+compute calls: there is no GPU here), the binding derived from that header is complete, strict and
+laid out as the host compiler lays it out, and the product path fails loudly without a device."""
 import ctypes
 import os
 import re
@@ -221,3 +222,183 @@ def test_occgrid_refresh_host_side():
     assert lib.dsu_occgrid_refresh(C.byref(a), None) == -1              # NULL pointers
     assert lib.dsu_occgrid_refresh(None, None) == -1
     assert lib.dsu_nsr_driver_occ_refresh(None, C.byref(a), None) == -1
+
+
+# ------------------------------------------------------------------ the binding is derived from the header
+def test_reader_returns_every_declared_function():
+    """The strict reader against this file's own regex scan: a declaration it dropped silently would
+    leave the function without argument types."""
+    from drawingspinup_amd import _header, _lib
+    h = _header.read()
+    assert sorted(h.protos) == _declared() and len(h.protos) >= 166
+    assert set(_lib._PROTOS) == set(h.protos)
+    assert all(_lib._PROTOS[n] is args for n, (_, args) in _lib._HEADER.protos.items())
+    assert sorted(_lib._STRUCT_NAMES) == sorted(h.structs) and len(h.structs) == 12
+    for c_name, py_name in _lib._STRUCT_NAMES.items():
+        cls = getattr(_lib, py_name)
+        assert cls is _lib._HEADER.structs[c_name] and cls.__name__ == py_name
+    assert h.opaque == {"dsu_nsr_driver"}
+    assert _lib.ABI_VERSION == h.defines["DSU_ABI_VERSION"] == 3
+    assert _lib.MAX_LEVELS == h.defines["DSU_MAX_LEVELS"]
+    assert _lib.ADAMW_MAX_TENSORS == h.defines["DSU_ADAMW_MAX_TENSORS"]
+
+
+def test_header_missing_is_an_error(tmp_path):
+    from drawingspinup_amd import _header
+    with pytest.raises(_header.DsuError, match=r"dsu_hip\.h is missing"):
+        _header.read(str(tmp_path / "include" / "dsu_hip.h"))
+
+
+_WELL_FORMED = """
+/* every accepted form */
+#ifndef DSU_X_H
+#define DSU_X_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define DSU_N 4
+#define DSU_NEG (-2)   /* trailing comment */
+typedef struct { uint32_t a; double b; } dsu_a;   // line comment
+typedef struct dsu_b {
+  int32_t x, y;
+  const float* p;
+  float *q, *r;
+  uint64_t v[DSU_N + 1];
+  float* t[3];
+  dsu_a inner;
+  int64_t z[2];
+  int i; float f;
+} dsu_b;
+typedef struct dsu_h dsu_h;
+const char* dsu_name(int code);
+void dsu_free(dsu_h* h);
+dsu_h* dsu_make(const dsu_b* cfg, dsu_h** out, void* stream);
+int64_t dsu_bytes(int64_t n, uint32_t k, float f, double d, uint64_t s, const uint8_t* m,
+                  int32_t* out, dsu_a* a);
+int32_t dsu_count(void);
+int dsu_rc(const uint16_t *w);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_reader_maps_every_accepted_form():
+    import ctypes as C
+    from drawingspinup_amd import _header
+    h = _header.parse(_WELL_FORMED)
+    assert h.defines == {"DSU_N": 4, "DSU_NEG": -2} and h.opaque == {"dsu_h"}
+    a, b = h.structs["dsu_a"], h.structs["dsu_b"]
+    assert list(h.structs) == ["dsu_a", "dsu_b"] and issubclass(b, C.Structure)
+    assert a._fields_ == [("a", C.c_uint32), ("b", C.c_double)]
+    assert b._fields_ == [("x", C.c_int32), ("y", C.c_int32), ("p", C.c_void_p), ("q", C.c_void_p),
+                          ("r", C.c_void_p), ("v", C.c_uint64 * 5), ("t", C.c_void_p * 3), ("inner", a),
+                          ("z", C.c_int64 * 2), ("i", C.c_int), ("f", C.c_float)]
+    assert h.protos == {
+        "dsu_name": (C.c_char_p, [C.c_int]),
+        "dsu_free": (None, [C.c_void_p]),
+        "dsu_make": (C.c_void_p, [C.POINTER(b), C.c_void_p, C.c_void_p]),
+        "dsu_bytes": (C.c_int64, [C.c_int64, C.c_uint32, C.c_float, C.c_double, C.c_uint64, C.c_void_p,
+                                  C.c_void_p, C.POINTER(a)]),
+        "dsu_count": (C.c_int32, []),
+        "dsu_rc": (C.c_int, [C.c_void_p]),
+    }
+    assert b(1, 2).y == 2                                  # positional construction in the header's order
+
+
+@pytest.mark.parametrize("snippet, offending", [
+    ("int dsu_f(int (*cb)(int), void* s);", r"\(\*cb\)"),                                  # function pointer
+    ("typedef struct { union { int a; float b; } u; } dsu_s;", "union"),                   # union
+    ("typedef union { int a; float b; } dsu_s;", "union"),
+    ("typedef struct { int32_t a : 3; } dsu_s;", "a : 3"),                                 # bit-field
+    ("typedef struct { struct { int a; } in; int b; } dsu_s;", r"struct \{ int a; \}"),   # anonymous nested struct
+    ("typedef struct { size_t n; } dsu_s;", "size_t"),                                     # unknown type words
+    ("int dsu_f(size_t n);", "size_t"),
+    ("int dsu_f(const dsu_missing* p);", "dsu_missing"),
+    ("typedef struct { unsigned int n; } dsu_s;", "unsigned int n"),
+    ("float dsu_f(void);", "float"),
+    ("int dsu_f(float v[3]);", r"v\[3\]"),                                                 # array parameter
+    ("int dsu_f(int n, ...);", r"\.\.\."),                                                 # variadic list
+    ("int dsu_f();", r"dsu_f\(\)"),                                                        # no prototype
+    ("int dsu_f(int32_t);", r"dsu_f\(int32_t\)"),                                          # unnamed parameter
+    ("typedef struct dsu_h dsu_h; int dsu_f(dsu_h h);", "dsu_h h"),                        # opaque by value
+    ("typedef struct { float a[DSU_UNSEEN]; } dsu_s;", "DSU_UNSEEN"),                      # extent not yet read
+    ("typedef struct { int32_t a } dsu_s;", "int32_t a"),                                  # no `;`
+    ("typedef int dsu_t;", "typedef int dsu_t"),
+    ("#define DSU_SCALE 1.5\n", "DSU_SCALE 1.5"),                                          # not an integer
+    ("#define DSU_TWICE(x) (2 * (x))\n", "DSU_TWICE"),                                     # function-like macro
+    ("#pragma pack(1)\n", "pragma pack"),
+    ("int dsu_f(void); int dsu_f(void);", "dsu_f"),                                        # declared twice
+    ("static inline int dsu_f(void) { return 0; }", "static inline"),                      # a definition
+    ("int dsu_f(void)", r"dsu_f\(void\)"),                                                 # no final `;`
+    ("int other_f(void);", "other_f"),                                                     # not a dsu_ name
+])
+def test_reader_raises_on_what_is_outside_its_grammar(snippet, offending):
+    """Never skipped, never guessed: the error carries the offending text."""
+    from drawingspinup_amd import _header
+    with pytest.raises(_header.DsuError, match=offending):
+        _header.parse(snippet)
+
+
+def _host_cc():
+    """cc, or the clang that stands beside hipcc in the ROCm tree."""
+    import shutil
+    from drawingspinup_amd import build
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(build._hipcc())))
+    for c in (shutil.which("cc"), os.path.join(rocm, "lib", "llvm", "bin", "clang"),
+              os.path.join(rocm, "llvm", "bin", "clang")):
+        if c and os.path.exists(c):
+            return c
+    raise AssertionError("no host C compiler (cc, or clang of the ROCm tree)")
+
+
+def test_struct_layouts_and_defines_match_the_host_compiler(tmp_path):
+    """A stand-alone C program that includes dsu_hip.h prints sizeof of every struct, offsetof of every
+    field and the value of every #define; the generated ctypes classes and DEFINES must say the same."""
+    import subprocess
+    from drawingspinup_amd import _lib
+    h = _lib._HEADER
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "dsu_hip.h"', "int main(void) {"]
+    for name, cls in h.structs.items():
+        lines.append(f'  printf("S {name} %zu\\n", sizeof({name}));')
+        lines += [f'  printf("F {name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in cls._fields_]
+    lines += [f'  printf("D {d} %lld\\n", (long long)({d}));' for d in h.defines]
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([_host_cc(), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                        str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    want = {}
+    for name, cls in h.structs.items():
+        want[f"S {name}"] = ctypes.sizeof(cls)
+        want.update({f"F {name}.{f}": getattr(cls, f).offset for f, _ in cls._fields_})
+    want.update({f"D {d}": v for d, v in h.defines.items()})
+    got = {k: int(v) for k, v in (ln.rsplit(" ", 1) for ln in out.splitlines())}
+    assert len(h.structs) == 12 and len(got) == len(out.splitlines())
+    diff = {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+    assert not diff, diff
+    assert got["S dsu_nsr_step_args"] == 248 and got["F dsu_nsr_step_args.terms_out"] == 240
+    # the defines the library's own sources use, as the compiler sees them
+    for d in ("DSU_ABI_VERSION", "DSU_MAX_LEVELS", "DSU_RAY_LOSS_MAX_RAYS", "DSU_ADAMW_MAX_TENSORS",
+              "DSU_OK", "DSU_EINVAL", "DSU_ELAUNCH", "DSU_EUNSUP"):
+        assert got[f"D {d}"] == _lib.DEFINES[d]
+
+
+def test_ops_constants_are_the_headers():
+    from drawingspinup_amd import _lib, ops
+    D = _lib.DEFINES
+    assert ops.RAY_LOSS_MAX_RAYS == D["DSU_RAY_LOSS_MAX_RAYS"] == 8192
+    assert (ops.RENDER_COUNT, ops.RENDER_FILL, ops.RENDER_RASTER) == \
+        (D["DSU_RENDER_COUNT"], D["DSU_RENDER_FILL"], D["DSU_RENDER_RASTER"])
+    assert (ops.UV_COUNT, ops.UV_FILL, ops.UV_RASTER) == (D["DSU_UV_COUNT"], D["DSU_UV_FILL"], D["DSU_UV_RASTER"])
+    assert (ops.SKIN_COUNT, ops.SKIN_FILL, ops.SKIN_RUN) == (D["DSU_SKIN_COUNT"], D["DSU_SKIN_FILL"], D["DSU_SKIN_RUN"])
+    assert ops.TEXTURE_FILTERS == {"nearest": D["DSU_TEX_NEAREST"], "bilinear": D["DSU_TEX_BILINEAR"],
+                                   "trilinear": D["DSU_TEX_TRILINEAR"]}
+    # each binned plan passes its own entry point's stage constants
+    assert (ops.MeshRenderPlan.COUNT, ops.MeshRenderPlan.FILL) == (ops.RENDER_COUNT, ops.RENDER_FILL)
+    assert (ops.UvBakePlan.COUNT, ops.UvBakePlan.FILL) == (ops.UV_COUNT, ops.UV_FILL)
+    assert (ops.BoneVisibilityPlan.COUNT, ops.BoneVisibilityPlan.FILL) == (ops.SKIN_COUNT, ops.SKIN_FILL)
