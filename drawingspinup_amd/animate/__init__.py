@@ -12,10 +12,12 @@ pos2edge (run_render.py:31-57) runs on the position pass.  Both passes, all fram
 run on the device (csrc/mesh_render.hip).  A caller-supplied (F,V,3) vertex animation is accepted
 as well: a skinned animation made elsewhere renders through the same path.
 
-Deviations from the reference (Blender itself is not here to compare against): a box filter over
-ss^2 sub-samples stands in for Blender's pixel filter; no view transform or tone curve is applied
-(the reference selects 'Standard'); the turntable's frame count lives in a .blend file that is not
-in the snapshot, so it is a parameter.
+Deviations from the reference (Blender itself is not here to compare against): by default a box
+filter over ss^2 sub-samples stands in for Blender's pixel filter (`pixel_filter="eevee"` or
+`"cycles"` puts a Blackman-Harris window in its place, see `pixel_filter`; the widths are read from
+Blender's source and unpinned); no view transform or tone curve is applied (the reference selects
+'Standard'); the turntable's frame count lives in a .blend file that is not in the snapshot, so it
+is a parameter.
 
 Textured frames: `read_obj_textured` keeps a textured export's uvs and atlas, and `render_frames` /
 `animate_mesh` with `texture=` and `uvs=` sample the atlas inside the rasteriser's resolve, per
@@ -38,8 +40,8 @@ skinned frames and puts the rest mesh's detail back (delta mush, Blender's Corre
 `smoothing_topology` builds the welded graph it walks): it repairs creases from bad weights, not the
 collapse of a twisted limb.
 """
-from .render import (DEFAULT_SIZE, DEFAULT_SPAN, frame_window, motion_frames, position_colours,
-                     read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
+from .render import (DEFAULT_SIZE, DEFAULT_SPAN, PIXEL_FILTER_PRESETS, frame_window, motion_frames, pixel_filter,
+                     position_colours, read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
 from .skeleton import (Clip, Skeleton, dual_quaternions, fit_to_mesh, quaternion_rotations, read_bvh, resample_clip,
                        rest_clip, rotation_quaternions, skinning_matrices)
 from . import corrective
@@ -47,5 +49,5 @@ from .corrective import smoothing_topology
 from .skin import animate_mesh, bone_heat_weights
 
 __all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "dual_quaternions", "fit_to_mesh",
-           "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "frame_window", "motion_frames", "position_colours",
+           "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "PIXEL_FILTER_PRESETS", "frame_window", "motion_frames", "pixel_filter", "position_colours",
            "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate", "smoothing_topology"]

@@ -254,6 +254,63 @@ def _texture_args(texture, uvs, texture_filter, n_verts, dev, faces=None, mip_co
     return tex
 
 
+# The reconstruction filters of the reference's two engines (run_render.py --engine_type), as
+# (window, width in pixels).  Both are UNPINNED: Blender is not here to render against, and the widths
+# are read from its source — the width is the only thing a correction would change.
+#   cycles  Blackman-Harris; Cycles' filter_width (1.50 px) is the total support.
+#   eevee   Blackman-Harris; EEVEE's filter_size (1.50 px) scales a jitter table that spans [-1, 1]
+#           (Blender 3.6, eevee_temporal_sampling.c), so the support is 2 x 1.50 px, separable.
+PIXEL_FILTER_PRESETS = {"cycles": ("blackman_harris", 1.5), "eevee": ("blackman_harris", 3.0)}
+PIXEL_FILTERS = ("box", "blackman_harris", *PIXEL_FILTER_PRESETS)
+
+
+def _blackman_harris(d, width):
+    """k(d) = 0.35875 - 0.48829 cos(2 pi u) + 0.14128 cos(4 pi u) - 0.01168 cos(6 pi u), u = d / width + 0.5,
+    evaluated at -|d| so that the two sides of the window agree bit for bit."""
+    u = -np.abs(np.asarray(d, np.float64)) / float(width) + 0.5
+    return (0.35875 - 0.48829 * np.cos(2.0 * np.pi * u) + 0.14128 * np.cos(4.0 * np.pi * u)
+            - 0.01168 * np.cos(6.0 * np.pi * u))
+
+
+def pixel_filter(kind, width=None, ss=4):
+    """The 1-D table of a separable pixel filter for ops.mesh_render_ortho(pixel_filter=...) (include/dsu_hip.h,
+    "Pixel filter") -> (taps float64 (ss + 2 halo,), halo).
+
+    kind "box": ones and halo 0, the unfiltered rule.  "blackman_harris": the window of total support
+    `width` pixels.  "eevee" / "cycles": PIXEL_FILTER_PRESETS, with `width` overriding the preset's.
+    halo = ceil((width / 2 - 0.5) ss) sub-samples, never below 0; tap q + halo = k(d_q) at
+    d_q = (q + 0.5) / ss - 0.5 px where |d_q| < width / 2, else 0.  A width whose halo exceeds 2 ss (the
+    rasteriser's LDS tile) is refused."""
+    ss = int(ss)
+    if ss not in (1, 2, 4):
+        raise ValueError("ss must be 1, 2 or 4")
+    if kind == "box":
+        return np.ones(ss, np.float64), 0
+    if kind in PIXEL_FILTER_PRESETS:
+        kind, preset = PIXEL_FILTER_PRESETS[kind]
+        width = preset if width is None else width
+    if kind != "blackman_harris":
+        raise ValueError(f"pixel filter {kind!r}: one of {list(PIXEL_FILTERS)}")
+    if width is None or not np.isfinite(width) or not width > 0:
+        raise ValueError("blackman_harris needs a width > 0 (pixels)")
+    width = float(width)
+    halo = max(int(math.ceil((width / 2.0 - 0.5) * ss)), 0)
+    if halo > 2 * ss:
+        raise ValueError(f"filter width {width} px reaches {halo} sub-samples beyond the pixel at ss {ss}: "
+                         f"at most {2 * ss} (width 5 px)")
+    d = (np.arange(-halo, ss + halo, dtype=np.float64) + 0.5) / float(ss) - 0.5
+    return np.where(np.abs(d) < width / 2.0, _blackman_harris(d, width), 0.0), halo
+
+
+def _pixel_filter_args(pixel_filter_kind, filter_width, ss):
+    """The pixel_filter keyword of ops.mesh_render_ortho: {} for None (the call as it always was)."""
+    if pixel_filter_kind is None:
+        if filter_width is not None:
+            raise ValueError("filter_width goes with a pixel_filter")
+        return {}
+    return {"pixel_filter": pixel_filter(pixel_filter_kind, filter_width, ss)}
+
+
 def _vertex_colours(colours, n_verts, textured):
     """(V,3) f32 vertex colours; None is allowed (and stays None) when a texture gives the colour."""
     if colours is None and textured:
@@ -269,7 +326,8 @@ def _vertex_colours(colours, n_verts, textured):
 
 @torch.no_grad()
 def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24, device="cuda",
-                  window=None, want=(), texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces"):
+                  window=None, want=(), texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces",
+                  pixel_filter=None, filter_width=None):
     """Render the motion of one mesh.  verts (V,3) in save_mesh's frame (x right, y up, z front; the
     viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
 
@@ -284,6 +342,12 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     every texel — the choice for a foreign OBJ whose charts are mirrored (clockwise in uv), which
     "faces" would count as uncovered.
 
+    pixel_filter None is the box over a pixel's own ss^2 samples.  "eevee", "cycles" or
+    "blackman_harris" (with filter_width in pixels; it overrides a preset's) reconstruct a pixel with
+    that window, which reaches into the neighbouring pixels (see `pixel_filter`): silhouettes soften,
+    more pixels are partially covered and the edge lines of pos2edge thicken accordingly.  "box" is the
+    same rule through the filtered kernel.
+
     rest_pose keeps the default camera (origin-centred, 512 px across 1.35: the exported character
     fills the frame as in the reference); every other motion goes through frame_window.  `window`
     (cx, cy, size, span) overrides both.
@@ -296,7 +360,8 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
     tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
-    c = _vertex_colours(colours, len(v), bool(tex))
+    tex.update(_pixel_filter_args(pixel_filter, filter_width, ss))
+    c = _vertex_colours(colours, len(v), texture is not None)
     xyz = motion_frames(v, motion, n_frames)
     if window is not None:
         cx, cy, size, span = window

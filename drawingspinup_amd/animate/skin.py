@@ -14,7 +14,7 @@ import torch
 from .. import ops
 from ..nsr.thinning import _weld, cotmatrix
 from .corrective import check_parameters, smoothing_topology
-from .render import _texture_args, _vertex_colours, frame_window, position_colours
+from .render import _pixel_filter_args, _texture_args, _vertex_colours, frame_window, position_colours
 from .skeleton import dual_quaternions, skinning_matrices
 
 SKINNING = ("linear", "dual_quaternion")
@@ -142,15 +142,16 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 @torch.no_grad()
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
                  texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear",
-                 corrective_iterations=0, corrective_factor=0.5):
+                 corrective_iterations=0, corrective_factor=0.5, pixel_filter=None, filter_width=None):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
     weights)), skinning on the device, then the rasteriser of render_frames.  skinning: "linear"
     blends the joints' matrices (ops.skin_lbs, Blender's default), "dual_quaternion" their unit dual
     quaternions (ops.skin_dqs, Blender's "Preserve Volume": a twisted or bent limb keeps its
     radius); the weights are the same for both.  The skinned vertices never leave the device; the
     window is frame_window's rule on their bounding box over all frames (Blender uses the object's
-    bound_box).  texture, uvs, texture_filter, mip_coverage: as in render_frames (colours may be None
-    with a texture).  corrective_iterations N > 0 runs the corrective smoothing (delta mush,
+    bound_box).  texture, uvs, texture_filter, mip_coverage, pixel_filter, filter_width: as in
+    render_frames (colours may be None with a texture).
+    corrective_iterations N > 0 runs the corrective smoothing (delta mush,
     ops.corrective_smooth: N smoothing steps of strength corrective_factor, then the rest mesh's
     detail put back) on the skinned vertices of either blend: it repairs the creases that wrong or
     abruptly changing weights leave at a joint; the topology and the bind are computed once per call
@@ -166,7 +167,8 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
     tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
-    c = _vertex_colours(colours, len(v), bool(tex))
+    tex.update(_pixel_filter_args(pixel_filter, filter_width, ss))
+    c = _vertex_colours(colours, len(v), texture is not None)
     if weights is None:
         weights = bone_heat_weights(v, f, skeleton, K=K, device=device)
     infl, w = (to_np(a) for a in weights)

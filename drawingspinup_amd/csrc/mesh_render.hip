@@ -31,8 +31,17 @@
 // blends the bilinear reads of two neighbouring levels (mip_sample.h).  The view is orthographic and
 // uv is affine on a face, so the level is constant per (frame, face): it is computed where the
 // face's attributes are loaded.  The two levels of a face lie near each other in the buffer.
+//
+// Pixel filter (dsu_mesh_render_ortho_filtered): a pixel gathers the samples of its own square and of
+// `halo` sub-samples around it, weighted by a separable table the caller hands in (film_filter.h
+// holds the accumulation, for the kernel and for dsu_pixel_filter_resolve_host).  The workgroup's key
+// tile grows by hp = ceil(halo / ss) pixels on every side, (frame, triangle) pairs are binned onto
+// the grown tiles, and a sample's attributes are recomputed by every pixel that reaches it: staging
+// six f32 per sample of the grown tile would not fit beside the keys.  The kernels of the unfiltered
+// entry point are not touched by any of this.
 #include "common.h"
 #include "bin_sort.h"
+#include "film_filter.h"
 #include "mesh_geom.h"
 #include "mip_sample.h"
 
@@ -101,6 +110,30 @@ struct FrameTriangleTiles {
     const int T = RT_TILE * view.ss;
     for (int ty = r0 / T; ty <= r1 / T; ++ty)
       for (int tx = c0 / T; tx <= c1 / T; ++tx) emit((f * view.G + ty) * view.G + tx);
+  }
+};
+
+// The same pairs for the filtered resolve: every tile whose rectangle, grown by `grow` samples on each
+// side (hp pixels) and clipped to the frame, the triangle's sample range touches.
+struct FrameTriangleGrownTiles {
+  FrameTriangleTiles base;
+  int32_t grow;
+  __device__ __forceinline__ int32_t id(int64_t i) const { return base.id(i); }
+  template <class Emit>
+  __device__ __forceinline__ void bins(int64_t i, Emit emit) const {
+    const RenderView& view = base.view;
+    const int f = (int)(i / base.M);
+    const int64_t m = i - (int64_t)f * base.M;
+    int ia, ib, ic;
+    if (!face_indices(base.faces, m, base.V, ia, ib, ic)) return;
+    const TriXY t = load_xy(base.screen + (int64_t)f * base.V * 3, ia, ib, ic);
+    int c0, c1, r0, r1;
+    if (!sample_range(view, t, c0, c1, r0, r1)) return;
+    const int T = RT_TILE * view.ss;
+    const int ty0 = max(r0 - grow, 0) / T, ty1 = min((r1 + grow) / T, view.G - 1);
+    const int tx0 = max(c0 - grow, 0) / T, tx1 = min((c1 + grow) / T, view.G - 1);
+    for (int ty = ty0; ty <= ty1; ++ty)
+      for (int tx = tx0; tx <= tx1; ++tx) emit((f * view.G + ty) * view.G + tx);
   }
 };
 
@@ -356,6 +389,193 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_textured_kernel(
                                   n_items, tex, out);
 }
 
+// ---- the filtered resolve (include/dsu_hip.h, "Pixel filter")
+// The visibility loop, the face's attributes and the pixel's stores are written out again below, not
+// shared with raster_resolve_tile: with them factored into common functions the compiler unrolls and
+// schedules the twelve unfiltered kernels differently (up to four times the instructions at ss 4), and
+// those are to stay the code they were.
+struct FilmTaps {
+  double t[dsu_film::MAX_TAPS];   // ss + 2 halo of them
+  int32_t halo;
+};
+
+// The winning face of a sample and what the resolve reads of it: loaded when the face changes.
+template <int TEX>
+struct FaceAttributes {
+  uint32_t face = 0xffffffffu;
+  TriXY t = {};
+  float a0[6], a1[6], a2[6];
+  float ua = 0.0f, va = 0.0f, ub = 0.0f, vb = 0.0f, uc = 0.0f, vc = 0.0f;
+  int lod_k = 0, lod_at = 0;
+  double lod_t = 0.0;
+
+  __device__ __forceinline__ void load(uint32_t m, const float* __restrict__ sv, const int32_t* __restrict__ faces,
+                                       const float* __restrict__ colour, const float* __restrict__ pos, int64_t V,
+                                       const RenderView& view, const RenderTexture& tex) {
+    int ia, ib, ic;
+    face_indices(faces, m, V, ia, ib, ic);          // validated when the key was written
+    t = load_xy(sv, ia, ib, ic);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      if constexpr (TEX == TEX_NONE) {
+        a0[ch] = clamp01(colour[(int64_t)ia * 3 + ch]);
+        a1[ch] = clamp01(colour[(int64_t)ib * 3 + ch]);
+        a2[ch] = clamp01(colour[(int64_t)ic * 3 + ch]);
+      }
+      a0[3 + ch] = clamp01(pos[(int64_t)ia * 3 + ch]);
+      a1[3 + ch] = clamp01(pos[(int64_t)ib * 3 + ch]);
+      a2[3 + ch] = clamp01(pos[(int64_t)ic * 3 + ch]);
+    }
+    if constexpr (TEX != TEX_NONE) {
+      ua = tex.uv[(int64_t)ia * 2]; va = tex.uv[(int64_t)ia * 2 + 1];
+      ub = tex.uv[(int64_t)ib * 2]; vb = tex.uv[(int64_t)ib * 2 + 1];
+      uc = tex.uv[(int64_t)ic * 2]; vc = tex.uv[(int64_t)ic * 2 + 1];
+    }
+    if constexpr (TEX == TEX_TRILINEAR) {
+      const double rho = dsu_mip::footprint(t.ax, t.ay, t.bx, t.by, t.cx, t.cy, ua, va, ub, vb, uc, vc, tex.T,
+                                            view.span / (double)view.N);
+      dsu_mip::lod(rho, dsu_mip::levels(tex.T), lod_k, lod_t);
+      lod_at = (int)dsu_mip::level_offset(tex.T, lod_k);
+    }
+    face = m;
+  }
+
+  // the six f32 attributes of the sample at (x, y): the unfiltered resolve's per-sample values
+  __device__ __forceinline__ void at(double x, double y, const RenderTexture& tex, float s[6]) const {
+    constexpr int CH0 = TEX == TEX_NONE ? 0 : 3;
+    double w0, w1, w2;
+    edge_functions(t, x, y, w0, w1, w2);
+    const double area = w0 + w1 + w2;
+    if constexpr (TEX != TEX_NONE) {
+      const double u = (w0 * (double)ua + w1 * (double)ub + w2 * (double)uc) / area;
+      const double v = (w0 * (double)va + w1 * (double)vb + w2 * (double)vc) / area;
+      if constexpr (TEX == TEX_TRILINEAR)
+        dsu_mip::sample(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, lod_k, lod_t, lod_at, s);
+      else
+        sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, s);
+    }
+#pragma unroll
+    for (int ch = CH0; ch < 6; ++ch)
+      s[ch] = (float)((w0 * (double)a0[ch] + w1 * (double)a1[ch] + w2 * (double)a2[ch]) / area);
+  }
+};
+
+// One workgroup of four waves per (frame, tile), as above, over the tile grown by hp pixels per side.
+// Dynamic LDS: keys (TG^2) | xs (TG) | ys (TG) | taps (MAX_TAPS), TG = (16 + 2 hp) SS.
+template <int SS, int TEX>
+__global__ __launch_bounds__(256) void mesh_raster_resolve_filtered_kernel(
+    const float* __restrict__ screen, const int32_t* __restrict__ faces, const float* __restrict__ colour,
+    const float* __restrict__ pos, int64_t V, int64_t M, RenderView view, const int32_t* __restrict__ offsets,
+    const int32_t* __restrict__ items, int64_t n_items, RenderTexture tex, FilmTaps film, RenderOut out) {
+  extern __shared__ unsigned long long film_lds[];
+  constexpr int T = RT_TILE * SS;
+  const int halo = film.halo;
+  const int grow = dsu_film::halo_pixels(halo, SS) * SS;
+  const int TG = T + 2 * grow;
+  unsigned long long* keys = film_lds;
+  double* xs = reinterpret_cast<double*>(film_lds + TG * TG);
+  double* ys = xs + TG;
+  double* taps = ys + TG;
+  const int tid = threadIdx.x;
+  const int bin = blockIdx.x;
+  const int f = bin / (view.G * view.G);
+  const int ty = (bin - f * view.G * view.G) / view.G, tx = bin - (f * view.G + ty) * view.G;
+  const int R0 = ty * T - grow, C0 = tx * T - grow;   // first sample of the grown tile; may lie outside the frame
+  const float* __restrict__ sv = screen + (int64_t)f * V * 3;
+  for (int s = tid; s < TG * TG; s += 256) keys[s] = 0ull;
+  if (tid < TG) xs[tid] = lattice_x(view, C0 + tid);
+  else if (tid < 2 * TG) ys[tid - TG] = lattice_y(view, R0 + tid - TG);
+  if (tid == 255) {
+#pragma unroll
+    for (int k = 0; k < dsu_film::MAX_TAPS; ++k) taps[k] = film.t[k];
+  }
+  __syncthreads();
+
+  // ---- visibility over the grown tile (sample_range has clipped the triangle to the frame)
+  const int wave = tid >> 6, lane = tid & 63;
+  const int64_t beg = offsets[bin], end = min((int64_t)offsets[bin + 1], n_items);
+  for (int64_t k = max(beg, (int64_t)0) + wave; k < end; k += 4) {
+    const int m = items[k];
+    if (m < 0 || m >= M) continue;
+    int ia, ib, ic;
+    if (!face_indices(faces, m, V, ia, ib, ic)) continue;
+    const TriXY t = load_xy(sv, ia, ib, ic);
+    int c0, c1, r0, r1;
+    if (!sample_range(view, t, c0, c1, r0, r1)) continue;
+    c0 = max(c0, C0); r0 = max(r0, R0); c1 = min(c1, C0 + TG - 1); r1 = min(r1, R0 + TG - 1);
+    if (c1 < c0 || r1 < r0) continue;
+    const double za = sv[(int64_t)ia * 3 + 2], zb = sv[(int64_t)ib * 3 + 2], zc = sv[(int64_t)ic * 3 + 2];
+    const int w = c1 - c0 + 1, n = w * (r1 - r0 + 1);
+    const uint32_t low = ~(uint32_t)m;
+    for (int i = lane; i < n; i += 64) {
+      const int rr = i / w;
+      const int lr = r0 - R0 + rr, lc = c0 - C0 + (i - rr * w);
+      double w0, w1, w2;
+      edge_functions(t, xs[lc], ys[lr], w0, w1, w2);
+      const double area = w0 + w1 + w2;
+      if (area == 0.0 || !covers(w0, w1, w2)) continue;
+      float z = (float)((w0 * za + w1 * zb + w2 * zc) / area);
+      if (!(z == z)) continue;
+      if (z == 0.0f) z = 0.0f;                       // -0 and +0 are the same depth
+      atomicMax(&keys[lr * TG + lc], ((unsigned long long)ordered_bits(z) << 32) | low);
+    }
+  }
+  __syncthreads();
+
+  // ---- per-sample outputs: the tile's own samples, not the margin (its owners write those)
+  if (out.face_id || out.depth) {
+    for (int s = tid; s < T * T; s += 256) {
+      const int lr = s / T, lc = s - lr * T;
+      const int R = ty * T + lr, C = tx * T + lc;
+      if (R >= view.N || C >= view.N) continue;
+      const unsigned long long key = keys[(lr + grow) * TG + lc + grow];
+      const int64_t at = ((int64_t)f * view.N + R) * view.N + C;
+      if (out.face_id) out.face_id[at] = key ? (int32_t)~(uint32_t)key : -1;
+      if (out.depth) out.depth[at] = key ? ordered_float((uint32_t)(key >> 32)) : 0.0f;
+    }
+  }
+
+  // ---- resolve: one pixel per thread gathers its footprint (film_filter.h)
+  const int py = tid / RT_TILE, px = tid - py * RT_TILE;
+  const int Y = ty * RT_TILE + py, X = tx * RT_TILE + px;
+  if (Y >= view.S || X >= view.S) return;
+  FaceAttributes<TEX> face;
+  double alpha, v[6];
+  dsu_film::gather(taps, halo, SS, view.N, Y, X, [&](int R, int C, float s[6]) {
+    const int lr = R - R0, lc = C - C0;
+    const unsigned long long key = keys[lr * TG + lc];
+    if (!key) return false;
+    const uint32_t m = ~(uint32_t)key;
+    if (m != face.face) face.load(m, sv, faces, colour, pos, V, view, tex);
+    face.at(xs[lc], ys[lr], tex, s);
+    return true;
+  }, alpha, v);
+  const uint32_t a8 = dsu_film::quantise(alpha);
+  uint32_t q[6];
+#pragma unroll
+  for (int ch = 0; ch < 6; ++ch) q[ch] = dsu_film::quantise(v[ch]);
+  const int64_t pix = ((int64_t)f * view.S + Y) * view.S + X;
+  if (out.color_u8)
+    reinterpret_cast<uint32_t*>(out.color_u8)[pix] = q[0] | (q[1] << 8) | (q[2] << 16) | (a8 << 24);
+  if (out.pos_u8)
+    reinterpret_cast<uint32_t*>(out.pos_u8)[pix] = q[3] | (q[4] << 8) | (q[5] << 16) | (a8 << 24);
+  if (out.pixels) {
+    float4* p = reinterpret_cast<float4*>(out.pixels) + pix * 2;
+    p[0] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)alpha);
+    p[1] = make_float4((float)v[3], (float)v[4], (float)v[5], (float)alpha);
+  }
+  if (out.frames) {                                  // the DatasetFullImages tensor, as in the unfiltered resolve
+    const int64_t plane = (int64_t)view.S * view.S;
+    float* fr = out.frames + (int64_t)f * 6 * plane + (int64_t)Y * view.S + X;
+    fr[0] = ((float)q[0] / 255.0f - 0.5f) / 0.5f;
+    fr[plane] = ((float)q[1] / 255.0f - 0.5f) / 0.5f;
+    fr[2 * plane] = ((float)q[2] / 255.0f - 0.5f) / 0.5f;
+    fr[3 * plane] = (float)a8 / 255.0f;
+    fr[4 * plane] = ((float)q[3] / 255.0f - 0.5f) / 0.5f;
+    fr[5 * plane] = ((float)q[4] / 255.0f - 0.5f) / 0.5f;
+  }
+}
+
 // pos2edge (run_render.py:31-57) + the inversion of :120 on the RGBA8 position image: channels
 // u8 -> f32 / 255, every channel 2 where alpha8 < 255 (alpha < 1), 3x3 Sobel per channel in
 // float64 (cv2.Sobel(..., CV_64F, ksize=3), default border BORDER_REFLECT_101), magnitude, maximum
@@ -437,7 +657,78 @@ struct RasterCall {
     else if (ss == 2) go<2, TEX>();
     else go<4, TEX>();
   }
+
+  // the filtered resolve of the same pair; at most 52 640 B of dynamic LDS (ss 4, halo 8)
+  template <int SS, int TEX>
+  void go_filtered(const FilmTaps& film) const {
+    const int TG = (RT_TILE + 2 * dsu_film::halo_pixels(film.halo, SS)) * SS;
+    const size_t lds = sizeof(double) * ((size_t)TG * TG + 2 * TG + dsu_film::MAX_TAPS);
+    mesh_raster_resolve_filtered_kernel<SS, TEX><<<bins, 256, lds, st>>>(screen, faces, colour, pos, V, M, view,
+                                                                         offsets, items, n_items, tex, film, out);
+  }
+  template <int TEX>
+  void launch_filtered(int ss, const FilmTaps& film) const {
+    if (ss == 1) go_filtered<1, TEX>(film);
+    else if (ss == 2) go_filtered<2, TEX>(film);
+    else go_filtered<4, TEX>(film);
+  }
 };
+
+// Both entry points.  filtered == false is dsu_mesh_render_ortho: taps and halo are not looked at.
+int render_ortho(bool filtered, int32_t stage, const float* screen, const int32_t* faces, const float* colour,
+                 const float* pos, const dsu_render_texture* tex, int32_t n_frames, int64_t n_verts,
+                 int64_t n_faces, double cx, double cy, double span, int32_t size, int32_t ss, const double* taps,
+                 int32_t halo, void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
+                 const RenderOut& out, void* stream) {
+  if (stage < DSU_RENDER_COUNT || stage > DSU_RENDER_RASTER) return DSU_EINVAL;
+  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
+  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
+      n_verts > (int64_t)1 << 30)
+    return DSU_EINVAL;
+  if (filtered && (halo < 0 || halo > 2 * ss)) return DSU_EINVAL;
+  const int64_t nb = bins_of(n_frames, size);
+  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
+  if (n_faces && (!screen || !faces || n_verts == 0)) return DSU_EINVAL;
+  if (stage != DSU_RENDER_COUNT && n_items && !items) return DSU_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
+  if (stage != DSU_RENDER_RASTER) {
+    const FrameTriangleTiles tiles{screen, faces, n_verts, n_faces, view};
+    const int64_t n = (int64_t)n_frames * n_faces;
+    if (!filtered) return dsu_bin::run_stage(stage, tiles, n, workspace, nb, items, n_items, st);
+    return dsu_bin::run_stage(stage, FrameTriangleGrownTiles{tiles, dsu_film::halo_pixels(halo, ss) * ss}, n,
+                              workspace, nb, items, n_items, st);
+  }
+  if (n_faces && !pos) return DSU_EINVAL;
+  if (tex ? !texture_ok(*tex) : (n_faces && !colour)) return DSU_EINVAL;
+  if (filtered && !dsu_film::taps_ok(taps, halo, ss)) return DSU_EINVAL;
+  const RasterCall call{(unsigned)nb, st, screen, faces, colour, pos, n_verts, n_faces, view,
+                        dsu_bin::split(workspace, nb).offsets, items, n_faces ? n_items : 0,
+                        tex ? RenderTexture{tex->uv, reinterpret_cast<const uint32_t*>(tex->texels), tex->tex_size}
+                            : RenderTexture{nullptr, nullptr, 0},
+                        out};
+  const int source = tex ? tex->filter : TEX_NONE;
+  if (!filtered) {
+    switch (source) {   // source first, then ss: the order the kernels have in the code object
+      case TEX_NONE: call.launch<TEX_NONE>(ss); break;
+      case TEX_NEAREST: call.launch<TEX_NEAREST>(ss); break;
+      case TEX_BILINEAR: call.launch<TEX_BILINEAR>(ss); break;
+      case TEX_TRILINEAR: call.launch<TEX_TRILINEAR>(ss); break;
+    }
+  } else {
+    FilmTaps film = {};
+    for (int k = 0; k < ss + 2 * halo; ++k) film.t[k] = taps[k];
+    film.halo = halo;
+    switch (source) {
+      case TEX_NONE: call.launch_filtered<TEX_NONE>(ss, film); break;
+      case TEX_NEAREST: call.launch_filtered<TEX_NEAREST>(ss, film); break;
+      case TEX_BILINEAR: call.launch_filtered<TEX_BILINEAR>(ss, film); break;
+      case TEX_TRILINEAR: call.launch_filtered<TEX_TRILINEAR>(ss, film); break;
+    }
+  }
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
 
 }  // namespace
 
@@ -454,34 +745,60 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
                           double span, int32_t size, int32_t ss, void* workspace, int64_t workspace_bytes,
                           int32_t* items, int64_t n_items, uint8_t* color_u8, uint8_t* pos_u8,
                           int32_t* face_id, float* depth, float* frames, float* pixels, void* stream) {
-  if (stage < DSU_RENDER_COUNT || stage > DSU_RENDER_RASTER) return DSU_EINVAL;
-  if (!view_ok(n_frames, size, ss, span) || !(cx == cx) || !(cy == cy)) return DSU_EINVAL;
-  if (n_verts < 0 || n_faces < 0 || n_items < 0 || (int64_t)n_frames * n_faces > (int64_t)1 << 31 ||
-      n_verts > (int64_t)1 << 30)
-    return DSU_EINVAL;
-  const int64_t nb = bins_of(n_frames, size);
-  if (!workspace || workspace_bytes < dsu_bin::bytes(nb)) return DSU_EINVAL;
-  if (n_faces && (!screen || !faces || n_verts == 0)) return DSU_EINVAL;
-  if (stage != DSU_RENDER_COUNT && n_items && !items) return DSU_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  RenderView view{cx, cy, span, size, ss, size * ss, (size + RT_TILE - 1) / RT_TILE};
-  if (stage != DSU_RENDER_RASTER)
-    return dsu_bin::run_stage(stage, FrameTriangleTiles{screen, faces, n_verts, n_faces, view},
-                              (int64_t)n_frames * n_faces, workspace, nb, items, n_items, st);
-  if (n_faces && !pos) return DSU_EINVAL;
-  if (tex ? !texture_ok(*tex) : (n_faces && !colour)) return DSU_EINVAL;
-  const RasterCall call{(unsigned)nb, st, screen, faces, colour, pos, n_verts, n_faces, view,
-                        dsu_bin::split(workspace, nb).offsets, items, n_faces ? n_items : 0,
-                        tex ? RenderTexture{tex->uv, reinterpret_cast<const uint32_t*>(tex->texels), tex->tex_size}
-                            : RenderTexture{nullptr, nullptr, 0},
-                        RenderOut{color_u8, pos_u8, face_id, depth, frames, pixels}};
-  switch (tex ? tex->filter : TEX_NONE) {   // source first, then ss: the order the kernels have in the code object
-    case TEX_NONE: call.launch<TEX_NONE>(ss); break;
-    case TEX_NEAREST: call.launch<TEX_NEAREST>(ss); break;
-    case TEX_BILINEAR: call.launch<TEX_BILINEAR>(ss); break;
-    case TEX_TRILINEAR: call.launch<TEX_TRILINEAR>(ss); break;
+  return render_ortho(false, stage, screen, faces, colour, pos, tex, n_frames, n_verts, n_faces, cx, cy, span, size,
+                      ss, nullptr, 0, workspace, workspace_bytes, items, n_items,
+                      RenderOut{color_u8, pos_u8, face_id, depth, frames, pixels}, stream);
+}
+
+int dsu_mesh_render_ortho_filtered(int32_t stage, const float* screen, const int32_t* faces, const float* colour,
+                                   const float* pos, const dsu_render_texture* tex, int32_t n_frames,
+                                   int64_t n_verts, int64_t n_faces, double cx, double cy, double span,
+                                   int32_t size, int32_t ss, const double* taps, int32_t halo, void* workspace,
+                                   int64_t workspace_bytes, int32_t* items, int64_t n_items, uint8_t* color_u8,
+                                   uint8_t* pos_u8, int32_t* face_id, float* depth, float* frames, float* pixels,
+                                   void* stream) {
+  return render_ortho(true, stage, screen, faces, colour, pos, tex, n_frames, n_verts, n_faces, cx, cy, span, size,
+                      ss, taps, halo, workspace, workspace_bytes, items, n_items,
+                      RenderOut{color_u8, pos_u8, face_id, depth, frames, pixels}, stream);
+}
+
+// HOST: the filtered resolve evaluated on the CPU by the text the kernel compiles (film_filter.h) —
+// colour, pos (F,N,N,3) f32 and covered (F,N,N) u8 per sample, N = size ss; every array is host memory.
+int dsu_pixel_filter_resolve_host(const float* colour, const float* pos, const uint8_t* covered, int32_t n_frames,
+                                  int32_t size, int32_t ss, const double* taps, int32_t halo, float* pixels,
+                                  uint8_t* color_u8, uint8_t* pos_u8) {
+  if (!view_ok(n_frames, size, ss, 1.0) || !colour || !pos || !covered) return DSU_EINVAL;
+  if (!dsu_film::taps_ok(taps, halo, ss)) return DSU_EINVAL;
+  const int N = size * ss;
+  for (int f = 0; f < n_frames; ++f) {
+    const int64_t base = (int64_t)f * N * N;
+    for (int i = 0; i < size; ++i)
+      for (int j = 0; j < size; ++j) {
+        double alpha, v[6];
+        dsu_film::gather(taps, halo, ss, N, i, j, [&](int R, int C, float s[6]) {
+          const int64_t at = base + (int64_t)R * N + C;
+          if (!covered[at]) return false;
+          for (int ch = 0; ch < 3; ++ch) {
+            s[ch] = colour[at * 3 + ch];
+            s[3 + ch] = pos[at * 3 + ch];
+          }
+          return true;
+        }, alpha, v);
+        const int64_t pix = ((int64_t)f * size + i) * size + j;
+        const uint8_t a8 = (uint8_t)dsu_film::quantise(alpha);
+        for (int ch = 0; ch < 3; ++ch) {
+          if (pixels) {
+            pixels[pix * 8 + ch] = (float)v[ch];
+            pixels[pix * 8 + 4 + ch] = (float)v[3 + ch];
+          }
+          if (color_u8) color_u8[pix * 4 + ch] = (uint8_t)dsu_film::quantise(v[ch]);
+          if (pos_u8) pos_u8[pix * 4 + ch] = (uint8_t)dsu_film::quantise(v[3 + ch]);
+        }
+        if (pixels) pixels[pix * 8 + 3] = pixels[pix * 8 + 7] = (float)alpha;
+        if (color_u8) color_u8[pix * 4 + 3] = a8;
+        if (pos_u8) pos_u8[pix * 4 + 3] = a8;
+      }
   }
-  DSU_CHECK_LAUNCH();
   return DSU_OK;
 }
 

@@ -89,6 +89,7 @@ class DrawingPipeline:
             raise ValueError("frames: 'synthetic' or 'rendered'")
         self.frames = frames                 # what stage 3 stylises: synthetic maps, or the mesh rendered
         self.render_ss = 4                   # sub-samples per pixel side of the rendered frames
+        self.render_filter = None            # their pixel filter (animate.render_frames' pixel_filter); None = box
         self.device = torch.device(device)
         self.mv_steps, self.nsr_steps, self.n_frames = mv_steps, nsr_steps, n_frames
         self.guidance_scale = guidance_scale  # the multi-view pipeline's; 1.0 (the shipped YAML) = no guidance
@@ -324,7 +325,8 @@ class DrawingPipeline:
             return None
         from . import animate
         r = animate.render_frames(mesh_post["verts"], mesh_post["faces"], mesh_post["colors"], "rest_rotate",
-                                  ss=self.render_ss, n_frames=self.n_frames, device=self.device)
+                                  ss=self.render_ss, n_frames=self.n_frames, device=self.device,
+                                  pixel_filter=self.render_filter)
         return r["frames"], r["edge"]
 
     def run(self, seed, drawing=None):

@@ -32,6 +32,12 @@ modifier; animate_mesh(corrective_iterations=N)) on the skinned vertices of ever
 abruptly changing weights are smoothed out and the rest mesh's detail is put back.  The bind is
 recomputed per run (one frame's worth of work); `skin_weights.npz` is neither read differently nor
 rewritten.  0 (default) is off; rest_pose and rest_rotate are rigid and are not touched.
+
+`--pixel_filter eevee` or `cycles` reconstructs every pixel with the Blackman-Harris window of that
+engine of the reference's `--engine_type` (animate.pixel_filter; the widths, 3.0 and 1.5 px, are read
+from Blender's source and not pinned against it), `blackman_harris` with `--filter_width W` pixels
+any other width, `box` the default rule through the filtered kernel.  It applies to every action and
+every `--texture` mode.  Without the flag a pixel is the box over its own sub-samples, as before.
 """
 import argparse
 import glob
@@ -103,6 +109,10 @@ def run(argv=None):
                     help="corrective smoothing (delta mush) of the BVH actions: N smoothing steps, 0..255 (0: off)")
     ap.add_argument("--corrective_factor", type=float, default=0.5,
                     help="strength of one corrective smoothing step, in [0, 1]")
+    ap.add_argument("--pixel_filter", default=None, choices=list(animate.render.PIXEL_FILTERS),
+                    help="reconstruction filter of a pixel (default: the box over its own sub-samples)")
+    ap.add_argument("--filter_width", type=float, default=None, metavar="W",
+                    help="total support of --pixel_filter in pixels (blackman_harris needs it; it overrides a preset's)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     try:
@@ -111,6 +121,11 @@ def run(argv=None):
         ap.error(str(e))
     if args.fps is not None and not args.fps > 0:
         ap.error("--fps must be positive")
+    try:
+        animate.render._pixel_filter_args(args.pixel_filter, args.filter_width, args.ss)
+    except ValueError as e:
+        ap.error(str(e))
+    flt = {} if args.pixel_filter is None else dict(pixel_filter=args.pixel_filter, filter_width=args.filter_width)
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
     if not found:
         raise FileNotFoundError(f"no OBJ under {os.path.join(args.data_dir, args.uid, 'mesh')}")
@@ -130,7 +145,7 @@ def run(argv=None):
         start = time.time()
         if clip_path is None:
             rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
-                                             device=args.device, **tex)
+                                             device=args.device, **tex, **flt)
         else:
             skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
             weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
@@ -139,7 +154,7 @@ def run(argv=None):
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
                                             ss=args.ss, device=args.device, skinning=args.skinning,
                                             corrective_iterations=args.corrective_smooth,
-                                            corrective_factor=args.corrective_factor, **tex)
+                                            corrective_factor=args.corrective_factor, **tex, **flt)
         n = write_frames(out_dir, rendered)
         print((time.time() - start) / n, n)
     return out_dir, rendered

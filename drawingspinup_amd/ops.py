@@ -1461,11 +1461,14 @@ TEXTURE_FILTERS = {k: _lib.DEFINES["DSU_TEX_" + k.upper()] for k in ("nearest", 
 class MeshRenderPlan(_BinnedPlan):
     """The binning half of dsu_mesh_render_ortho for one (screen, faces, window): (frame, triangle)
     pairs counted per 16x16-pixel tile, the prefix sum (torch), the triangle ids filled in.
-    screen (F,V,3) f32, faces (M,3) i32 on the device; size a multiple of 4 (<= 2048), ss 1 | 2 | 4."""
+    screen (F,V,3) f32, faces (M,3) i32 on the device; size a multiple of 4 (<= 2048), ss 1 | 2 | 4.
+    halo: the reach of the pixel filter the plan will be rastered with, in sub-samples (0 .. 2 ss;
+    animate.pixel_filter gives it with the taps): the tiles are grown by it when the pairs are listed."""
     COUNT, FILL = RENDER_COUNT, RENDER_FILL
 
-    def __init__(self, screen, faces, cx, cy, span, size, ss):
+    def __init__(self, screen, faces, cx, cy, span, size, ss, halo=0):
         self.screen, self.faces = _f32c(screen), faces.to(torch.int32).contiguous()
+        self.halo = int(halo)                         # of the pixel filter, in sub-samples: the tiles grow by it
         if self.screen.dim() != 3 or self.screen.shape[2] != 3 or self.faces.dim() != 2:
             raise ValueError("screen (F,V,3) and faces (M,3) expected")
         self.F, self.V, self.M = self.screen.shape[0], self.screen.shape[1], self.faces.shape[0]
@@ -1474,15 +1477,20 @@ class MeshRenderPlan(_BinnedPlan):
         self._alloc(lib().dsu_mesh_render_ortho_workspace_bytes(self.F, self.size),
                     "dsu_mesh_render_ortho_workspace_bytes", self.screen.device)
 
-    def _stage(self, stage, colour=None, pos=None, tex=None, outs=(None,) * 6):
-        check(lib().dsu_mesh_render_ortho(
-            stage, ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), ptr(colour), ptr(pos),
-            None if tex is None else C.byref(tex),
-            self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss,
-            *self._bin_args(), *[ptr(o) for o in outs], stream()), "dsu_mesh_render_ortho")
+    def _stage(self, stage, colour=None, pos=None, tex=None, outs=(None,) * 6, taps=None):
+        head = (stage, ptr(self.screen, torch.float32), ptr(self.faces, torch.int32), ptr(colour), ptr(pos),
+                None if tex is None else C.byref(tex),
+                self.F, self.V, self.M, self.cx, self.cy, self.span, self.size, self.ss)
+        tail = (*self._bin_args(), *[ptr(o) for o in outs], stream())
+        if taps is None and self.halo == 0:           # the unfiltered entry point; its bins are those of halo 0
+            check(lib().dsu_mesh_render_ortho(*head, *tail), "dsu_mesh_render_ortho")
+        else:                                         # taps: a host table, read at RASTER only
+            check(lib().dsu_mesh_render_ortho_filtered(
+                *head, None if taps is None else taps.ctypes.data_as(C.c_void_p), self.halo, *tail),
+                "dsu_mesh_render_ortho_filtered")
 
     def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames"), uv=None, texture=None,
-               filter="bilinear", pyramid=None):
+               filter="bilinear", pyramid=None, taps=None):
         """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
         (F,S,S,4) uint8, face_id (F,N,N) i32, depth (F,N,N) f32, frames (F,6,S,S) f32, pixels
         (F,S,S,8) f32.
@@ -1492,9 +1500,22 @@ class MeshRenderPlan(_BinnedPlan):
         "nearest") and `colour` may be None; without them this is the vertex-colour call.
         filter "trilinear" reads the texture's mip pyramid: `pyramid`, a
         MipPyramid of this texture from mip_pyramid(), or None to build it here with every texel
-        covered and the default gutter."""
+        covered and the default gutter.
+
+        taps: None = the box over a pixel's own samples (dsu_mesh_render_ortho); otherwise the
+        ss + 2 halo float64 taps of a separable pixel filter (animate.pixel_filter) for the halo this
+        plan was binned with (dsu_mesh_render_ortho_filtered)."""
         if self.items is None:
             raise DsuError("MeshRenderPlan.raster before bin()")
+        if taps is None:
+            if self.halo:
+                raise ValueError(f"this plan was binned for a pixel filter of halo {self.halo}: taps are needed")
+        else:
+            import numpy as np
+            taps = np.ascontiguousarray(taps, np.float64).reshape(-1)
+            if len(taps) != self.ss + 2 * self.halo:
+                raise ValueError(f"{len(taps)} taps do not belong to ss {self.ss} and the halo {self.halo} this plan "
+                                 f"was binned with ({self.ss + 2 * self.halo} expected)")
         if (uv is None) != (texture is None) or (texture is None and (filter == MIP_TRILINEAR or pyramid is not None)):
             raise ValueError("uv and texture come together or not at all (and a trilinear read needs both)")
         F, S, N, dev = self.F, self.size, self.size * self.ss, self.screen.device
@@ -1530,7 +1551,7 @@ class MeshRenderPlan(_BinnedPlan):
             colour = None                             # not read
             tex = _lib.RenderTexture(ptr(uv), ptr(texels, torch.uint8), T, TEXTURE_FILTERS[filter])
         out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
-        self._stage(RENDER_RASTER, colour, pos, tex, [out.get(k) for k in shapes])
+        self._stage(RENDER_RASTER, colour, pos, tex, [out.get(k) for k in shapes], taps)
         return out
 
 
@@ -1589,13 +1610,15 @@ def mip_pyramid(texture, covered=None, gutter=2):
 
 def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
                       want=("color_u8", "pos_u8", "frames"), uv=None, texture=None, filter="bilinear",
-                      pyramid=None):
+                      pyramid=None, pixel_filter=None):
     """Orthographic render of F frames of one mesh with two attribute sets (include/dsu_hip.h,
     dsu_mesh_render_ortho): bin, then rasterise and resolve.  The colours are the vertex colours,
     or with uv and texture the texture's (filter "trilinear": its mip `pyramid`, built from the
-    texture when None)."""
-    return MeshRenderPlan(screen, faces, cx, cy, span, size, ss).bin().raster(colour, pos, want, uv, texture,
-                                                                              filter, pyramid)
+    texture when None).  pixel_filter: None = the box over a pixel's own samples, or the (taps, halo)
+    of animate.pixel_filter for this ss (dsu_mesh_render_ortho_filtered)."""
+    taps, halo = (None, 0) if pixel_filter is None else pixel_filter
+    return MeshRenderPlan(screen, faces, cx, cy, span, size, ss, halo).bin().raster(colour, pos, want, uv, texture,
+                                                                                    filter, pyramid, taps)
 
 
 def pos_edge_u8(pos_rgba):

@@ -1088,7 +1088,9 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
  * face index.  The attributes of the winning face are (w0 va + w1 vb + w2 vc) / area per sample
  * (rounded to f32).  Per pixel over its ss^2 samples: alpha = covered / ss^2, rgb = the float64
  * mean over the covered samples in row-major order (straight alpha; 0 where nothing is covered),
- * uint8 = floor(v * 255 + 0.5).  No products are fused.
+ * uint8 = floor(v * 255 + 0.5).  No products are fused.  This box over the pixel's own samples stands
+ * in for Blender's pixel filter; dsu_mesh_render_ortho_filtered ("Pixel filter" below) puts a
+ * reconstruction window that reaches into the neighbouring pixels in its place.
  *
  * Outputs, each optional (NULL): color_u8, pos_u8 (n_frames, size, size, 4) RGBA; face_id
  * (n_frames, N, N) i32, -1 = empty; depth (n_frames, N, N) f32, 0 where empty; frames
@@ -1213,6 +1215,58 @@ int dsu_mip_pyramid_build(const uint8_t* texture, const uint8_t* covered, int32_
                           uint8_t* pyramid, void* workspace, int64_t workspace_bytes, void* stream);
 int dsu_mip_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tx, const double* ty,
                         const double* rho, int64_t n, float* rgb_out);
+/* Pixel filter: dsu_mesh_render_ortho_filtered is dsu_mesh_render_ortho with the reconstruction
+ * filter of the reference's renderer in the resolve (Blender's EEVEE and Cycles weight the samples
+ * of a pixel with a Blackman-Harris window that reaches beyond the pixel's own square) where
+ * dsu_mesh_render_ortho has a box over the pixel's own ss^2 samples.  The arguments are those of
+ * dsu_mesh_render_ortho with `taps` and `halo` after ss; the three stages, the workspace and
+ * dsu_mesh_render_ortho_workspace_bytes are the same; dsu_mesh_render_ortho itself is unchanged.
+ *
+ * The library calls no transcendental: the caller hands in the 1-D window as a table (HOST memory),
+ * so host and device agree bit for bit and any separable window is the caller's matter
+ * (animate.pixel_filter makes the tables).  taps holds ss + 2 halo f64 values; halo is counted in
+ * sub-samples, 0 <= halo <= 2 ss.  Tap index q + halo belongs to sub-sample offset q in
+ * [-halo, ss + halo) from the pixel's first sample; its distance from the pixel centre is
+ * d_q = (q + 0.5) / ss - 0.5 px.
+ *
+ * Rule.  Visibility and the per-sample attributes v (f32: the interpolated vertex colour, or the
+ * nearest, bilinear or trilinear read; the interpolated position) are those of dsu_mesh_render_ortho.
+ * For pixel (i, j): rows R = i ss + qy, columns C = j ss + qx.  A sample with R or C outside [0, N)
+ * does not exist and enters no sum: the weights are renormalised at the image border.  The samples
+ * are walked row-major over (qy, qx), everything in float64, no products fused:
+ *     w = taps[qy + halo] * taps[qx + halo];   W_all += w;
+ *     covered sample:  W_cov += w,  A_ch += w * (double)v_ch  for the six channels;
+ *     alpha = W_cov / W_all;   channel = W_cov > 0 ? A_ch / W_cov : 0;
+ * both rounded to f32 in `pixels`; uint8 = floor(v 255 + 0.5) of the float64 values, `frames` from the
+ * uint8 values, as in dsu_mesh_render_ortho.  face_id and depth are per sample and do not depend on
+ * the filter.  With halo = 0 and all taps 1.0 every output is byte-equal to dsu_mesh_render_ortho.
+ * A pixel all of whose existing samples are covered has alpha exactly 1 (W_cov and W_all are the
+ * same sum), which is what pos2edge asks of the interior.
+ *
+ * hp = ceil(halo / ss).  COUNT / FILL list a (frame, triangle) pair in every tile whose 16x16-pixel
+ * rectangle, grown by hp pixels and clipped to the image, the triangle's sample range touches; RASTER
+ * keeps the keys of the grown tile, ((16 + 2 hp) ss)^2 of them, in LDS (at most 51 200 B).  halo is
+ * read at all three stages and must be the same in each; taps is read at RASTER only.
+ * DSU_EINVAL before any launch: everything dsu_mesh_render_ortho refuses; halo out of range (every
+ * stage); at RASTER taps NULL, a tap negative or not finite, the ss central taps summing to 0.
+ *
+ * dsu_pixel_filter_resolve_host: HOST function on HOST arrays — the accumulation above evaluated on
+ * the CPU by the text the kernel compiles (csrc/film_filter.h), from per-sample colour and pos
+ * (n_frames, N, N, 3) f32 and covered (n_frames, N, N) u8, N = size ss.  Outputs, each optional:
+ * pixels (n_frames, size, size, 8) f32, color_u8 and pos_u8 (n_frames, size, size, 4).  The inputs
+ * are any f32: a uint8 is 0 for a value that is not a number and clamped to 0..255 otherwise (on the
+ * device every v lies in [0, 1]).  DSU_EINVAL: n_frames, size or ss out of dsu_mesh_render_ortho's
+ * range, an input NULL, taps or halo as above. */
+int dsu_mesh_render_ortho_filtered(int32_t stage, const float* screen, const int32_t* faces,
+                                   const float* colour, const float* pos, const dsu_render_texture* tex,
+                                   int32_t n_frames, int64_t n_verts, int64_t n_faces, double cx, double cy,
+                                   double span, int32_t size, int32_t ss, const double* taps, int32_t halo,
+                                   void* workspace, int64_t workspace_bytes, int32_t* items, int64_t n_items,
+                                   uint8_t* color_u8, uint8_t* pos_u8, int32_t* face_id, float* depth,
+                                   float* frames, float* pixels, void* stream);
+int dsu_pixel_filter_resolve_host(const float* colour, const float* pos, const uint8_t* covered,
+                                  int32_t n_frames, int32_t size, int32_t ss, const double* taps, int32_t halo,
+                                  float* pixels, uint8_t* color_u8, uint8_t* pos_u8);
 /* pos2edge (run_render.py:31-57) and the inversion of run_render.py:120 on RGBA8 position images
  * (n_frames, H, W, 4): channels u8 -> f32 / 255, every channel 2 where alpha8 < 255, per-channel 3x3
  * Sobel in float64 with reflect-101 borders, magnitude, maximum over the three colour channels,
