@@ -38,7 +38,10 @@ that blender_animation.py:17-18 applies to two named clips is not restated.  FBX
 frame rate (slerp of the local rotations).  `animate_mesh(corrective_iterations=N)` smooths the
 skinned frames and puts the rest mesh's detail back (delta mush, Blender's Corrective Smooth;
 `smoothing_topology` builds the welded graph it walks): it repairs creases from bad weights, not the
-collapse of a twisted limb.
+collapse of a twisted limb.  `animate_mesh(skinning="centre_of_rotation")` rotates every vertex about
+its own centre of rotation (Le & Hodgins 2016; `cor_centres` computes them once per character, a sum
+over all vertex-triangle pairs on the device): the radius is kept as with dual quaternions, without
+their bulge on the outside of a sharp bend.
 """
 from .render import (DEFAULT_SIZE, DEFAULT_SPAN, PIXEL_FILTER_PRESETS, frame_window, motion_frames, pixel_filter,
                      position_colours, read_obj, read_obj_textured, render_frames, rest_pose, rest_rotate)
@@ -46,8 +49,8 @@ from .skeleton import (Clip, Skeleton, dual_quaternions, fit_to_mesh, quaternion
                        rest_clip, rotation_quaternions, skinning_matrices)
 from . import corrective
 from .corrective import smoothing_topology
-from .skin import animate_mesh, bone_heat_weights
+from .skin import animate_mesh, bone_heat_weights, cor_centres
 
-__all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "dual_quaternions", "fit_to_mesh",
+__all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "cor_centres", "dual_quaternions", "fit_to_mesh",
            "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "PIXEL_FILTER_PRESETS", "frame_window", "motion_frames", "pixel_filter", "position_colours",
            "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate", "smoothing_topology"]

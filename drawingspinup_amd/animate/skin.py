@@ -15,9 +15,10 @@ from .. import ops
 from ..nsr.thinning import _weld, cotmatrix
 from .corrective import check_parameters, smoothing_topology
 from .render import _pixel_filter_args, _texture_args, _vertex_colours, frame_window, position_colours
-from .skeleton import dual_quaternions, skinning_matrices
+from .skeleton import dual_quaternions, rotation_quaternions, skinning_matrices
 
-SKINNING = ("linear", "dual_quaternion")
+SKINNING = ("linear", "dual_quaternion", "centre_of_rotation")
+COR_SIGMA = 0.1      # width of the weight similarity of the centres of rotation (Le & Hodgins 2016)
 NEAR = 1e-4          # bones within (1 + NEAR) of the nearest visible one share a vertex's heat
 D_FLOOR = 1e-6       # d_i is taken no smaller than this fraction of the bounding-box diagonal
 
@@ -140,14 +141,41 @@ def bone_heat_weights(verts, faces, skeleton, K=4, device="cuda", tol=1e-10, max
 
 
 @torch.no_grad()
+def cor_centres(verts, faces, weights, n_joints, device="cuda", sigma=COR_SIGMA):
+    """The centres of rotation of a rigged mesh (ops.skin_cor_centres; Le & Hodgins, "Real-time
+    skeletal skinning with optimized centers of rotation", 2016), once per character: for every
+    vertex the area-weighted mean of the centroids of the triangles whose weights resemble its own,
+    a sum over all (vertex, triangle) pairs on the device.  verts (V,3), faces (T,3) 0-based, weights
+    = (influences, weights) as bone_heat_weights returns them, n_joints of the skeleton.
+    -> (centres (V,3) float64, valid (V,) uint8) on the device; a vertex on one joint alone has none
+    (valid 0) and is blended linearly.  They depend on the rest mesh and the weights only, so one
+    result serves every clip: animate_mesh(centres=...)."""
+    dev = torch.device(device)
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    v = to_np(verts).astype(np.float32).reshape(-1, 3)
+    f = to_np(faces).astype(np.int32).reshape(-1, 3)
+    infl, w = (to_np(a) for a in weights)
+    return ops.skin_cor_centres(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev), infl, w, int(n_joints),
+                                sigma=float(sigma))
+
+
+@torch.no_grad()
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
                  texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear",
-                 corrective_iterations=0, corrective_factor=0.5, pixel_filter=None, filter_width=None):
+                 corrective_iterations=0, corrective_factor=0.5, pixel_filter=None, filter_width=None,
+                 centres=None, cor_sigma=COR_SIGMA):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
     weights)), skinning on the device, then the rasteriser of render_frames.  skinning: "linear"
     blends the joints' matrices (ops.skin_lbs, Blender's default), "dual_quaternion" their unit dual
     quaternions (ops.skin_dqs, Blender's "Preserve Volume": a twisted or bent limb keeps its
-    radius); the weights are the same for both.  The skinned vertices never leave the device; the
+    radius), "centre_of_rotation" the joints' rotation quaternions about a centre of rotation per
+    vertex that itself moves by the linear blend (ops.skin_cor, Le & Hodgins 2016: the radius is kept
+    and the outside of a sharp bend does not bulge); the weights are the same for all three.
+    centres: the (centres, valid) of cor_centres for this mesh and these weights; None computes them
+    with cor_sigma (once per call), and the result carries them as `cor_centres` for the next clip.
+    The other blends ignore both.  Under a rest clip a vertex with a centre returns its rest position
+    bit for bit; one without (a single joint, or joints no triangle shares) takes the linear blend.
+    The skinned vertices never leave the device; the
     window is frame_window's rule on their bounding box over all frames (Blender uses the object's
     bound_box).  texture, uvs, texture_filter, mip_coverage, pixel_filter, filter_width: as in
     render_frames (colours may be None with a texture).
@@ -158,7 +186,8 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     from the rest mesh, and window and `vertices` are taken from the corrected tensor.  0 (default)
     is off.
 
-    Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor."""
+    Returns the dictionary of render_frames plus `vertices`, the (F,V,3) device tensor (and
+    `cor_centres` with skinning="centre_of_rotation")."""
     if skinning not in SKINNING:
         raise ValueError(f"skinning {skinning!r}: one of {SKINNING}")
     check_parameters(corrective_iterations, corrective_factor)
@@ -177,8 +206,15 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     if skinning == "linear":
         mats = skinning_matrices(skeleton, clip).astype(np.float32)
         screen = ops.skin_lbs(rest, ti, tw, torch.from_numpy(mats).to(dev))
-    else:
+    elif skinning == "dual_quaternion":
         screen = ops.skin_dqs(rest, ti, tw, torch.from_numpy(dual_quaternions(skinning_matrices(skeleton, clip))).to(dev))
+    else:
+        mats = skinning_matrices(skeleton, clip)
+        if centres is None:
+            centres = cor_centres(v, f, (infl, w), mats.shape[1], device=dev, sigma=cor_sigma)
+        centres = tuple(a.to(dev) for a in centres)
+        screen = ops.skin_cor(rest, ti, tw, torch.from_numpy(mats).to(dev),
+                              torch.from_numpy(rotation_quaternions(mats[..., :3])).to(dev), *centres)
     if corrective_iterations:
         topology = ops.corrective_topology(smoothing_topology(v, f), dev)
         delta, valid = ops.corrective_bind(rest, topology, corrective_factor, corrective_iterations)
@@ -191,5 +227,7 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     res = {"color": out["color_u8"], "pos": out["pos_u8"], "edge": ops.pos_edge_u8(out["pos_u8"]),
            "frames": out["frames"], "size": int(size), "span": float(span), "centre": (cx, cy),
            "vertices": screen}
+    if skinning == "centre_of_rotation":
+        res["cor_centres"] = centres
     res.update({k: out[k] for k in want})
     return res

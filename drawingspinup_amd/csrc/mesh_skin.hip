@@ -8,6 +8,10 @@
 //   dsu_skin_lbs          out[f, v] = sum_k w_k (R_k x + t_k)
 //   dsu_skin_dqs          out[f, v] = the rigid transform of the blended unit dual quaternion
 //                         (dqs_blend.h; dsu_skin_dqs_host runs the same text on host arrays)
+//   dsu_skin_cor_centres  once per character: every vertex's centre of rotation, a sum over all
+//                         (vertex, triangle) pairs (cor_blend.h; brute force, the hot one of this blend)
+//   dsu_skin_cor          out[f, v] = x + the linear blend's displacement of the centre p* + the blended
+//                         rotation's displacement of (x - p*)
 //
 // The rules (include/dsu_hip.h states them in full; tests/skin_ref.py restates them in float64).
 //
@@ -22,11 +26,15 @@
 // against each staged triangle whose box meets its segment's box.  A triangle listed in several
 // cells is tested several times; the answer is an OR, so the order and the repeats do not matter.
 // The walk stops as soon as every segment of the workgroup is blocked.
+#include <new>
+#include <vector>
+
 #include "common.h"
 #include "bin_sort.h"
 #include "mesh_geom.h"
 #include "partial_reduce.h"
 #include "dqs_blend.h"
+#include "cor_blend.h"
 
 namespace {
 
@@ -407,6 +415,190 @@ __global__ __launch_bounds__(256) void skin_dqs_kernel(const float* __restrict__
   out[i * 3 + 2] = o[2];
 }
 
+// ------------------------------------------------------------------ centre-of-rotation skinning
+// Centres, once per character (V * T pairs).  cor_rows_kernel writes every triangle's canonical row
+// (its ascending (joint, w^) pairs, centroid and area) once.  cor_centres_kernel: one thread per
+// vertex with its <= COR_KR pairs in registers; the rows stream through LDS DSU_COR_TILE triangles
+// at a time and every lane reads the same triangle (a broadcast).  A (vertex, triangle) pair looks
+// the vertex's joints up in the triangle's row and leaves before any exponential when fewer than two
+// are shared.  V / 256 workgroups do not fill the device, so blockIdx.y splits the triangle range
+// into runs of whole tiles; cor_reduce_kernel adds the partial sums in ascending order: no atomics,
+// two runs give the same bits.  K above COR_KR: cor_centres_wide_kernel, the same sums with both
+// rows read from memory.
+constexpr int COR_TILE = DSU_COR_TILE;
+constexpr int COR_KR = 4;
+constexpr int COR_RW = 3 * COR_KR;
+
+struct CorRows {
+  int32_t* n;      // (T) pairs of the row, 0: skipped
+  int32_t* j;      // (T, rw)
+  double* w;       // (T, rw)
+  double* geo;     // (T, 4) centroid, area
+  int32_t rw;
+};
+
+struct CorPlan {
+  int32_t rw, parts;
+  int64_t tiles_per_part;
+};
+
+bool cor_shape_ok(int64_t V, int64_t T, int32_t K, int32_t J, double sigma) {
+  return V >= 0 && V <= (int64_t)1 << 26 && T >= 0 && T <= (int64_t)1 << 28 && K >= 1 && K <= 4096 && J >= 1 &&
+         V * K <= (int64_t)1 << 31 && sigma > 0.0 && sigma * sigma > 0.0 &&
+         sigma * sigma <= 1.7976931348623157e308;
+}
+
+CorPlan cor_plan(int64_t V, int64_t T, int32_t K, int32_t J) {
+  CorPlan pl;
+  pl.rw = (int32_t)min((int64_t)3 * K, (int64_t)J);
+  const int64_t nbx = max((V + 255) / 256, (int64_t)1);
+  pl.parts = (int32_t)min((int64_t)DSU_COR_MAX_PARTS, (1024 + nbx - 1) / nbx);
+  const int64_t tiles = (T + COR_TILE - 1) / COR_TILE;
+  pl.tiles_per_part = max((tiles + pl.parts - 1) / pl.parts, (int64_t)1);
+  return pl;
+}
+
+// doubles first (partials, geo, w), then the int32 arrays; rounded up to whole doubles
+int64_t cor_bytes(const CorPlan& pl, int64_t V, int64_t T) {
+  const int64_t ints = T + T * pl.rw;
+  return ((int64_t)pl.parts * V * 4 + T * 4 + T * pl.rw + (ints + 1) / 2) * 8;
+}
+
+__global__ __launch_bounds__(256) void cor_rows_kernel(const float* __restrict__ rest,
+                                                       const int32_t* __restrict__ faces,
+                                                       const int32_t* __restrict__ joints,
+                                                       const float* __restrict__ weights, int64_t V, int64_t T,
+                                                       int32_t K, int32_t J, CorRows r) {
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  double geo[4];
+  r.n[t] = dsu_cor::triangle_row(rest, faces, t, V, joints, weights, K, J, r.rw, r.j + t * r.rw, r.w + t * r.rw, geo);
+  r.geo[t * 4] = geo[0]; r.geo[t * 4 + 1] = geo[1]; r.geo[t * 4 + 2] = geo[2]; r.geo[t * 4 + 3] = geo[3];
+}
+
+__global__ __launch_bounds__(256) void cor_centres_kernel(const int32_t* __restrict__ joints,
+                                                          const float* __restrict__ weights, int64_t V, int32_t K,
+                                                          int32_t J, CorRows r, int64_t T, int64_t tiles_per_part,
+                                                          double s2, double* __restrict__ partial) {
+  __shared__ double s_geo[COR_TILE * 4];
+  __shared__ double s_w[COR_TILE * COR_RW];
+  __shared__ int32_t s_j[COR_TILE * COR_RW];
+  __shared__ int32_t s_n[COR_TILE];
+  const int tid = threadIdx.x;
+  const int64_t v = blockIdx.x * (int64_t)blockDim.x + tid;
+  const int rw = r.rw;                       // <= COR_RW here
+  int32_t vj[COR_KR];
+  double vw[COR_KR];
+  int nv = 0;
+#pragma unroll
+  for (int a = 0; a < COR_KR; ++a) { vj[a] = -1; vw[a] = 0.0; }
+  if (v < V) {
+    nv = dsu_cor::row_length(joints + v * K, K, J);
+#pragma unroll
+    for (int a = 0; a < COR_KR; ++a)
+      if (a < nv) { vj[a] = joints[v * K + a]; vw[a] = (double)weights[v * K + a]; }
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const int64_t t_beg = min((int64_t)blockIdx.y * tiles_per_part * COR_TILE, T);
+  const int64_t t_end = min(((int64_t)blockIdx.y + 1) * tiles_per_part * COR_TILE, T);
+  for (int64_t base = t_beg; base < t_end; base += COR_TILE) {
+    const int nt = (int)min((int64_t)COR_TILE, t_end - base);
+    __syncthreads();                         // the previous tile is consumed
+    if (tid < nt * 4) s_geo[tid] = r.geo[base * 4 + tid];
+    if (tid < nt) s_n[tid] = r.n[base + tid];
+    for (int i = tid; i < nt * rw; i += 256) {
+      s_w[i] = r.w[base * rw + i];
+      s_j[i] = r.j[base * rw + i];
+    }
+    __syncthreads();
+    if (nv < 2) continue;
+    for (int s = 0; s < nt; ++s) {
+      const int n = s_n[s];
+      if (n < 2) continue;
+      double th[COR_KR];
+#pragma unroll
+      for (int a = 0; a < COR_KR; ++a) th[a] = 0.0;
+      int shared = 0;
+      for (int e = 0; e < n; ++e) {
+        const int32_t je = s_j[s * rw + e];
+        const double we = s_w[s * rw + e];
+#pragma unroll
+        for (int a = 0; a < COR_KR; ++a)
+          if (je == vj[a] && we != 0.0 && vw[a] != 0.0) { th[a] = we; ++shared; }
+      }
+      if (shared < 2) continue;
+      double sim = 0.0;
+#pragma unroll
+      for (int a = 0; a < COR_KR; ++a)
+#pragma unroll
+        for (int b = a + 1; b < COR_KR; ++b)
+          if (th[a] != 0.0 && th[b] != 0.0) sim = sim + dsu_cor::pair_term(vw[a], vw[b], th[a], th[b], s2);
+      if (sim != 0.0) dsu_cor::add_triangle(acc, sim, s_geo + s * 4);
+    }
+  }
+  if (v < V) {
+    double* __restrict__ o = partial + ((int64_t)blockIdx.y * V + v) * 4;
+    o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
+  }
+}
+
+__global__ __launch_bounds__(256) void cor_centres_wide_kernel(const int32_t* __restrict__ joints,
+                                                               const float* __restrict__ weights, int64_t V,
+                                                               int32_t K, int32_t J, CorRows r, int64_t T,
+                                                               int64_t tiles_per_part, double s2,
+                                                               double* __restrict__ partial) {
+  const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int32_t* __restrict__ vj = joints + v * K;
+  const float* __restrict__ vw = weights + v * K;
+  const int nv = dsu_cor::row_length(vj, K, J);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const int64_t t_beg = min((int64_t)blockIdx.y * tiles_per_part * COR_TILE, T);
+  const int64_t t_end = min(((int64_t)blockIdx.y + 1) * tiles_per_part * COR_TILE, T);
+  if (nv >= 2)
+    for (int64_t t = t_beg; t < t_end; ++t) {
+      const int n = r.n[t];
+      if (n < 2) continue;
+      const double sim = dsu_cor::similarity(vj, vw, nv, r.j + t * r.rw, r.w + t * r.rw, n, s2);
+      if (sim != 0.0) dsu_cor::add_triangle(acc, sim, r.geo + t * 4);
+    }
+  double* __restrict__ o = partial + ((int64_t)blockIdx.y * V + v) * 4;
+  o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
+}
+
+__global__ __launch_bounds__(256) void cor_reduce_kernel(const double* __restrict__ partial, int64_t V, int32_t parts,
+                                                         double* __restrict__ centres, uint8_t* __restrict__ valid) {
+  const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int p = 0; p < parts; ++p) {
+    const double* __restrict__ q = partial + ((int64_t)p * V + v) * 4;
+    acc[0] = acc[0] + q[0]; acc[1] = acc[1] + q[1]; acc[2] = acc[2] + q[2]; acc[3] = acc[3] + q[3];
+  }
+  dsu_cor::finish(acc, centres + v * 3, valid + v);
+}
+
+// Apply: skin_dqs_kernel's shape, one thread per (frame, vertex), vertex fastest; the frame's tables
+// (J * 128 B) are shared by every thread of the frame.
+__global__ __launch_bounds__(256) void skin_cor_kernel(const float* __restrict__ rest,
+                                                       const int32_t* __restrict__ infl,
+                                                       const float* __restrict__ wts,
+                                                       const double* __restrict__ mats,
+                                                       const double* __restrict__ quats,
+                                                       const double* __restrict__ centres,
+                                                       const uint8_t* __restrict__ valid, int64_t V, int32_t K,
+                                                       int32_t F, int32_t J, float* __restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)F * V) return;
+  const int64_t f = i / V, v = i - f * V;
+  float o[3];
+  dsu_cor::blend(infl + v * K, wts + v * K, K, mats + f * J * 12, quats + f * J * 4, J, rest[v * 3], rest[v * 3 + 1],
+                 rest[v * 3 + 2], centres + v * 3, valid[v], o);
+  out[i * 3] = o[0];
+  out[i * 3 + 1] = o[1];
+  out[i * 3 + 2] = o[2];
+}
+
 bool skin_shape_ok(int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints) {
   return !(n_verts < 0 || K < 1 || K > 4096 || n_frames < 1 || n_frames > 65535 || n_joints < 1 ||
            (int64_t)n_frames * n_verts > (int64_t)1 << 31 || n_verts * K > (int64_t)1 << 31);
@@ -542,6 +734,105 @@ int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float*
     for (int64_t v = 0; v < n_verts; ++v)
       dsu_dqs::blend(influences + v * K, weights + v * K, K, dualquats + f * n_joints * 8, n_joints, rest[v * 3],
                      rest[v * 3 + 1], rest[v * 3 + 2], out + (f * n_verts + v) * 3);
+  return DSU_OK;
+}
+
+int64_t dsu_skin_cor_centres_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints) {
+  if (!cor_shape_ok(n_verts, n_faces, K, n_joints, 1.0)) return DSU_EINVAL;
+  return cor_bytes(cor_plan(n_verts, n_faces, K, n_joints), n_verts, n_faces);
+}
+
+int dsu_skin_cor_centres(const float* rest, const int32_t* faces, const int32_t* joints, const float* weights,
+                         int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints, double sigma,
+                         void* workspace, int64_t workspace_bytes, double* centres, uint8_t* valid, void* stream) {
+  if (!cor_shape_ok(n_verts, n_faces, K, n_joints, sigma)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  const CorPlan pl = cor_plan(n_verts, n_faces, K, n_joints);
+  if (!rest || (n_faces && !faces) || !joints || !weights || !centres || !valid || !workspace ||
+      workspace_bytes < cor_bytes(pl, n_verts, n_faces))
+    return DSU_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t V = n_verts, T = n_faces;
+  double* partial = (double*)workspace;
+  CorRows r;
+  r.geo = partial + (int64_t)pl.parts * V * 4;
+  r.w = r.geo + T * 4;
+  r.n = (int32_t*)(r.w + T * pl.rw);
+  r.j = r.n + T;
+  r.rw = pl.rw;
+  if (T) cor_rows_kernel<<<dsu_blocks_for(T, 256), 256, 0, st>>>(rest, faces, joints, weights, V, T, K, n_joints, r);
+  const dim3 grid((unsigned)dsu_blocks_for(V, 256), (unsigned)pl.parts);
+  if (K <= COR_KR)
+    cor_centres_kernel<<<grid, dim3(256), 0, st>>>(joints, weights, V, K, n_joints, r, T, pl.tiles_per_part,
+                                                   sigma * sigma, partial);
+  else
+    cor_centres_wide_kernel<<<grid, dim3(256), 0, st>>>(joints, weights, V, K, n_joints, r, T, pl.tiles_per_part,
+                                                        sigma * sigma, partial);
+  cor_reduce_kernel<<<dsu_blocks_for(V, 256), 256, 0, st>>>(partial, V, pl.parts, centres, valid);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+// HOST: the same text (cor_blend.h) on host arrays, the triangles in one ascending run.
+int dsu_skin_cor_centres_host(const float* rest, const int32_t* faces, const int32_t* joints, const float* weights,
+                              int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints, double sigma,
+                              double* centres, uint8_t* valid) {
+  if (!cor_shape_ok(n_verts, n_faces, K, n_joints, sigma)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  if (!rest || (n_faces && !faces) || !joints || !weights || !centres || !valid) return DSU_EINVAL;
+  const int64_t V = n_verts, T = n_faces;
+  // the rows are host memory of this call: running out of it is an unsupported size, not an exception
+  try {
+    const int rw = cor_plan(V, T, K, n_joints).rw;
+    std::vector<int32_t> tn(T), tj(T * rw);
+    std::vector<double> tw(T * rw), geo(T * 4);
+    for (int64_t t = 0; t < T; ++t)
+      tn[t] = dsu_cor::triangle_row(rest, faces, t, V, joints, weights, K, n_joints, rw, tj.data() + t * rw,
+                                    tw.data() + t * rw, geo.data() + t * 4);
+    const double s2 = sigma * sigma;
+    for (int64_t v = 0; v < V; ++v) {
+      const int nv = dsu_cor::row_length(joints + v * K, K, n_joints);
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      if (nv >= 2)
+        for (int64_t t = 0; t < T; ++t) {
+          if (tn[t] < 2) continue;
+          const double sim = dsu_cor::similarity(joints + v * K, weights + v * K, nv, tj.data() + t * rw,
+                                                 tw.data() + t * rw, tn[t], s2);
+          if (sim != 0.0) dsu_cor::add_triangle(acc, sim, geo.data() + t * 4);
+        }
+      dsu_cor::finish(acc, centres + v * 3, valid + v);
+    }
+  } catch (const std::bad_alloc&) {
+    return DSU_EINVAL;
+  }
+  return DSU_OK;
+}
+
+int dsu_skin_cor(const float* rest, const int32_t* influences, const float* weights, const double* matrices,
+                 const double* quats, const double* centres, const uint8_t* valid, int64_t n_verts, int32_t K,
+                 int32_t n_frames, int32_t n_joints, float* out, void* stream) {
+  if (!skin_shape_ok(n_verts, K, n_frames, n_joints)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  if (!rest || !influences || !weights || !matrices || !quats || !centres || !valid || !out) return DSU_EINVAL;
+  const int64_t total = (int64_t)n_frames * n_verts;
+  skin_cor_kernel<<<dsu_blocks_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+      rest, influences, weights, matrices, quats, centres, valid, n_verts, K, n_frames, n_joints, out);
+  DSU_CHECK_LAUNCH();
+  return DSU_OK;
+}
+
+// HOST: the same blend (cor_blend.h) on host arrays.
+int dsu_skin_cor_host(const float* rest, const int32_t* influences, const float* weights, const double* matrices,
+                      const double* quats, const double* centres, const uint8_t* valid, int64_t n_verts, int32_t K,
+                      int32_t n_frames, int32_t n_joints, float* out) {
+  if (!skin_shape_ok(n_verts, K, n_frames, n_joints)) return DSU_EINVAL;
+  if (n_verts == 0) return DSU_OK;
+  if (!rest || !influences || !weights || !matrices || !quats || !centres || !valid || !out) return DSU_EINVAL;
+  for (int64_t f = 0; f < n_frames; ++f)
+    for (int64_t v = 0; v < n_verts; ++v)
+      dsu_cor::blend(influences + v * K, weights + v * K, K, matrices + f * n_joints * 12, quats + f * n_joints * 4,
+                     n_joints, rest[v * 3], rest[v * 3 + 1], rest[v * 3 + 2], centres + v * 3, valid[v],
+                     out + (f * n_verts + v) * 3);
   return DSU_OK;
 }
 

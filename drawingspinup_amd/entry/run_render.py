@@ -23,8 +23,12 @@ from every texel (an OBJ from elsewhere with mirrored charts).
 For the BVH actions, `--skinning dual_quaternion` blends the joints' unit dual quaternions instead of
 their matrices (Blender's "Preserve Volume"; the default `linear` is Blender's default and the
 reference's), and `--fps N` resamples each clip to 1 / N s per frame after it is fitted to the mesh
-(default: the clip's own rate).  The cached weights serve both blends.  rest_pose and rest_rotate
-have no skeleton and ignore both.
+(default: the clip's own rate).  `--skinning centre_of_rotation` rotates every vertex about its own
+centre of rotation (Le & Hodgins 2016; animate.cor_centres): the radius is kept without the bulge of
+dual quaternions on the outside of a sharp bend.  The centres are computed once per character and
+kept in `<uid>/mesh/skin_cor.npz` (keyed by the joints' names, the vertex and face counts and sigma);
+without that value of the flag the file is neither read nor written.  The cached weights serve all
+three blends.  rest_pose and rest_rotate have no skeleton and ignore both flags.
 
 `--corrective_smooth N` runs N steps of corrective smoothing (delta mush, Blender's Corrective Smooth
 modifier; animate_mesh(corrective_iterations=N)) on the skinned vertices of every BVH action, with
@@ -88,6 +92,23 @@ def skin_weights(mesh_dir, verts, faces, skeleton, device):
     return infl, w
 
 
+def skin_centres(mesh_dir, verts, faces, skeleton, weights, device, sigma=animate.skin.COR_SIGMA):
+    """The centres of rotation of the mesh for these weights, from `skin_cor.npz` when it holds them
+    (same joints, vertex count, face count and sigma), else computed and stored there.
+    -> (centres, valid) on the device."""
+    import torch
+    path = os.path.join(mesh_dir, "skin_cor.npz")
+    if os.path.exists(path):
+        with np.load(path) as z:
+            if list(z["joints"]) == list(skeleton.names) and len(z["centres"]) == len(verts) \
+                    and int(z["n_faces"]) == len(faces) and float(z["sigma"]) == float(sigma):
+                return tuple(torch.from_numpy(z[k]).to(device) for k in ("centres", "valid"))
+    centres, valid = animate.cor_centres(verts, faces, weights, len(skeleton.names), device=device, sigma=sigma)
+    np.savez(path, centres=centres.cpu().numpy(), valid=valid.cpu().numpy(), joints=np.asarray(skeleton.names),
+             n_faces=np.int64(len(faces)), sigma=np.float64(sigma))
+    return centres, valid
+
+
 def run(argv=None):
     ap = argparse.ArgumentParser(description="frame rendering")
     ap.add_argument("--data_dir", default="../dataset/AnimatedDrawings/preprocessed", help="data root")
@@ -102,7 +123,8 @@ def run(argv=None):
     ap.add_argument("--mip_coverage", default="faces", choices=["faces", "all"],
                     help="texels the mip levels of --texture_filter trilinear average: those the uv faces cover, or all")
     ap.add_argument("--skinning", default="linear", choices=list(animate.skin.SKINNING),
-                    help="blend of the BVH actions: the joints' matrices, or their dual quaternions (preserve volume)")
+                    help="blend of the BVH actions: the joints' matrices, their dual quaternions (preserve volume), or "
+                         "their rotations about a centre of rotation per vertex")
     ap.add_argument("--fps", type=float, default=None,
                     help="resample each BVH clip to this many frames per second (default: the clip's own rate)")
     ap.add_argument("--corrective_smooth", type=int, default=0, metavar="N",
@@ -151,10 +173,13 @@ def run(argv=None):
             weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
             if args.fps is not None:
                 clip = animate.resample_clip(clip, 1.0 / args.fps)
+            cor = {}
+            if args.skinning == "centre_of_rotation":
+                cor["centres"] = skin_centres(mesh_dir, verts, faces, skeleton, weights, args.device)
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
                                             ss=args.ss, device=args.device, skinning=args.skinning,
                                             corrective_iterations=args.corrective_smooth,
-                                            corrective_factor=args.corrective_factor, **tex, **flt)
+                                            corrective_factor=args.corrective_factor, **cor, **tex, **flt)
         n = write_frames(out_dir, rendered)
         print((time.time() - start) / n, n)
     return out_dir, rendered

@@ -2000,6 +2000,93 @@ def skin_dqs(rest, influences, weights, dualquats):
     return out
 
 
+def skin_cor_table(influences, weights, n_joints):
+    """The canonical influence table of dsu_skin_cor_centres from any (influences (V,K), weights
+    (V,K)), in numpy: an influence outside [0, n_joints) or with a weight that is not > 0 is dropped,
+    duplicate joints are added in float64 in k order and rounded to f32, the joints of a row ascend
+    and the padding after them is -1 / 0.  -> joints (V,K') int32, weights (V,K') float32 with K' the
+    longest row (at least 1)."""
+    import numpy as np
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    infl = to_np(influences).astype(np.int64)
+    w = to_np(weights).astype(np.float32).astype(np.float64)
+    if infl.ndim != 2 or w.shape != infl.shape:
+        raise ValueError("influences / weights (V,K) expected")
+    V, K = infl.shape
+    J = int(n_joints)
+    with np.errstate(invalid="ignore"):
+        use = (infl >= 0) & (infl < J) & (w > 0.0)
+    key = np.where(use, infl, J)
+    order = np.argsort(key, axis=1, kind="stable")                   # by joint; k order within a joint
+    sj, sw = np.take_along_axis(key, order, 1), np.take_along_axis(w, order, 1)
+    first = np.ones((V, K), bool)
+    first[:, 1:] = sj[:, 1:] != sj[:, :-1]
+    slot = np.cumsum(first, 1) - 1
+    acc = np.zeros((V, max(K, 1)))
+    joints = np.full((V, max(K, 1)), -1, np.int32)
+    for k in range(K):
+        rows = np.flatnonzero(sj[:, k] < J)
+        acc[rows, slot[rows, k]] = acc[rows, slot[rows, k]] + sw[rows, k]
+        joints[rows, slot[rows, k]] = sj[rows, k]
+    n = int((joints >= 0).sum(1).max()) if V else 0
+    n = max(n, 1)
+    return np.ascontiguousarray(joints[:, :n]), np.ascontiguousarray(acc[:, :n].astype(np.float32))
+
+
+def skin_cor_centres(rest, faces, influences, weights, n_joints, sigma=0.1):
+    """Centres of rotation of a rigged mesh (dsu_skin_cor_centres; Le & Hodgins 2016), once per
+    character: rest (V,3) on the device, faces (T,3), any influences / weights (V,K) (the canonical
+    table is made here, skin_cor_table) -> (centres (V,3) f64, valid (V,) uint8) on the device.  A
+    vertex on one joint alone has no centre (valid 0): ops.skin_cor blends it linearly."""
+    rest = _f32c(rest)
+    if rest.dim() != 2 or rest.shape[1] != 3:
+        raise ValueError("rest (V,3) expected")
+    V = rest.shape[0]
+    joints, w = skin_cor_table(influences, weights, n_joints)
+    if joints.shape[0] != V:
+        raise ValueError("influences / weights (V,K) of the rest mesh expected")
+    faces = faces.to(device=rest.device, dtype=torch.int32).contiguous() if torch.is_tensor(faces) else \
+        torch.as_tensor(faces, dtype=torch.int32).reshape(-1, 3).contiguous().to(rest.device)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces (T,3) expected")
+    T, K = faces.shape[0], joints.shape[1]
+    tj, tw = torch.from_numpy(joints).to(rest.device), torch.from_numpy(w).to(rest.device)
+    centres = torch.zeros((V, 3), dtype=torch.float64, device=rest.device)
+    valid = torch.zeros((V,), dtype=torch.uint8, device=rest.device)
+    nbytes = lib().dsu_skin_cor_centres_workspace_bytes(V, T, K, int(n_joints))
+    if nbytes < 0:
+        check(int(nbytes), "dsu_skin_cor_centres_workspace_bytes")
+    ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=rest.device)   # never short of nbytes
+    check(lib().dsu_skin_cor_centres(ptr(rest, torch.float32), ptr(faces, torch.int32), ptr(tj, torch.int32),
+                                     ptr(tw, torch.float32), V, T, K, int(n_joints), float(sigma), ptr(ws), nbytes,
+                                     ptr(centres), ptr(valid), stream()), "dsu_skin_cor_centres")
+    return centres, valid
+
+
+def skin_cor(rest, influences, weights, matrices, quats, centres, valid):
+    """Centre-of-rotation skinning (dsu_skin_cor): rest (V,3), influences / weights (V,K) as skin_dqs
+    takes them, matrices (F,J,3,4) float64 (animate.skinning_matrices), quats (F,J,4) float64
+    (animate.rotation_quaternions of their rotations), centres (V,3) f64 and valid (V,) uint8 from
+    skin_cor_centres -> (F,V,3) f32 on the device."""
+    rest, weights = _f32c(rest), _f32c(weights)
+    influences = influences.to(torch.int32).contiguous()
+    matrices, quats = matrices.to(torch.float64).contiguous(), quats.to(torch.float64).contiguous()
+    centres, valid = centres.to(torch.float64).contiguous(), valid.to(torch.uint8).contiguous()
+    if rest.dim() != 2 or rest.shape[1] != 3 or influences.dim() != 2 or weights.shape != influences.shape \
+            or influences.shape[0] != rest.shape[0] or matrices.dim() != 4 or matrices.shape[2:] != (3, 4) \
+            or quats.shape != matrices.shape[:2] + (4,) or centres.shape != rest.shape \
+            or valid.shape != rest.shape[:1]:
+        raise ValueError("rest (V,3), influences / weights (V,K), matrices (F,J,3,4), quats (F,J,4), centres (V,3) "
+                         "and valid (V,) expected")
+    V, K = influences.shape
+    F, J = matrices.shape[:2]
+    out = torch.empty((F, V, 3), dtype=torch.float32, device=rest.device)
+    check(lib().dsu_skin_cor(ptr(rest, torch.float32), ptr(influences, torch.int32), ptr(weights, torch.float32),
+                             ptr(matrices, torch.float64), ptr(quats, torch.float64), ptr(centres, torch.float64),
+                             ptr(valid, torch.uint8), V, K, F, J, ptr(out), stream()), "dsu_skin_cor")
+    return out
+
+
 CORRECTIVE_KEYS = ("rep", "faces", "nbr_rowptr", "nbr_cols", "cor_rowptr", "cor_faces")
 
 

@@ -1385,7 +1385,7 @@ int dsu_skin_lbs(const float* rest, const int32_t* influences, const float* weig
  * Kernel: one thread per (frame, vertex), vertex fastest, 256 threads; no LDS, no atomics: two runs
  * give the same bits.  Skinning transforms here are rigid, so Blender's separate treatment of bone
  * scale does not arise; the known bulge of dual-quaternion blending on the outside of a sharp bend
- * is not corrected.
+ * is not corrected (by this blend: dsu_skin_cor below rotates about per-vertex centres instead).
  * dsu_skin_dqs_host: HOST function on HOST arrays, the same text evaluated on the CPU.
  * Both return -1 on a null pointer with work to do and 0 for n_verts = 0. */
 int dsu_skin_dqs(const float* rest, const int32_t* influences, const float* weights, const double* dualquats,
@@ -1393,6 +1393,117 @@ int dsu_skin_dqs(const float* rest, const int32_t* influences, const float* weig
 int dsu_skin_dqs_host(const float* rest, const int32_t* influences, const float* weights,
                       const double* dualquats, int64_t n_verts, int32_t K, int32_t n_frames, int32_t n_joints,
                       float* out);
+/* Centre-of-rotation skinning (Le & Hodgins, "Real-time skeletal skinning with optimized centers of
+ * rotation", SIGGRAPH 2016): the third blend.  Linear blending collapses a bent or twisted limb;
+ * dual-quaternion blending keeps the radius but swings every vertex near a joint about the joint's
+ * axis, which bulges the outside of a sharp bend.  Here every vertex gets, once per character, a
+ * centre of rotation p*: the area-weighted mean of the centroids of the triangles whose skinning
+ * weights resemble its own.  Per frame the normalised blend of the joints' rotation quaternions is
+ * applied about p*, and p* itself moves by the linear blend.  An extension of the reference;
+ * csrc/cor_blend.h holds the text, compiled for the kernels and for the host entries.
+ * Everything is float64 from the f32 / f64 inputs, no products are fused, sums of three are taken as
+ * (a + b) + c and sums of four as ((a + b) + c) + d.
+ *
+ * a. Centres, once per character: dsu_skin_cor_centres.
+ * Inputs: rest (n_verts, 3) f32; faces (n_faces, 3) i32; a CANONICAL influence table joints
+ * (n_verts, K) i32 and weights (n_verts, K) f32; n_joints; sigma (f64, > 0; the paper's 0.1 is the
+ * default of every Python layer).  Canonical, per row: the contributing joints strictly ascending,
+ * each once, with weights > 0; the padding after them is -1 / 0 (a row ends at its first joint outside
+ * [0, n_joints)).  ops.skin_cor_centres makes this table from any (influences, weights), in numpy: an
+ * influence outside [0, n_joints) or with a weight that is not > 0 is dropped, duplicate joints are
+ * added in float64 in k order and rounded to f32 once.
+ *   W_i(j) = vertex i's weight on joint j, 0 where absent.
+ *   Triangle t = (a, b, c), vertices in stored order:  w^_t(j) = ((W_a(j) + W_b(j)) + W_c(j)) / 3 for the
+ *     joints of its three rows (ascending: its canonical row, at most min(3K, n_joints) pairs);
+ *     c_t = ((a + b) + c) / 3 per coordinate;  n = (b - a) x (c - a) with (u x v)_x = u_y v_z - u_z v_y
+ *     (cyclic);  a_t = sqrt((n_x n_x + n_y n_y) + n_z n_z) / 2.  A triangle with an index outside
+ *     [0, n_verts) or whose area is zero or not finite is skipped (so a NaN or infinite vertex removes
+ *     its triangles and reaches no sum).
+ *   Similarity:  s(i, t) = sum over the joint pairs j < k, in ascending (j, k) order, from 0, of
+ *       (((W_i(j) W_i(k)) w^_t(j)) w^_t(k)) exp(-(d d) / sigma^2),   d = W_i(j) w^_t(k) - W_i(k) w^_t(j),
+ *     sigma^2 = sigma sigma.  A pair with a zero factor contributes nothing and its exponential is not
+ *     evaluated (every entry tests the four factors, so a table made elsewhere with a weight of 0 inside
+ *     a row follows the same rule); with fewer than two shared joints s = 0.
+ *   Sums:  den_i = sum_t s a_t,  num_i = sum_t (s a_t) c_t per coordinate, each from 0.  Within one
+ *     partition of the triangle range the triangles are added in ascending order; the partitions are
+ *     combined in ascending order by a second pass.  No floating-point atomics: two runs give the same
+ *     bits, and two vertices with equal rows get equal bits.
+ *   valid_i = den_i > 0 and den_i, num_i finite;  centre_i = num_i / den_i, or 0 where not valid.  A
+ *     vertex on one joint alone has s = 0 everywhere and is not valid: the paper's case for the plain
+ *     linear blend.
+ * Outputs: centres (n_verts, 3) f64, valid (n_verts) u8.
+ * The partition is the implementation's choice — the device entry cuts the triangle range into
+ * `parts` runs of whole tiles of DSU_COR_TILE triangles, parts = min(DSU_COR_MAX_PARTS,
+ * ceil(1024 / ceil(n_verts / 256))), ceil(ceil(n_faces / tile) / parts) tiles each (the last runs may
+ * be empty); the host entry takes one run — and exp is each side's own.  The result is therefore
+ * held to a bound, not to bits: per coordinate 2 (n_faces + 1 / sigma^2 + 64) 2^-52 times the
+ * bounding-box diagonal (a centre is a convex combination of centroids; a weight carries the
+ * relative error of its exponential's argument, at most 1 / sigma^2 of them, plus a few roundings;
+ * the sums add n_faces roundings).
+ * Kernels (csrc/mesh_skin.hip): one thread per triangle writes the rows; one thread per vertex, 256
+ * per workgroup, the partition in blockIdx.y, walks them (K <= 4: the vertex's pairs in registers,
+ * the rows through LDS, every lane on the same triangle; above: both from memory); a third adds
+ * the partitions.  workspace_bytes: the partial sums (parts, n_verts, 4) f64 and the rows, rounded up
+ * to a multiple of 8.
+ * n_verts <= 2^26, n_faces <= 2^28, K <= 4096.
+ *
+ * b. Apply, per (frame, vertex): dsu_skin_cor.
+ * rest, influences, weights, out: as dsu_skin_dqs takes them (any table, not only a canonical one),
+ * with its skipping rule — an influence outside [0, n_joints) or with a weight that is not > 0
+ * contributes nothing, to either part — and its pivot and sign rule.  matrices (n_frames, n_joints,
+ * 3, 4) FLOAT64 = [R | t];  quats (n_frames, n_joints, 4) FLOAT64 unit quaternions (w, x, y, z) of R
+ * (animate.rotation_quaternions);  centres, valid: of a.
+ *   With y_k(p) = ((R_c0 p_x + R_c1 p_y) + R_c2 p_z) + t_c per coordinate c of influence k's transform:
+ *   Linear blend:  L(x) = sum_k w_k y_k(x), accumulated from 0 in k order over the contributing
+ *     influences.  The weights are used as given, not renormalised, as in dsu_skin_lbs.
+ *   Not valid:  out = (float) L(x).
+ *   Valid:  M = sum_k w_k (y_k(p*) - p*_c), accumulated from 0 in k order: the displacement of the centre
+ *     under the linear blend;  b = sum_k (s_k w_k) r_k, with the first contributing influence as the
+ *     pivot and s_k = -1 where ((r_k.w r_p.w + r_k.x r_p.x) + r_k.y r_p.y) + r_k.z r_p.z < 0, else +1 (step
+ *     2 of the dual-quaternion rule);  n2 = ((b_0 b_0 + b_1 b_1) + b_2 b_2) + b_3 b_3.  Unless n2 > 0 and
+ *     finite (no contributing influence, rotations that cancel, NaN in a quaternion), out = (float) L(x).
+ *     r = b / sqrt(n2) component by component;  d = x - p*;  a = r_v x d,  c = r_v x a;
+ *     out = (float)(x + (M + ((2 r_w) a + 2 c))), the one rounding to f32.
+ * This is p* + M + r d r^-1 — the centre moved by the linear blend, the offset turned by the blended
+ * rotation — with the rotation in the form of step 7 there, r d r^-1 = d + (2 r_w) a + 2 c, and p* + d
+ * collected into x.  Written as L(p*) + r d r^-1 with L(p*) = sum_k w_k y_k(p*), the same value when the
+ * weights sum to 1, the f32 weights' sum leaves (sum w - 1) p* in every coordinate: under identity
+ * transforms a coordinate x_c = 0 would come out as (sum w - 1) p*_c, outside any bound relative to
+ * |x_c|, and the blend would depend on where the origin lies.  In the form above identity transforms
+ * give M = 0 and r_v = 0 exactly, so a vertex with a centre returns its rest position bit for bit; a
+ * vertex without one takes L(x) and is reproduced within the linear blend's bound, (2K + 4) 2^-24
+ * (|R||x| + |t|), bit for bit only where its weights sum to 1 in float64 (one influence of weight 1).
+ * So the rest clip need not render byte-equal to rest_pose in this mode; the other two blends keep
+ * their guarantees.
+ * The two forms differ by more than rounding where a row's weights do NOT sum to 1 (a caller's table,
+ * influences dropped by the skipping rule): L scales the whole position by S = sum w, the form above
+ * does not.  Under one transform [R | t] on every joint a vertex with a centre comes out as
+ * R x + S t + (S - 1)(R - I) p*, a vertex on the L(x) branches (not valid, n2 not > 0) as S (R x + t); under
+ * identity the first returns x and the second S x.  Two neighbouring vertices with the same row can
+ * land on different branches (one without a centre, one with), so with S far from 1 the surface tears
+ * there by about |S - 1| |x|: the blend is meant for rows that sum to 1 up to their f32 rounding, as
+ * animate.bone_heat_weights makes them, and a caller with other rows should normalise them first.  Negating any quaternion, the pivot's included, leaves the output bits unchanged.
+ * Kernel: skin_dqs_kernel's shape, one thread per (frame, vertex), vertex fastest, 256 threads; no
+ * LDS, no atomics: two runs give the same bits.
+ * dsu_skin_cor_centres_host / dsu_skin_cor_host: HOST functions on HOST arrays, the same text
+ * evaluated on the CPU (the centres without a workspace; -1 too when the host memory for the rows, about
+ * 52 + 12 min(3K, n_joints) bytes per face, cannot be had).  All return -1 on a null pointer with work
+ * to do (faces may be null when n_faces = 0) or a short workspace, and 0 for n_verts = 0. */
+#define DSU_COR_TILE 64
+#define DSU_COR_MAX_PARTS 16
+int64_t dsu_skin_cor_centres_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints);
+int dsu_skin_cor_centres(const float* rest, const int32_t* faces, const int32_t* joints, const float* weights,
+                         int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints, double sigma,
+                         void* workspace, int64_t workspace_bytes, double* centres, uint8_t* valid, void* stream);
+int dsu_skin_cor_centres_host(const float* rest, const int32_t* faces, const int32_t* joints, const float* weights,
+                              int64_t n_verts, int64_t n_faces, int32_t K, int32_t n_joints, double sigma,
+                              double* centres, uint8_t* valid);
+int dsu_skin_cor(const float* rest, const int32_t* influences, const float* weights, const double* matrices,
+                 const double* quats, const double* centres, const uint8_t* valid, int64_t n_verts, int32_t K,
+                 int32_t n_frames, int32_t n_joints, float* out, void* stream);
+int dsu_skin_cor_host(const float* rest, const int32_t* influences, const float* weights, const double* matrices,
+                      const double* quats, const double* centres, const uint8_t* valid, int64_t n_verts, int32_t K,
+                      int32_t n_frames, int32_t n_joints, float* out);
 /* Corrective smoothing of skinned frames ("delta mush", Mancewicz et al., "Delta Mush: smoothing
  * deformations while preserving detail", 2014; Blender's Corrective Smooth modifier).  Skinning moves
  * every vertex by its own influences alone, so wrong or abruptly changing weights shear and crease
