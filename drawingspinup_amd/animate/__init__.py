@@ -30,9 +30,14 @@ Rigged animations: `read_bvh` reads a skeleton and a motion clip, `bone_heat_wei
 to the skeleton (distances, visibility and the solve on the device, csrc/mesh_skin.hip),
 `animate_mesh` skins every frame on the device and renders it through the same rasteriser.  The
 weighting follows the published bone-heat form, not Blender's source; the view box is taken over
-the deformed vertices where Blender uses the object's bound_box; there is no retargeting and no
-automatic joint placement (`fit_to_mesh` only scales and centres a skeleton); the 30 degree turn
+the deformed vertices where Blender uses the object's bound_box; there is no automatic joint
+placement (`fit_to_mesh` only scales and centres a skeleton); the 30 degree turn
 that blender_animation.py:17-18 applies to two named clips is not restated.  FBX is not read.
+A rig from marks (rig.py): `read_marks` reads the 2-D joint marks of a drawing (AnimatedDrawings'
+char_cfg.yaml), `pixels_to_mesh` takes them to the exported OBJ's frame, `lift_marks` places every
+joint at the middle of the mesh's thickness under its mark (one thickness map on the device,
+csrc/mesh_thickness.hip), and `retarget_clip` turns any BVH clip into a clip of that skeleton by the
+world directions of the source's bones, whatever pose the character was drawn in.
 `animate_mesh(skinning="dual_quaternion")` blends unit dual quaternions instead of matrices (Blender's
 "Preserve Volume"; `dual_quaternions` makes the table), and `resample_clip` brings a clip to another
 frame rate (slerp of the local rotations).  `animate_mesh(corrective_iterations=N)` smooths the
@@ -50,7 +55,10 @@ from .skeleton import (Clip, Skeleton, dual_quaternions, fit_to_mesh, quaternion
 from . import corrective
 from .corrective import smoothing_topology
 from .skin import animate_mesh, bone_heat_weights, cor_centres
+from . import rig
+from .rig import lift_marks, minimal_rotation, pixels_to_mesh, read_marks, retarget_clip
 
 __all__ = ["Clip", "Skeleton", "animate_mesh", "bone_heat_weights", "cor_centres", "dual_quaternions", "fit_to_mesh",
            "quaternion_rotations", "read_bvh", "resample_clip", "rest_clip", "rotation_quaternions", "skinning_matrices", "DEFAULT_SIZE", "DEFAULT_SPAN", "PIXEL_FILTER_PRESETS", "frame_window", "motion_frames", "pixel_filter", "position_colours",
-           "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate", "smoothing_topology"]
+           "read_obj", "read_obj_textured", "render_frames", "rest_pose", "rest_rotate", "smoothing_topology",
+           "lift_marks", "minimal_rotation", "pixels_to_mesh", "read_marks", "retarget_clip"]

@@ -42,9 +42,22 @@ engine of the reference's `--engine_type` (animate.pixel_filter; the widths, 3.0
 from Blender's source and not pinned against it), `blackman_harris` with `--filter_width W` pixels
 any other width, `box` the default rule through the filtered kernel.  It applies to every action and
 every `--texture` mode.  Without the flag a pixel is the box over its own sub-samples, as before.
+
+`--marks FILE` rigs the BVH actions from the 2-D joint marks of the drawing (AnimatedDrawings'
+`char_cfg.yaml` layout, animate.read_marks) instead of scaling each clip's own skeleton to the mesh:
+the marks, in pixels of the `<uid>/mv` front image of side `--marks_res N` (default: the file's `width`,
+which must then equal its `height`), are taken to the OBJ's frame (animate.pixels_to_mesh) and lifted to
+the middle of the mesh's thickness under each mark (animate.lift_marks, one thickness map on the
+device); every clip is retargeted to that skeleton (animate.retarget_clip; `--joint_map JSON`, a file
+or the text itself, maps its joint names to the clip's, default: equal names ignoring case) before
+`--fps`, `--skinning`, `--corrective_smooth` and the rest, which compose unchanged.  The bone-heat
+weights of that skeleton are kept in `<uid>/mesh/skin_weights_marks.npz` (keyed by the joints' names and
+positions and the vertex count); `skin_weights.npz` and `skin_cor.npz` are neither read nor written
+then.  Without `--marks` nothing changes.
 """
 import argparse
 import glob
+import json
 import os
 import time
 
@@ -92,11 +105,57 @@ def skin_weights(mesh_dir, verts, faces, skeleton, device):
     return infl, w
 
 
-def skin_centres(mesh_dir, verts, faces, skeleton, weights, device, sigma=animate.skin.COR_SIGMA):
+def marks_skeleton(path, marks_res, verts, faces, device):
+    """The skeleton of --marks: the file's marks, from pixels of the front image to the OBJ's frame,
+    lifted into the mesh."""
+    names, parents, xy = animate.read_marks(path)
+    res = marks_res
+    if res is None:
+        width, height = animate.rig.marks_size(path)
+        if width is None or width != height:
+            raise ValueError(f"{path}: width {width} and height {height}: give the side of the front image "
+                             "with --marks_res")
+        res = width
+    return animate.lift_marks(names, parents, animate.pixels_to_mesh(xy, res), verts, faces, device=device)
+
+
+def read_joint_map(text):
+    """--joint_map: a JSON object {target joint: source joint}, as a file or as the text itself."""
+    if text is None:
+        return None
+    if os.path.exists(text):
+        with open(text) as fh:
+            text = fh.read()
+    jm = json.loads(text)
+    if not isinstance(jm, dict) or not all(isinstance(k, str) and isinstance(v, str) for k, v in jm.items()):
+        raise ValueError("--joint_map: a JSON object of joint names expected")
+    return jm
+
+
+def skin_weights_marks(mesh_dir, verts, faces, skeleton, device):
+    """The bone-heat weights of the mesh for the skeleton lifted from marks, from
+    `skin_weights_marks.npz` when it holds them (same joint names, same joint and end-site positions,
+    same vertex count), else computed and stored there."""
+    path = os.path.join(mesh_dir, "skin_weights_marks.npz")
+    points = skeleton.rest_points()
+    if os.path.exists(path):
+        with np.load(path) as z:
+            if list(z["joints"]) == list(skeleton.names) and z["points"].shape == points.shape \
+                    and (z["points"] == points).all() and len(z["influences"]) == len(verts):
+                return z["influences"], z["weights"]
+    infl, w = animate.bone_heat_weights(verts, faces, skeleton, device=device)
+    np.savez(path, influences=infl, weights=w, joints=np.asarray(skeleton.names), points=points)
+    return infl, w
+
+
+def skin_centres(mesh_dir, verts, faces, skeleton, weights, device, sigma=animate.skin.COR_SIGMA, cache=True):
     """The centres of rotation of the mesh for these weights, from `skin_cor.npz` when it holds them
-    (same joints, vertex count, face count and sigma), else computed and stored there.
-    -> (centres, valid) on the device."""
+    (same joints, vertex count, face count and sigma), else computed and stored there; cache=False
+    (a skeleton from --marks, whose weights are not those of `skin_weights.npz`) computes them and
+    leaves the file alone.  -> (centres, valid) on the device."""
     import torch
+    if not cache:
+        return animate.cor_centres(verts, faces, weights, len(skeleton.names), device=device, sigma=sigma)
     path = os.path.join(mesh_dir, "skin_cor.npz")
     if os.path.exists(path):
         with np.load(path) as z:
@@ -135,8 +194,23 @@ def run(argv=None):
                     help="reconstruction filter of a pixel (default: the box over its own sub-samples)")
     ap.add_argument("--filter_width", type=float, default=None, metavar="W",
                     help="total support of --pixel_filter in pixels (blackman_harris needs it; it overrides a preset's)")
+    ap.add_argument("--marks", default=None, metavar="FILE",
+                    help="rig the BVH actions from the drawing's 2-D joint marks (char_cfg.yaml layout) and retarget "
+                         "every clip to that skeleton")
+    ap.add_argument("--joint_map", default=None, metavar="JSON",
+                    help="with --marks: {joint of the marks: joint of the clips}, a file or the text (default: equal names)")
+    ap.add_argument("--marks_res", type=int, default=None, metavar="N",
+                    help="with --marks: side of the front image the marks are in pixels of (default: the file's width)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    if args.marks is None and (args.joint_map is not None or args.marks_res is not None):
+        ap.error("--joint_map and --marks_res need --marks")
+    if args.marks_res is not None and args.marks_res < 2:
+        ap.error("--marks_res must be at least 2")
+    try:
+        joint_map = read_joint_map(args.joint_map)
+    except ValueError as e:
+        ap.error(str(e))
     try:
         animate.corrective.check_parameters(args.corrective_smooth, args.corrective_factor)
     except ValueError as e:
@@ -162,6 +236,7 @@ def run(argv=None):
         if colours is None:
             raise ValueError(f"{found[0]} has no vertex colours")
     mesh_dir = os.path.join(args.data_dir, args.uid, "mesh")
+    lifted = None                                     # the skeleton of --marks, made for the first clip
     for action, clip_path in plan_actions(mesh_dir, args.test):
         out_dir = os.path.join(mesh_dir, "blender_render", action)
         start = time.time()
@@ -169,13 +244,21 @@ def run(argv=None):
             rendered = animate.render_frames(verts, faces, colours, action, ss=args.ss, n_frames=args.frames,
                                              device=args.device, **tex, **flt)
         else:
-            skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
-            weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
+            if args.marks is None:
+                skeleton, clip = animate.fit_to_mesh(*animate.read_bvh(clip_path), verts)
+                weights = skin_weights(mesh_dir, verts, faces, skeleton, args.device)
+            else:
+                if lifted is None:
+                    lifted = marks_skeleton(args.marks, args.marks_res, verts, faces, args.device)
+                skeleton = lifted
+                clip = animate.retarget_clip(*animate.read_bvh(clip_path), skeleton, joint_map)
+                weights = skin_weights_marks(mesh_dir, verts, faces, skeleton, args.device)
             if args.fps is not None:
                 clip = animate.resample_clip(clip, 1.0 / args.fps)
             cor = {}
             if args.skinning == "centre_of_rotation":
-                cor["centres"] = skin_centres(mesh_dir, verts, faces, skeleton, weights, args.device)
+                cor["centres"] = skin_centres(mesh_dir, verts, faces, skeleton, weights, args.device,
+                                              cache=args.marks is None)
             rendered = animate.animate_mesh(verts, faces, colours, skeleton, clip, weights=weights,
                                             ss=args.ss, device=args.device, skinning=args.skinning,
                                             corrective_iterations=args.corrective_smooth,

@@ -1409,6 +1409,61 @@ def knn8_blend(query_xy, known_xy, known_rgb):
     return out
 
 
+# ------------------------------------------------------------------ thickness map (animate/rig.py)
+THICKNESS_TILE = 16          # samples per side of a workgroup of dsu_mesh_thickness_ortho
+
+
+def _thickness_lattice(x0, y0, h, W, H):
+    x0, y0, h, W, H = float(x0), float(y0), float(h), int(W), int(H)
+    side = _lib.DEFINES["DSU_THICKNESS_MAX_SIDE"]
+    if not (0 <= W <= side and 0 <= H <= side):
+        raise ValueError(f"a thickness lattice has 0 .. {side} samples per side")
+    if not (h > 0.0 and all(abs(v) < float("inf") for v in (x0, y0, h))):
+        raise ValueError("a thickness lattice needs finite x0, y0 and h > 0")
+    return x0, y0, h, W, H
+
+
+def mesh_thickness(verts, faces, x0, y0, h, W, H):
+    """dsu_mesh_thickness_ortho: where along z the inside of the mesh lies under every sample of an xy
+    lattice (sample (r, c) at (x0 + (c + 1/2) h, y0 + (r + 1/2) h)).  verts (V,3) f32 and faces (T,3)
+    i32 on the device -> (mid (H,W) f64, thickness (H,W) f64, count (H,W) i32); the rule is stated in
+    include/dsu_hip.h.  The triangles are binned by ZGrid's counting sort on cells of 16 x 16
+    samples, so that a workgroup walks one list."""
+    x0, y0, h, W, H = _thickness_lattice(x0, y0, h, W, H)
+    verts, faces = _f32c(verts), faces.to(torch.int32).contiguous()
+    dev = verts.device
+    V, T = verts.shape[0], faces.shape[0]
+    mid = torch.zeros((H, W), dtype=torch.float64, device=dev)
+    thick = torch.zeros((H, W), dtype=torch.float64, device=dev)
+    count = torch.zeros((H, W), dtype=torch.int32, device=dev)
+    if not (V and T and W and H):
+        return mid, thick, count
+    # a face with an index outside [0, V) is ignored by the kernel; it is binned as if it named vertex 0
+    tris = verts[faces.long().clamp(0, V - 1)].contiguous()
+    g = max(1, -(-max(W, H) // THICKNESS_TILE))
+    span = g * THICKNESS_TILE * h
+    grid = ZGrid(tris, (x0, y0), (x0 + span, y0 + span), cells_per_axis=g)
+    gx0, gy0, cell, g, off, items = grid.args()
+    check(lib().dsu_mesh_thickness_ortho(ptr(verts, torch.float32), V, ptr(faces, torch.int32), T, gx0, gy0, cell, g,
+                                         off, items, grid.items.shape[0], x0, y0, h, W, H, ptr(mid), ptr(thick),
+                                         ptr(count), stream()), "dsu_mesh_thickness_ortho")
+    return mid, thick, count
+
+
+def mesh_thickness_host(verts, faces, x0, y0, h, W, H):
+    """dsu_mesh_thickness_ortho_host: mesh_thickness on numpy arrays, without a device."""
+    import numpy as np
+    x0, y0, h, W, H = _thickness_lattice(x0, y0, h, W, H)
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    mid, thick = np.zeros((H, W), np.float64), np.zeros((H, W), np.float64)
+    count = np.zeros((H, W), np.int32)
+    p = [a.ctypes.data_as(C.c_void_p) for a in (v, f, mid, thick, count)]
+    check(lib().dsu_mesh_thickness_ortho_host(p[0], len(v), p[1], len(f), x0, y0, h, W, H, p[2], p[3], p[4]),
+          "dsu_mesh_thickness_ortho_host")
+    return mid, thick, count
+
+
 # ------------------------------------------------------------------ binning of the staged mesh entry points
 class _BinnedPlan:
     """The binning half of a staged entry point (csrc/bin_sort.h): stage 0 counts the items per bin

@@ -1885,6 +1885,53 @@ int dsu_umbrella_implicit_solve(const int32_t* offsets, const int32_t* neighbour
 int dsu_distance_transform_l2_5x5(const uint8_t* mask, int32_t H, int32_t W, float* out);
 int dsu_skeletonize_lee_2d(const uint8_t* img, int32_t H, int32_t W, uint8_t* out);
 
+/* ------------------------------------------------------------------------------------
+ * Thickness map: where along z the inside of a mesh lies under every sample of an xy lattice.
+ * An extension of the reference (its skeletons come fitted from Mixamo):
+ * drawingspinup_amd/animate/rig.py lifts 2-D joint marks into the mesh with it.
+ * csrc/mesh_thickness.h holds the text, compiled for the kernel and for the host entry;
+ * tests/mesh_thickness_ref.py restates it in float64 numpy.
+ *
+ * verts (n_verts,3) f32, faces (n_faces,3) i32.  Lattice x0, y0, h > 0 (finite), W x H samples
+ * (0 .. DSU_THICKNESS_MAX_SIDE each): sample (r, c) is the point s = (x0 + (c + 1/2) h,
+ * y0 + (r + 1/2) h), its ray runs along z.
+ *
+ * Rule per sample, in float64 from the f32 inputs, in one operand order, no fused products.  A
+ * triangle with an index outside [0, n_verts) or a non-finite coordinate is ignored.  For triangle
+ * (a, b, c): area2 = (b.x - a.x)(c.y - a.y) - (b.y - a.y)(c.x - a.x); area2 == 0 skips it; area2 < 0
+ * swaps b and c (and negates area2).  E(p->q) = (q.x - p.x)(s.y - p.y) - (q.y - p.y)(s.x - p.x) for
+ * the edges a->b, b->c, c->a.  The sample is covered when every E > 0, or E == 0 on a top-left
+ * edge of the counter-clockwise triangle (dy < 0, or dy == 0 and dx < 0, with d = q - p): a sample
+ * on an edge that two triangles share is counted once where they face the same way, 0 or 2 times on
+ * a silhouette.  The crossing's z = ((E(b->c) / area2) a.z + (E(c->a) / area2) b.z) + (E(a->b) /
+ * area2) c.z.
+ * The crossings are ordered by (z, face index) and paired (0,1), (2,3), ...; an odd last one is
+ * dropped.  The thickest pair wins (z1 - z0), ties go to the lower z.
+ *   mid (H,W) f64        (z0 + z1) / 2 of that pair, 0 without a pair
+ *   thickness (H,W) f64  z1 - z0, 0 without a pair
+ *   count (H,W) i32      the number of crossings (odd: the mesh is open there)
+ * Deviation from a winding-number inside test: parity.  Closed components that interpenetrate
+ * cancel where they overlap; a marching-cubes export has none.
+ *
+ * dsu_mesh_thickness_ortho: device arrays.  The triangles come through the xy grid of
+ * dsu_zgrid_count / dsu_zgrid_fill over verts[faces] (grid_x0, grid_y0, grid_cell, g, offsets
+ * (g*g + 1), items (n_items)); any such grid gives the same result, a cell of 16 x 16 samples
+ * (ops.mesh_thickness) lets a workgroup walk one list.  One thread per sample, 256 = 16 x 16 per
+ * workgroup, the lists staged through LDS 256 triangles at a time; a thread holds no array of its
+ * crossings: walk k finds pair k as the two lowest (z, face) above pair k - 1.  No atomics:
+ * two runs give the same bits, and the bits of the host entry.
+ * dsu_mesh_thickness_ortho_host: a HOST function on HOST arrays, the same text; it bins the
+ * triangles itself. */
+#define DSU_THICKNESS_MAX_SIDE 4096
+int dsu_mesh_thickness_ortho(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                             float grid_x0, float grid_y0, float grid_cell, int32_t g,
+                             const int32_t* offsets, const int32_t* items, int64_t n_items, double x0,
+                             double y0, double h, int32_t W, int32_t H, double* mid, double* thickness,
+                             int32_t* count, void* stream);
+int dsu_mesh_thickness_ortho_host(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                                  double x0, double y0, double h, int32_t W, int32_t H, double* mid,
+                                  double* thickness, int32_t* count);
+
 #ifdef __cplusplus
 }
 #endif
