@@ -23,7 +23,7 @@ __device__ __forceinline__ bool finite_xy(const TriXY& t) {
 
 // 2-D edge functions in float64: w0 weighs vertex a (edge b->c), w1 b (c->a), w2 c (a->b).  The
 // operand order is part of the result (-ffp-contract=off): every user gets the same bits.
-__device__ __forceinline__ void edge_functions(const TriXY& t, double px, double py, double& w0,
+__host__ __device__ __forceinline__ void edge_functions(const TriXY& t, double px, double py, double& w0,
                                                double& w1, double& w2) {
   w0 = (px - t.bx) * (t.cy - t.by) - (py - t.by) * (t.cx - t.bx);
   w1 = (px - t.cx) * (t.ay - t.cy) - (py - t.cy) * (t.ax - t.cx);
@@ -31,7 +31,7 @@ __device__ __forceinline__ void edge_functions(const TriXY& t, double px, double
 }
 
 // inside or on the boundary, either orientation
-__device__ __forceinline__ bool covers(double w0, double w1, double w2) {
+__host__ __device__ __forceinline__ bool covers(double w0, double w1, double w2) {
   return (w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0);
 }
 
@@ -41,7 +41,7 @@ struct ZGrid {
   int32_t g;   // cells per axis
 };
 
-__device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g) {
+__host__ __device__ __forceinline__ int cell_of(float v, float v0, float inv_cell, int g) {
   int c = (int)floorf((v - v0) * inv_cell);
   return min(max(c, 0), g - 1);
 }

@@ -48,6 +48,11 @@ def parse(argv=None):
                     help="export.texture_source: what export.export_uv bakes into the atlas")
     ap.add_argument("--texture_seam", default=None, choices=["none", "level"],
                     help="export.texture_seam: level the fallback texels to the drawings (texture_source drawings)")
+    ap.add_argument("--texture_drawing_samples", type=int, default=None,
+                    help="export.texture_drawing_samples: points per texel side at which the drawings are read, 1..8 "
+                         "(texture_source drawings)")
+    ap.add_argument("--texture_drawing_filter", default=None, choices=["nearest", "bilinear"],
+                    help="export.texture_drawing_filter: how a drawing is read at a point (texture_source drawings)")
     for name in ("remeshing", "thinning", "smoothing", "shearing", "color_back_projection"):
         _bool_flag(ap, name)
     ap.add_argument("overrides", nargs="*", help="OmegaConf-style dotlist, e.g. trainer.max_steps=100")
@@ -61,7 +66,9 @@ def parse(argv=None):
                            ("thinning", ex, "thinning"), ("smoothing", ex, "smoothing"),
                            ("shearing", ex, "shearing"), ("thinning_type", ex, "thinning_type"),
                            ("color_back_projection", ex, "color_back_projection"),
-                           ("texture_source", ex, "texture_source"), ("texture_seam", ex, "texture_seam")):
+                           ("texture_source", ex, "texture_source"), ("texture_seam", ex, "texture_seam"),
+                           ("texture_drawing_samples", ex, "texture_drawing_samples"),
+                           ("texture_drawing_filter", ex, "texture_drawing_filter")):
         if getattr(args, key) is not None:
             dst[name] = getattr(args, key)
     if args.max_steps is not None:
@@ -85,6 +92,14 @@ def parse(argv=None):
         ap.error(f"export.texture_seam must be 'none' or 'level', not {seam!r}")
     if seam == "level" and source != "drawings":
         ap.error("texture_seam 'level' needs texture_source 'drawings'")
+    n = ex.get("texture_drawing_samples", 1)
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
+        ap.error(f"export.texture_drawing_samples must be an integer 1..8, not {n!r}")
+    how = ex.get("texture_drawing_filter", "nearest")
+    if how not in ("nearest", "bilinear"):
+        ap.error(f"export.texture_drawing_filter must be 'nearest' or 'bilinear', not {how!r}")
+    if ("texture_drawing_samples" in ex or "texture_drawing_filter" in ex) and source != "drawings":
+        ap.error("texture_drawing_samples / texture_drawing_filter need texture_source 'drawings'")
     return args, conf
 
 
@@ -153,7 +168,9 @@ def recon(uid, thinning, conf, dev):
                     # the field is the drawings' fallback too: what neither view sees comes from the network
                     texture_field=field_colours(system.model) if source in ("field", "drawings") else None,
                     texture_samples=int(ex.get("texture_samples", 2)),
-                    texture_seam=str(ex.get("texture_seam", "none")))
+                    texture_seam=str(ex.get("texture_seam", "none")),
+                    texture_drawing_samples=int(ex.get("texture_drawing_samples", 1)),
+                    texture_drawing_filter=str(ex.get("texture_drawing_filter", "nearest")))
     torch.save(system.model.state_dict(), os.path.join(out, f"it{system.global_step}.ckpt"))
     return path
 

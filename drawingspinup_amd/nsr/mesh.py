@@ -973,7 +973,8 @@ def write_obj_textured(path, verts, faces, uvs, image, name):
 
 def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False, shearing=False,
              color_back_projection=None, thinning=None, export_uv=False, texture_size=1024,
-             texture_source="vertex", texture_field=None, texture_samples=2, texture_seam="none"):
+             texture_source="vertex", texture_field=None, texture_samples=2, texture_seam="none",
+             texture_drawing_samples=1, texture_drawing_filter="nearest"):
     """save_mesh (mesh_utils.py:25-73) = post_process_mesh + write_obj, or with export_uv
     (mesh_utils.py:65-67) + uv_mapping and the textured triple named after the file.
     texture_source: "vertex" bakes the vertex colours (the reference's texture); "drawings" (an
@@ -986,7 +987,11 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
     field bake as its fallback; "vertex" ignores it.
     texture_seam: "level" (needs texture_source="drawings") levels the fallback texels to the
     drawings where the two meet (nsr/uv.bake_drawings, seam="level"); "none" composes them as they
-    are."""
+    are.
+    texture_drawing_samples, texture_drawing_filter (other than 1 and "nearest" they need
+    texture_source="drawings"): the drawings are read at that many points per texel side (1..8),
+    each at its "nearest" pixel or "bilinear", and averaged (nsr/uv.bake_drawings, samples and
+    pixel_filter); texture_samples stays the field's alone."""
     if texture_source not in ("vertex", "drawings", "field"):
         raise ValueError("texture_source must be 'vertex', 'drawings' or 'field'")
     if texture_seam not in ("none", "level"):
@@ -994,6 +999,13 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
     drawings = texture_source == "drawings"
     if texture_seam == "level" and not drawings:
         raise ValueError("texture_seam='level' needs texture_source='drawings'")
+    if isinstance(texture_drawing_samples, bool) or not isinstance(texture_drawing_samples, int) or \
+            not 1 <= texture_drawing_samples <= 8:
+        raise ValueError("texture_drawing_samples must be an integer 1..8")
+    if texture_drawing_filter not in ("nearest", "bilinear"):
+        raise ValueError("texture_drawing_filter must be 'nearest' or 'bilinear'")
+    if (texture_drawing_samples != 1 or texture_drawing_filter != "nearest") and not drawings:
+        raise ValueError("texture_drawing_samples / texture_drawing_filter need texture_source='drawings'")
     if drawings and not (export_uv and color_back_projection is not None):
         raise ValueError("texture_source='drawings' needs export_uv=True and the color_back_projection images")
     if texture_source == "field" and not (export_uv and callable(texture_field)):
@@ -1007,7 +1019,8 @@ def save_obj(path, verts, faces, colors=None, ortho_scale=1.35, smoothing=False,
             raise ValueError("export_uv needs vertex colours")
         from .uv import uv_mapping
         name = os.path.splitext(os.path.basename(path))[0]
-        projection = dict(color_back_projection, positions=frame[0], seam=texture_seam) if drawings else None
+        projection = dict(color_back_projection, positions=frame[0], seam=texture_seam,
+                          samples=texture_drawing_samples, filter=texture_drawing_filter) if drawings else None
         field = None
         if texture_source != "vertex" and texture_field is not None:
             field = {"positions": verts.detach().float().cpu().numpy(), "eval_colours": texture_field,

@@ -34,9 +34,10 @@ per texel, which pixel of the front or back drawing the texel's surface point se
 nsr/mesh_post.color_projection asks per vertex (same frame, same masks, same nearest-pixel read) —
 and keeps the vertex-colour bake where neither view sees it (dsu_uv_project in include/dsu_hip.h
 has the rule in full).  What remains visible of the composition: a seam where projected and
-fallback texels meet (unless it is levelled, below), nearest-pixel sampling (no bilinear or area
-filter), and a fallback band along the silhouette as wide as the erosion of the masks (19 pixels of
-the 2048^2 drawings).
+fallback texels meet (unless it is levelled, below), nearest-pixel sampling by default (samples > 1
+or pixel_filter="bilinear" reads samples x samples points per texel and averages them:
+dsu_uv_project_area), and a fallback band along the silhouette as wide as the erosion of the masks
+(19 pixels of the 2048^2 drawings).
 
 Field.  bake_field asks the network the export has just optimised instead: every covered texel's
 surface point (samples x samples of them, a texel wide) goes back to the field's own frame through
@@ -84,6 +85,7 @@ Z_TOLERANCE = 1e-4
 SEAM_MIN_WEIGHT = 1 << 20
 SEAM_TOL = 1e-10
 SEAM_MAX_ITERS = 20000
+PIXEL_FILTERS = ("nearest", "bilinear")     # how bake_drawings reads a drawing at a sample point
 
 
 # ------------------------------------------------------------------ host parts
@@ -215,18 +217,32 @@ class DeviceBackend:
         from .. import ops
         return ops.uv_dilate(image, covered, rounds)[0]
 
-    def project(self, uvs, indices, positions, face_id, color_front, mask_front, color_back, z_tolerance,
-                erode, cells_per_axis=None):
-        """Mask preparation as color_projection's + dsu_uv_project -> image (S,S,3) u8, source (S,S) u8."""
-        from .. import ops
+    def _projection_inputs(self, uvs, indices, positions, color_front, mask_front, color_back, erode):
+        """-> (uvs, indices, positions) and (color_front, mask_front, color_back, mask_back) on the
+        device, the masks prepared as color_projection prepares them: what ops.uv_project takes before
+        and after face_id."""
         from .mesh_post import projection_masks
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(_host(a), dt)).to(self.dev)
         pos, ind = t(positions, np.float32), t(indices, np.int64)
         cf, mf, cb = (torch.as_tensor(a).to(self.dev, torch.uint8).contiguous()
                       for a in (color_front, mask_front, color_back))
         front, back = projection_masks(pos, ind, mf, res=cf.shape[0], ksize=int(erode))
-        return ops.uv_project(t(uvs, np.float32), ind, pos, face_id, cf, front, cb, back, z_tolerance,
-                              cells_per_axis=cells_per_axis)
+        return (t(uvs, np.float32), ind, pos), (cf, front, cb, back)
+
+    def project(self, uvs, indices, positions, face_id, color_front, mask_front, color_back, z_tolerance,
+                erode, cells_per_axis=None):
+        """Mask preparation as color_projection's + dsu_uv_project -> image (S,S,3) u8, source (S,S) u8."""
+        from .. import ops
+        atlas, images = self._projection_inputs(uvs, indices, positions, color_front, mask_front, color_back, erode)
+        return ops.uv_project(*atlas, face_id, *images, z_tolerance, cells_per_axis=cells_per_axis)
+
+    def project_area(self, uvs, indices, positions, face_id, color_front, mask_front, color_back, z_tolerance,
+                     erode, samples, pixel_filter, cells_per_axis=None):
+        """project with dsu_uv_project_area in dsu_uv_project's place -> image (S,S,3) u8, source (S,S) u8."""
+        from .. import ops
+        atlas, images = self._projection_inputs(uvs, indices, positions, color_front, mask_front, color_back, erode)
+        return ops.uv_project_area(*atlas, face_id, *images, z_tolerance, samples, pixel_filter,
+                                   cells_per_axis=cells_per_axis)[:2]
 
     def field_points(self, uvs, indices, positions, face_id, texels, samples):
         from .. import ops
@@ -385,7 +401,8 @@ def seam_offsets(num, den, group_faces, backend):
 
 def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_back_u8, fallback_colours,
                   size=1024, gutter=2, z_tolerance=Z_TOLERANCE, erode=19, device=None, backend=None,
-                  return_maps=False, fallback_image=None, seam="none", groups=None, group_faces=None):
+                  return_maps=False, fallback_image=None, seam="none", groups=None, group_faces=None, samples=1,
+                  pixel_filter="nearest"):
     """The atlas with the drawings projected into it: positions (V',3) are the atlas vertices in
     color_projection's frame (x right, y up, z front, inside [-0.5, 0.5]: after thinning and
     smoothing, before shear and ortho_scale), color_*_u8 (res,res,3) and mask_front_u8 (res,res) the
@@ -398,16 +415,28 @@ def bake_drawings(uvs, indices, positions, color_front_u8, mask_front_u8, color_
     seam: "none" composes with a hard where(source > 0, drawing, fallback); "level" leaves the
     drawing texels alone and adds to the fallback texels a smooth offset that meets the drawing at
     the border (dsu_uv_seam_gather, seam_offsets, dsu_uv_seam_apply); it needs groups (V') and
-    group_faces (F,3) from seam_groups."""
+    group_faces (F,3) from seam_groups.
+    samples, pixel_filter: the drawings read at samples x samples points per texel (1..8), each at its
+    "nearest" pixel or "bilinear", and averaged (dsu_uv_project_area); 1 and "nearest" are
+    dsu_uv_project, one nearest pixel per texel."""
     if seam not in ("none", "level"):
         raise ValueError("seam must be 'none' or 'level'")
+    if not 1 <= int(samples) <= 8:
+        raise ValueError("samples must be 1..8")
+    if pixel_filter not in PIXEL_FILTERS:
+        raise ValueError("pixel_filter must be 'nearest' or 'bilinear'")
     if seam == "level" and (groups is None or group_faces is None):
         raise ValueError("seam='level' needs groups and group_faces (seam_groups)")
     be = backend if backend is not None else DeviceBackend(device)
     uvs, indices = np.asarray(uvs, np.float32), np.asarray(indices, np.int64)
     img, fid, _ = be.bake(uvs, indices, np.asarray(fallback_colours, np.float32).reshape(-1, 3), int(size))
-    proj, src = be.project(uvs, indices, np.asarray(_host(positions), np.float32).reshape(-1, 3), fid,
-                           color_front_u8, mask_front_u8, color_back_u8, float(z_tolerance), int(erode))
+    pos = np.asarray(_host(positions), np.float32).reshape(-1, 3)
+    if int(samples) > 1 or pixel_filter != "nearest":
+        proj, src = be.project_area(uvs, indices, pos, fid, color_front_u8, mask_front_u8, color_back_u8,
+                                    float(z_tolerance), int(erode), int(samples), pixel_filter)
+    else:
+        proj, src = be.project(uvs, indices, pos, fid, color_front_u8, mask_front_u8, color_back_u8,
+                               float(z_tolerance), int(erode))
     if fallback_image is not None:
         img = torch.as_tensor(_host(fallback_image)).to(src.device) if torch.is_tensor(src) else _host(fallback_image)
         if tuple(img.shape) != tuple(proj.shape):
@@ -487,9 +516,10 @@ def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=
     Returns the textured mesh as a dict (verts (V',3) f64, faces (M,3) i64, uvs (V',2) f32, image
     (size,size,3) u8, name) — what trimesh.Trimesh + TextureVisuals hold in the reference.
     projection: dict(positions (V,3) in the order of v_np and in color_projection's frame,
-    color_front, mask_front, color_back[, z_tolerance, erode, seam]) bakes with bake_drawings, the
-    vertex colours being the fallback (seam "level": the fallback texels levelled to the drawings,
-    the groups built from v_np, faces and vmapping); None = the vertex colours alone.
+    color_front, mask_front, color_back[, z_tolerance, erode, seam, samples, filter]) bakes with
+    bake_drawings, the vertex colours being the fallback (seam "level": the fallback texels levelled
+    to the drawings, the groups built from v_np, faces and vmapping; samples / filter: bake_drawings'
+    samples / pixel_filter); None = the vertex colours alone.
     field: dict(positions (V,3) in the order of v_np and in the field's frame, eval_colours[,
     samples, chunk]) bakes with bake_field, the vertex colours staying where no sample is valid; with
     `projection` as well the drawings are composed over the field bake instead of the vertex bake."""
@@ -514,5 +544,6 @@ def uv_mapping(v_np, faces, vert_colors, save_name, size=1024, gutter=2, device=
                               pr["mask_front"], pr["color_back"], colours, size, gutter,
                               z_tolerance=pr.get("z_tolerance", Z_TOLERANCE), erode=pr.get("erode", 19),
                               device=device, backend=backend, fallback_image=fallback_image, seam=seam,
-                              groups=groups, group_faces=group_faces)
+                              groups=groups, group_faces=group_faces, samples=pr.get("samples", 1),
+                              pixel_filter=pr.get("filter", "nearest"))
     return {"verts": v_np[vmapping], "faces": indices, "uvs": uvs, "image": image, "name": save_name}

@@ -1810,6 +1810,41 @@ def uv_project(uvs, indices, positions, face_id, color_front, mask_front, color_
     (S,S) i32 from uv_bake, color_* (res,res,3) u8 and the eroded masks (res,res) u8, all on the
     device.  `grid`: the ZGrid over positions[indices], built here when absent (`cells_per_axis`
     overrides its resolution).  -> image (S,S,3) u8, source (S,S) u8 (0 none, 1 front, 2 back)."""
+    return _uv_project(None, uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
+                       z_tolerance, grid, cells_per_axis)
+
+
+def uv_area_cells(n_faces):
+    """Cells per axis of the z-grid uv_project_area builds when it is handed none: three times
+    ZGrid's default.  The kernel's time goes into the edge functions of the listed triangles at
+    every sub-sample, so shorter lists pay: on the ~50 000-face probe mesh 160 / 320 / 480 / 640
+    cells give 1470 / 1141 / 977 / 1122 us at s = 4 (tools/uv_project_area_probe.py --cells); the
+    result does not depend on the grid."""
+    import math
+    return int(min(1024, max(8, 3.0 * math.sqrt(max(n_faces, 1) / 2.0))))
+
+
+UV_PIXEL_FILTERS = ("nearest", "bilinear")             # the `filter` argument of dsu_uv_project_area
+
+
+def uv_project_area(uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
+                    z_tolerance, samples, pixel_filter="nearest", grid=None, cells_per_axis=None):
+    """dsu_uv_project_area (include/dsu_hip.h, UV export j.): uv_project with the drawings read at
+    samples x samples points per texel (1..8), each at its nearest pixel or bilinearly, and averaged.
+    Arguments as uv_project.  -> image (S,S,3) u8, source (S,S) u8, count (S,S) u8: the sub-samples
+    that passed (0 with source > 0: the texel's own point decided)."""
+    s = int(samples)
+    if not 1 <= s <= 8:
+        raise ValueError("samples must be 1..8")
+    if pixel_filter not in UV_PIXEL_FILTERS:
+        raise ValueError("pixel_filter must be 'nearest' or 'bilinear'")
+    return _uv_project((s, UV_PIXEL_FILTERS.index(pixel_filter)), uvs, indices, positions, face_id, color_front,
+                       mask_front, color_back, mask_back, z_tolerance, grid, cells_per_axis)
+
+
+def _uv_project(area, uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
+                z_tolerance, grid, cells_per_axis):
+    """uv_project (area None) and uv_project_area (area = (s, filter)): one preparation of the arguments."""
     uvs, positions = _f32c(uvs), _f32c(positions)
     indices = indices.to(torch.int32).contiguous()
     V, M, S, dev = uvs.shape[0], indices.shape[0], face_id.shape[0], uvs.device
@@ -1825,16 +1860,22 @@ def uv_project(uvs, indices, positions, face_id, color_front, mask_front, color_
         xy = tris[..., :2].reshape(-1, 2)
         xy = xy[torch.isfinite(xy).all(1)]                   # a non-finite vertex must not set the extent
         lo, hi = (xy.amin(0).tolist(), xy.amax(0).tolist()) if xy.shape[0] else ([0.0, 0.0], [0.0, 0.0])
+        if area is not None and cells_per_axis is None:
+            cells_per_axis = uv_area_cells(M)
         grid = ZGrid(tris, lo, hi, cells_per_axis=cells_per_axis)
     image = torch.empty((S, S, 3), dtype=torch.uint8, device=dev)
     source = torch.empty((S, S), dtype=torch.uint8, device=dev)
     gargs = (ptr(grid.data, torch.float32),) + grid.args() if M else (None, 0.0, 0.0, 1.0, 1, None, None)
-    check(lib().dsu_uv_project(ptr(uvs), ptr(indices), ptr(positions), V, M, S,
-                               ptr(face_id.contiguous(), torch.int32), *gargs,
-                               ptr(color_front.contiguous()), ptr(mask_front.contiguous()),
-                               ptr(color_back.contiguous()), ptr(mask_back.contiguous()), res,
-                               float(z_tolerance), ptr(image), ptr(source), stream()), "dsu_uv_project")
-    return image, source
+    args = (ptr(uvs), ptr(indices), ptr(positions), V, M, S, ptr(face_id.contiguous(), torch.int32), *gargs,
+            ptr(color_front.contiguous()), ptr(mask_front.contiguous()), ptr(color_back.contiguous()),
+            ptr(mask_back.contiguous()), res, float(z_tolerance))
+    if area is None:
+        check(lib().dsu_uv_project(*args, ptr(image), ptr(source), stream()), "dsu_uv_project")
+        return image, source
+    count = torch.empty((S, S), dtype=torch.uint8, device=dev)
+    check(lib().dsu_uv_project_area(*args, area[0], area[1], ptr(image), ptr(source), ptr(count), stream()),
+          "dsu_uv_project_area")
+    return image, source, count
 
 
 def uv_field_points(uvs, indices, positions, face_id, texels, samples):

@@ -1782,7 +1782,53 @@ int dsu_corrective_smooth_host(const float* skinned, const int32_t* rep, const i
  *
  * dsu_uv_seam_gather_host / dsu_uv_seam_apply_host: HOST functions on HOST arrays — the same two
  * texts (csrc/uv_seam.h) compiled for the CPU (a plain loop over the texels and a plain +=), with
- * the same argument checks. */
+ * the same argument checks.
+ *
+ * j. dsu_uv_project_area: e. with the drawings read at s x s points per texel instead of one (an
+ * extension; csrc/uv_project_area.hip).  At 1024^2 texels over 2048^2 drawings a texel is about
+ * three pixels wide and e. reads one pixel in ten: ink lines alias before any later filter sees
+ * them.  The inputs are exactly e.'s, plus s (sub-samples per axis, 1..8) and filter (0 nearest, 1
+ * bilinear).  Outputs image (size, size, 3) u8, source (size, size) u8 as in e., and count (size,
+ * size) u8, which may be NULL.  One thread per texel, one workgroup per 16x16 tile.  Everything in
+ * float64 from the f32 / u8 inputs, in this operand order:
+ *   1. the texel (row r, column c) with m = face_id[r][c]; m outside [0, n_faces), or an index of m
+ *      outside [0, n_verts), projects nothing.
+ *   2. the view is a property of the face: with nz = (Pbx - Pax)(Pcy - Pay) - (Pby - Pay)(Pcx - Pax)
+ *      as in e. step 3, front (sign +1) if nz > 0, back (sign -1) if nz < 0, otherwise none (this is
+ *      e.'s "front, then back, first that passes": a face passes the facing test of at most one
+ *      view).
+ *   3. sub-sample j = jy s + jx sits at (x, y) = (c + o(jx), (size - 1 - r) + o(jy)), o(i) =
+ *      (2 i + 1 - s) / (2 s): the grid of f.  w0, w1, w2, area and b_i = w_i / area as in c., NOT
+ *      clamped: a sub-sample outside face m lies on the affine extension of m (no second raster).
+ *      p = (b0 Pa + b1 Pb) + b2 Pc per coordinate.
+ *   4. a sub-sample PASSES when p is finite; the mask of its NEAREST pixel (X, Y of e., half to even,
+ *      clamped) is > 0; and it is unoccluded by e.'s test at (px, py, pz): the cell of ((float)px,
+ *      (float)py), f != m skipped, the same z_tolerance.
+ *   5. a passing sub-sample's value per channel: filter 0, the byte at [Y][X].  Filter 1, with
+ *      fx = (+-px + 0.5)(res - 1) and fy = (-py + 0.5)(res - 1), both clamped to [0, res - 1],
+ *      x0 = min(floor(fx), max(res - 2, 0)), x1 = min(x0 + 1, res - 1), tx = fx - x0, likewise y0, y1,
+ *      ty:  value = ((1 - ty)((1 - tx) c00 + tx c10)) + (ty ((1 - tx) c01 + tx c11)), c_xy the byte at
+ *      [y_][x_].  The mask is still tested at the nearest pixel only (the erosion keeps the other
+ *      three inside the drawing).
+ *   6. n = the number of passing sub-samples; count = n.  If n = 0, one more sample at the texel's
+ *      own point (o = 0) is put through steps 3-5 (for odd s it would repeat the centre sample and
+ *      change nothing); if that fails as well, source = 0 and image = 0.
+ *   7. otherwise source = 1 (front) or 2 (back); per channel the values are summed in ascending j and
+ *      the byte is floor(sum / n + 0.5) clipped to [0, 255], n being 1 when the extra sample was used.
+ * It follows that (a) s = 1, filter = 0 is e. byte for byte; (b) wherever e. gives source != 0 this
+ * entry gives the same source for any s and filter (the texel's own point is a sample of every odd
+ * grid and the extra sample of every even one), so the projected set can only grow; (c) the result
+ * does not depend on the grid, for e.'s reason.  The kernel takes the sub-samples four at a time,
+ * walks each cell the four points name once and tests every listed triangle against all of them: a
+ * triangle met through another point's cell, or twice, changes nothing, since occlusion is an OR
+ * and a triangle that covers a point is in that point's own list.  No atomics: two runs give the
+ * same bits.
+ * DSU_EINVAL before any launch: as e., and s outside 1..8 or filter outside {0, 1}.  n_faces == 0:
+ * DSU_OK, image, source and count (when given) zeroed, the other pointers unread.
+ *
+ * dsu_uv_project_area_host: a HOST function on HOST arrays (tris and the grid arrays included; a
+ * grid of one cell, g = 1 with offsets [0, n_faces] and items 0 .. n_faces - 1, is valid by (c)) —
+ * the same text (csrc/uv_project_area.h) compiled for the CPU, with the same argument checks. */
 #define DSU_UV_COUNT 0
 #define DSU_UV_FILL 1
 #define DSU_UV_RASTER 2
@@ -1829,6 +1875,18 @@ int dsu_uv_seam_apply_host(const float* uvs, const int32_t* indices, const int32
                            int64_t n_faces, int64_t n_groups, int32_t size, const int32_t* face_id,
                            const uint8_t* source, const uint8_t* proj, const uint8_t* fallback, const double* d,
                            uint8_t* image);
+int dsu_uv_project_area(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                        int64_t n_faces, int32_t size, const int32_t* face_id, const float* tris, float x0, float y0,
+                        float cell, int32_t g, const int32_t* offsets, const int32_t* items,
+                        const uint8_t* color_front, const uint8_t* mask_front, const uint8_t* color_back,
+                        const uint8_t* mask_back, int32_t res, double z_tolerance, int32_t s, int32_t filter,
+                        uint8_t* image, uint8_t* source, uint8_t* count, void* stream);
+int dsu_uv_project_area_host(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
+                             int64_t n_faces, int32_t size, const int32_t* face_id, const float* tris, float x0,
+                             float y0, float cell, int32_t g, const int32_t* offsets, const int32_t* items,
+                             const uint8_t* color_front, const uint8_t* mask_front, const uint8_t* color_back,
+                             const uint8_t* mask_back, int32_t res, double z_tolerance, int32_t s, int32_t filter,
+                             uint8_t* image, uint8_t* source, uint8_t* count);
 
 /* remesh() (instant_nsr/utils/mesh_utils.py:10-22, called by models/geometry.py:63-64 with
  * face_count 50000): quadric edge-collapse decimation of a triangle mesh down to `target_faces`
