@@ -3,7 +3,8 @@
 // ResnetBlock2D (norm1/norm2 + nonlinearity), TransformerMV2DModel.norm
 // (mvdiffusion/models/transformer_mv2d.py:304), BasicMVTransformerBlock.norm1/2/3/norm_joint_mid
 // (:532-625) and FeedForward(GEGLU) (:483)).  All HBM-bound: every kernel reads its input once
-// with 16-byte accesses and keeps statistics in f32.
+// with 16-byte accesses and keeps statistics in f32; no variance is taken as E[x^2] - E[x]^2 of
+// the raw values (GroupNorm: centred or shifted per kernel, see each; LayerNorm: centred).
 #include "common.h"
 
 namespace {
@@ -13,6 +14,18 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ---- GroupNorm statistics: per (image, channel) partial sums over a slab of pixels, folded
 // to per-(image, group) sum / sum-of-squares with one atomic pair per workgroup and group.
+// Both sums are taken of x - K, K = gn_shift() being the group's own first element.  Sums of x and
+// x*x lose mean^2/var of their digits (at mean 1000, std 2 the f32 result is noise and clamps to
+// 0); the shifted ones lose (K - mean)^2/var instead, which is what the group's offset from zero
+// no longer enters.  The limit: K is ONE element.  Tens of standard deviations from the mean cost
+// a few hundred of f32's 1.7e7 and are harmless; an element thousands of standard deviations out,
+// sitting exactly at pixel 0 of the group's first channel, would cancel as the raw sums did.
+// out must not alias x: gn_apply_kernel reads K from x while other threads write out.
+__device__ __forceinline__ float gn_shift(const f16* __restrict__ x, int n, int HW, int C, int cpg,
+                                          int g) {
+  return (float)x[(size_t)n * HW * C + g * cpg];
+}
+
 // grid = (pixel slabs, B); block = 256 threads; thread t owns 8-channel group (t % C8) of
 // pixels t / C8, t / C8 + 256 / C8 ...   (C8 = C/8 <= 256)
 __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x, int HW, int C,
@@ -29,17 +42,20 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
   __syncthreads();
   const int p0 = blockIdx.x * pix_per_block;
   const int p1 = min(p0 + pix_per_block, HW);
+  const int cpg = C / G;
   for (int sp = 0; sp < nsplit; ++sp) {
     const int cg = sp * lanes_per_pix + threadIdx.x % lanes_per_pix;
-    float s[8], q[8];
+    float s[8], q[8], K[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.0f;
     if (pl < pix_par) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) K[e] = gn_shift(x, n, HW, C, cpg, (cg * 8 + e) / cpg);
       for (int p = p0 + pl; p < p1; p += pix_par) {
         const f16x8 v = *reinterpret_cast<const f16x8*>(x + ((size_t)n * HW + p) * C + cg * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float f = (float)v[e];
+          const float f = (float)v[e] - K[e];
           s[e] += f;
           q[e] += f * f;
         }
@@ -52,7 +68,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
     }
   }
   __syncthreads();
-  const int cpg = C / G;
   for (int g = threadIdx.x; g < G; g += 256) {
     float ss = 0.0f, qq = 0.0f;
     for (int c = 0; c < cpg; ++c) {
@@ -83,12 +98,19 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
     const f16x8 gm = *reinterpret_cast<const f16x8*>(gamma + c0);
     const f16x8 bt = *reinterpret_cast<const f16x8*>(beta + c0);
     f16x8 o;
+    int g_cur = -1;
+    float mean = 0.0f, rstd = 0.0f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int g = (c0 + e) / cpg;
-      const float mean = stats[((size_t)n * G + g) * 2] * inv_cnt;
-      const float var = fmaxf(stats[((size_t)n * G + g) * 2 + 1] * inv_cnt - mean * mean, 0.0f);
-      float y = ((float)v[e] - mean) * rsqrtf(var + eps) * (float)gm[e] + (float)bt[e];
+      if (g != g_cur) {   // the shifted sums of gn_stats_kernel: mean = K + S/n, var = Q/n - (S/n)^2
+        g_cur = g;
+        const float ds = stats[((size_t)n * G + g) * 2] * inv_cnt;
+        const float var = fmaxf(stats[((size_t)n * G + g) * 2 + 1] * inv_cnt - ds * ds, 0.0f);
+        mean = gn_shift(x, n, HW, C, cpg, g) + ds;
+        rstd = rsqrtf(var + eps);
+      }
+      float y = ((float)v[e] - mean) * rstd * (float)gm[e] + (float)bt[e];
       if (do_silu) y = silu(y);
       o[e] = (f16)y;
     }
@@ -99,7 +121,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
 // ---- small tensors (every GroupNorm of the UNet): ONE launch, one workgroup per (image, group).
 // The memset + statistics + apply sequence above costs three dependent launches (25-60 us of
 // mostly launch latency on 0.1-6 MB tensors); here the group's HW x cpg elements (<= 64 KB, L2
-// resident) are read twice by the same workgroup.
+// resident) are read twice by the same workgroup.  Variance: where the group's values stay in
+// registers, the centred sum of (x - mean)^2 over them once the mean is known; where they are read
+// a second time, the shifted sums of x - K as in gn_stats_kernel.
 __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restrict__ x,
                                                              const f16* __restrict__ gamma,
                                                              const f16* __restrict__ beta, int HW,
@@ -109,7 +133,7 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restri
   // half2 pairs; up to GN_KEEP pairs per thread stay in registers between the two passes
   constexpr int GN_KEEP = 16;
   typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  __shared__ float red[2][4];
+  __shared__ float red[3][4];
   const int n = blockIdx.x / G, g = blockIdx.x % G;
   const int cpg = C / G, cp2 = cpg >> 1;
   const int cnt2 = HW * cp2;
@@ -117,7 +141,7 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restri
   f16* ob = out + (size_t)n * HW * C + g * cpg;
   const bool keep = cnt2 <= GN_KEEP * 256;
   f16x2 kv[GN_KEEP];
-  float s = 0.0f, q = 0.0f;
+  float s = 0.0f, q = 0.0f, shift = 0.0f;
   if (keep) {
 #pragma unroll
     for (int k = 0; k < GN_KEEP; ++k) {
@@ -129,15 +153,14 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restri
         v = *reinterpret_cast<const f16x2*>(xb + (size_t)p * C + 2 * c);
       }
       kv[k] = v;
-      const float f0 = (float)v[0], f1 = (float)v[1];
-      s += f0 + f1;
-      q += f0 * f0 + f1 * f1;
+      s += (float)v[0] + (float)v[1];
     }
   } else {
+    shift = (float)xb[0];
     for (int e = threadIdx.x; e < cnt2; e += 256) {
       const int p = e / cp2, c = e - p * cp2;
       const f16x2 v = *reinterpret_cast<const f16x2*>(xb + (size_t)p * C + 2 * c);
-      const float f0 = (float)v[0], f1 = (float)v[1];
+      const float f0 = (float)v[0] - shift, f1 = (float)v[1] - shift;
       s += f0 + f1;
       q += f0 * f0 + f1 * f1;
     }
@@ -153,10 +176,28 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restri
   }
   __syncthreads();
   s = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-  q = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
   const float inv_cnt = 1.0f / ((float)HW * (float)cpg);
-  const float mean = s * inv_cnt;
-  const float var = fmaxf(q * inv_cnt - mean * mean, 0.0f);
+  const float ds = s * inv_cnt;
+  const float mean = shift + ds;
+  float var;
+  if (keep) {
+    q = 0.0f;
+#pragma unroll
+    for (int k = 0; k < GN_KEEP; ++k) {
+      if (threadIdx.x + 256 * k < cnt2) {          // the zero padding is no part of the group
+        const float d0 = (float)kv[k][0] - mean, d1 = (float)kv[k][1] - mean;
+        q += d0 * d0 + d1 * d1;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    if ((threadIdx.x & 63) == 0) red[2][threadIdx.x >> 6] = q;
+    __syncthreads();
+    var = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * inv_cnt;
+  } else {
+    q = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    var = fmaxf(q * inv_cnt - ds * ds, 0.0f);
+  }
   const float rstd = rsqrtf(var + eps);
   auto apply = [&](int e, f16x2 v) {
     const int p = e / cp2, c = e - p * cp2;
@@ -193,36 +234,96 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const f16* __restri
 // Here a thread keeps its <= GS_KEEP chunks in registers between the statistics and the apply pass.
 constexpr int GS_KEEP = 16;
 constexpr int GS_THREADS = 1024;
+
+// sum over each row of 16 lanes, in all of its lanes, on the VALU's lane-permute path (DPP): the
+// LDS permutes behind __shfl_xor were 80 LDS instructions per wave of gn_super_kernel, 16 waves deep
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float t) {
+  return t + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float row_sum(float v) {
+  v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]: lane ^ 1
+  v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]: lane ^ 2
+  v = dpp_add<0x141>(v);   // row_half_mirror: 7 - lane within 8
+  v = dpp_add<0x140>(v);   // row_mirror: 15 - lane within 16
+  return v;
+}
+// sum over the wave, uniform
+__device__ __forceinline__ float wave_sum(float v) {
+  const int r = __float_as_int(row_sum(v));
+  return (__int_as_float(__builtin_amdgcn_readlane(r, 0)) + __int_as_float(__builtin_amdgcn_readlane(r, 16))) +
+         (__int_as_float(__builtin_amdgcn_readlane(r, 32)) + __int_as_float(__builtin_amdgcn_readlane(r, 48)));
+}
 __global__ __launch_bounds__(GS_THREADS) void gn_super_kernel(const f16* __restrict__ x,
                                                               const f16* __restrict__ gamma,
                                                               const f16* __restrict__ beta, int HW,
                                                               int C, int cpg, int SG, float eps,
                                                               int do_silu, f16* __restrict__ out) {
-  __shared__ float red[GS_THREADS / 64][8];
-  __shared__ float stat[8];                       // mean[4] | rstd[4]
+  static_assert(GS_THREADS / 64 == 16, "the cross-wave sums below fold 16 partials");
+  __shared__ float red[GS_THREADS / 64][8];       // per wave: shifted sum[4] | shifted sum of squares[4]
   const int nsg = C / SG, CH = SG >> 3;
   const int n = blockIdx.x / nsg, c_base = (blockIdx.x % nsg) * SG;
   const int total = HW * CH;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const f16* xb = x + (size_t)n * HW * C + c_base;
   f16* ob = out + (size_t)n * HW * C + c_base;
   f16x8 kv[GS_KEEP];
-  int off[GS_KEEP];                                // element offset of the chunk, -1 = none
+  auto pick = [](const float (&t)[4], int g) {
+    return g == 0 ? t[0] : (g == 1 ? t[1] : (g == 2 ? t[2] : t[3]));
+  };
+  // sums of x - K, K the group's own first element (see gn_shift): nothing cancels off zero, and
+  // the statistics stay one pass over the registers with one workgroup-wide reduction
+  float K[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    // workgroup-uniform, so read through the scalar unit as the aligned 32-bit word that holds it
+    // (as vector loads these were 64 wave instructions per workgroup, beside 16-80 for the chunks);
+    // unconditional: a group the super-group lacks reads group 0's
+    const size_t i = (size_t)n * HW * C + c_base + (g * cpg < SG ? g * cpg : 0);
+    const uint32_t w = reinterpret_cast<const uint32_t*>(x)[i >> 1];
+    const uint16_t h = (uint16_t)(i & 1 ? w >> 16 : w);
+    f16 hv;
+    __builtin_memcpy(&hv, &h, sizeof(hv));
+    K[g] = (float)hv;
+  }
   float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+  // chunk e = threadIdx.x + GS_THREADS k is chunk c of pixel p.  One division per thread; from k
+  // to k + 1 the pair moves by a workgroup-uniform step, and a channel's group (at most 4 per
+  // super-group) comes from compares: the kernel is bound by its instruction count, not by HBM
+  const int dp = GS_THREADS / CH, dc = GS_THREADS - dp * CH;
+  const int p_first = (int)threadIdx.x / CH, c_first = (int)threadIdx.x - p_first * CH;
+  auto step = [&](int& p, int& c) {
+    p += dp;
+    c += dc;
+    if (c >= CH) { c -= CH; ++p; }
+  };
+  auto group_of = [&](int c8) { return (c8 >= cpg) + (c8 >= 2 * cpg) + (c8 >= 3 * cpg); };
+  // every chunk is requested before the first is used: the loads overlap instead of each being
+  // waited for in turn
+  int p = p_first, c = c_first;
+#pragma unroll
+  for (int k = 0; k < GS_KEEP; ++k) {
+    if ((int)threadIdx.x + GS_THREADS * k < total) {
+      kv[k] = *reinterpret_cast<const f16x8*>(xb + (p * C + 8 * c));
+      step(p, c);
+    }
+  }
+  p = p_first;
+  c = c_first;
 #pragma unroll
   for (int k = 0; k < GS_KEEP; ++k) {
     const int e = threadIdx.x + GS_THREADS * k;
-    off[k] = -1;
     if (e < total) {
-      const int p = e / CH, c = e - p * CH;
-      off[k] = p * C + 8 * c;
-      const f16x8 v = *reinterpret_cast<const f16x8*>(xb + off[k]);
-      kv[k] = v;
+      const int c8 = 8 * c;
+      const f16x8 v = kv[k];
       // cpg >= 8: a chunk touches at most two groups, g0 for its first `split` channels
-      const int g0 = (8 * c) / cpg, split = (g0 + 1) * cpg - 8 * c;
+      const int g0 = group_of(c8), split = (g0 + 1) * cpg - c8;
+      step(p, c);
+      const float K0 = pick(K, g0), K1 = pick(K, g0 + 1);
       float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j];
+        const float f = (float)v[j] - (j < split ? K0 : K1);
         if (j < split) { s0 += f; q0 += f * f; } else { s1 += f; q1 += f * f; }
       }
 #pragma unroll
@@ -233,48 +334,54 @@ __global__ __launch_bounds__(GS_THREADS) void gn_super_kernel(const f16* __restr
     }
   }
 #pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s[g] += __shfl_xor(s[g], o);
-      q[g] += __shfl_xor(q[g], o);
-    }
-  if ((threadIdx.x & 63) == 0) {
+  for (int g = 0; g < 4; ++g) {
+    s[g] = wave_sum(s[g]);
+    q[g] = wave_sum(q[g]);
+  }
+  if (lane == 0) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      red[threadIdx.x >> 6][g] = s[g];
-      red[threadIdx.x >> 6][4 + g] = q[g];
+      red[wave][g] = s[g];
+      red[wave][4 + g] = q[g];
     }
   }
   __syncthreads();
-  if (threadIdx.x < 4) {
-    float ss = 0.f, qq = 0.f;
-    for (int w = 0; w < GS_THREADS / 64; ++w) { ss += red[w][threadIdx.x]; qq += red[w][4 + threadIdx.x]; }
-    const float inv_cnt = 1.0f / ((float)HW * (float)cpg);
-    const float mean = ss * inv_cnt;
-    const float var = fmaxf(qq * inv_cnt - mean * mean, 0.0f);
-    stat[threadIdx.x] = mean;
-    stat[4 + threadIdx.x] = rsqrtf(var + eps);
+  // every wave folds the 16 wave partials itself (same additions in the same order everywhere, so
+  // all waves hold the same bits): no second barrier, no serial loop
+  const float inv_cnt = 1.0f / ((float)HW * (float)cpg);
+  auto uniform = [](float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+  };
+  float mean[4], rstd[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float ss = row_sum(red[lane & 15][g]), qq = row_sum(red[lane & 15][4 + g]);
+    const float ds = ss * inv_cnt;
+    // uniform across the workgroup: kept in scalar registers (the kept chunks fill the vector file)
+    mean[g] = uniform(K[g] + ds);
+    rstd[g] = uniform(rsqrtf(fmaxf(qq * inv_cnt - ds * ds, 0.0f) + eps));
   }
-  __syncthreads();
+  p = p_first;
+  c = c_first;
 #pragma unroll
   for (int k = 0; k < GS_KEEP; ++k) {
-    if (off[k] < 0) continue;
-    const int c8 = off[k] % C;                     // 8 * chunk index inside the super-group
-    const int g0 = c8 / cpg, split = (g0 + 1) * cpg - c8;
-    const float m0 = stat[g0], r0 = stat[4 + g0];
-    const float m1 = stat[g0 + 1 < 4 ? g0 + 1 : 3], r1 = stat[4 + (g0 + 1 < 4 ? g0 + 1 : 3)];
+    if ((int)threadIdx.x + GS_THREADS * k >= total) continue;
+    const int c8 = 8 * c, off = p * C + c8;        // the same walk as above: nothing kept per chunk
+    const int g0 = group_of(c8), split = (g0 + 1) * cpg - c8;
+    step(p, c);
+    const float m0 = pick(mean, g0), r0 = pick(rstd, g0);
+    const float m1 = pick(mean, g0 + 1), r1 = pick(rstd, g0 + 1);
     const f16x8 gm = *reinterpret_cast<const f16x8*>(gamma + c_base + c8);
     const f16x8 bt = *reinterpret_cast<const f16x8*>(beta + c_base + c8);
     f16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float mean = j < split ? m0 : m1, rstd = j < split ? r0 : r1;
-      float y = ((float)kv[k][j] - mean) * rstd * (float)gm[j] + (float)bt[j];
+      const float mu = j < split ? m0 : m1, rs = j < split ? r0 : r1;
+      float y = ((float)kv[k][j] - mu) * rs * (float)gm[j] + (float)bt[j];
       if (do_silu) y = silu(y);
       o[j] = (f16)y;
     }
-    *reinterpret_cast<f16x8*>(ob + off[k]) = o;
+    *reinterpret_cast<f16x8*>(ob + off) = o;
   }
 }
 
@@ -404,9 +511,10 @@ int dsu_groupnorm_nhwc_f16(const void* x, const void* gamma, const void* beta, i
 
 int dsu_layernorm_f16(const void* x, const void* gamma, const void* beta, int64_t rows,
                       int32_t C, float eps, void* out, void* stream) {
-  if (!x || !gamma || !beta || !out || rows < 0 || C <= 0) return DSU_EINVAL;
+  if (!gamma || !beta || rows < 0 || C <= 0) return DSU_EINVAL;
   if (C % 8 != 0 || C > 2048) return DSU_EUNSUP;
-  if (rows == 0) return DSU_OK;
+  if (rows == 0) return DSU_OK;   // an empty tensor has no storage: x and out may be null here
+  if (!x || !out) return DSU_EINVAL;
   layernorm_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(
       (const f16*)x, (const f16*)gamma, (const f16*)beta, rows, C, eps, (f16*)out);
   DSU_CHECK_LAUNCH();
@@ -414,9 +522,10 @@ int dsu_layernorm_f16(const void* x, const void* gamma, const void* beta, int64_
 }
 
 int dsu_geglu_f16(const void* h, int64_t rows, int32_t D, void* out, void* stream) {
-  if (!h || !out || rows < 0 || D <= 0) return DSU_EINVAL;
+  if (rows < 0 || D <= 0) return DSU_EINVAL;
   if (D % 8 != 0) return DSU_EUNSUP;
   if (rows == 0) return DSU_OK;
+  if (!h || !out) return DSU_EINVAL;
   geglu_kernel<<<dsu_capped_blocks(rows * (D / 8), 256, 4096), 256, 0, (hipStream_t)stream>>>(
       (const f16*)h, rows, D, (f16*)out);
   DSU_CHECK_LAUNCH();

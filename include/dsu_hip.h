@@ -731,7 +731,9 @@ int dsu_gemm_geglu_fwd(const void* x, const void* w, const void* bias, int64_t M
 /* nn.GroupNorm(G, C, eps) on NHWC f16 (+ optional fused SiLU): diffusers ResnetBlock2D
  * norm1/norm2 + nonlinearity, TransformerMV2DModel.norm (transformer_mv2d.py:304),
  * conv_norm_out + conv_act (unet_mv2d_condition.py:1046-1048).  x/out (B,HW,C) f16;
- * gamma/beta (C) f16; stats_ws: caller-owned f32 scratch of B*G*2 floats. */
+ * gamma/beta (C) f16; stats_ws: caller-owned f32 scratch of B*G*2 floats.  out must not alias
+ * x: the statistics are sums of x - K, K being x[n, 0, g*C/G], and the apply pass reads K from x
+ * while other threads write out. */
 int dsu_groupnorm_nhwc_f16(const void* x, const void* gamma, const void* beta, int32_t B,
                            int32_t HW, int32_t C, int32_t G, float eps, int32_t silu,
                            float* stats_ws, void* out, void* stream);

@@ -31,7 +31,9 @@ def test_norm_kernels(dev):
     g = torch.Generator().manual_seed(0)
     # every channels-per-group of the UNet (10 ... 80) and the VAE's 16: the 16-byte super-group
     # kernel where a super-group fits one workgroup's registers, else the one-launch half2 kernel
-    # ((3,5,7)) or the statistics + apply pair ((1,5,7), (1,64,64) at 320: 20480 chunks)
+    # ((3,5,7)) or the statistics + apply pair ((1,5,7), (1,64,64) at 320: 20480 chunks).
+    # Zero-mean groups against torch float32 only: groups far from zero, float64 references and
+    # the per-branch edge shapes are in test_gpu_mv_leaf_edges.py
     for C, shp in [(320, (3, 5, 7)), (640, (3, 5, 7)), (1280, (3, 5, 7)), (1920, (3, 5, 7)),
                    (2560, (3, 5, 7)), (640, (1, 5, 7)), (320, (1, 64, 64)), (960, (12, 32, 32)),
                    (320, (2, 32, 32)), (640, (2, 16, 16)), (1280, (2, 8, 8)), (512, (1, 64, 64)),
