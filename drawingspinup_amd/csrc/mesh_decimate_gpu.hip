@@ -19,6 +19,18 @@
 // A collapse rejected by the flip / link tests is remembered (direct-mapped table keyed by the
 // edge, valid while neither end point's neighbourhood changed) so that it does not keep winning
 // its neighbourhood round after round.
+// How the four selection passes of a round are run (claim_kernel / collapse_kernel, one launch per
+// pass and kernel; none of it changes which collapses are taken):
+//   * records: pass 0 reads a candidate's rank, edge and end points once and writes (r, v0, v1);
+//     the later kernels of the round read records, handed on through two lists that keep only the
+//     candidates still undecided (see Cand);
+//   * stamping: a candidate writes each vertex of its closed neighbourhood once per fan, not once
+//     per triangle, and only where a plain read of the word shows it could still lower it
+//     (see fan_ring, stamp);
+//   * marks: the end points of an applied collapse get round * 16 + pass in ONE array; a pass takes a
+//     vertex for dirty when its mark is of an earlier pass of the same round
+//     (see DSU_MARK_ROUND_BITS);
+//   * the round's three counters and the list appends take one atomic per wave.
 // The rounds stop above the target (`stop_faces`) and never go below `floor_faces`; the caller
 // finishes the last stretch with the serial code seeded with the accumulated quadrics
 // (dsu_mesh_decimate_quadric_q), which also lands on the exact face count.
@@ -303,45 +315,178 @@ __device__ inline unsigned long long priority_of(int32_t v0, int32_t v1, uint32_
   return (k << 32) | r;                                      // unique: r is the candidate's index
 }
 
-// every candidate stamps its priority on all vertices of its closed neighbourhood (v0, v1, rings)
 // Several selection passes share one round's lists, edge list and cost order.  After a pass, the
 // lists of the end points of applied collapses are stale (v1 is gone, v0 gained triangles) and so
 // is every triangle that held a v1: a candidate is `dirty` — skipped until the next round — when
-// any vertex of its closed neighbourhood was an end point of a collapse applied earlier in this
-// round (`touched[v] == round`).  Everything a clean candidate reads is as it was at round start.
-__device__ inline bool is_dirty(const Mesh& m, int32_t v0, int32_t v1, const uint32_t* touched, uint32_t round) {
-  for (int pass = 0; pass < 2; ++pass) {
-    const int32_t v = pass ? v1 : v0;
-    for (int32_t i = m.voff[v]; i < m.voff[v + 1]; ++i) {
-      const int32_t t = m.vfaces[i];
-      for (int k = 0; k < 3; ++k)
-        if (touched[m.F[3 * t + k]] == round) return true;
+// any vertex of its closed neighbourhood was an end point of a collapse applied in an earlier pass
+// of this round (its mark in `touched`).  Everything a clean candidate reads is as it was at round
+// start.
+//
+// ONE array of marks serves all passes: a collapse applied in pass p of round R writes
+// mark_base(R) + p on its two end points, and pass q tests `mark - mark_base(R) < q` (unsigned):
+// true exactly for the marks of earlier passes of this round.  Marks of earlier rounds lie below
+// mark_base(R) and wrap to huge values, the initial 0xffffffff stays >= 2^31 above any base, and
+// the marks the running pass itself writes (difference == q) do not count — what the second array
+// and the copy after every pass were for.  mark_base(R) = (R mod 2^27) * 16; the host refills the
+// array whenever R mod 2^27 returns to 0, so no mark of an earlier epoch can alias.
+#define DSU_MARK_ROUND_BITS 27
+#define DSU_MARK_PASS_SLOTS 16u
+
+// A candidate of the round: its rank r in the cost order (the low word of its priority, see
+// priority_of) and the end points of its edge.  Pass 0 reads sorted_cost[r], edges[sorted_idx[r]] and
+// the edge's end points ONCE and writes the record; every later kernel of the round reads records.
+// The records still undecided travel from kernel to kernel through two lists: a candidate leaves
+// when it is dirty (marks are never taken back inside a round: dirty once, dirty in every later
+// pass) or when its collapse was applied (its end points then carry a mark: it would be dirty).
+// A REJECTED candidate stays, also while the table remembers it: the table is direct-mapped, another
+// rejection of the round may take its slot in any pass, and the candidate is then tested (and
+// counted as rejected) again, as it was when every pass asked every candidate.  Each pass after the
+// first therefore makes that code's probe for every record.  The order of a list depends on the order the waves
+// appended in; nothing computed depends on that order: r travels with the record, claim[] takes
+// minima, the counters are integer sums, the table takes maxima.
+typedef uint4 Cand;                                           // x = r, y = v0, z = v1
+
+#define DSU_FAN 8
+// The corners of the triangles around v, as at most 2 * DSU_FAN vertex ids in registers (-1: none),
+// each DISTINCT vertex other than v at least once.  Triangle j of the list gives u[j], the corner
+// after v, and u[DSU_FAN + j], the corner before v, unless that vertex is the corner after v of one
+// of these triangles.  In a closed fan every ring vertex is the corner after v of one triangle and
+// the corner before v of another, so the second half empties; on an open fan, a fan of mixed
+// orientation or a non-manifold one a vertex that is nobody's `after` stays in the second half
+// (and one held by three triangles may stay twice: more stamps than needed, never fewer vertices).
+// Triangles past the DSU_FAN-th (the poles) are left to the caller, corner by corner.
+// A triangle of a stale list may no longer hold v (v was collapsed away in an earlier pass): then
+// two of its corners are returned, and the caller's test of v's own mark decides (claim_kernel).
+__device__ inline void fan_ring(const Mesh& m, int32_t v, int32_t (&u)[2 * DSU_FAN]) {
+  const int32_t b = m.voff[v], e = m.voff[v + 1];
+#pragma unroll
+  for (int j = 0; j < DSU_FAN; ++j) {
+    int32_t nx = -1, pv = -1;
+    if (b + j < e) {
+      const int32_t t = m.vfaces[b + j];
+      const int32_t a0 = m.F[3 * t], a1 = m.F[3 * t + 1], a2 = m.F[3 * t + 2];
+      if (a0 == v) { nx = a1; pv = a2; }
+      else if (a1 == v) { nx = a2; pv = a0; }
+      else { nx = a0; pv = a1; }
     }
+    u[j] = nx;
+    u[DSU_FAN + j] = pv;
   }
-  return touched[v0] == round || touched[v1] == round;
+#pragma unroll
+  for (int j = 0; j < DSU_FAN; ++j) {                         // a `before` that is somebody's `after` goes
+    int32_t same = 0;
+#pragma unroll
+    for (int i = 0; i < DSU_FAN; ++i) same |= (int32_t)(u[i] == u[DSU_FAN + j]);
+    u[DSU_FAN + j] = same ? -1 : u[DSU_FAN + j];
+  }
 }
 
+__device__ inline bool mark_earlier_pass(const uint32_t* touched, int32_t u, uint32_t mark_base, uint32_t pass) {
+  return touched[u] - mark_base < pass;
+}
+
+// `claim[u]` only falls while the kernel runs, so whatever a plain load returns (a stale line of
+// the vector cache included) is >= the word's current value: when it is already <= pr, the
+// atomicMin could not have changed the word, and leaving it out leaves the final claim[] — the
+// minimum over the same set of (vertex, priority) pairs — as it was.
+__device__ inline void stamp(unsigned long long* claim, int32_t u, unsigned long long pr) {
+  if (claim[u] > pr) atomicMin(&claim[u], pr);
+}
+
+// one record per lane with `keep` -> out[*n_out ...]; one atomic per wave.  Whole waves call this.
+__device__ inline void wave_append(bool keep, Cand c, Cand* out, int32_t* n_out) {
+  const unsigned long long mask = __ballot(keep);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & (DSU_WAVE - 1);
+  int32_t base = 0;
+  if (lane == 0) base = atomicAdd(n_out, (int32_t)__popcll(mask));
+  base = __shfl(base, 0);
+  if (keep) out[base + __popcll(mask & ((1ull << lane) - 1ull))] = c;
+}
+
+__device__ inline int wave_sum(int x) {
+#pragma unroll
+  for (int o = DSU_WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
+// Every candidate stamps its priority on all vertices of its closed neighbourhood (v0, v1, rings).
+// What is stamped is the SET of vertices the earlier kernel reached by writing every corner of
+// every triangle around v0 and around v1 (about 36 atomics for about 10 vertices): v0 and v1 once
+// (each lies in a triangle of the edge), the ring of each fan through fan_ring, every corner of the
+// triangles past DSU_FAN.  The same set of pairs under a minimum: the same claim[].
+// FIRST (pass 0 of a round): reads the cost order and writes the records; no mark of this round
+// exists yet (nothing dirty), and the table was probed by edge_cost_kernel a moment ago with the
+// same versions (remembered == +inf cost), so neither test is made.
+template <bool FIRST>
 __global__ void claim_kernel(Mesh m, const int32_t* edges, const uint32_t* sorted_idx, const uint32_t* sorted_cost,
-                             int64_t ncand, uint32_t round, uint32_t seed, const uint32_t* touched,
+                             int64_t ncand, const Cand* in, const int32_t* n_in, Cand* out, int32_t* n_out,
+                             uint32_t mark_base, uint32_t pass, uint32_t seed, const uint32_t* touched,
                              const Reject* rej, uint32_t n_slots, const uint32_t* vver,
                              unsigned long long* claim) {
-  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < ncand; r += (int64_t)gridDim.x * blockDim.x) {
-    if (sorted_cost[r] == 0x7f800000u) continue;            // +inf: remembered rejection
-    int32_t v0, v1;
-    edge_ends(m, edges[sorted_idx[r]], v0, v1);
-    if (is_dirty(m, v0, v1, touched, round)) continue;
-    {                                                       // rejected in an earlier pass of this round
-      const unsigned long long key = ekey(v0, v1);
-      if ((rej[slot_of(key, n_slots)] & 0xffffffffffffull) == reject_tag(key, vver[v0], vver[v1])) continue;
-    }
-    const unsigned long long pr = priority_of(v0, v1, seed, (uint32_t)r);
-    for (int pass = 0; pass < 2; ++pass) {
-      const int32_t v = pass ? v1 : v0;
-      for (int32_t i = m.voff[v]; i < m.voff[v + 1]; ++i) {
-        const int32_t t = m.vfaces[i];
-        for (int k = 0; k < 3; ++k) atomicMin(&claim[m.F[3 * t + k]], pr);
+  const int64_t n = FIRST ? ncand : (int64_t)*n_in;
+  const int lane = threadIdx.x & (DSU_WAVE - 1);
+  // whole waves go round the loop together (wave_append)
+  for (int64_t base = blockIdx.x * (int64_t)blockDim.x + (threadIdx.x - lane); base < n;
+       base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = base + lane;
+    bool keep = false, remembered = false;
+    Cand c = make_uint4(0u, 0u, 0u, 0u);
+    if (i < n) {
+      int32_t v0, v1;
+      if (FIRST) {
+        keep = sorted_cost[i] != 0x7f800000u;               // +inf: remembered rejection
+        if (keep) {
+          edge_ends(m, edges[sorted_idx[i]], v0, v1);
+          c = make_uint4((uint32_t)i, (uint32_t)v0, (uint32_t)v1, 0u);
+        }
+      } else {
+        c = in[i];
+        v0 = (int32_t)c.y; v1 = (int32_t)c.z;
+        // rejected in an earlier pass of this round and still remembered: sits this pass out, but
+        // stays on the list (the table may have forgotten it by the next pass)
+        const unsigned long long key = ekey(v0, v1);
+        remembered = (rej[slot_of(key, n_slots)] & 0xffffffffffffull) == reject_tag(key, vver[v0], vver[v1]);
+        keep = true;
+      }
+      if (keep && !remembered) {
+        int32_t u0[2 * DSU_FAN], u1[2 * DSU_FAN];
+        fan_ring(m, v0, u0);
+        fan_ring(m, v1, u1);
+        const int32_t t0 = m.voff[v0] + DSU_FAN, e0 = m.voff[v0 + 1];
+        const int32_t t1 = m.voff[v1] + DSU_FAN, e1 = m.voff[v1 + 1];
+        if (!FIRST) {
+          // dirty: a mark of an earlier pass on any vertex the earlier walk read, i.e. on any corner
+          // of any triangle of the two lists (fan_ring drops only repeats), or on v0 / v1
+          bool dirty = mark_earlier_pass(touched, v0, mark_base, pass) | mark_earlier_pass(touched, v1, mark_base, pass);
+#pragma unroll
+          for (int j = 0; j < 2 * DSU_FAN; ++j) {
+            if (u0[j] >= 0) dirty |= mark_earlier_pass(touched, u0[j], mark_base, pass);
+            if (u1[j] >= 0) dirty |= mark_earlier_pass(touched, u1[j], mark_base, pass);
+          }
+          for (int32_t q = t0; q < e0; ++q)
+            for (int k = 0; k < 3; ++k) dirty |= mark_earlier_pass(touched, m.F[3 * m.vfaces[q] + k], mark_base, pass);
+          for (int32_t q = t1; q < e1; ++q)
+            for (int k = 0; k < 3; ++k) dirty |= mark_earlier_pass(touched, m.F[3 * m.vfaces[q] + k], mark_base, pass);
+          keep = !dirty;
+        }
+        if (keep) {
+          const unsigned long long pr = priority_of(v0, v1, seed, c.x);
+          stamp(claim, v0, pr);
+          stamp(claim, v1, pr);
+#pragma unroll
+          for (int j = 0; j < 2 * DSU_FAN; ++j) {
+            if (u0[j] >= 0 && u0[j] != v1) stamp(claim, u0[j], pr);
+            if (u1[j] >= 0 && u1[j] != v0) stamp(claim, u1[j], pr);
+          }
+          for (int32_t q = t0; q < e0; ++q)
+            for (int k = 0; k < 3; ++k) stamp(claim, m.F[3 * m.vfaces[q] + k], pr);
+          for (int32_t q = t1; q < e1; ++q)
+            for (int k = 0; k < 3; ++k) stamp(claim, m.F[3 * m.vfaces[q] + k], pr);
+        }
       }
     }
+    wave_append(keep, c, out, n_out);
   }
 }
 
@@ -354,17 +499,14 @@ __global__ void claim_kernel(Mesh m, const int32_t* edges, const uint32_t* sorte
 // around v0 / v1 (not rewritten: they would have to contain another collapse's v1, which would
 // then be a ring vertex).  Rings may overlap.
 // selected -> admissibility tests of the serial code -> apply
-__global__ void collapse_kernel(Mesh m, const int32_t* edges, const uint32_t* sorted_idx, const uint32_t* sorted_cost,
-                                int64_t ncand, uint32_t round, uint32_t seed, const unsigned long long* claim,
-                                int link_test, uint8_t* f_alive, Reject* rej, uint32_t n_slots, uint32_t* vver,
-                                uint32_t* touched_next, const uint32_t* touched, int32_t* counters) {
-  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < ncand; r += (int64_t)gridDim.x * blockDim.x) {
-    if (sorted_cost[r] == 0x7f800000u) continue;
-    int32_t v0, v1;
-    edge_ends(m, edges[sorted_idx[r]], v0, v1);
-    const unsigned long long pr = priority_of(v0, v1, seed, (uint32_t)r);
-    if (claim[v0] != pr || claim[v1] != pr) continue;
-    if (is_dirty(m, v0, v1, touched, round)) continue;      // (its claim was never written: belt and braces)
+struct Outcome {
+  int what;      // 0 = not selected, 1 = rejected (remembered), 2 = applied
+  int removed;   // triangles the collapse removed
+};
+__device__ inline Outcome test_and_apply(const Mesh& m, int32_t v0, int32_t v1, uint32_t round, int link_test,
+                                     uint8_t* f_alive, Reject* rej, uint32_t n_slots, uint32_t* vver,
+                                     uint32_t* touched, uint32_t mark) {
+  {
     double cost; D3 vbar;
     edge_target(m, v0, v1, cost, vbar);
     const int32_t b0 = m.voff[v0], e0 = m.voff[v0 + 1], b1 = m.voff[v1], e1 = m.voff[v1 + 1];
@@ -413,13 +555,15 @@ __global__ void collapse_kernel(Mesh m, const int32_t* edges, const uint32_t* so
       for (int32_t j = b1; j < e1 && !bad; ++j) {
         const int32_t t1 = m.vfaces[j];
         if (tri_has(m, t1, v0)) continue;
-        int32_t xy[2], k2 = 0;
-        for (int k = 0; k < 3; ++k)
-          if (m.F[3 * t1 + k] != v1 && k2 < 2) xy[k2++] = m.F[3 * t1 + k];
+        int32_t x = -1, y = -1, k2 = 0;                       // (two scalars: an indexed pair went to LDS)
+        for (int k = 0; k < 3; ++k) {
+          const int32_t c = m.F[3 * t1 + k];
+          if (c != v1 && k2 < 2) { if (k2 == 0) x = c; else y = c; ++k2; }
+        }
         if (k2 < 2) continue;
         for (int32_t i = b0; i < e0; ++i) {
           const int32_t t0 = m.vfaces[i];
-          if (!tri_has(m, t0, v1) && tri_has(m, t0, xy[0]) && tri_has(m, t0, xy[1])) { bad = true; break; }
+          if (!tri_has(m, t0, v1) && tri_has(m, t0, x) && tri_has(m, t0, y)) { bad = true; break; }
         }
       }
     }
@@ -427,8 +571,7 @@ __global__ void collapse_kernel(Mesh m, const int32_t* edges, const uint32_t* so
       const unsigned long long key = ekey(v0, v1);
       atomicMax(&rej[slot_of(key, n_slots)],
                 ((unsigned long long)(round & 0xffffu) << 48) | reject_tag(key, vver[v0], vver[v1]));
-      atomicAdd(&counters[1], 1);
-      continue;
+      return {1, 0};
     }
     // ---- collapse v1 into v0 (this thread owns every vertex and triangle it touches)
     for (int pass = 0; pass < 2; ++pass) {                  // the neighbourhood changed: versions
@@ -451,10 +594,59 @@ __global__ void collapse_kernel(Mesh m, const int32_t* edges, const uint32_t* so
     }
     m.P[3 * v0] = vbar.x; m.P[3 * v0 + 1] = vbar.y; m.P[3 * v0 + 2] = vbar.z;
     for (int i = 0; i < 10; ++i) m.Q[10 * (int64_t)v0 + i] += m.Q[10 * (int64_t)v1 + i];
-    touched_next[v0] = round;                                // visible to the NEXT pass (separate array:
-    touched_next[v1] = round;                                // this pass's dirty tests read `touched`)
-    atomicAdd(&counters[0], 1);
-    atomicAdd(&counters[2], removed);
+    touched[v0] = mark;                                      // dirty for the LATER passes of this round only
+    touched[v1] = mark;                                      // (see DSU_MARK_ROUND_BITS)
+    return {2, removed};
+  }
+}
+
+// A candidate whose two end points carry its priority did stamp them: the low word of a priority
+// is the rank r, which no other candidate writes.  So it passed claim_kernel's tests in this same
+// pass (not remembered, not dirty), and the marks it read there are the ones it would read here:
+// the walk the earlier kernel repeated at this point could never find anything.
+// Records that stay undecided (not selected, or rejected: see Cand) go to `out` for the next pass;
+// out == nullptr in the last pass.  counters[0..2] (collapses, rejections, triangles removed) get
+// one add per wave: integer sums, the same totals.
+__global__ void collapse_kernel(Mesh m, const Cand* in, const int32_t* n_in, Cand* out, int32_t* n_out,
+                                uint32_t round, uint32_t mark, uint32_t seed, const unsigned long long* claim,
+                                int link_test, uint8_t* f_alive, Reject* rej, uint32_t n_slots, uint32_t* vver,
+                                uint32_t* touched, int32_t* counters) {
+  const int32_t n = *n_in;                                  // <= ncand <= 2^28: 32-bit arithmetic below
+  const int lane = threadIdx.x & (DSU_WAVE - 1);
+  // Every wave of the grid takes one contiguous run of the list, so that the few records of a late
+  // pass spread over all waves instead of filling a few: the selected lanes of a wave make their
+  // walks in lockstep, every load touching as many cache lines as lanes take part, and the launch
+  // lasts as long as its slowest wave (last pass of a round on a 465 k-face mesh: ~190 us with the
+  // list packed 64 to the wave, ~85 us spread out; on the export's own, larger mesh the two forms
+  // come out even over a call: profiles/remesh_rounds_ab.txt).
+  const int32_t waves = (int32_t)(gridDim.x * (blockDim.x / DSU_WAVE));   // <= 2048 * 4
+  const int32_t wave = (int32_t)(blockIdx.x * (blockDim.x / DSU_WAVE) + threadIdx.x / DSU_WAVE);
+  const int32_t per_wave = (n + waves - 1) / waves;
+  const int32_t end = (wave + 1) * per_wave < n ? (wave + 1) * per_wave : n;
+  int n_applied = 0, n_rejected = 0, n_removed = 0;
+  for (int32_t base = wave * per_wave; base < end; base += DSU_WAVE) {
+    const int32_t i = base + lane;
+    Outcome o = {0, 0};
+    bool stay = false;
+    Cand c = make_uint4(0u, 0u, 0u, 0u);
+    if (i < end) {
+      c = in[i];
+      const int32_t v0 = (int32_t)c.y, v1 = (int32_t)c.z;
+      const unsigned long long pr = priority_of(v0, v1, seed, c.x);
+      if (claim[v0] == pr && claim[v1] == pr)
+        o = test_and_apply(m, v0, v1, round, link_test, f_alive, rej, n_slots, vver, touched, mark);
+      stay = o.what != 2;
+    }
+    const int applied = (int)__popcll(__ballot(o.what == 2));
+    n_applied += applied;
+    n_rejected += (int)__popcll(__ballot(o.what == 1));
+    if (applied) n_removed += wave_sum(o.removed);
+    if (out) wave_append(stay, c, out, n_out);
+  }
+  if (lane == 0) {
+    if (n_applied) atomicAdd(&counters[0], n_applied);
+    if (n_rejected) atomicAdd(&counters[1], n_rejected);
+    if (n_removed) atomicAdd(&counters[2], n_removed);
   }
 }
 
@@ -466,7 +658,7 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
   size_t off_Q, off_F2, off_voff, off_cursor, off_vfaces, off_flag, off_edges, off_iota, off_cost, off_cost2,
-      off_idx, off_idx2, off_claim, off_vver, off_touched, off_touched2, off_rej, off_counters, off_nsel, off_cub, cub_bytes, total;
+      off_idx, off_idx2, off_claim, off_vver, off_touched, off_rej, off_counters, off_nsel, off_cub, cub_bytes, total;
   uint32_t n_slots;
 };
 
@@ -489,7 +681,6 @@ Layout make_layout(int64_t nv, int64_t nf) {
   L.off_claim = take((size_t)nv * sizeof(unsigned long long));
   L.off_vver = take((size_t)nv * sizeof(uint32_t));
   L.off_touched = take((size_t)nv * sizeof(uint32_t));
-  L.off_touched2 = take((size_t)nv * sizeof(uint32_t));
   L.n_slots = (uint32_t)(nv * 2 + 1024);
   L.off_rej = take((size_t)L.n_slots * sizeof(Reject));
   L.off_counters = take(64);
@@ -557,13 +748,19 @@ int dsu_mesh_decimate_parallel(double* verts, int64_t n_verts, int32_t* faces, i
   unsigned long long* claim = (unsigned long long*)(w + L.off_claim);
   uint32_t* vver = (uint32_t*)(w + L.off_vver);
   uint32_t* touched = (uint32_t*)(w + L.off_touched);
-  uint32_t* touched2 = (uint32_t*)(w + L.off_touched2);
   Reject* rej = (Reject*)(w + L.off_rej);
   int32_t* counters = (int32_t*)(w + L.off_counters);
   int32_t* nsel = (int32_t*)(w + L.off_nsel);
   void* cub = (void*)(w + L.off_cub);
   const int T = 256;
-  const int PASSES = 4;                     // selection passes per round (see is_dirty)
+  const int PASSES = 4;                     // selection passes per round (see claim_kernel)
+  static_assert(PASSES <= (int)DSU_MARK_PASS_SLOTS && 4 + 2 * PASSES <= 16, "marks and list counts of a round");
+  // The two candidate lists of the passes live in the radix sort's INPUT arrays, which nothing reads
+  // between the sort of a round and the edge costs of the next: a round has ncand <= budget <=
+  // nf / 2 records of 16 bytes (or the single one of `ncand < 1`, with nf >= 2), the arrays hold
+  // 3 nf words of 4 bytes each.
+  Cand* list_a = (Cand*)cost;
+  Cand* list_b = (Cand*)idx;
   const int link_test = !(flags & 1);
 
   int32_t* F = faces;                       // live triangles, compacted in place (through F2)
@@ -600,7 +797,6 @@ int dsu_mesh_decimate_parallel(double* verts, int64_t n_verts, int32_t* faces, i
   if (rc) return rc;
   DSU_HIP_TRY(hipMemsetAsync(vver, 0, (size_t)n_verts * sizeof(uint32_t), s));
   DSU_HIP_TRY(hipMemsetAsync(touched, 0xff, (size_t)n_verts * sizeof(uint32_t), s));
-  DSU_HIP_TRY(hipMemsetAsync(touched2, 0xff, (size_t)n_verts * sizeof(uint32_t), s));
   DSU_HIP_TRY(hipMemsetAsync(rej, 0, (size_t)L.n_slots * sizeof(Reject), s));
   iota_kernel<<<dsu_capped_blocks(3 * nf, T), T, 0, s>>>(iota, 3 * nf);
   if ((rc = build_csr())) return rc;
@@ -632,16 +828,29 @@ int dsu_mesh_decimate_parallel(double* verts, int64_t n_verts, int32_t* faces, i
     if (ncand < 1) ncand = 1;
     DSU_HIP_TRY(hipMemsetAsync(counters, 0, 64, s));
     DSU_HIP_TRY(hipMemsetAsync(flag, 1, (size_t)nf, s));
+    // counters (16 words, zeroed above): [0..2] collapses, rejections, triangles removed;
+    // [4 + 2 p] records claim_kernel of pass p passed on, [5 + 2 p] records collapse_kernel did
+    const uint32_t mark_round = (uint32_t)rounds & ((1u << DSU_MARK_ROUND_BITS) - 1u);
+    if (rounds > 0 && mark_round == 0)      // the marks start over: none of the last epoch may stay
+      DSU_HIP_TRY(hipMemsetAsync(touched, 0xff, (size_t)n_verts * sizeof(uint32_t), s));
+    const uint32_t mark_base = mark_round * DSU_MARK_PASS_SLOTS;
+    const int blocks = dsu_capped_blocks(ncand, T);
     for (int pass = 0; pass < PASSES; ++pass) {
       const uint32_t seed = (uint32_t)rounds * 16u + (uint32_t)pass;
+      int32_t* n_claimed = counters + 4 + 2 * pass;
+      int32_t* n_left = counters + 5 + 2 * pass;
       DSU_HIP_TRY(hipMemsetAsync(claim, 0xff, (size_t)n_verts * sizeof(unsigned long long), s));
-      claim_kernel<<<dsu_capped_blocks(ncand, T), T, 0, s>>>(m, edges, idx2, cost2, ncand, (uint32_t)rounds, seed,
-                                                             touched, rej, L.n_slots, vver, claim);
-      collapse_kernel<<<dsu_capped_blocks(ncand, T), T, 0, s>>>(m, edges, idx2, cost2, ncand, (uint32_t)rounds, seed,
-                                                                claim, link_test, flag, rej, L.n_slots, vver,
-                                                                touched2, touched, counters);
+      if (pass == 0)
+        claim_kernel<true><<<blocks, T, 0, s>>>(m, edges, idx2, cost2, ncand, nullptr, nullptr, list_b, n_claimed,
+                                                mark_base, 0u, seed, touched, rej, L.n_slots, vver, claim);
+      else
+        claim_kernel<false><<<blocks, T, 0, s>>>(m, edges, idx2, cost2, ncand, list_a, n_left - 2, list_b, n_claimed,
+                                                 mark_base, (uint32_t)pass, seed, touched, rej, L.n_slots, vver,
+                                                 claim);
+      collapse_kernel<<<blocks, T, 0, s>>>(m, list_b, n_claimed, pass + 1 < PASSES ? list_a : nullptr, n_left,
+                                           (uint32_t)rounds, mark_base + (uint32_t)pass, seed, claim, link_test, flag,
+                                           rej, L.n_slots, vver, touched, counters);
       DSU_CHECK_LAUNCH();
-      DSU_HIP_TRY(hipMemcpyAsync(touched, touched2, (size_t)n_verts * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     }
     int32_t hc[3];
     DSU_HIP_TRY(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, s));
