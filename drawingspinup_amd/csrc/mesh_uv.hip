@@ -17,8 +17,7 @@
 //                        thread keeps its own lowest covering face, so no atomics and no dependence
 //                        on the order of the tile's list
 //   dsu_uv_dilate        one gutter round per launch, integer arithmetic
-//   dsu_uv_project       per-texel back-projection of the front / back drawings: one thread per
-//                        texel, the occluders from the z-parallel grid of mesh_post.hip
+//   (dsu_uv_project and dsu_uv_project_area, the drawings into the atlas: uv_project_area.hip)
 //   dsu_uv_field_points  the field bake's sample points: one thread per (texel, sub-sample) of the
 //                        covered texels' list, the sub-sample fastest (uv_field.h has the text)
 //   dsu_uv_field_resolve the mean of a texel's evaluated samples into its three bytes: one thread
@@ -266,85 +265,6 @@ __global__ __launch_bounds__(256) void uv_dilate_kernel(const uint8_t* __restric
   cov_out[i] = cov;
 }
 
-// dsu_uv_project: which drawing pixel does this texel see?  One thread per texel, tiles as in
-// uv_raster_kernel (so a wave's texels are neighbours in one chart and map to neighbouring mesh
-// points).  The occluder walk reads the point's z-grid cell list straight through L1 / L2 and
-// nothing is staged in LDS: the lists are short (ops.ZGrid aims at two triangles per cell, a box
-// overlaps a few), neighbouring lanes mostly sit in the same cell and read the same addresses, and
-// a tile's texels may spread over any number of cells, so a per-tile staging would need the union
-// of lists it cannot bound.  A texel passes the facing test of at most one view (the sign of one
-// number), so the list is walked at most once.  No barrier, no atomics.
-__global__ __launch_bounds__(256) void uv_project_kernel(
-    const float* __restrict__ uvs, const int32_t* __restrict__ faces, const float* __restrict__ pos, int64_t V,
-    int64_t M, int32_t S, int32_t G, const int32_t* __restrict__ face_id, const float* __restrict__ tris, ZGrid gr,
-    const int32_t* __restrict__ offsets, const int32_t* __restrict__ items, const uint8_t* __restrict__ colour_front,
-    const uint8_t* __restrict__ mask_front, const uint8_t* __restrict__ colour_back,
-    const uint8_t* __restrict__ mask_back, int32_t res, double tolerance, uint8_t* __restrict__ image,
-    uint8_t* __restrict__ source) {
-  const int tid = threadIdx.x;
-  const int bin = blockIdx.x;
-  const int ty = bin / G, tx = bin - ty * G;
-  const int x = tx * UV_TILE + (tid & (UV_TILE - 1)), y = ty * UV_TILE + tid / UV_TILE;
-  if (x >= S || y >= S) return;
-  const int64_t at = (int64_t)(S - 1 - y) * S + x;
-  uint8_t q[3] = {0, 0, 0}, src = 0;
-  const int32_t m = face_id[at];
-  int ia, ib, ic;
-  if (m >= 0 && m < M && face_indices(faces, m, V, ia, ib, ic)) {
-    const TriXY t = uv_tri(uvs, ia, ib, ic, (double)S);
-    double w0, w1, w2;
-    uv_edges(t, (double)x, (double)y, w0, w1, w2);
-    const double area = (w0 + w1) + w2;
-    const double b0 = w0 / area, b1 = w1 / area, b2 = w2 / area;
-    double a[3], b[3], c[3], p[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      a[k] = pos[(int64_t)ia * 3 + k];
-      b[k] = pos[(int64_t)ib * 3 + k];
-      c[k] = pos[(int64_t)ic * 3 + k];
-      p[k] = (b0 * a[k] + b1 * b[k]) + b2 * c[k];
-    }
-    if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-      const double nz = (b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0]);
-      const double span = (double)(res - 1);
-      for (int view = 0; view < 2 && !src; ++view) {
-        const double sign = view ? -1.0 : 1.0;
-        if (!(nz * sign > 0.0)) continue;
-        // get_color_from_image: nearest pixel (half to even), clamped
-        double X = rint(((view ? -p[0] : p[0]) + 0.5) * span), Y = rint((-p[1] + 0.5) * span);
-        X = X < 0.0 ? 0.0 : (X > span ? span : X);
-        Y = Y < 0.0 ? 0.0 : (Y > span ? span : Y);
-        const int64_t pix = (int64_t)Y * res + (int64_t)X;
-        if (!((view ? mask_back : mask_front)[pix] > 0)) continue;
-        const int cell = cell_of((float)p[1], gr.y0, gr.inv_cell, gr.g) * gr.g +
-                         cell_of((float)p[0], gr.x0, gr.inv_cell, gr.g);
-        bool occluded = false;
-        for (int k = offsets[cell]; k < offsets[cell + 1]; ++k) {
-          const int32_t f = items[k];
-          if (f == m || f < 0 || f >= M) continue;
-          const float* tf = tris + (int64_t)f * 9;
-          const TriXY xy{tf[0], tf[1], tf[3], tf[4], tf[6], tf[7]};
-          double e0, e1, e2;
-          edge_functions(xy, p[0], p[1], e0, e1, e2);
-          const double ar = e0 + e1 + e2;
-          if (ar == 0.0) continue;
-          if (!covers(e0, e1, e2)) continue;
-          const double z = (e0 * (double)tf[2] + e1 * (double)tf[5] + e2 * (double)tf[8]) / ar;
-          if ((z - p[2]) * sign > tolerance) { occluded = true; break; }
-        }
-        if (occluded) continue;
-        src = (uint8_t)(view + 1);
-        const uint8_t* px = (view ? colour_back : colour_front) + pix * 3;
-        q[0] = px[0]; q[1] = px[1]; q[2] = px[2];
-      }
-    }
-  }
-  image[at * 3] = q[0];
-  image[at * 3 + 1] = q[1];
-  image[at * 3 + 2] = q[2];
-  source[at] = src;
-}
-
 // dsu_uv_field_points.  Neighbouring threads are the sub-samples of one texel, then the next listed
 // texel (ascending, so mostly the next column of one chart): a wave reads a handful of faces and
 // writes 64 consecutive points.  Nothing is shared, so no LDS and no barrier.
@@ -373,7 +293,7 @@ __global__ __launch_bounds__(256) void uv_field_resolve_kernel(const float* __re
   dsu_uvf::resolve(colours, valid, t, ss, S, texels[t], image);
 }
 
-// dsu_uv_seam_gather.  Tiles as in uv_project_kernel: a tile's texels are neighbours in one chart,
+// dsu_uv_seam_gather.  Tiles as in uv_raster_kernel: a tile's texels are neighbours in one chart,
 // so its up to 768 contributions go to the few groups of a handful of faces.  They are summed in LDS
 // first, in an open-addressing table keyed by group (SEAM_SLOTS >= 3 x 256 keys, so linear probing
 // always ends at the key or at a free slot; 36 KB, four workgroups per CU), and every used slot then
@@ -592,36 +512,6 @@ int dsu_uv_dilate(const uint8_t* image_in, const uint8_t* covered_in, int32_t si
     return DSU_EINVAL;
   uv_dilate_kernel<<<dsu_blocks_for((int64_t)size * size, 256), 256, 0, (hipStream_t)stream>>>(
       image_in, covered_in, size, image_out, covered_out);
-  DSU_CHECK_LAUNCH();
-  return DSU_OK;
-}
-
-int dsu_uv_project(const float* uvs, const int32_t* indices, const float* positions, int64_t n_verts,
-                   int64_t n_faces, int32_t size, const int32_t* face_id, const float* tris, float x0, float y0,
-                   float cell, int32_t g, const int32_t* offsets, const int32_t* items, const uint8_t* color_front,
-                   const uint8_t* mask_front, const uint8_t* color_back, const uint8_t* mask_back, int32_t res,
-                   double z_tolerance, uint8_t* image, uint8_t* source, void* stream) {
-  if (!uv_size_ok(size) || res < 1 || res > 16384 || g < 1 || g > 4096 || !(cell > 0.0f) || !std::isfinite(cell) ||
-      !std::isfinite(x0) || !std::isfinite(y0) || !(z_tolerance >= 0.0) || !std::isfinite(z_tolerance))
-    return DSU_EINVAL;
-  if (n_verts < 0 || n_faces < 0 || n_faces > (int64_t)1 << 30 || n_verts > (int64_t)1 << 30) return DSU_EINVAL;
-  if (!image || !source) return DSU_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t texels = (size_t)size * size;
-  if (n_faces == 0) {
-    if (hipMemsetAsync(image, 0, texels * 3, st) != hipSuccess || hipMemsetAsync(source, 0, texels, st) != hipSuccess)
-      return DSU_ELAUNCH;
-    return DSU_OK;
-  }
-  if (!uvs || !indices || !positions || n_verts == 0 || !face_id || !tris || !offsets || !items || !color_front ||
-      !mask_front || !color_back || !mask_back)
-    return DSU_EINVAL;
-  const int32_t G = (size + UV_TILE - 1) / UV_TILE;
-  const ZGrid gr{x0, y0, 1.0f / cell, g};
-  uv_project_kernel<<<(unsigned)uv_tiles(size), 256, 0, st>>>(uvs, indices, positions, n_verts, n_faces, size, G,
-                                                             face_id, tris, gr, offsets, items, color_front,
-                                                             mask_front, color_back, mask_back, res, z_tolerance,
-                                                             image, source);
   DSU_CHECK_LAUNCH();
   return DSU_OK;
 }

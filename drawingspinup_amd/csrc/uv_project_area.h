@@ -1,6 +1,6 @@
-// The drawings area-sampled into the atlas (include/dsu_hip.h, UV export j.): everything one texel
-// does, one text for the kernel of uv_project_area.hip (device) and for dsu_uv_project_area_host
-// (host), so the non-GPU suite pins the arithmetic the kernel runs.  Float64 in the operand order
+// The drawings projected into the atlas (include/dsu_hip.h, UV export e. and j.: e. is j. at s = 1,
+// filter 0): everything one texel does, one text for the kernel of uv_project_area.hip (device) and
+// for dsu_uv_project_area_host (host), so the non-GPU suite pins the arithmetic the kernel runs.  Float64 in the operand order
 // written here; the library is compiled with -ffp-contract=off, so no products are fused on either
 // side.  tests/uv_project_area_ref.py restates it in numpy.
 //
@@ -14,13 +14,17 @@
 //
 // What the sharing buys is the loads, and the loads are not where the time goes: measured on an
 // MI355X (profiles/uv_project_area_probe.json) the kernel costs about as much per sub-sample as
-// uv_project_kernel costs per texel.  The time is the float64 edge functions of every listed
+// the one-point instantiation costs per texel.  The time is the float64 edge functions of every listed
 // triangle at every point, on lanes that each walk a list of their own.  Tried and measured on the
 // same probe, none kept: a box reject per triangle before the edge functions (12 % faster, with
 // SGPR spills: some lane of a wave nearly always passes, so the wave runs the test anyway); eight
 // points per group (197 VGPR, slower); one walk per texel for all sub-samples with the points
 // recomputed where a triangle passes the box (three times slower, for the same reason).  What did
 // pay is shorter lists: ops.uv_project_area builds a grid three times finer than ZGrid's default.
+//
+// s = 1 is texel<true>: one point, a group of one, no step 6.  It walks as the grouped text does, in
+// 58 VGPR instead of 148 (8 waves per SIMD instead of 3): 62 us where the grouped text took 85 on
+// the 160-cell grid of the 51 200-face probe (profiles/uv_project_unified_probe.json).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -102,18 +106,19 @@ DSU_UVP_HD void add_value(const uint8_t* __restrict__ colour, int32_t res, int32
   }
 }
 
-// Sub-samples j0 .. j0 + nj - 1 (nj <= GROUP) of the s x s grid about (x, y), on face m with atlas
-// triangle t and positions A, B, C: steps 3 to 5.  The passing ones add their values to sum in
-// ascending j; -> how many passed.
+// Sub-samples j0 .. j0 + nj - 1 (nj <= G) of the s x s grid about (x, y), on face m with atlas
+// triangle t and positions A, B, C: steps 3 to 5, with G points in registers.  The passing ones add
+// their values to sum in ascending j; -> how many passed.
+template <int G>
 DSU_UVP_HD int group(const Args& a, const TriXY& t, const double A[3], const double B[3], const double C[3],
                      int32_t m, bool back, double x, double y, int32_t s, int32_t j0, int32_t nj, double sum[3]) {
   const uint8_t* __restrict__ mask = back ? a.mask_back : a.mask_front;
   const double sign = back ? -1.0 : 1.0;
-  double p[GROUP][3];
-  int32_t cell[GROUP];
+  double p[G][3];
+  int32_t cell[G];
   unsigned todo = 0;                                 // bit k: point k has passed every test so far
 #pragma unroll
-  for (int k = 0; k < GROUP; ++k) {
+  for (int k = 0; k < G; ++k) {
     p[k][0] = p[k][1] = p[k][2] = 0.0;
     cell[k] = 0;
     if (k >= nj) continue;
@@ -132,7 +137,7 @@ DSU_UVP_HD int group(const Args& a, const TriXY& t, const double A[3], const dou
   }
   unsigned walked = 0;                               // bit k: point k's cell has been walked
 #pragma unroll
-  for (int k = 0; k < GROUP; ++k) {
+  for (int k = 0; k < G; ++k) {
     if (!((todo >> k) & 1u)) continue;               // failed or occluded by now: nobody needs its list
     bool seen = false;
 #pragma unroll
@@ -146,14 +151,19 @@ DSU_UVP_HD int group(const Args& a, const TriXY& t, const double A[3], const dou
       if (f == m || f < 0 || f >= a.M) continue;
       const float* __restrict__ tf = a.tris + (int64_t)f * 9;
       const TriXY xy{tf[0], tf[1], tf[3], tf[4], tf[6], tf[7]};
-      const double z0 = (double)tf[2], z1 = (double)tf[5], z2 = (double)tf[8];
+      // A group widens the triangle's z once for all its points.  A lone point reads it only under a
+      // triangle that covers it: few do, and with the loads behind that branch the division stays
+      // there too, which the compiler otherwise runs for every listed triangle (62 against 85 us)
+      double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+      if (G > 1) z0 = (double)tf[2], z1 = (double)tf[5], z2 = (double)tf[8];
 #pragma unroll
-      for (int q = 0; q < GROUP; ++q) {
+      for (int q = 0; q < G; ++q) {
         if (!((todo >> q) & 1u)) continue;
         double e0, e1, e2;
         edge_functions(xy, p[q][0], p[q][1], e0, e1, e2);
         const double ar = (e0 + e1) + e2;
         if (ar == 0.0 || !covers(e0, e1, e2)) continue;
+        if (G == 1) z0 = (double)tf[2], z1 = (double)tf[5], z2 = (double)tf[8];
         const double z = ((e0 * z0 + e1 * z1) + e2 * z2) / ar;
         if ((z - p[q][2]) * sign > a.tolerance) todo &= ~(1u << q);
       }
@@ -162,7 +172,7 @@ DSU_UVP_HD int group(const Args& a, const TriXY& t, const double A[3], const dou
   int n = 0;
   const uint8_t* __restrict__ colour = back ? a.colour_back : a.colour_front;
 #pragma unroll
-  for (int k = 0; k < GROUP; ++k) {
+  for (int k = 0; k < G; ++k) {
     if (!((todo >> k) & 1u)) continue;
     add_value(colour, a.res, a.filter, back, p[k][0], p[k][1], sum);
     ++n;
@@ -170,8 +180,17 @@ DSU_UVP_HD int group(const Args& a, const TriXY& t, const double A[3], const dou
   return n;
 }
 
-// Texel (row r, column c): its three bytes, its source and its count.
+// Which of the two instantiations of texel() a call runs: every entry asks here, the host entry
+// included, so the host runs the instantiation the kernel runs.
+inline bool one_point(const Args& a) { return a.s == 1; }
+
+// Texel (row r, column c): its three bytes, its source and its count.  ONE: a.s is 1, so the
+// texel's own point is its only sample (rule e. when the filter is 0), alone in its group, and
+// step 6 has nothing to add.
+template <bool ONE>
 DSU_UVP_HD void texel(const Args& a, int32_t r, int32_t c) {
+  constexpr int G = ONE ? 1 : GROUP;
+  const int32_t s = ONE ? 1 : a.s;
   const int64_t at = (int64_t)r * a.S + c;
   uint8_t out[3] = {0, 0, 0}, src = 0, cnt = 0;
   const int32_t m = a.face_id[at];
@@ -191,12 +210,12 @@ DSU_UVP_HD void texel(const Args& a, int32_t r, int32_t c) {
       const double x = (double)c, y = (double)(a.S - 1 - r);
       double sum[3] = {0.0, 0.0, 0.0};
       int n = 0;
-      const int32_t ss = a.s * a.s;
-      for (int32_t j0 = 0; j0 < ss; j0 += GROUP)
-        n += group(a, t, A, B, C, m, back, x, y, a.s, j0, ss - j0 < GROUP ? ss - j0 : GROUP, sum);
+      const int32_t ss = s * s;
+      for (int32_t j0 = 0; j0 < ss; j0 += G)
+        n += group<G>(a, t, A, B, C, m, back, x, y, s, j0, ss - j0 < G ? ss - j0 : G, sum);
       cnt = (uint8_t)n;
       // step 6: the texel's own point; an odd grid has it as its centre sample already
-      if (n == 0 && !(a.s & 1)) n = group(a, t, A, B, C, m, back, x, y, 1, 0, 1, sum);
+      if (!ONE && n == 0 && !(s & 1)) n = group<1>(a, t, A, B, C, m, back, x, y, 1, 0, 1, sum);
       if (n > 0) {
         src = back ? 2 : 1;
 #pragma unroll

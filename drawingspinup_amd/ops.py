@@ -1809,7 +1809,9 @@ def uv_project(uvs, indices, positions, face_id, color_front, mask_front, color_
     sees.  uvs (V',2) f32, indices (M,3), positions (V',3) f32 in color_projection's frame, face_id
     (S,S) i32 from uv_bake, color_* (res,res,3) u8 and the eroded masks (res,res) u8, all on the
     device.  `grid`: the ZGrid over positions[indices], built here when absent (`cells_per_axis`
-    overrides its resolution).  -> image (S,S,3) u8, source (S,S) u8 (0 none, 1 front, 2 back)."""
+    overrides its resolution).  -> image (S,S,3) u8, source (S,S) u8 (0 none, 1 front, 2 back).
+    The kernel is uv_project_area's at one sample; the grid stays ZGrid's default, since the finer one
+    of uv_area_cells costs more to build than this one launch gains (profiles/uv_project_unified_probe.json)."""
     return _uv_project(None, uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
                        z_tolerance, grid, cells_per_axis)
 
@@ -1844,7 +1846,8 @@ def uv_project_area(uvs, indices, positions, face_id, color_front, mask_front, c
 
 def _uv_project(area, uvs, indices, positions, face_id, color_front, mask_front, color_back, mask_back,
                 z_tolerance, grid, cells_per_axis):
-    """uv_project (area None) and uv_project_area (area = (s, filter)): one preparation of the arguments."""
+    """uv_project (area None) and uv_project_area (area = (s, filter)): one preparation of the arguments
+    for the two C entries, which launch one kernel."""
     uvs, positions = _f32c(uvs), _f32c(positions)
     indices = indices.to(torch.int32).contiguous()
     V, M, S, dev = uvs.shape[0], indices.shape[0], face_id.shape[0], uvs.device

@@ -1689,6 +1689,7 @@ int dsu_corrective_smooth_host(const float* skinned, const int32_t* rep, const i
  * other pointer NULL.  n_faces == 0: DSU_OK, image and source zeroed, the other pointers unread.
  * The mesh must be wound outward in this frame (as marching cubes leaves it): the facing test reads
  * the winding, and a mesh wound inward projects nothing its views can see.
+ * It is computed by j.'s text at s = 1, filter 0, count = NULL (csrc/uv_project_area.h).
  *
  * f. dsu_uv_field_points: the sample points of the field bake (an extension: the reference bakes
  * vertex colours, which hold no more detail than the vertices do; here the optimised texture field
@@ -1823,14 +1824,16 @@ int dsu_corrective_smooth_host(const float* skinned, const int32_t* rep, const i
  * does not depend on the grid, for e.'s reason.  The kernel takes the sub-samples four at a time,
  * walks each cell the four points name once and tests every listed triangle against all of them: a
  * triangle met through another point's cell, or twice, changes nothing, since occlusion is an OR
- * and a triangle that covers a point is in that point's own list.  No atomics: two runs give the
- * same bits.
+ * and a triangle that covers a point is in that point's own list.  At s = 1 every entry, the host
+ * entry included, runs the one-point instantiation of the same text instead: the texel's own point,
+ * alone in its group.  No atomics: two runs give the same bits.
  * DSU_EINVAL before any launch: as e., and s outside 1..8 or filter outside {0, 1}.  n_faces == 0:
  * DSU_OK, image, source and count (when given) zeroed, the other pointers unread.
  *
  * dsu_uv_project_area_host: a HOST function on HOST arrays (tris and the grid arrays included; a
  * grid of one cell, g = 1 with offsets [0, n_faces] and items 0 .. n_faces - 1, is valid by (c)) —
- * the same text (csrc/uv_project_area.h) compiled for the CPU, with the same argument checks. */
+ * the same text (csrc/uv_project_area.h) compiled for the CPU, with the same argument checks.  At
+ * s = 1, filter 0, count = NULL this call is the host statement of dsu_uv_project. */
 #define DSU_UV_COUNT 0
 #define DSU_UV_FILL 1
 #define DSU_UV_RASTER 2

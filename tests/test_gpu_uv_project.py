@@ -1,8 +1,10 @@
-"""GPU: dsu_uv_project (csrc/mesh_uv.hip) against the float64 restatement of its rule
+"""GPU: dsu_uv_project (csrc/uv_project_area.hip) against the float64 restatement of its rule
 (tests/uv_project_ref.py).  The device runs the restatement's float64 operations in the same order
 (no fused products, IEEE division, rint), so EQUALITY is asserted on image and source; the texels
 the restatement marks fragile may be left out, at most 0.5 % of them and none on the lattice case.
-tests/test_uv_project_host.py checks on the CPU that these cases are not vacuous.
+tests/test_uv_project_host.py checks on the CPU that these cases are not vacuous.  Beside that, the
+kernel against its own text compiled for the host (dsu_uv_project_area_host at s = 1, filter 0, which
+tests/test_uv_project_host.py holds to the restatement): every byte, no texel left out.
 
 tools/uv_project_probe.py counts the differences and the fragile texels on these cases and writes
 them to profiles/uv_project_probe.json (`accuracy`)."""
@@ -14,6 +16,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import uv_project_area_ref as A  # noqa: E402
 import uv_project_ref as P  # noqa: E402
 import uv_ref as R  # noqa: E402
 from drawingspinup_amd import ops  # noqa: E402
@@ -74,6 +77,35 @@ def test_project_equals_restatement(dev, name, size, masks):
     if name == "body_and_arm":
         # covered texels that neither view takes: behind the arm, edge-on, or outside the mask
         assert ((c["source"] == 0) & (c["face_id"] >= 0)).sum() > 100
+
+
+def assert_equals_the_host_entry(dev, c, **kw):
+    want = A.host_project_area(c, 1, "nearest", with_count=False)
+    img, src = device_project(dev, c, **kw)
+    img, src = img.cpu().numpy(), src.cpu().numpy()
+    assert np.array_equal(src, want[1]), int((src != want[1]).sum())
+    assert np.array_equal(img, want[0]), int((img != want[0]).any(-1).sum())
+    return src
+
+
+@pytest.mark.parametrize("name,size,masks", A.GPU_CASES)
+def test_project_equals_the_host_entry(dev, name, size, masks):
+    """Long lists, fragile texels, both views, an atlas that is no multiple of the tile."""
+    c = A.case(name, size, masks)
+    src = assert_equals_the_host_entry(dev, c)
+    assert (src == 1).sum() > 50 and ((src == 2).sum() > 50 or name not in P.CLOSED)
+    assert name != "helicoid" or c["fragile"].sum() > 10
+
+
+def test_non_finite_position_equals_the_host_entry(dev):
+    assert_equals_the_host_entry(dev, P.nan_vertex_case())
+
+
+@pytest.mark.parametrize("cells", (1, 2))
+def test_long_cell_lists_equal_the_host_entry(dev, cells):
+    """The walk's long-list path: one list of every triangle, four of hundreds (the host's grid is its
+    own 24 x 24)."""
+    assert_equals_the_host_entry(dev, P.case("body_and_arm", 64), cells_per_axis=cells)
 
 
 def test_long_cell_lists(dev):

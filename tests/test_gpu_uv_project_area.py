@@ -2,7 +2,7 @@
 dsu_uv_project_area_host — one text (csrc/uv_project_area.h) compiled twice, float64 without fused
 products on both sides — so image, source and count are held to EQUALITY in every byte.
 tests/test_uv_project_area_host.py holds the host entry to the numpy restatement of the rule.  Then
-determinism, the old path, bake_drawings on the device against the numpy backend, and the file
+determinism, dsu_uv_project, bake_drawings on the device against the numpy backend, and the file
 save_obj writes."""
 import os
 import sys
@@ -45,7 +45,7 @@ def assert_equal(got, want):
 # ------------------------------------------------------------------ 1. the kernel against the host entry
 @pytest.mark.parametrize("name,size,masks", A.GPU_CASES)
 def test_kernel_equals_the_host_entry(dev, name, size, masks):
-    """s = 1, 2, 3, 4, 8 (one sample, one group, a group and a tail, whole groups, sixteen groups) under
+    """s = 1, 2, 3, 4, 8 (the one-point instantiation, one group, a group and a tail, whole groups, sixteen groups) under
     both filters; the device's grid is ops.ZGrid's, the host's a numpy one."""
     c = A.case(name, size, masks)
     inputs = device_inputs(dev, c)
@@ -57,7 +57,7 @@ def test_kernel_equals_the_host_entry(dev, name, size, masks):
             got = device_project_area(dev, c, s, pixel_filter, inputs)
             assert_equal(got, want)
             assert (want[1] > 0).sum() > 50 and want[2].max() == s * s
-    # the old path: one nearest sample is dsu_uv_project, byte for byte
+    # (a): one nearest sample is dsu_uv_project (the same launch without a count), byte for byte
     img, src = ops.uv_project(*inputs)
     one = device_project_area(dev, c, 1, "nearest", inputs)
     assert np.array_equal(one[0], img.cpu().numpy()) and np.array_equal(one[1], src.cpu().numpy())
@@ -84,7 +84,7 @@ def test_edge_rows_equal_the_host_entry(dev, row):
     tris, ok = A.case_tris(c)
     grid = A.HostGrid(tris, 24, ok)
     inputs = device_inputs(dev, c)
-    for s, pixel_filter in ((1, "nearest"), (2, "bilinear"), (3, "nearest"), (3, "bilinear")):
+    for s, pixel_filter in ((1, "nearest"), (1, "bilinear"), (2, "bilinear"), (3, "nearest"), (3, "bilinear")):
         want = A.host_project_area(c, s, pixel_filter, grid=grid)
         assert_equal(device_project_area(dev, c, s, pixel_filter, inputs, grid=A.DeviceGrid(grid, dev)), want)
 

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import uv_project_area_ref as A  # noqa: E402
 import uv_project_ref as P  # noqa: E402
 from drawingspinup_amd.nsr import uv as U  # noqa: E402
 
@@ -249,3 +250,35 @@ def test_gpu_cases_are_sound(name, size, tol, masks):
     assert counts[0] > (c["face_id"] < 0).sum(), counts                      # some covered texel is left to the fallback
     if tol == 0.0:                                                           # a tolerance only ever admits texels
         assert not ((c["source"] > 0) & (P.case(name, size, P.Z_TOL, masks)["source"] == 0)).any()
+
+
+# ------------------------------------------------------------------ the host statement of dsu_uv_project
+def assert_host_entry_is_rule_e(c, **kw):
+    """dsu_uv_project_area_host at s = 1, filter 0, count = NULL — the call dsu_uv_project's kernel is
+    held to in tests/test_gpu_uv_project.py — against the restatement: every byte, fragile texels
+    included."""
+    image, source, count = A.host_project_area(c, 1, "nearest", with_count=False, **kw)
+    assert count is None and image.dtype == source.dtype == np.uint8
+    assert np.array_equal(source, c["source"]), int((source != c["source"]).sum())
+    assert np.array_equal(image, c["image"]), int((image != c["image"]).any(-1).sum())
+
+
+@pytest.mark.parametrize("name,size,tol,masks", GPU_CASES)
+def test_host_entry_equals_the_restatement(name, size, tol, masks):
+    assert_host_entry_is_rule_e(P.case(name, size, tol, masks))
+
+
+def test_host_entry_with_a_non_finite_position():
+    c = P.nan_vertex_case()
+    bad = int(np.nonzero(np.isnan(c["positions"]).any(1))[0][0])
+    touched = np.isin(c["face_id"], np.nonzero((c["indices"] == bad).any(1))[0])
+    assert (P.case("character", 100)["source"][touched] > 0).any() and not c["source"][touched].any()
+    assert_host_entry_is_rule_e(c)
+
+
+@pytest.mark.parametrize("cells", (1, 40))
+def test_host_entry_does_not_depend_on_the_grid(cells):
+    c = P.case("body_and_arm", 64)
+    grid = A.HostGrid(A.case_tris(c)[0], cells)
+    assert len(grid.offsets) == cells * cells + 1 and (cells == 1 or (np.diff(grid.offsets) == 0).any())
+    assert_host_entry_is_rule_e(c, grid=grid)

@@ -1,5 +1,5 @@
 """Float64 numpy restatement of dsu_uv_project (include/dsu_hip.h, UV export e.), independent of
-csrc/mesh_uv.hip: the texel's point from the atlas barycentrics, the facing / pixel / mask tests
+csrc/uv_project_area.h: the texel's point from the atlas barycentrics, the facing / pixel / mask tests
 and a brute-force occluder search over ALL triangles (no grid: a triangle that covers the point
 is in the point's cell whatever the grid, so the device's answer must not depend on it).  The
 raster itself is tests/uv_ref.py's.  RefBackend plugs the restatement into
@@ -239,3 +239,13 @@ def case(name, size, z_tolerance=Z_TOL, masks="disc"):
     full = np.full((RES, RES), 255, np.uint8)
     m = disc_masks() if masks == "disc" else prepare_masks(c["positions"], c["indices"], full, SIL_ERODE)
     return restate(c, m, z_tolerance)
+
+
+@functools.lru_cache(maxsize=None)
+def nan_vertex_case():
+    """case("character", 100) with a vertex of a projected face turned into NaN, restated."""
+    c = case("character", 100)
+    seen = np.unique(c["face_id"][c["source"] > 0])
+    pos = c["positions"].copy()
+    pos[int(c["indices"][seen[len(seen) // 2], 0])] = np.nan
+    return restate(dict(fixed("character", 100), positions=pos), (c["mask_front"], c["mask_back"]), Z_TOL)

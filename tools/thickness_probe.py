@@ -1,8 +1,8 @@
 """Measure the thickness map (dsu_mesh_thickness_ortho, csrc/mesh_thickness.hip) at production size:
 the 51 200-face probe mesh of tools/uv_probe.py on the 512^2 lattice animate.lift_marks lays over it.
 Records
-  * the kernel's time beside uv_project_kernel's (tools/uv_project_probe.py's setting: 1024^2 atlas,
-    2048^2 drawings) from ONE `rocprofv3 --kernel-trace --stats` run of `--trace-launches N`, no
+  * the kernel's time beside that of dsu_uv_project's kernel (tools/uv_project_probe.py's setting: 1024^2
+    atlas, 2048^2 drawings) from ONE `rocprofv3 --kernel-trace --stats` run of `--trace-launches N`, no
     counters, read back with --kernel-stats,
   * the histogram of crossings per sample, the triangles per grid cell, the share of samples inside,
   * device against the host entry: samples that differ (0 expected),
@@ -33,7 +33,7 @@ from drawingspinup_amd import animate, ops  # noqa: E402
 from drawingspinup_amd.animate import rig  # noqa: E402
 from uv_probe import character  # noqa: E402
 
-KERNELS = ("mesh_thickness_kernel", "uv_project_kernel")
+KERNELS = ("mesh_thickness_kernel", "uv_project_area_kernel<true>")   # the latter: what dsu_uv_project launches
 
 
 def kernel_stats(folder):

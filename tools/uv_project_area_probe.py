@@ -2,12 +2,13 @@
 csrc/uv_project_area.hip; nsr/uv.bake_drawings(samples=, pixel_filter=)) at production size: mesh,
 atlas and drawings as tools/uv_project_probe.py has them (the ~50 000-face probe mesh, a 1024^2
 atlas, 2048^2 drawings).  Records
-  * `kernel_us`: the kernels' own durations from ONE `rocprofv3 --kernel-trace --stats` run of
-    `--trace-launches N` (no counters): uv_project_kernel, the yardstick, on its own grid and on the
-    finer one ops.uv_project_area builds (--cells overrides it), and uv_project_area_kernel at
-    s = 1, 2, 4 under both filters.  The new kernel has one name for all six, so its dispatches
-    are told apart by their order in the kernel trace (N of each, in the order of CONFIGS), and
-    `ratio_to_uv_project` = mean / uv_project_kernel's mean of the same run,
+  * `kernel_us`: the kernel's own durations from ONE `rocprofv3 --kernel-trace --stats` run of
+    `--trace-launches N` (no counters): ops.uv_project, the yardstick, on the grid it builds for
+    itself, and ops.uv_project_area at s = 1, 2, 4 under both filters on the finer grid it builds
+    (--cells overrides it).  All are instantiations of uv_project_area_kernel (s = 1 the one-point
+    one, which is also what ops.uv_project launches), so the dispatches are told apart by their
+    order in the kernel trace (N of each, ops.uv_project first, then in the order of CONFIGS), and
+    `ratio_to_uv_project` = mean / ops.uv_project's mean of the same run,
   * per configuration: count / s^2 over the projected texels, texels gained over s = 1,
   * the standard deviation of the projected texels' blue channel at s = 1, 2, 4 for drawings whose
     blue channel is a one-pixel checker (what aliasing leaves of a pattern a texel cannot hold),
@@ -44,32 +45,27 @@ CONFIGS = [(s, f) for s in (1, 2, 4) for f in ("nearest", "bilinear")]
 
 
 def kernel_trace(folder, launches):
-    """Durations (us) per kernel from the kernel trace under `folder`: uv_project_kernel, and the
-    dispatches of uv_project_area_kernel in start order, `launches` per configuration; uv_project_kernel
-    ran `launches` times on the grid ops.uv_project builds for itself, then as often on the area grid."""
+    """Durations (us) from the kernel trace under `folder`: the dispatches of uv_project_area_kernel in
+    start order, `launches` of ops.uv_project on the grid it builds for itself, then `launches` per
+    configuration."""
     import csv
     import glob
-    old, new = [], []
+    found = []
     for path in sorted(glob.glob(os.path.join(folder, "**", "*kernel_trace.csv"), recursive=True)):
         for row in csv.DictReader(open(path)):
-            name = row.get("Kernel_Name", "")
-            t0, t1 = int(row["Start_Timestamp"]), int(row["End_Timestamp"])
-            if "uv_project_area_kernel" in name:
-                new.append((t0, (t1 - t0) / 1e3))
-            elif "uv_project_kernel" in name:
-                old.append((t0, (t1 - t0) / 1e3))
-    if len(old) != 2 * launches or len(new) != launches * len(CONFIGS):
-        raise SystemExit(f"--kernel-trace {folder}: expected {2 * launches} dispatches of uv_project_kernel and "
-                         f"{launches * len(CONFIGS)} of uv_project_area_kernel, found {len(old)} and {len(new)}")
+            if "uv_project_area_kernel" in row.get("Kernel_Name", ""):
+                t0, t1 = int(row["Start_Timestamp"]), int(row["End_Timestamp"])
+                found.append((t0, (t1 - t0) / 1e3))
+    if len(found) != launches * (1 + len(CONFIGS)):
+        raise SystemExit(f"--kernel-trace {folder}: expected {launches * (1 + len(CONFIGS))} dispatches of "
+                         f"uv_project_area_kernel, found {len(found)}")
     row = lambda d: {"calls": len(d), "mean": statistics.mean(d), "min": min(d), "max": max(d)}
-    old = [d for _, d in sorted(old)]
-    out = {"uv_project_kernel": row(old[:launches]), "uv_project_kernel on the area grid": row(old[launches:])}
-    new = [d for _, d in sorted(new)]
+    found = [d for _, d in sorted(found)]
+    out = {"uv_project": row(found[:launches])}
     for k, (s, f) in enumerate(CONFIGS):
-        r = row(new[k * launches:(k + 1) * launches])
-        r["ratio_to_uv_project"] = r["mean"] / out["uv_project_kernel"]["mean"]
-        r["ratio_to_uv_project_on_the_area_grid"] = r["mean"] / out["uv_project_kernel on the area grid"]["mean"]
-        out[f"uv_project_area_kernel s={s} {f}"] = r
+        r = row(found[(k + 1) * launches:(k + 2) * launches])
+        r["ratio_to_uv_project"] = r["mean"] / out["uv_project"]["mean"]
+        out[f"uv_project_area s={s} {f}"] = r
     return out
 
 
@@ -115,22 +111,21 @@ def main():
                      cells_per_axis=args.cells or ops.uv_area_cells(len(faces)))
 
     own = ops.ZGrid(tris, xy.amin(0).tolist(), xy.amax(0).tolist())          # what ops.uv_project builds
-    old = lambda g=own: ops.uv_project(duv, dind, dpos, fid, cf, front, cb, back, U.Z_TOLERANCE, grid=g)
-    new = lambda s, f: ops.uv_project_area(duv, dind, dpos, fid, cf, front, cb, back, U.Z_TOLERANCE, s, f, grid=grid)
+    one = lambda: ops.uv_project(duv, dind, dpos, fid, cf, front, cb, back, U.Z_TOLERANCE, grid=own)
+    area = lambda s, f: ops.uv_project_area(duv, dind, dpos, fid, cf, front, cb, back, U.Z_TOLERANCE, s, f, grid=grid)
     if args.trace_launches:
-        for g in (own, grid):
-            for _ in range(args.trace_launches):
-                old(g)
+        for _ in range(args.trace_launches):
+            one()
         for s, f in CONFIGS:
             for _ in range(args.trace_launches):
-                new(s, f)
+                area(s, f)
         torch.cuda.synchronize()
         return
     covered = fid >= 0
-    base_img, base_src = old()
+    base_src = one()[1]
     quality = {}
     for s, f in CONFIGS:
-        img, src, cnt = new(s, f)
+        img, src, cnt = area(s, f)
         on = src > 0
         blue = img[..., 2][on].double()
         # the back drawing carries the checker in its red channel (the channels are permuted)
@@ -142,9 +137,7 @@ def main():
             "mean_count_over_s2": float(cnt[on].double().mean()) / (s * s),
             "own_point_texels": int((on & (cnt == 0)).sum()),
             "blue_std_projected": float(blue.std()),
-            "checker_channel_std_projected": float(chk.std()),
-            "s1_nearest_equals_uv_project": bool(torch.equal(img, base_img) and torch.equal(src, base_src))
-            if (s, f) == (1, "nearest") else None}
+            "checker_channel_std_projected": float(chk.std())}
     fallback = colours[vm]
 
     def bake(s, f):
@@ -163,7 +156,7 @@ def main():
         "z_tolerance": U.Z_TOLERANCE, "erode": 19, "covered_texels": int(covered.sum()),
         "grid_cells_per_axis": int(grid.g), "uv_project_grid_cells_per_axis": int(own.g),
         "kernel_us": kernel_trace(args.kernel_trace, args.traced_launches) if args.kernel_trace else None,
-        "kernel_us_source": "one rocprofv3 --kernel-trace --stats run of --trace-launches, no counters; the new "
+        "kernel_us_source": "one rocprofv3 --kernel-trace --stats run of --trace-launches, no counters; the "
                             "kernel's dispatches split by start order (null: not collected)",
         "quality": quality,
         "bake_drawings_wall_ms": wall,

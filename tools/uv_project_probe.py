@@ -1,5 +1,5 @@
-"""Measure the per-texel projection of the drawings into the atlas (dsu_uv_project, csrc/mesh_uv.hip;
-nsr/uv.bake_drawings) at production size: the ~50 000-face probe mesh of tools/uv_probe.py, a
+"""Measure the per-texel projection of the drawings into the atlas (dsu_uv_project,
+csrc/uv_project_area.hip; nsr/uv.bake_drawings) at production size: the ~50 000-face probe mesh of tools/uv_probe.py, a
 1024^2 atlas, 2048^2 drawings.  Records
   * the time of dsu_uv_project beside dsu_uv_bake's raster from the same run, two ways:
     `kernel_us` = the kernels' own durations from a `rocprofv3 --kernel-trace --stats` run of
@@ -38,6 +38,7 @@ from drawingspinup_amd.nsr.mesh_post import projection_masks  # noqa: E402
 from uv_probe import character  # noqa: E402
 
 TOLERANCES = (0.0, 1e-5, 1e-4, 1e-3)
+PROJECT_KERNEL = "uv_project_area_kernel<true>"         # what dsu_uv_project launches
 
 
 def timed_batch(fn, runs, batch, warmup=3):
@@ -56,13 +57,14 @@ def timed_batch(fn, runs, batch, warmup=3):
 
 
 def kernel_stats(folder):
-    """The uv_project / uv_raster rows of rocprofv3's kernel statistics under `folder`, microseconds."""
+    """The rows of dsu_uv_project's kernel (the one-point instantiation of uv_project_area_kernel) and of
+    uv_raster_kernel in rocprofv3's kernel statistics under `folder`, microseconds."""
     import csv
     import glob
     out = {}
     for path in sorted(glob.glob(os.path.join(folder, "**", "*kernel_stats.csv"), recursive=True)):
         for row in csv.DictReader(open(path)):
-            for key in ("uv_project_kernel", "uv_raster_kernel"):
+            for key in (PROJECT_KERNEL, "uv_raster_kernel"):
                 if key in row.get("Name", ""):
                     out[key] = {"calls": int(row["Calls"]), "mean": float(row["AverageNs"]) / 1e3,
                                 "min": float(row["MinNs"]) / 1e3, "max": float(row["MaxNs"]) / 1e3}

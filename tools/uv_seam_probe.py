@@ -3,7 +3,7 @@ nsr/uv.bake_drawings(seam="level")) at production size: the ~50 000-face probe m
 tools/uv_project_probe.py, a 1024^2 atlas, 2048^2 drawings.  The drawings are a smooth function of
 the surface point (the same one in both views); the fallback is the vertex bake of that function
 scaled by 0.8 and shifted by 10 levels: the tone difference levelling is for.  Records
-  * `kernel_us`: the two kernels' own durations beside uv_project_kernel from one
+  * `kernel_us`: the two kernels' own durations beside dsu_uv_project's kernel from one
     `rocprofv3 --kernel-trace --stats` run of `--trace-launches N` (read back with --kernel-stats),
   * the CG iteration count and the counts of known and unknown groups,
   * the wall time of bake_drawings with and without levelling (host clock around the whole call,
@@ -36,7 +36,7 @@ from drawingspinup_amd import ops  # noqa: E402
 from drawingspinup_amd.nsr import uv as U  # noqa: E402
 from uv_probe import character  # noqa: E402
 
-KERNELS = ("uv_seam_gather_kernel", "uv_seam_apply_kernel", "uv_project_kernel")
+KERNELS = ("uv_seam_gather_kernel", "uv_seam_apply_kernel", "uv_project_area_kernel<true>")   # dsu_uv_project's
 # tools/isa_stats.py drawingspinup_amd/csrc/mesh_uv.hip --filter uv_seam (static, from the code object's metadata)
 ISA = {"uv_seam_gather_kernel": {"vgpr": 40, "scratch": 0, "lds": 37120},
        "uv_seam_apply_kernel": {"vgpr": 48, "scratch": 0, "lds": 0}}
