@@ -24,7 +24,10 @@
 // triangles on the edge), so that a closed 2-manifold stays one — Open3D does not test it; the
 // host steps behind this one (cotangent Laplacian of the thinning deformation, z-ray caster)
 // want a manifold.  `flags & 1` switches it off.
+// The arithmetic of the quadrics, the edge's target, the initial planes and the flip test is
+// decimate_quadric.h, shared with the device rounds (mesh_decimate_gpu.hip).
 #include "common.h"
+#include "decimate_quadric.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -37,76 +40,8 @@
 
 namespace {
 
-struct V3 {
-  double x, y, z;
-};
-inline V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-inline V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline V3 operator*(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline V3 cross(V3 a, V3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-inline double norm(V3 a) { return sqrt(dot(a, a)); }
-
-// symmetric 4x4 [A b; b^T c]: error(v) = v^T A v + 2 b^T v + c
-struct Quadric {
-  double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, b0 = 0, b1 = 0, b2 = 0, c = 0;
-  void add_plane(V3 n, double d, double w) {
-    a00 += w * n.x * n.x; a01 += w * n.x * n.y; a02 += w * n.x * n.z;
-    a11 += w * n.y * n.y; a12 += w * n.y * n.z; a22 += w * n.z * n.z;
-    b0 += w * n.x * d; b1 += w * n.y * d; b2 += w * n.z * d;
-    c += w * d * d;
-  }
-  void add(const Quadric& q) {
-    a00 += q.a00; a01 += q.a01; a02 += q.a02; a11 += q.a11; a12 += q.a12; a22 += q.a22;
-    b0 += q.b0; b1 += q.b1; b2 += q.b2; c += q.c;
-  }
-  double eval(V3 v) const {
-    return v.x * (a00 * v.x + 2 * a01 * v.y + 2 * a02 * v.z) + v.y * (a11 * v.y + 2 * a12 * v.z) +
-           a22 * v.z * v.z + 2 * (b0 * v.x + b1 * v.y + b2 * v.z) + c;
-  }
-  // minimiser -A^-1 b when A is well conditioned relative to its own scale, as o + d with
-  // A d = -(b + A o) for a point o near the answer (the edge's midpoint), by elimination with
-  // partial pivoting.  Not the cofactor inverse: on a near-planar quadric (eigenvalues l1 >> l2 of
-  // A) every 2x2 minor cancels to ~l1 l2 with rounding eps l1^2, which puts a factor l1 / l2 on top
-  // of the eps cond(A) |x| a stable solve loses — 8e-8 on marching-cubes vertices at |x| ~ 20,
-  // cond(A) = 3e4.  About o the right-hand side is small, so what is left is eps cond(A) |x| from
-  // its rounding.  The determinant still decides whether to solve at all.
-  struct Row4 {
-    double c[4];
-  };
-  static void swap_if(Row4& a, Row4& b, bool s) {
-    if (s) std::swap(a, b);
-  }
-  static void eliminate(Row4& r, const Row4& piv, int col) {
-    const double f = r.c[col] / piv.c[col];
-    for (int k = 0; k < 4; ++k) r.c[k] -= f * piv.c[k];
-  }
-  bool minimum(V3 o, V3& out) const {
-    const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-    const double det = a00 * c00 + a01 * c01 + a02 * c02;
-    const double tr = a00 + a11 + a22;
-    if (!(tr > 0.0) || !(fabs(det) > 1e-9 * tr * tr * tr)) return false;
-    Row4 r0 = {{a00, a01, a02, -(b0 + (a00 * o.x + a01 * o.y + a02 * o.z))}};
-    Row4 r1 = {{a01, a11, a12, -(b1 + (a01 * o.x + a11 * o.y + a12 * o.z))}};
-    Row4 r2 = {{a02, a12, a22, -(b2 + (a02 * o.x + a12 * o.y + a22 * o.z))}};
-    swap_if(r0, r1, fabs(r1.c[0]) > fabs(r0.c[0]));
-    swap_if(r0, r2, fabs(r2.c[0]) > fabs(r0.c[0]));
-    if (!(fabs(r0.c[0]) > 0.0)) return false;
-    eliminate(r1, r0, 0);
-    eliminate(r2, r0, 0);
-    swap_if(r1, r2, fabs(r2.c[1]) > fabs(r1.c[1]));
-    if (!(fabs(r1.c[1]) > 0.0)) return false;
-    eliminate(r2, r1, 1);
-    if (!(fabs(r2.c[2]) > 0.0)) return false;
-    const double z = r2.c[3] / r2.c[2];
-    const double y = (r1.c[3] - r1.c[2] * z) / r1.c[1];
-    const double x = (r0.c[3] - r0.c[1] * y - r0.c[2] * z) / r0.c[0];
-    out = {o.x + x, o.y + y, o.z + z};
-    return true;
-  }
-};
+using dsu_dq::Quadric;
+using dsu_dq::V3;
 
 struct Entry {
   double cost;
@@ -151,22 +86,7 @@ struct Mesh {
 void edge_target(const Mesh& m, int32_t v0, int32_t v1, double& cost, V3& vbar) {
   Quadric q = m.q[v0];
   q.add(m.q[v1]);
-  const V3 mid = (m.v[v0] + m.v[v1]) * 0.5;
-  if (q.minimum(mid, vbar)) {
-    // a minimiser far outside the edge's neighbourhood means the conditioning test was too kind
-    const double len = norm(m.v[v1] - m.v[v0]);
-    if (norm(vbar - mid) <= 4.0 * len) {
-      cost = q.eval(vbar);
-      return;
-    }
-  }
-  const V3 cand[3] = {m.v[v0], m.v[v1], (m.v[v0] + m.v[v1]) * 0.5};
-  cost = q.eval(cand[0]);
-  vbar = cand[0];
-  for (int i = 1; i < 3; ++i) {
-    const double c = q.eval(cand[i]);
-    if (c < cost) { cost = c; vbar = cand[i]; }
-  }
+  dsu_dq::edge_target(q, m.v[v0], m.v[v1], cost, vbar);
 }
 
 }  // namespace
@@ -214,9 +134,8 @@ static int decimate_impl(const double* verts, int64_t n_verts, const int32_t* fa
     const V3 cr = m.tri_cross(t);
     const double l = norm(cr);
     if (l > 0.0 && !init_quadrics) {
-      const V3 n = cr * (1.0 / l);
-      const double area = 0.5 * l, d = -dot(n, m.v[m.f[3 * t]]);
-      for (int k = 0; k < 3; ++k) m.q[m.f[3 * t + k]].add_plane(n, d, area);
+      const dsu_dq::Plane p = dsu_dq::face_plane(cr, l, m.v[m.f[3 * t]]);
+      for (int k = 0; k < 3; ++k) m.q[m.f[3 * t + k]].add_plane(p.n, p.d, p.w);
     }
     for (int k = 0; k < 3; ++k) {
       const uint64_t key = ekey(m.f[3 * t + k], m.f[3 * t + (k + 1) % 3]);
@@ -225,14 +144,10 @@ static int decimate_impl(const double* verts, int64_t n_verts, const int32_t* fa
     }
   }
   if (init_quadrics) {
-    // quadrics accumulated by earlier collapses (dsu_mesh_decimate_parallel): (n_verts,10) in this
-    // file's member order a00 a01 a02 a11 a12 a22 b0 b1 b2 c
-    for (int64_t i = 0; i < n_verts; ++i) {
-      const double* p = init_quadrics + 10 * i;
-      Quadric& q = m.q[i];
-      q.a00 = p[0]; q.a01 = p[1]; q.a02 = p[2]; q.a11 = p[3]; q.a12 = p[4]; q.a22 = p[5];
-      q.b0 = p[6]; q.b1 = p[7]; q.b2 = p[8]; q.c = p[9];
-    }
+    // quadrics accumulated by earlier collapses (dsu_mesh_decimate_parallel): (n_verts,10), the ten
+    // doubles of Quadric
+    static_assert(sizeof(Quadric) == 10 * sizeof(double), "Quadric is the ABI's ten doubles");
+    if (n_verts) memcpy(m.q.data(), init_quadrics, (size_t)n_verts * sizeof(Quadric));
   }
   if (boundary_weight > 0.0 && !init_quadrics) {
     for (const auto& kv : edge_count) {
@@ -242,13 +157,12 @@ static int decimate_impl(const double* verts, int64_t n_verts, const int32_t* fa
       const V3 cr = m.tri_cross(t);
       const double l = norm(cr);
       if (!(l > 0.0)) continue;
-      V3 en = cross(m.v[b] - m.v[a], cr * (1.0 / l));
+      const V3 en = dsu_dq::boundary_cross(m.v[a], m.v[b], dsu_dq::unit(cr, l));   // a < b: the key's order
       const double el = norm(en);
       if (!(el > 0.0)) continue;
-      en = en * (1.0 / el);
-      const double w = boundary_weight * 0.5 * l, d = -dot(en, m.v[a]);
-      m.q[a].add_plane(en, d, w);
-      m.q[b].add_plane(en, d, w);
+      const dsu_dq::Plane p = dsu_dq::boundary_plane(en, el, m.v[a], l, boundary_weight);
+      m.q[a].add_plane(p.n, p.d, p.w);
+      m.q[b].add_plane(p.n, p.d, p.w);
     }
   }
   // ---- queue of all edges
@@ -285,11 +199,12 @@ static int decimate_impl(const double* verts, int64_t n_verts, const int32_t* fa
       const int32_t mv = pass ? v0 : v1, other = pass ? v1 : v0;
       for (int32_t t : m.vt[mv]) {
         if (m.has(t, other)) { if (!pass) ++shared; continue; }
-        const V3 before = m.tri_cross(t);
-        V3 p[3];
-        for (int k = 0; k < 3; ++k) p[k] = m.f[3 * t + k] == mv ? vbar : m.v[m.f[3 * t + k]];
-        const V3 after = cross(p[1] - p[0], p[2] - p[0]);
-        if (dot(before, after) < 0.0) { bad = true; break; }
+        V3 p[3], q[3];
+        for (int k = 0; k < 3; ++k) {
+          p[k] = m.v[m.f[3 * t + k]];
+          q[k] = m.f[3 * t + k] == mv ? vbar : p[k];
+        }
+        if (flips(p, q)) { bad = true; break; }
       }
     }
     if (bad || shared == 0) continue;

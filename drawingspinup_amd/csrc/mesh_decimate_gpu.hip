@@ -8,7 +8,7 @@
 // core at that size — three times the whole NSR optimisation.  Here the same admissible-collapse
 // rules run as ROUNDS of independent collapses:
 //   1. vertex -> triangle lists (CSR) of the live mesh; one "owner" half-edge per edge;
-//   2. cost + target of every edge (identical arithmetic to the serial code: edge_target);
+//   2. cost + target of every edge;
 //   3. the cheapest `budget` edges are candidates, ranked by (cost, edge order);
 //   4. every candidate writes a (hashed, unique) priority into all vertices of its closed
 //      neighbourhood (v0, v1 and their one-rings) with atomicMin; a candidate whose two END POINTS
@@ -40,7 +40,10 @@
 // run in list order; atomics only take minima of unique integers.
 // Scans / compaction / radix sort: hipCUB device primitives (header-only), on the caller's stream
 // with the caller's workspace.
+// The arithmetic of the quadrics, the edge's target, the initial planes and the flip test is
+// decimate_quadric.h, shared with the serial queue (mesh_decimate.hip).
 #include "common.h"
+#include "decimate_quadric.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -49,72 +52,8 @@
 
 namespace {
 
-struct D3 {
-  double x, y, z;
-};
-__device__ inline D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ inline D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline D3 operator*(D3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ inline double dot3(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ inline D3 cross3(D3 a, D3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ inline double norm3(D3 a) { return sqrt(dot3(a, a)); }
-
-// [A b; b^T c], 10 doubles: a00 a01 a02 a11 a12 a22 b0 b1 b2 c  (the serial code's Quadric)
-struct Quad {
-  double q[10];
-};
-__device__ inline void quad_zero(Quad& a) {
-  for (int i = 0; i < 10; ++i) a.q[i] = 0.0;
-}
-__device__ inline void quad_add_plane(Quad& a, D3 n, double d, double w) {
-  a.q[0] += w * n.x * n.x; a.q[1] += w * n.x * n.y; a.q[2] += w * n.x * n.z;
-  a.q[3] += w * n.y * n.y; a.q[4] += w * n.y * n.z; a.q[5] += w * n.z * n.z;
-  a.q[6] += w * n.x * d; a.q[7] += w * n.y * d; a.q[8] += w * n.z * d;
-  a.q[9] += w * d * d;
-}
-__device__ inline double quad_eval(const Quad& a, D3 v) {
-  return v.x * (a.q[0] * v.x + 2 * a.q[1] * v.y + 2 * a.q[2] * v.z) +
-         v.y * (a.q[3] * v.y + 2 * a.q[4] * v.z) + a.q[5] * v.z * v.z +
-         2 * (a.q[6] * v.x + a.q[7] * v.y + a.q[8] * v.z) + a.q[9];
-}
-// mesh_decimate.hip: Quadric::minimum (same arithmetic: see there why it is not the cofactor inverse)
-struct Row4 {
-  double c[4];
-};
-__device__ inline void row_swap_if(Row4& a, Row4& b, bool s) {
-  if (s) { const Row4 t = a; a = b; b = t; }
-}
-__device__ inline void row_eliminate(Row4& r, const Row4& piv, int col) {
-  const double f = r.c[col] / piv.c[col];
-  for (int k = 0; k < 4; ++k) r.c[k] -= f * piv.c[k];
-}
-__device__ inline bool quad_minimum(const Quad& a, D3 o, D3& out) {
-  const double a00 = a.q[0], a01 = a.q[1], a02 = a.q[2], a11 = a.q[3], a12 = a.q[4], a22 = a.q[5];
-  const double b0 = a.q[6], b1 = a.q[7], b2 = a.q[8];
-  const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-  const double det = a00 * c00 + a01 * c01 + a02 * c02;
-  const double tr = a00 + a11 + a22;
-  if (!(tr > 0.0) || !(fabs(det) > 1e-9 * tr * tr * tr)) return false;
-  Row4 r0 = {{a00, a01, a02, -(b0 + (a00 * o.x + a01 * o.y + a02 * o.z))}};
-  Row4 r1 = {{a01, a11, a12, -(b1 + (a01 * o.x + a11 * o.y + a12 * o.z))}};
-  Row4 r2 = {{a02, a12, a22, -(b2 + (a02 * o.x + a12 * o.y + a22 * o.z))}};
-  row_swap_if(r0, r1, fabs(r1.c[0]) > fabs(r0.c[0]));
-  row_swap_if(r0, r2, fabs(r2.c[0]) > fabs(r0.c[0]));
-  if (!(fabs(r0.c[0]) > 0.0)) return false;
-  row_eliminate(r1, r0, 0);
-  row_eliminate(r2, r0, 0);
-  row_swap_if(r1, r2, fabs(r2.c[1]) > fabs(r1.c[1]));
-  if (!(fabs(r1.c[1]) > 0.0)) return false;
-  row_eliminate(r2, r1, 1);
-  if (!(fabs(r2.c[2]) > 0.0)) return false;
-  const double z = r2.c[3] / r2.c[2];
-  const double y = (r1.c[3] - r1.c[2] * z) / r1.c[1];
-  const double x = (r0.c[3] - r0.c[1] * y - r0.c[2] * z) / r0.c[0];
-  out = {o.x + x, o.y + y, o.z + z};
-  return true;
-}
+using dsu_dq::Quadric;
+using dsu_dq::V3;
 
 struct Mesh {
   double* P;        // (nv,3)
@@ -125,37 +64,19 @@ struct Mesh {
   int64_t nv, nf;
 };
 
-__device__ inline D3 ldP(const Mesh& m, int32_t v) { return {m.P[3 * v], m.P[3 * v + 1], m.P[3 * v + 2]}; }
-__device__ inline Quad ldQ(const Mesh& m, int32_t v) {
-  Quad a;
+__device__ inline V3 ldP(const Mesh& m, int32_t v) { return {m.P[3 * v], m.P[3 * v + 1], m.P[3 * v + 2]}; }
+__device__ inline Quadric ldQ(const Mesh& m, int32_t v) {
+  Quadric a;
   for (int i = 0; i < 10; ++i) a.q[i] = m.Q[10 * (int64_t)v + i];
   return a;
 }
 __device__ inline bool tri_has(const Mesh& m, int32_t t, int32_t v) {
   return m.F[3 * t] == v || m.F[3 * t + 1] == v || m.F[3 * t + 2] == v;
 }
-
-// mesh_decimate.hip: edge_target
-__device__ inline void edge_target(const Mesh& m, int32_t v0, int32_t v1, double& cost, D3& vbar) {
-  Quad q = ldQ(m, v0);
-  const Quad q1 = ldQ(m, v1);
-  for (int i = 0; i < 10; ++i) q.q[i] += q1.q[i];
-  const D3 p0 = ldP(m, v0), p1 = ldP(m, v1);
-  const D3 mid = (p0 + p1) * 0.5;
-  if (quad_minimum(q, mid, vbar)) {
-    const double len = norm3(p1 - p0);
-    if (norm3(vbar - mid) <= 4.0 * len) {
-      cost = quad_eval(q, vbar);
-      return;
-    }
-  }
-  const D3 cand[3] = {p0, p1, (p0 + p1) * 0.5};
-  cost = quad_eval(q, cand[0]);
-  vbar = cand[0];
-  for (int i = 1; i < 3; ++i) {
-    const double c = quad_eval(q, cand[i]);
-    if (c < cost) { cost = c; vbar = cand[i]; }
-  }
+__device__ inline void edge_target(const Mesh& m, int32_t v0, int32_t v1, double& cost, V3& vbar) {
+  Quadric q = ldQ(m, v0);
+  q.add(ldQ(m, v1));
+  dsu_dq::edge_target(q, ldP(m, v0), ldP(m, v1), cost, vbar);
 }
 
 // ------------------------------------------------------------------------------------ CSR
@@ -205,17 +126,16 @@ __device__ inline bool has_half_edge(const Mesh& m, int32_t a, int32_t b) {
 // ------------------------------------------------------------------------------------ quadrics
 __global__ void init_quadrics_kernel(Mesh m, double boundary_weight) {
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < m.nv; v += (int64_t)gridDim.x * blockDim.x) {
-    Quad q;
-    quad_zero(q);
+    Quadric q;
     for (int32_t i = m.voff[v]; i < m.voff[v + 1]; ++i) {
       const int32_t t = m.vfaces[i];
       const int32_t a = m.F[3 * t], b = m.F[3 * t + 1], c = m.F[3 * t + 2];
-      const D3 pa = ldP(m, a), pb = ldP(m, b), pc = ldP(m, c);
-      const D3 cr = cross3(pb - pa, pc - pa);
-      const double l = norm3(cr);
+      const V3 pa = ldP(m, a), pb = ldP(m, b), pc = ldP(m, c);
+      const V3 cr = cross(pb - pa, pc - pa);
+      const double l = norm(cr);
       if (!(l > 0.0)) continue;
-      const D3 n = cr * (1.0 / l);
-      quad_add_plane(q, n, -dot3(n, pa), 0.5 * l);
+      const dsu_dq::Plane fp = dsu_dq::face_plane(cr, l, pa);
+      q.add_plane(fp.n, fp.d, fp.w);
       if (boundary_weight > 0.0) {
         // the two edges of t at v; an edge with no opposite half-edge is a boundary edge
         for (int k = 0; k < 3; ++k) {
@@ -231,11 +151,12 @@ __global__ void init_quadrics_kernel(Mesh m, double boundary_weight) {
           }
           if (same != 1) continue;
           const int32_t lo = e0 < e1 ? e0 : e1, hi = e0 < e1 ? e1 : e0;
-          D3 en = cross3(ldP(m, hi) - ldP(m, lo), n);
-          const double el = norm3(en);
+          const V3 phi = ldP(m, hi), plo = ldP(m, lo);     // hi first: the order the kernel was generated in
+          const V3 en = dsu_dq::boundary_cross(plo, phi, fp.n);
+          const double el = norm(en);
           if (!(el > 0.0)) continue;
-          en = en * (1.0 / el);
-          quad_add_plane(q, en, -dot3(en, ldP(m, lo)), boundary_weight * 0.5 * l);
+          const dsu_dq::Plane bp = dsu_dq::boundary_plane(en, el, plo, l, boundary_weight);
+          q.add_plane(bp.n, bp.d, bp.w);
         }
       }
     }
@@ -286,7 +207,7 @@ __global__ void edge_cost_kernel(Mesh m, const int32_t* edges, int64_t ne, const
     const int32_t t = h / 3, k = h % 3;
     const int32_t a = m.F[3 * t + k], b = m.F[3 * t + (k + 1) % 3];
     const int32_t v0 = a < b ? a : b, v1 = a < b ? b : a;
-    double cost; D3 vb;
+    double cost; V3 vb;
     edge_target(m, v0, v1, cost, vb);
     float c = (float)(cost > 0.0 ? cost : 0.0);
     const unsigned long long key = ekey(v0, v1);
@@ -507,7 +428,7 @@ __device__ inline Outcome test_and_apply(const Mesh& m, int32_t v0, int32_t v1, 
                                      uint8_t* f_alive, Reject* rej, uint32_t n_slots, uint32_t* vver,
                                      uint32_t* touched, uint32_t mark) {
   {
-    double cost; D3 vbar;
+    double cost; V3 vbar;
     edge_target(m, v0, v1, cost, vbar);
     const int32_t b0 = m.voff[v0], e0 = m.voff[v0 + 1], b1 = m.voff[v1], e1 = m.voff[v1 + 1];
     int shared = 0;
@@ -517,14 +438,12 @@ __device__ inline Outcome test_and_apply(const Mesh& m, int32_t v0, int32_t v1, 
       for (int32_t i = m.voff[mv]; i < m.voff[mv + 1]; ++i) {
         const int32_t t = m.vfaces[i];
         if (tri_has(m, t, other)) { if (!pass) ++shared; continue; }
-        D3 p[3], q[3];
+        V3 p[3], q[3];
         for (int k = 0; k < 3; ++k) {
           p[k] = ldP(m, m.F[3 * t + k]);
           q[k] = m.F[3 * t + k] == mv ? vbar : p[k];
         }
-        const D3 before = cross3(p[1] - p[0], p[2] - p[0]);
-        const D3 after = cross3(q[1] - q[0], q[2] - q[0]);
-        if (dot3(before, after) < 0.0) { bad = true; break; }
+        if (flips(p, q)) { bad = true; break; }
       }
     }
     if (!bad && shared == 0) bad = true;
