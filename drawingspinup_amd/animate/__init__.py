@@ -22,7 +22,9 @@ is a parameter.
 Textured frames: `read_obj_textured` keeps a textured export's uvs and atlas, and `render_frames` /
 `animate_mesh` with `texture=` and `uvs=` sample the atlas inside the rasteriser's resolve, per
 sub-sample (nearest, bilinear, or trilinear on the atlas's mip pyramid — `texture_filter="trilinear"`,
-isotropic, for an atlas finer than the sample lattice; no anisotropic filtering, no seam blending),
+isotropic, for an atlas finer than the sample lattice —, or `texture_filter="anisotropic"` with up to
+`max_anisotropy` probes of that pyramid along the long axis of each face's footprint, for the faces
+that turn edge-on towards the silhouette; no seam blending),
 where Blender reads `map_Kd`.
 Without them the colour frames interpolate the vertex colours, as before.
 

@@ -225,32 +225,53 @@ def frame_window(frames_xyz):
 MIP_COVERAGE = ("faces", "all")
 
 
-def _texture_args(texture, uvs, texture_filter, n_verts, dev, faces=None, mip_coverage="faces"):
+def _texture_args(texture, uvs, texture_filter, n_verts, dev, faces=None, mip_coverage="faces",
+                  max_anisotropy=None):
     """The uv / texture / filter keywords of ops.mesh_render_ortho from a host or device texture
     (T,T,3|4) uint8 and uvs (V,2), or {} without a texture.  texture_filter "trilinear" adds the
     texture's mip pyramid, built here once for all frames: mip_coverage "faces" averages only the
-    texels the uv faces (M,3) cover, "all" every texel."""
+    texels the uv faces (M,3) cover, "all" every texel.  "anisotropic" adds the same pyramid with
+    gutter = max(2, max_anisotropy) rounds — the reach of the outermost probe (include/dsu_hip.h,
+    "Anisotropic frames") — and under "faces" dilates level 0 by as many rounds first (ops.uv_dilate:
+    covered texels keep their bytes), so a probe that leaves its chart reads the chart's own border."""
     if mip_coverage not in MIP_COVERAGE:
         raise ValueError(f"mip_coverage must be one of {list(MIP_COVERAGE)}")
-    if (texture is None) != (uvs is None) or (texture is None and texture_filter == ops.MIP_TRILINEAR):
-        raise ValueError("texture and uvs come together or not at all (texture_filter 'trilinear' needs both)")
+    if texture_filter == ops.ANISOTROPIC or max_anisotropy is not None:      # the cap, before anything is built
+        try:
+            cap = ops.check_texture_filter(texture_filter, max_anisotropy)
+        except ValueError as e:
+            raise ValueError(f"texture_filter / max_anisotropy: {e}") from None
+    else:
+        cap = None
+    if (texture is None) != (uvs is None) or (texture is None and texture_filter in ops.PYRAMID_FILTERS):
+        raise ValueError("texture and uvs come together or not at all (texture_filter 'trilinear' and 'anisotropic' "
+                         "need both)")
     if texture is None:
         return {}
-    if texture_filter not in ops.TEXTURE_FILTERS:
-        raise ValueError(f"texture_filter must be one of {sorted(ops.TEXTURE_FILTERS)}")
+    if cap is None and texture_filter not in ops.TEXTURE_FILTERS:
+        raise ValueError(f"texture_filter must be one of {sorted([*ops.TEXTURE_FILTERS, ops.ANISOTROPIC])}")
     to_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
     uv = to_t(uvs).to(dev, torch.float32).reshape(-1, 2)
     if len(uv) != n_verts:
         raise ValueError("one uv per vertex")
     tex = {"uv": uv, "texture": to_t(texture).to(dev), "filter": texture_filter}
-    if texture_filter == ops.MIP_TRILINEAR:
+    if texture_filter in ops.PYRAMID_FILTERS:
         covered = None
         if mip_coverage == "faces":
             # the bake's own coverage rule (dsu_uv_bake): counter-clockwise uv faces only
             idx = to_t(faces).to(dev).reshape(-1, 3)
             T = tex["texture"].shape[0]
             covered = ops.uv_bake(uv, idx, torch.zeros(n_verts, 3, device=dev), T)[1] >= 0
-        tex["pyramid"] = ops.mip_pyramid(tex["texture"], covered)
+        if cap is None:
+            tex["pyramid"] = ops.mip_pyramid(tex["texture"], covered)
+        else:
+            gutter = max(2, cap)
+            tex["max_anisotropy"] = cap
+            if covered is not None:
+                rgba = ops.texture_rgba(tex["texture"])
+                rgb, covered = ops.uv_dilate(rgba[..., :3].contiguous(), covered, gutter)
+                tex["texture"] = torch.cat([rgb, rgba[..., 3:]], -1).contiguous()
+            tex["pyramid"] = ops.mip_pyramid(tex["texture"], covered, gutter)
     return tex
 
 
@@ -327,7 +348,7 @@ def _vertex_colours(colours, n_verts, textured):
 @torch.no_grad()
 def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24, device="cuda",
                   window=None, want=(), texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces",
-                  pixel_filter=None, filter_width=None):
+                  pixel_filter=None, filter_width=None, max_anisotropy=None):
     """Render the motion of one mesh.  verts (V,3) in save_mesh's frame (x right, y up, z front; the
     viewer sits on +z), faces (M,3) 0-based, colours (V,3) in [0,1].
 
@@ -340,7 +361,12 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     average: "faces" (default) those a uv face covers under the bake's rule (ops.uv_bake: counter-
     clockwise uv faces only), so the background of the atlas does not bleed into the charts; "all"
     every texel — the choice for a foreign OBJ whose charts are mirrored (clockwise in uv), which
-    "faces" would count as uncovered.
+    "faces" would count as uncovered.  "anisotropic" reads the same pyramid with up to max_anisotropy
+    (1..16, default 8) probes per sub-sample along the long axis of the face's texel footprint, each at
+    the level of the footprint divided by their number: a face that turns edge-on towards the
+    silhouette keeps the detail along the axis that is not compressed, where "trilinear" blurs both
+    (include/dsu_hip.h, "Anisotropic frames").  Its pyramid has max(2, max_anisotropy) gutter rounds
+    and, under mip_coverage "faces", a level 0 dilated by as many.
 
     pixel_filter None is the box over a pixel's own ss^2 samples.  "eevee", "cycles" or
     "blackman_harris" (with filter_width in pixels; it overrides a preset's) reconstruct a pixel with
@@ -359,7 +385,7 @@ def render_frames(verts, faces, colours, motion="rest_rotate", ss=4, n_frames=24
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage, max_anisotropy)
     tex.update(_pixel_filter_args(pixel_filter, filter_width, ss))
     c = _vertex_colours(colours, len(v), texture is not None)
     xyz = motion_frames(v, motion, n_frames)

@@ -163,7 +163,7 @@ def cor_centres(verts, faces, weights, n_joints, device="cuda", sigma=COR_SIGMA)
 def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, device="cuda", K=4, want=(),
                  texture=None, uvs=None, texture_filter="bilinear", mip_coverage="faces", skinning="linear",
                  corrective_iterations=0, corrective_factor=0.5, pixel_filter=None, filter_width=None,
-                 centres=None, cor_sigma=COR_SIGMA):
+                 centres=None, cor_sigma=COR_SIGMA, max_anisotropy=None):
     """Render a skinned animation of one mesh: weights (bone heat unless given as (influences,
     weights)), skinning on the device, then the rasteriser of render_frames.  skinning: "linear"
     blends the joints' matrices (ops.skin_lbs, Blender's default), "dual_quaternion" their unit dual
@@ -177,7 +177,7 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     bit for bit; one without (a single joint, or joints no triangle shares) takes the linear blend.
     The skinned vertices never leave the device; the
     window is frame_window's rule on their bounding box over all frames (Blender uses the object's
-    bound_box).  texture, uvs, texture_filter, mip_coverage, pixel_filter, filter_width: as in
+    bound_box).  texture, uvs, texture_filter, max_anisotropy, mip_coverage, pixel_filter, filter_width: as in
     render_frames (colours may be None with a texture).
     corrective_iterations N > 0 runs the corrective smoothing (delta mush,
     ops.corrective_smooth: N smoothing steps of strength corrective_factor, then the rest mesh's
@@ -195,7 +195,7 @@ def animate_mesh(verts, faces, colours, skeleton, clip, weights=None, ss=4, devi
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     v = to_np(verts).astype(np.float64).reshape(-1, 3)
     f = to_np(faces).astype(np.int64).reshape(-1, 3)
-    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage)
+    tex = _texture_args(texture, uvs, texture_filter, len(v), dev, f, mip_coverage, max_anisotropy)
     tex.update(_pixel_filter_args(pixel_filter, filter_width, ss))
     c = _vertex_colours(colours, len(v), texture is not None)
     if weights is None:

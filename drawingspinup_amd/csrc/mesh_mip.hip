@@ -178,4 +178,31 @@ int dsu_mip_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* 
   return DSU_OK;
 }
 
+// HOST: the anisotropic resolve's per-face and per-sample text (include/dsu_hip.h, "Anisotropic frames")
+// on host arrays, one (face, sample) pair per item.
+int dsu_aniso_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tri, const float* uv, double h,
+                          const double* tx, const double* ty, int32_t max_aniso, int64_t n, float* rgb_out,
+                          int32_t* probes_out, double* rho_out, double* axis_out) {
+  if (!size_ok(tex_size) || n < 0 || max_aniso < 1 || max_aniso > dsu_mip::MAX_ANISO || !dsu_mip::finite(h))
+    return DSU_EINVAL;
+  if (n && (!pyramid || (uintptr_t)pyramid % 4 || !tri || !uv || !tx || !ty || !rgb_out)) return DSU_EINVAL;
+  const uint32_t* pyr = reinterpret_cast<const uint32_t*>(pyramid);
+  const int L = dsu_mip::levels(tex_size);
+  for (int64_t i = 0; i < n; ++i) {
+    const double* p = tri + 6 * i;
+    const float* q = uv + 6 * i;
+    const dsu_mip::AnisoFace f = dsu_mip::footprint_aniso(p[0], p[1], p[2], p[3], p[4], p[5], q[0], q[1], q[2], q[3],
+                                                          q[4], q[5], tex_size, h, max_aniso, L);
+    dsu_mip::sample_aniso(pyr, tex_size, tx[i], ty[i], f.s1, f.N, f.ax, f.ay, f.k, f.t,
+                          dsu_mip::level_offset(tex_size, f.k), rgb_out + 3 * i);
+    if (probes_out) probes_out[i] = f.N;
+    if (rho_out) rho_out[i] = f.rho;
+    if (axis_out) {
+      axis_out[2 * i] = f.ax;
+      axis_out[2 * i + 1] = f.ay;
+    }
+  }
+  return DSU_OK;
+}
+
 }  // extern "C"

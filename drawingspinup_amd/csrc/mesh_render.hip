@@ -32,6 +32,11 @@
 // uv is affine on a face, so the level is constant per (frame, face): it is computed where the
 // face's attributes are loaded.  The two levels of a face lie near each other in the buffer.
 //
+// Anisotropic frames (`tex` with filter ANISOTROPIC): the same pyramid, read N times per sample along the
+// major axis of the face's footprint, at the level of the footprint divided by N (mip_sample.h).  Axis,
+// length, N and level are per (frame, face) like the trilinear level; the probes of a sample are a loop
+// in the resolve, 4 or 8 texel loads each, on texels that neighbouring samples' probes share.
+//
 // Pixel filter (dsu_mesh_render_ortho_filtered): a pixel gathers the samples of its own square and of
 // `halo` sub-samples around it, weighted by a separable table the caller hands in (film_filter.h
 // holds the accumulation, for the kernel and for dsu_pixel_filter_resolve_host).  The workgroup's key
@@ -164,10 +169,11 @@ struct RenderTexture {
   const float* __restrict__ uv;
   const uint32_t* __restrict__ texels;
   int32_t T;
+  int32_t max_aniso;          // TEX_ANISO: the cap on the probes of a sample
 };
 
 constexpr int TEX_NONE = -1, TEX_NEAREST = DSU_TEX_NEAREST, TEX_BILINEAR = DSU_TEX_BILINEAR,
-              TEX_TRILINEAR = DSU_TEX_TRILINEAR;
+              TEX_TRILINEAR = DSU_TEX_TRILINEAR, TEX_ANISO = DSU_TEX_ANISOTROPIC;
 
 __device__ __forceinline__ float texel_channel(uint32_t p, int ch) { return (float)((p >> (8 * ch)) & 255u); }
 
@@ -199,8 +205,8 @@ __device__ __forceinline__ void sample_atlas(const RenderTexture& tex, double tx
 }
 
 // One workgroup of four waves per (frame, tile).  TEX: where the colour channels of a sample come
-// from — TEX_NONE the vertex colours, TEX_NEAREST / TEX_BILINEAR the atlas, TEX_TRILINEAR its pyramid
-// (tex.texels is then the pyramid buffer, tex.T the side of level 0).
+// from — TEX_NONE the vertex colours, TEX_NEAREST / TEX_BILINEAR the atlas, TEX_TRILINEAR / TEX_ANISO its
+// pyramid (tex.texels is then the pyramid buffer, tex.T the side of level 0).
 template <int SS, int TEX>
 __device__ __forceinline__ void raster_resolve_tile(
     unsigned long long* keys, double* xs, double* ys,
@@ -279,6 +285,7 @@ __device__ __forceinline__ void raster_resolve_tile(
   float ua = 0.0f, va = 0.0f, ub = 0.0f, vb = 0.0f, uc = 0.0f, vc = 0.0f;
   int lod_k = 0, lod_at = 0;                        // TEX_TRILINEAR: the face's level, its texel offset
   double lod_t = 0.0;                               // and the weight of level lod_k + 1
+  dsu_mip::AnisoFace an;                            // TEX_ANISO: the face's axis, probes and level
   for (int sy = 0; sy < SS; ++sy)
     for (int sx = 0; sx < SS; ++sx) {
       const int lr = py * SS + sy, lc = px * SS + sx;
@@ -311,6 +318,11 @@ __device__ __forceinline__ void raster_resolve_tile(
           dsu_mip::lod(rho, dsu_mip::levels(tex.T), lod_k, lod_t);
           lod_at = (int)dsu_mip::level_offset(tex.T, lod_k);
         }
+        if constexpr (TEX == TEX_ANISO) {
+          an = dsu_mip::footprint_aniso(t.ax, t.ay, t.bx, t.by, t.cx, t.cy, ua, va, ub, vb, uc, vc, tex.T,
+                                        view.span / (double)view.N, tex.max_aniso, dsu_mip::levels(tex.T));
+          lod_at = (int)dsu_mip::level_offset(tex.T, an.k);
+        }
         last = m;
       }
       double w0, w1, w2;
@@ -322,6 +334,9 @@ __device__ __forceinline__ void raster_resolve_tile(
         float rgb[3];
         if constexpr (TEX == TEX_TRILINEAR)
           dsu_mip::sample(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, lod_k, lod_t, lod_at, rgb);
+        else if constexpr (TEX == TEX_ANISO)
+          dsu_mip::sample_aniso(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, an.s1, an.N, an.ax, an.ay,
+                                an.k, an.t, lod_at, rgb);
         else
           sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, rgb);
 #pragma unroll
@@ -374,7 +389,7 @@ __global__ __launch_bounds__(256) void mesh_raster_resolve_kernel(
   __shared__ unsigned long long keys[T * T];
   __shared__ double xs[T], ys[T];
   raster_resolve_tile<SS, TEX_NONE>(keys, xs, ys, screen, faces, colour, pos, V, M, view, offsets, items,
-                                    n_items, RenderTexture{nullptr, nullptr, 0}, out);
+                                    n_items, RenderTexture{nullptr, nullptr, 0, 0}, out);
 }
 
 template <int SS, int FILTER>
@@ -408,6 +423,7 @@ struct FaceAttributes {
   float ua = 0.0f, va = 0.0f, ub = 0.0f, vb = 0.0f, uc = 0.0f, vc = 0.0f;
   int lod_k = 0, lod_at = 0;
   double lod_t = 0.0;
+  dsu_mip::AnisoFace an;
 
   __device__ __forceinline__ void load(uint32_t m, const float* __restrict__ sv, const int32_t* __restrict__ faces,
                                        const float* __restrict__ colour, const float* __restrict__ pos, int64_t V,
@@ -437,6 +453,11 @@ struct FaceAttributes {
       dsu_mip::lod(rho, dsu_mip::levels(tex.T), lod_k, lod_t);
       lod_at = (int)dsu_mip::level_offset(tex.T, lod_k);
     }
+    if constexpr (TEX == TEX_ANISO) {
+      an = dsu_mip::footprint_aniso(t.ax, t.ay, t.bx, t.by, t.cx, t.cy, ua, va, ub, vb, uc, vc, tex.T,
+                                    view.span / (double)view.N, tex.max_aniso, dsu_mip::levels(tex.T));
+      lod_at = (int)dsu_mip::level_offset(tex.T, an.k);
+    }
     face = m;
   }
 
@@ -451,6 +472,9 @@ struct FaceAttributes {
       const double v = (w0 * (double)va + w1 * (double)vb + w2 * (double)vc) / area;
       if constexpr (TEX == TEX_TRILINEAR)
         dsu_mip::sample(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, lod_k, lod_t, lod_at, s);
+      else if constexpr (TEX == TEX_ANISO)
+        dsu_mip::sample_aniso(tex.texels, tex.T, u * (double)tex.T, v * (double)tex.T, an.s1, an.N, an.ax, an.ay,
+                              an.k, an.t, lod_at, s);
       else
         sample_atlas<TEX>(tex, u * (double)tex.T, v * (double)tex.T, s);
     }
@@ -623,7 +647,8 @@ int64_t bins_of(int32_t F, int32_t S) {
 
 bool texture_ok(const dsu_render_texture& t) {
   return t.uv && t.texels && (uintptr_t)t.texels % 4 == 0 &&   // a texel is one 32-bit load
-         t.tex_size >= 1 && t.tex_size <= dsu_mip::MAX_T && t.filter >= TEX_NEAREST && t.filter <= TEX_TRILINEAR;
+         t.tex_size >= 1 && t.tex_size <= dsu_mip::MAX_T && t.filter >= TEX_NEAREST && t.filter <= TEX_ANISO &&
+         (t.filter != TEX_ANISO || (t.max_aniso >= 1 && t.max_aniso <= dsu_mip::MAX_ANISO));   // read with ANISO only
 }
 
 // The arguments of the RASTER launch, and the kernel of a (SS, colour source) pair.
@@ -704,8 +729,9 @@ int render_ortho(bool filtered, int32_t stage, const float* screen, const int32_
   if (filtered && !dsu_film::taps_ok(taps, halo, ss)) return DSU_EINVAL;
   const RasterCall call{(unsigned)nb, st, screen, faces, colour, pos, n_verts, n_faces, view,
                         dsu_bin::split(workspace, nb).offsets, items, n_faces ? n_items : 0,
-                        tex ? RenderTexture{tex->uv, reinterpret_cast<const uint32_t*>(tex->texels), tex->tex_size}
-                            : RenderTexture{nullptr, nullptr, 0},
+                        tex ? RenderTexture{tex->uv, reinterpret_cast<const uint32_t*>(tex->texels), tex->tex_size,
+                                            tex->filter == TEX_ANISO ? tex->max_aniso : 0}
+                            : RenderTexture{nullptr, nullptr, 0, 0},
                         out};
   const int source = tex ? tex->filter : TEX_NONE;
   if (!filtered) {
@@ -714,6 +740,7 @@ int render_ortho(bool filtered, int32_t stage, const float* screen, const int32_
       case TEX_NEAREST: call.launch<TEX_NEAREST>(ss); break;
       case TEX_BILINEAR: call.launch<TEX_BILINEAR>(ss); break;
       case TEX_TRILINEAR: call.launch<TEX_TRILINEAR>(ss); break;
+      case TEX_ANISO: call.launch<TEX_ANISO>(ss); break;
     }
   } else {
     FilmTaps film = {};
@@ -724,6 +751,7 @@ int render_ortho(bool filtered, int32_t stage, const float* screen, const int32_
       case TEX_NEAREST: call.launch_filtered<TEX_NEAREST>(ss, film); break;
       case TEX_BILINEAR: call.launch_filtered<TEX_BILINEAR>(ss, film); break;
       case TEX_TRILINEAR: call.launch_filtered<TEX_TRILINEAR>(ss, film); break;
+      case TEX_ANISO: call.launch_filtered<TEX_ANISO>(ss, film); break;
     }
   }
   DSU_CHECK_LAUNCH();

@@ -1,8 +1,10 @@
-// Level of detail and trilinear sampling of the atlas pyramid (include/dsu_hip.h, "Mip-mapped
-// frames"): one text for the resolve of mesh_render.hip (device) and for dsu_mip_sample_host (host),
-// so the non-GPU suite pins the arithmetic the kernel runs.  Everything is float64 in the operand
+// Level of detail, trilinear and anisotropic sampling of the atlas pyramid (include/dsu_hip.h,
+// "Mip-mapped frames" and "Anisotropic frames"): one text for the resolve of mesh_render.hip (device)
+// and for dsu_mip_sample_host / dsu_aniso_sample_host (host), so the non-GPU suite pins the arithmetic
+// the kernel runs.  Everything is float64 in the operand
 // order written here; the library is compiled with -ffp-contract=off, so no products are fused on
-// either side.  tests/frame_render_mip_ref.py restates it in numpy.
+// either side.  tests/frame_render_mip_ref.py and
+// tests/frame_render_aniso_ref.py restate it in numpy.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -76,9 +78,17 @@ DSU_MIP_HD void blend(const uint32_t* __restrict__ level, int Tj, double x, doub
             k10 * (double)(float)((p10 >> (8 * ch)) & 255u) + k11 * (double)(float)((p11 >> (8 * ch)) & 255u);
 }
 
-// Colour of one sample: tx, ty = uv T; (k, t) from lod(); at = level_offset(T, k).
-DSU_MIP_HD void sample(const uint32_t* __restrict__ pyramid, int T, double tx, double ty, int k, double t,
-                       int64_t at, float rgb[3]) {
+// One trilinear read: tx, ty = uv T; (k, t) from lod(); at = level_offset(T, k).  V = B_k, or
+// (1 - t) B_k + t B_{k+1}, per channel, goes to out[ch] through put(): divided by 255 and rounded once
+// to f32 for the trilinear filter's colour (sample), as it is for the anisotropic filter's sum
+// (sample_aniso).  A template over the output type and not a value array or a callback: with either of
+// those the compiler schedules the plain trilinear kernels of mesh_render.hip differently.
+DSU_MIP_HD void put(float& out, double V) { out = (float)(V / 255.0); }
+DSU_MIP_HD void put(double& out, double V) { out = V; }
+
+template <class Out>
+DSU_MIP_HD void trilinear(const uint32_t* __restrict__ pyramid, int T, double tx, double ty, int k, double t,
+                          int64_t at, Out out[3]) {
   if (!finite(tx)) tx = 0.0;
   if (!finite(ty)) ty = 0.0;
   const double x0 = tx, y0 = (double)(T - 1) - ty;
@@ -90,14 +100,85 @@ DSU_MIP_HD void sample(const uint32_t* __restrict__ pyramid, int T, double tx, d
   blend(pyramid + at, Tk, (x0 - half) * inv, (y0 - half) * inv, B0);
   if (t == 0.0) {
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)(B0[ch] / 255.0);
+    for (int ch = 0; ch < 3; ++ch) put(out[ch], B0[ch]);
     return;
   }
   const double half1 = ((double)(2 << k) - 1.0) * 0.5, inv1 = ldexp(1.0, -(k + 1));
   double B1[3];
   blend(pyramid + at + (int64_t)Tk * Tk, (Tk + 1) >> 1, (x0 - half1) * inv1, (y0 - half1) * inv1, B1);
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)(((1.0 - t) * B0[ch] + t * B1[ch]) / 255.0);
+  for (int ch = 0; ch < 3; ++ch) put(out[ch], (1.0 - t) * B0[ch] + t * B1[ch]);
+}
+
+// Colour of one sample under the trilinear rule.
+DSU_MIP_HD void sample(const uint32_t* __restrict__ pyramid, int T, double tx, double ty, int k, double t,
+                       int64_t at, float rgb[3]) {
+  trilinear(pyramid, T, tx, ty, k, t, at, rgb);
+}
+
+// ---- anisotropic frames (include/dsu_hip.h, "Anisotropic frames"; tests/frame_render_aniso_ref.py)
+constexpr int MAX_ANISO = 16;
+
+// What one (frame, face) hands its samples: the major axis of the footprint (unit, in tx, ty), its
+// length s1 in level-0 texels, the number of probes N along it, and the level (k, t) of one probe's
+// footprint rho = s1 / N.
+struct AnisoFace {
+  double s1 = 0.0, ax = 1.0, ay = 0.0, rho = 0.0, t = 0.0;
+  int N = 1, k = 0;
+};
+
+// The arguments of footprint(), the cap on N (1 .. MAX_ANISO) and the number of levels L.
+DSU_MIP_HD AnisoFace footprint_aniso(double ax, double ay, double bx, double by, double cx, double cy, float ua,
+                                     float va, float ub, float vb, float uc, float vc, int T, double h, int cap,
+                                     int L) {
+  AnisoFace f;
+  const double e1x = bx - ax, e1y = by - ay, e2x = cx - ax, e2y = cy - ay;
+  const double p1 = ((double)ub - (double)ua) * (double)T, q1 = ((double)vb - (double)va) * (double)T;
+  const double p2 = ((double)uc - (double)ua) * (double)T, q2 = ((double)vc - (double)va) * (double)T;
+  const double det = e1x * e2y - e1y * e2x;
+  if (det == 0.0) return f;
+  const double dpx = (p1 * e2y - p2 * e1y) / det, dpy = (p2 * e1x - p1 * e2x) / det;
+  const double dqx = (q1 * e2y - q2 * e1y) / det, dqy = (q2 * e1x - q1 * e2x) / det;
+  const double hh = h * h;
+  const double A = hh * (dpx * dpx + dpy * dpy), C = hh * (dqx * dqx + dqy * dqy);
+  const double B = hh * (dpx * dqx + dpy * dqy), D = hh * (dpx * dqy - dpy * dqx);
+  const double m = (A + C) * 0.5, d = (A - C) * 0.5;
+  const double r = sqrt(d * d + B * B);
+  const double s1 = sqrt(m + r);
+  if (!finite(A) || !finite(B) || !finite(C) || !finite(D) || !finite(r) || !finite(s1)) return f;
+  const double s2 = fabs(D) / s1;                  // from the determinant: m - r cancels
+  const double vx = d >= 0.0 ? d + r : B, vy = d >= 0.0 ? B : r - d;   // neither form cancels
+  const double n = sqrt(vx * vx + vy * vy);
+  if (n != 0.0 && finite(n)) {
+    f.ax = vx / n;
+    f.ay = vy / n;
+  }
+  f.s1 = s1;
+  if (!(s1 > 1.0)) f.N = 1;
+  else if (!(s2 > 0.0)) f.N = cap;
+  else {
+    const double q = ceil(s1 / s2);
+    f.N = q < (double)cap ? (int)q : cap;
+  }
+  f.rho = s1 / (double)f.N;
+  lod(f.rho, L, f.k, f.t);
+  return f;
+}
+
+// Colour of one sample under the anisotropic rule: N probes along the axis, their unrounded trilinear
+// values summed in ascending order, one rounding to f32.  at = level_offset(T, k).
+DSU_MIP_HD void sample_aniso(const uint32_t* __restrict__ pyramid, int T, double tx, double ty, double s1, int N,
+                             double ax, double ay, int k, double t, int64_t at, float rgb[3]) {
+  double sum[3] = {0.0, 0.0, 0.0};
+  for (int i = 0; i < N; ++i) {
+    const double o = ((double)(2 * i + 1) / (double)(2 * N) - 0.5) * s1;
+    double V[3];
+    trilinear(pyramid, T, tx + o * ax, ty + o * ay, k, t, at, V);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) sum[ch] += V[ch];
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)((sum[ch] / (double)N) / 255.0);
 }
 
 }  // namespace dsu_mip

@@ -19,6 +19,10 @@ renders vertex colours (for a textured export: the atlas's nearest texel at each
 `--texture_filter trilinear` reads the atlas's mip pyramid, so an atlas finer than the sample lattice
 does not alias; `--mip_coverage faces` (default) builds it from the texels the uv faces cover, `all`
 from every texel (an OBJ from elsewhere with mirrored charts).
+`--texture_filter anisotropic` reads the same pyramid with up to `--max_anisotropy N` (1..16, default
+8) probes per sub-sample along the long axis of the face's texel footprint: the faces that turn
+edge-on towards the silhouette, where the drawings' ink contours lie, keep their detail along the
+axis that is not compressed.  It applies to every action and composes with the flags below.
 
 For the BVH actions, `--skinning dual_quaternion` blends the joints' unit dual quaternions instead of
 their matrices (Blender's "Preserve Volume"; the default `linear` is Blender's default and the
@@ -64,7 +68,7 @@ import time
 import numpy as np
 from PIL import Image
 
-from .. import animate
+from .. import animate, ops
 from ..animate.skeleton import bvh_files
 
 
@@ -177,10 +181,13 @@ def run(argv=None):
     ap.add_argument("--ss", type=int, default=4, choices=[1, 2, 4], help="sub-samples per pixel side")
     ap.add_argument("--texture", default="vertex", choices=["vertex", "atlas"],
                     help="colour source: vertex colours, or the OBJ's map_Kd atlas sampled per sub-sample")
-    ap.add_argument("--texture_filter", default="bilinear", choices=["bilinear", "nearest", "trilinear"],
+    ap.add_argument("--texture_filter", default="bilinear", choices=["bilinear", "nearest", "trilinear", "anisotropic"],
                     help="how --texture atlas samples the atlas")
+    ap.add_argument("--max_anisotropy", type=int, default=None, metavar="N",
+                    help="with --texture_filter anisotropic: at most N probes per sub-sample along the footprint's long "
+                         "axis, 1..16 (default 8)")
     ap.add_argument("--mip_coverage", default="faces", choices=["faces", "all"],
-                    help="texels the mip levels of --texture_filter trilinear average: those the uv faces cover, or all")
+                    help="texels the mip levels of --texture_filter trilinear / anisotropic average: those the uv faces cover, or all")
     ap.add_argument("--skinning", default="linear", choices=list(animate.skin.SKINNING),
                     help="blend of the BVH actions: the joints' matrices, their dual quaternions (preserve volume), or "
                          "their rotations about a centre of rotation per vertex")
@@ -221,6 +228,10 @@ def run(argv=None):
         animate.render._pixel_filter_args(args.pixel_filter, args.filter_width, args.ss)
     except ValueError as e:
         ap.error(str(e))
+    try:
+        ops.check_texture_filter(args.texture_filter, args.max_anisotropy)
+    except ValueError as e:
+        ap.error(f"--texture_filter / --max_anisotropy: {e}")
     flt = {} if args.pixel_filter is None else dict(pixel_filter=args.pixel_filter, filter_width=args.filter_width)
     found = sorted(glob.glob(os.path.join(args.data_dir, args.uid, "mesh", "*.obj")))
     if not found:
@@ -229,8 +240,10 @@ def run(argv=None):
     if args.texture == "atlas":
         verts, faces, uvs, image = animate.read_obj_textured(found[0])     # refuses an untextured OBJ
         colours, tex = None, dict(texture=image, uvs=uvs, texture_filter=args.texture_filter)
-        if args.texture_filter == "trilinear":
+        if args.texture_filter in ops.PYRAMID_FILTERS:
             tex["mip_coverage"] = args.mip_coverage
+        if args.texture_filter == ops.ANISOTROPIC:
+            tex["max_anisotropy"] = args.max_anisotropy
     else:
         verts, faces, colours = animate.read_obj(found[0])
         if colours is None:

@@ -1511,6 +1511,27 @@ class _BinnedPlan:
 RENDER_COUNT, RENDER_FILL, RENDER_RASTER = (_lib.DEFINES["DSU_RENDER_" + k] for k in ("COUNT", "FILL", "RASTER"))
 MIP_TRILINEAR = "trilinear"
 TEXTURE_FILTERS = {k: _lib.DEFINES["DSU_TEX_" + k.upper()] for k in ("nearest", "bilinear", MIP_TRILINEAR)}
+# the fourth filter carries a parameter of its own (max_anisotropy), so it is named beside the table
+ANISOTROPIC = "anisotropic"
+TEX_ANISOTROPIC = _lib.DEFINES["DSU_TEX_ANISOTROPIC"]
+MAX_ANISOTROPY = 16
+DEFAULT_ANISOTROPY = 8
+PYRAMID_FILTERS = (MIP_TRILINEAR, ANISOTROPIC)              # the filters that read the mip pyramid
+
+
+def check_texture_filter(filter, max_anisotropy=None):
+    """Refuses an unknown texture filter, a max_anisotropy outside 1..16 and one given to another filter
+    than "anisotropic"; -> the cap as an int (the default for None), or None for the other filters."""
+    if filter != ANISOTROPIC:
+        if filter not in TEXTURE_FILTERS:
+            raise ValueError(f"filter must be one of {sorted([*TEXTURE_FILTERS, ANISOTROPIC])}")
+        if max_anisotropy is not None:
+            raise ValueError("max_anisotropy goes with filter 'anisotropic'")
+        return None
+    cap = DEFAULT_ANISOTROPY if max_anisotropy is None else max_anisotropy
+    if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= MAX_ANISOTROPY:
+        raise ValueError(f"max_anisotropy must be an integer in 1..{MAX_ANISOTROPY}")
+    return int(cap)
 
 
 class MeshRenderPlan(_BinnedPlan):
@@ -1545,7 +1566,7 @@ class MeshRenderPlan(_BinnedPlan):
                 "dsu_mesh_render_ortho_filtered")
 
     def raster(self, colour, pos, want=("color_u8", "pos_u8", "frames"), uv=None, texture=None,
-               filter="bilinear", pyramid=None, taps=None):
+               filter="bilinear", pyramid=None, taps=None, max_anisotropy=None):
         """Visibility + resolve.  Returns a dict of the requested outputs among color_u8, pos_u8
         (F,S,S,4) uint8, face_id (F,N,N) i32, depth (F,N,N) f32, frames (F,6,S,S) f32, pixels
         (F,S,S,8) f32.
@@ -1555,7 +1576,10 @@ class MeshRenderPlan(_BinnedPlan):
         "nearest") and `colour` may be None; without them this is the vertex-colour call.
         filter "trilinear" reads the texture's mip pyramid: `pyramid`, a
         MipPyramid of this texture from mip_pyramid(), or None to build it here with every texel
-        covered and the default gutter.
+        covered and the default gutter.  filter "anisotropic" reads the same pyramid with up to
+        max_anisotropy (1..16, default 8) probes per sample along the long axis of the face's footprint
+        (include/dsu_hip.h, "Anisotropic frames"); a pyramid built here gets max(2, max_anisotropy)
+        gutter rounds.
 
         taps: None = the box over a pixel's own samples (dsu_mesh_render_ortho); otherwise the
         ss + 2 halo float64 taps of a separable pixel filter (animate.pixel_filter) for the halo this
@@ -1571,8 +1595,9 @@ class MeshRenderPlan(_BinnedPlan):
             if len(taps) != self.ss + 2 * self.halo:
                 raise ValueError(f"{len(taps)} taps do not belong to ss {self.ss} and the halo {self.halo} this plan "
                                  f"was binned with ({self.ss + 2 * self.halo} expected)")
-        if (uv is None) != (texture is None) or (texture is None and (filter == MIP_TRILINEAR or pyramid is not None)):
-            raise ValueError("uv and texture come together or not at all (and a trilinear read needs both)")
+        if (uv is None) != (texture is None) or (texture is None and (filter in PYRAMID_FILTERS or pyramid is not None)):
+            raise ValueError("uv and texture come together or not at all (and a trilinear or anisotropic read "
+                             "needs both)")
         F, S, N, dev = self.F, self.size, self.size * self.ss, self.screen.device
         shapes = {"color_u8": ((F, S, S, 4), torch.uint8), "pos_u8": ((F, S, S, 4), torch.uint8),
                   "face_id": ((F, N, N), torch.int32), "depth": ((F, N, N), torch.float32),
@@ -1589,22 +1614,24 @@ class MeshRenderPlan(_BinnedPlan):
             if colour.shape != (self.V, 3):
                 raise ValueError("colour and pos must be (V,3)")
         else:
-            if filter not in TEXTURE_FILTERS:
-                raise ValueError(f"filter must be one of {sorted(TEXTURE_FILTERS)}")
+            cap = check_texture_filter(filter, max_anisotropy)
             uv, texels = _f32c(uv), texture_rgba(texture)
             if uv.shape != (self.V, 2):
                 raise ValueError("uv must be (V,2)")
             T = texels.shape[0]
-            if filter == MIP_TRILINEAR:
+            if filter in PYRAMID_FILTERS:
                 if pyramid is None:
-                    pyramid = mip_pyramid(texels)
+                    pyramid = mip_pyramid(texels) if cap is None else mip_pyramid(texels, gutter=max(2, cap))
                 if not isinstance(pyramid, MipPyramid) or pyramid.T != T or pyramid.buffer.device != dev:
                     raise ValueError("pyramid must be the MipPyramid of this texture, on the mesh's device")
                 texels = pyramid.buffer
             elif pyramid is not None:
-                raise ValueError("a pyramid goes with filter 'trilinear'")
+                raise ValueError("a pyramid goes with filter 'trilinear' or 'anisotropic'")
             colour = None                             # not read
-            tex = _lib.RenderTexture(ptr(uv), ptr(texels, torch.uint8), T, TEXTURE_FILTERS[filter])
+            if cap is None:
+                tex = _lib.RenderTexture(ptr(uv), ptr(texels, torch.uint8), T, TEXTURE_FILTERS[filter])
+            else:
+                tex = _lib.RenderTexture(ptr(uv), ptr(texels, torch.uint8), T, TEX_ANISOTROPIC, cap)
         out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in shapes.items() if k in want}
         self._stage(RENDER_RASTER, colour, pos, tex, [out.get(k) for k in shapes], taps)
         return out
@@ -1665,15 +1692,17 @@ def mip_pyramid(texture, covered=None, gutter=2):
 
 def mesh_render_ortho(screen, faces, colour, pos, cx, cy, span, size, ss=4,
                       want=("color_u8", "pos_u8", "frames"), uv=None, texture=None, filter="bilinear",
-                      pyramid=None, pixel_filter=None):
+                      pyramid=None, pixel_filter=None, max_anisotropy=None):
     """Orthographic render of F frames of one mesh with two attribute sets (include/dsu_hip.h,
     dsu_mesh_render_ortho): bin, then rasterise and resolve.  The colours are the vertex colours,
     or with uv and texture the texture's (filter "trilinear": its mip `pyramid`, built from the
-    texture when None).  pixel_filter: None = the box over a pixel's own samples, or the (taps, halo)
+    texture when None; filter "anisotropic": the same pyramid, up to max_anisotropy probes per sample).
+    pixel_filter: None = the box over a pixel's own samples, or the (taps, halo)
     of animate.pixel_filter for this ss (dsu_mesh_render_ortho_filtered)."""
     taps, halo = (None, 0) if pixel_filter is None else pixel_filter
     return MeshRenderPlan(screen, faces, cx, cy, span, size, ss, halo).bin().raster(colour, pos, want, uv, texture,
-                                                                                    filter, pyramid, taps)
+                                                                                    filter, pyramid, taps,
+                                                                                    max_anisotropy)
 
 
 def pos_edge_u8(pos_rgba):

@@ -1114,7 +1114,8 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
  * from a UV atlas instead of the vertex colours (the reference's Blender reads the OBJ's map_Kd).
  * uv (n_verts, 2) f32; texels (tex_size, tex_size, 4) uint8 RGBA, 4-byte aligned (a texel is one
  * 32-bit load; the fourth byte is not read); 1 <= tex_size <= 8192.  DSU_EINVAL before any launch:
- * uv or texels NULL, texels misaligned, tex_size out of range, filter not one of DSU_TEX_*.
+ * uv or texels NULL, texels misaligned, tex_size out of range, filter not one of DSU_TEX_*, or
+ * DSU_TEX_ANISOTROPIC with max_aniso outside 1..16.
  *
  * Rule.  Visibility, depth, alpha, the position pass, frames, the layout of pixels and everything
  * downstream of pos_u8 are as without tex: the texture enters through the three colour
@@ -1133,21 +1134,24 @@ int dsu_knn8_blend(const double* query_xy, int64_t n_query, const double* known_
  * The per-sample value goes where the interpolated vertex colour goes: accumulated in float64 over
  * the pixel's covered samples in row-major order, divided by their count, uint8 = floor(v 255 + 0.5).
  * These two filters read level 0 only: a texture much finer than the sample lattice aliases under
- * them.  DSU_TEX_TRILINEAR ("Mip-mapped frames" below) is the filtered read; there is no area or
- * anisotropic sampling.  The library cannot tell a level-0 image from a pyramid: texels that hold
- * only the former, passed with DSU_TEX_TRILINEAR, are read past their end. */
+ * them.  DSU_TEX_TRILINEAR ("Mip-mapped frames" below) is the filtered read and DSU_TEX_ANISOTROPIC
+ * ("Anisotropic frames" below) the one that follows the footprint's long axis; there is no area
+ * sampling.  The library cannot tell a level-0 image from a pyramid: texels that hold only the
+ * former, passed with DSU_TEX_TRILINEAR or DSU_TEX_ANISOTROPIC, are read past their end. */
 #define DSU_RENDER_COUNT 0
 #define DSU_RENDER_FILL 1
 #define DSU_RENDER_RASTER 2
 #define DSU_TEX_NEAREST   0
 #define DSU_TEX_BILINEAR  1
 #define DSU_TEX_TRILINEAR 2
+#define DSU_TEX_ANISOTROPIC 3
 typedef struct dsu_render_texture {
   const float*   uv;        /* (n_verts, 2) f32 */
-  const uint8_t* texels;    /* NEAREST / BILINEAR: (T, T, 4) RGBA8.  TRILINEAR: the pyramid buffer of
-                               dsu_mip_pyramid_build for a level 0 of side T.  4-byte aligned. */
+  const uint8_t* texels;    /* NEAREST / BILINEAR: (T, T, 4) RGBA8.  TRILINEAR / ANISOTROPIC: the pyramid
+                               buffer of dsu_mip_pyramid_build for a level 0 of side T.  4-byte aligned. */
   int32_t tex_size;         /* T, 1 .. 8192 */
   int32_t filter;           /* DSU_TEX_* */
+  int32_t max_aniso;        /* ANISOTROPIC: the cap on the probes of a sample, 1 .. 16; not read otherwise */
 } dsu_render_texture;
 int64_t dsu_mesh_render_ortho_workspace_bytes(int32_t n_frames, int32_t size);
 int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* faces,
@@ -1205,7 +1209,7 @@ int dsu_mesh_render_ortho(int32_t stage, const float* screen, const int32_t* fac
  * Deviations from the textbook filter.  The blend weight is linear in rho inside an octave where
  * log2 rho would be the usual choice (they differ by at most 0.086 of a level); in exchange the rule
  * is reproducible bit for bit on the host.  rho is the isotropic (max) rule: a face seen edge-on is
- * blurred along both axes.  No anisotropic filtering.
+ * blurred along both axes; DSU_TEX_ANISOTROPIC ("Anisotropic frames" below) is the filter that is not.
  *
  * c. dsu_mip_sample_host: HOST function on HOST arrays — the sampling above (level and weight from
  * rho[i], then the sample at tx[i], ty[i]) evaluated on the CPU by the text the kernel compiles:
@@ -1217,6 +1221,61 @@ int dsu_mip_pyramid_build(const uint8_t* texture, const uint8_t* covered, int32_
                           uint8_t* pyramid, void* workspace, int64_t workspace_bytes, void* stream);
 int dsu_mip_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tx, const double* ty,
                         const double* rho, int64_t n, float* rgb_out);
+/* Anisotropic frames: dsu_mesh_render_ortho (and _filtered), tex with DSU_TEX_ANISOTROPIC and max_aniso
+ * = cap in 1..16.  texels is the pyramid buffer as for DSU_TEX_TRILINEAR; visibility, depth, alpha, the
+ * position pass, frames and pixels are untouched.  Where the trilinear rule takes one isotropic
+ * footprint, this one takes the footprint's two axes: up to `cap` trilinear probes are spread along
+ * the long axis, each at the level of the footprint divided by their number, so a face seen edge-on
+ * keeps its detail along the axis that is not compressed.  (csrc/mip_sample.h is the text of both
+ * sides; tests/frame_render_aniso_ref.py restates it.)
+ *
+ * Rule.  Everything is float64 in the operand order written, no products fused, no transcendental:
+ * IEEE sqrt and division only.  Per (frame, face), from the f32 screen vertices and the f32 uvs, with
+ * dpx, dpy, dqx, dqy, det and h exactly as in "Mip-mapped frames":
+ *     A = (h h)(dpx dpx + dpy dpy),  C = (h h)(dqx dqx + dqy dqy),
+ *     B = (h h)(dpx dqx + dpy dqy),  D = (h h)(dpx dqy - dpy dqx)
+ * — the entries and the determinant's root of M M^T, M the texel-per-sample Jacobian —,
+ *     m = (A + C) 0.5,  d = (A - C) 0.5,  r = sqrt(d d + B B),  s1 = sqrt(m + r),  s2 = |D| / s1
+ * (s2 from the determinant: m - r cancels).  Major axis in (tx, ty): (d + r, B) when d >= 0, else
+ * (B, r - d) — neither form cancels —, divided by its norm sqrt(x x + y y); (1, 0) where the norm is 0
+ * or not finite.
+ *   det == 0, or one of A, B, C, D, r, s1 not finite: N = 1, rho' = 0, s1 taken as 0, axis (1, 0).
+ *   Otherwise !(s1 > 1): N = 1;  else !(s2 > 0): N = cap;  else N = min(ceil(s1 / s2), cap) (the
+ *   comparison is made in float64, before the conversion to int);  rho' = s1 / N;
+ *   (k, t) = the level and weight of "Mip-mapped frames" for rho'.
+ * Per sample, with tx, ty as in "Textured frames": probe i = 0 .. N - 1 sits at
+ *     o_i = ((double)(2 i + 1) / (double)(2 N) - 0.5) s1,   (tx + o_i ax, ty + o_i ay)
+ * (a non-finite coordinate is taken as 0, per probe); V_i is the unrounded trilinear value there at
+ * (k, t): B_k, or (1 - t) B_k + t B_{k+1};
+ *     channel = (float)(((sum_i V_i) / (double)N) / 255.0),
+ * the sum started at 0 and taken in ascending i, one rounding to f32.
+ *   The gutter.  2^k <= rho' = s1 / N, so |o_i| <= (N - 1) s1 / (2 N) < (N - 1) 2^k: the outermost
+ *   probe lies less than N - 1 texels of level k from the sample, and its bilinear read reaches one
+ *   texel further.  A chart therefore needs max(2, cap) texels of margin on every level for no probe
+ *   to read its neighbour: animate.render_frames builds the pyramid with that many gutter rounds (and
+ *   dilates level 0 by as many).  This entry point does not dilate: it reads the pyramid it is given.
+ * What follows from the rule (and the tests assert):
+ *   (a) s1 <= 1: N = 1, k = 0, t = 0, o_0 = 0 — the bilinear rule bit for bit;
+ *   (b) an axis-aligned map of equal scale on both axes (dpy = dqx = 0, |dpx| = |dqy|): A = C has the
+ *       bits of the trilinear (h h) gx, so s1 has the bits of the trilinear rho; where s1 / s2 does not
+ *       exceed 1 in float64 (every scale whose square root is exact) N = 1 and the output is the
+ *       trilinear one bit for bit;
+ *   (c) cap = 1 is a trilinear filter on s1 (the larger singular value where "Mip-mapped frames" takes
+ *       the larger screen-axis gradient).
+ * Deviations from the textbook filter.  The probes have equal weights: no Gaussian, no EWA.  The blend
+ * is linear in rho', as the trilinear rule's is in rho.  A probe may leave its chart: nothing clips it
+ * to the face's uv triangle, the gutter above is what it then reads.  Beyond the cap the probes are
+ * spaced wider than their footprint (rho' > s2): the remainder of the ratio is blurred isotropically.
+ *
+ * dsu_aniso_sample_host: HOST function on HOST arrays — the rule above evaluated on the CPU by the text
+ * the kernel compiles, item by item.  tri (n, 6) f64: screen x, y of a, b, c (the f32 vertices widened);
+ * uv (n, 6) f32: u, v of a, b, c; h the sample spacing; tx, ty (n) f64 the sample's texel coordinates;
+ * max_aniso the cap.  rgb_out (n, 3) f32; optional (NULL): probes_out (n) i32 = N, rho_out (n) f64 =
+ * rho', axis_out (n, 2) f64.  DSU_EINVAL: tex_size or max_aniso out of range, n < 0, h not finite, or
+ * with n > 0 a required pointer NULL or pyramid not 4-byte aligned. */
+int dsu_aniso_sample_host(const uint8_t* pyramid, int32_t tex_size, const double* tri, const float* uv, double h,
+                          const double* tx, const double* ty, int32_t max_aniso, int64_t n, float* rgb_out,
+                          int32_t* probes_out, double* rho_out, double* axis_out);
 /* Pixel filter: dsu_mesh_render_ortho_filtered is dsu_mesh_render_ortho with the reconstruction
  * filter of the reference's renderer in the resolve (Blender's EEVEE and Cycles weight the samples
  * of a pixel with a Blackman-Harris window that reaches beyond the pixel's own square) where
